@@ -1,9 +1,14 @@
 #!/usr/bin/env python
 """Benchmark of the GPz objective+gradient evaluation on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c4|c3|c2]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c4|c3|c2] [--dump-outputs DIR] [--full]
 
 A "step" is one gpz_eval: theta on the host -> [f, grad, 4 statistics] on the host, data resident in HBM.
+A plain run sets up, warms up, times the K steps and prints the result line (headline, roofline of the dominant kernels from the
+timed region's own events, bitwise fingerprint of the last step).  --dump-outputs DIR writes what the last timed step returned
+(f.npy, grad.npy and the statistics, float64) for output-by-output comparison of two builds.  --full adds everything that takes
+runs of its own: the stage pass (events around every stage), the single-graph pass, the gap pass, and on one GPU the CPU baseline
+with its parity gate against the oracle.
 Metric (BASELINE.json): objective+gradient evaluations per second, whole job.  N > 1 shards the n rows of the SAME
 problem (strong scaling); only the m x m / m x (d^2+d) partials are all-reduced over RCCL.  Two launch forms:
   * `python -m torch.distributed.run --nproc-per-node N bench.py --gpus N`: one rank per process, RCCL communicator
@@ -142,6 +147,24 @@ def synth_psi(cfg, rows, cube=False):
     return Psi
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, f, g, stats):
+    """What a caller of the timed path received from its last step, one float64 .npy per array: f (nlogML), grad and the
+    statistics gpz_eval returns beside them.  A gradient too large for the 64 MB budget is written as a fixed, seeded sample of its
+    entries (grad_sample.npy, with their positions in grad_index.npy)."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {"f": np.array([f], dtype=np.float64), "grad": np.asarray(g, dtype=np.float64)}
+    arrays.update({k: np.array([v], dtype=np.float64) for k, v in stats.items()})
+    if arrays["grad"].nbytes > DUMP_LIMIT_BYTES // 2:
+        g = arrays.pop("grad")
+        idx = np.sort(np.random.default_rng(0).choice(g.size, DUMP_LIMIT_BYTES // 32, replace=False))
+        arrays["grad_sample"], arrays["grad_index"] = g[idx], idx.astype(np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def cpu_baseline(cfg, model, theta, X, y, omega, rows):
     """The oracle (as-written NumPy restatement of the reference path) timed on a bounded row sample."""
     from oracle import gpz_oracle as O
@@ -217,6 +240,68 @@ def cpu_baseline(cfg, model, theta, X, y, omega, rows):
     return ref, out
 
 
+def extra_passes(args, ctx, thetas, barrier, multi, tim):
+    """--full: the passes beyond the timed region, each over the same K steps -> (stage_pass, single_graph, gaps, per-rank records,
+    the kernel times of the roofline)."""
+    # Second pass, events around EVERY stage (eager launches): the per-stage breakdown (allreduce1 / allreduce2 are the two exchange points)
+    ctx.enable_timing(1)
+    ctx.reset_timings()
+    barrier()
+    ts0 = time.perf_counter()
+    for i in range(args.steps):
+        ctx.eval(thetas[args.warmup + i])
+    barrier()
+    ts1 = time.perf_counter() - ts0
+    tim_full = ctx.timings()
+    if multi:
+        rank_stage_t = {r: ctx.timings(r) for r in range(ctx.n_gpus)}   # (the gap pass below resets the timers)
+    if not tim:            # --timed-events none: the kernel times of the roofline come from the stage pass
+        tim = tim_full
+    stage_pass = {"ms_per_step": ts1 / args.steps * 1e3, "evals_per_s": args.steps / ts1,
+                  "note": "same K steps with HIP events around every stage: eager launches, not replay",
+                  "stage_ms_per_eval": {k: v[0] / args.steps for k, v in tim_full.items()}}
+    # The same K steps once more WITHOUT any event: the whole evaluation one graph launch - what a default caller gets (ADVICE r05: the
+    # timed region above is cut into segments with events between them, which shows on the latency-bound configurations).  Reported
+    # beside the headline, never instead of it: the roofline's kernel durations must come from the timed region itself.
+    single_graph = None
+    if args.timed_events == "dominant":
+        ctx.enable_timing(0)
+        for i in range(max(2, args.warmup)):
+            ctx.eval(thetas[i % len(thetas)])
+        barrier()
+        tq0 = time.perf_counter()
+        for i in range(args.steps):
+            ctx.eval(thetas[args.warmup + i])
+        barrier()
+        tq1 = time.perf_counter() - tq0
+        single_graph = {"ms_per_step": tq1 / args.steps * 1e3, "evals_per_s": args.steps / tq1,
+                        "note": "same K steps, no HIP events: the evaluation as ONE hipGraph launch (the default caller's path)"}
+    # Third pass (<= 5 steps), timing level 3: the replay of the timed region with events around EVERY graph segment and around the
+    # all-reduce hooks.  Wall time of a call minus the sum of all of them = what the device spent between segments (launch-to-launch gaps,
+    # waiting for the host, the result copy's latency): the figure a real N-GPU run is read against the single-device loopback line with.
+    gsteps = min(args.steps, 5)
+    ctx.enable_timing(3)
+    for i in range(2):
+        ctx.eval(thetas[i])
+    ctx.reset_timings()
+    barrier()
+    tg0 = time.perf_counter()
+    for i in range(gsteps):
+        ctx.eval(thetas[args.warmup + i])
+    wall_gap = (time.perf_counter() - tg0) / gsteps * 1e3
+    barrier()
+
+    def gap_record(t):
+        seg = sum(v[0] for v in t.values()) / gsteps
+        return {"wall_ms_per_eval": wall_gap, "segments_ms_per_eval": seg - t.get("exchange", (0.0, 0))[0] / gsteps,
+                "exchange_ms_per_eval": t.get("exchange", (0.0, 0))[0] / gsteps, "gap_ms_per_eval": wall_gap - seg,
+                "note": f"{gsteps} replayed evaluations, HIP events around every graph segment and every all-reduce; gap = wall - segments - exchange"}
+    gaps = gap_record(ctx.timings()) if not multi else None
+    rank_records = {r: {"stage_ms_per_eval": {k: v[0] / args.steps for k, v in rank_stage_t[r].items()},
+                        "gaps": gap_record(ctx.timings(r))} for r in range(ctx.n_gpus)} if multi else {}
+    return stage_pass, single_graph, gaps, rank_records, tim
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -234,7 +319,13 @@ def main():
                          "none (the whole evaluation one graph: the latency-bound configurations, where eight extra graph launches show)")
     ap.add_argument("--validation", type=float, default=0.0,
                     help="fraction of the rows turned into validation rows (GPz.m:239-261 priced inside the step; SURVEY 8d: c2 with 0.15)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (f, grad, statistics) as DIR/<name>.npy, float64")
+    ap.add_argument("--full", action="store_true",
+                    help="also the stage, single-graph and gap passes, and on one GPU the CPU baseline with its parity gate")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
 
     import torch
     import gpz_amd
@@ -339,8 +430,8 @@ def main():
 
     # The timed region runs what a caller gets: from the third evaluation on, hipGraph replays (cut into segments at the two exchange
     # points of a sharded run).  Timing level 2 keeps that and records HIP events around the dominant stages only, BETWEEN the graph
-    # launches (events inside a graph cannot be timed on ROCm 7: tools/graph_event_probe.hip); the all-stage breakdown comes from a
-    # second pass of the same K steps with events around every stage, which runs as eager launches ("stage_pass").
+    # launches (events inside a graph cannot be timed on ROCm 7: tools/graph_event_probe.hip); with --full, the all-stage breakdown comes
+    # from a second pass of the same K steps with events around every stage, which runs as eager launches ("stage_pass").
     ctx.enable_timing(2 if args.timed_events == "dominant" else 0)
     for i in range(args.warmup):      # (the graph is recorded on the second evaluation: W >= 2 keeps the recording out of the timed region)
         ctx.eval(thetas[i])
@@ -362,72 +453,25 @@ def main():
     tim = ctx.timings()
     route = ctx.route() if hasattr(ctx, "route") else None
     rank_routes = [ctx.route(r) for r in range(ctx.n_gpus)] if multi else None
-    # Second pass, events around EVERY stage (eager launches): the per-stage breakdown (allreduce1 / allreduce2 are the two exchange points)
-    ctx.enable_timing(1)
-    ctx.reset_timings()
-    barrier()
-    ts0 = time.perf_counter()
-    for i in range(args.steps):
-        ctx.eval(thetas[args.warmup + i])
-    barrier()
-    ts1 = time.perf_counter() - ts0
-    tim_full = ctx.timings()
-    if multi:
-        rank_stage_t = {r: ctx.timings(r) for r in range(ctx.n_gpus)}   # (the gap pass below resets the timers)
-    if not tim:            # --timed-events none: the kernel times of the roofline come from the stage pass
-        tim = tim_full
-    stage_pass = {"ms_per_step": ts1 / args.steps * 1e3, "evals_per_s": args.steps / ts1,
-                  "note": "same K steps with HIP events around every stage: eager launches, not replay",
-                  "stage_ms_per_eval": {k: v[0] / args.steps for k, v in tim_full.items()}}
-    # The same K steps once more WITHOUT any event: the whole evaluation one graph launch - what a default caller gets (the
-    # timed region above is cut into segments with events between them, which shows on the latency-bound configurations).  Reported
-    # beside the headline, never instead of it: the roofline's kernel durations must come from the timed region itself.
-    single_graph = None
-    if args.timed_events == "dominant":
-        ctx.enable_timing(0)
-        for i in range(max(2, args.warmup)):
-            ctx.eval(thetas[i % len(thetas)])
-        barrier()
-        tq0 = time.perf_counter()
-        for i in range(args.steps):
-            ctx.eval(thetas[args.warmup + i])
-        barrier()
-        tq1 = time.perf_counter() - tq0
-        single_graph = {"ms_per_step": tq1 / args.steps * 1e3, "evals_per_s": args.steps / tq1,
-                        "note": "same K steps, no HIP events: the evaluation as ONE hipGraph launch (the default caller's path)"}
-    # Third pass (<= 5 steps), timing level 3: the replay of the timed region with events around EVERY graph segment and around the
-    # all-reduce hooks.  Wall time of a call minus the sum of all of them = what the device spent between segments (launch-to-launch gaps,
-    # waiting for the host, the result copy's latency): the figure a real N-GPU run is read against the single-device loopback line with.
-    gsteps = min(args.steps, 5)
-    ctx.enable_timing(3)
-    for i in range(2):
-        ctx.eval(thetas[i])
-    ctx.reset_timings()
-    barrier()
-    tg0 = time.perf_counter()
-    for i in range(gsteps):
-        ctx.eval(thetas[args.warmup + i])
-    wall_gap = (time.perf_counter() - tg0) / gsteps * 1e3
-    barrier()
-
-    def gap_record(t):
-        seg = sum(v[0] for v in t.values()) / gsteps
-        return {"wall_ms_per_eval": wall_gap, "segments_ms_per_eval": seg - t.get("exchange", (0.0, 0))[0] / gsteps,
-                "exchange_ms_per_eval": t.get("exchange", (0.0, 0))[0] / gsteps, "gap_ms_per_eval": wall_gap - seg,
-                "note": f"{gsteps} replayed evaluations, HIP events around every graph segment and every all-reduce; gap = wall - segments - exchange"}
-    gaps = gap_record(ctx.timings()) if not multi else None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, fs[-1], g, ctx.stats)
+    stage_pass = single_graph = gaps = None
+    rank_passes = {}
+    if args.full:
+        stage_pass, single_graph, gaps, rank_passes, tim = extra_passes(args, ctx, thetas, barrier, multi, tim)
     per_rank = None
     if multi:
-        per_rank = [dict({"rank": r, "rows": ctx.rows_per_gpu[r], "rccl": rccl_origin, "route": rank_routes[r],
-                          "stage_ms_per_eval": {k: v[0] / args.steps for k, v in rank_stage_t[r].items()},
-                          "gaps": gap_record(ctx.timings(r))}, **ctx.comm_info(r))
+        per_rank = [dict({"rank": r, "rows": ctx.rows_per_gpu[r], "rccl": rccl_origin, "route": rank_routes[r]}, **ctx.comm_info(r))
                     for r in range(ctx.n_gpus)]
+        for q in per_rank if args.full else ():
+            q.update(rank_passes[q["rank"]])
     elif use_dist:
         # per rank: its rows, every stage and what the communicator itself reports (ncclCommCount / ncclCommUserRank / device + PCI bus
         # id) - the first real multi-GPU line proves N ranks on N devices from its own output and can be read stage by stage against
         # the single-GPU shard line (profiles/*_shard125k.json)
-        mine = dict({"rank": rank, "rows": n_local, "comm": comm, "rccl": rccl_origin, "route": route,
-                     "stage_ms_per_eval": stage_pass["stage_ms_per_eval"], "gaps": gaps}, **ctx.comm_info())
+        mine = dict({"rank": rank, "rows": n_local, "comm": comm, "rccl": rccl_origin, "route": route}, **ctx.comm_info())
+        if args.full:
+            mine.update({"stage_ms_per_eval": stage_pass["stage_ms_per_eval"], "gaps": gaps})
         if comm == "torch":
             # no communicator inside the library: what the process group behind the hook says about itself, and this rank's device
             mine.update({"nccl_count": dist.get_world_size(), "nccl_rank": dist.get_rank(), "comm_record": f"torch.distributed process group ({backend})"})
@@ -506,7 +550,7 @@ def main():
                          "frac_of_ubench": ach / (F32_MFMA_UBENCH_TFLOPS if f32_route else F64_MFMA_UBENCH_TFLOPS)},
             "kernels": {"syrk_tflops_algorithmic": ach_sy, "syrk_avg_ms": sy_avg,
                         "phi_build_GBs_algorithmic": phi_gbs, "phi_build_avg_ms": ph_avg,
-                        "stage_ms_per_eval": stage_pass["stage_ms_per_eval"],
+                        **({"stage_ms_per_eval": stage_pass["stage_ms_per_eval"]} if stage_pass else {}),
                         "dominant_stage_ms_per_eval_in_the_timed_region": {k: v[0] / args.steps for k, v in tim.items()}},
             # BASELINE.json's metric names it: "MFMA util on PHI'W PHI".  Flops-based from this run (n m (m+1) algorithmic flops per launch
             # over the kernel's HIP-event time in the timed region); counter-based from the committed rocprofv3 PMC passes of the same
@@ -541,7 +585,8 @@ def main():
             out["graph_pass"] = graph_pass
         if single_graph:
             out["single_graph_pass"] = single_graph
-        out["stage_pass"] = {k: v for k, v in stage_pass.items() if k != "stage_ms_per_eval"}
+        if stage_pass:
+            out["stage_pass"] = {k: v for k, v in stage_pass.items() if k != "stage_ms_per_eval"}
         if cfg.get("psi") and not f32_route:
             # config 5 in fp64: the per-pair sweeps of k_cpsi4.hip (four pairs per wave on v_mfma_f64_4x4x4).  Algorithmic work per
             # (sample, basis) pair at d = 20 in the M = Psi + Sigma form: PHI d^3/6 + d^2 = 1733 FMA, moments d^3/2 + 2 d^2 = 4800 FMA.
@@ -582,7 +627,7 @@ def main():
                                "traffic": (pmc_traffic(args.config) or {}).get("moments_bytes_per_launch") if world == 1 and not multi and not args.n else None,
                                "avg_ms": mo_avg}
             out["roofline_f32_pair_kernels"] = pair
-        if world == 1 and not args.no_cpu_baseline and va_mask is None and not multi:
+        if args.full and world == 1 and not args.no_cpu_baseline and va_mask is None and not multi:
             rows = max(2000, min(n, n // 8 if n >= 200000 else n))        # ~13 s of CPU work at c4 (16 BLAS threads), the whole problem at c2 / c3
             if cfg.get("psi"):
                 rows = 60                                                  # per-pair d x d loops in NumPy: ~1e5 pairs

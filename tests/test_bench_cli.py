@@ -50,7 +50,7 @@ def test_gpus_1_native_mgpu_1_and_plain_are_bitwise_identical():
     common = ["--config", "c2", "--rows", "6000", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"]
     plain = line_of(run_bench(*common))
     g1 = line_of(run_bench("--gpus", "1", *common))
-    nm1 = line_of(run_bench("--native-mgpu", "1", *common))
+    nm1 = line_of(run_bench("--native-mgpu", "1", "--full", *common))      # (per-stage times: the stage pass of --full)
     assert plain["n_gpus"] == g1["n_gpus"] == nm1["n_gpus"] == 1
     assert plain["check"] == g1["check"] == nm1["check"]
     # (c2 has m + 1 <= 256 columns: the T-GEMM, the row scalars and the moment sums are the one kernel k_small_tail)
@@ -66,7 +66,7 @@ def test_gpus_n_runs_the_in_library_rccl_driver_when_the_node_has_the_devices():
         pytest.skip("needs two GPUs")
     common = ["--config", "c2", "--rows", "6000", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"]
     one = line_of(run_bench(*common))
-    two = line_of(run_bench("--gpus", "2", *common))
+    two = line_of(run_bench("--gpus", "2", "--full", *common))
     assert two["n_gpus"] == 2 and len(two["per_rank"]) == 2 and two["config"]["rccl"]
     assert "allreduce1" in two["per_rank"][1]["stage_ms_per_eval"]
     f1, f2 = float.fromhex(one["check"]["f_last"]), float.fromhex(two["check"]["f_last"])
@@ -104,6 +104,45 @@ def test_injected_rank_failure_is_reported_and_does_not_hang():
             mg.eval(theta)
         assert ei.value.code == -4 and "dead" in str(ei.value)
         mg.close()
+
+
+@pytest.mark.gpu
+def test_plain_run_is_lean_and_dumps_what_the_last_timed_step_returned(tmp_path):
+    """A plain run times exactly --steps steps and nothing else (no stage / single-graph / gap pass, no CPU baseline); --dump-outputs
+    writes the last timed step's f, grad and statistics, identical from run to run; --full adds the passes and the parity gate."""
+    common = ["--config", "c2", "--rows", "6000", "--steps", "3", "--warmup", "2"]
+    a = line_of(run_bench(*common, "--dump-outputs", str(tmp_path / "a")))
+    b = line_of(run_bench(*common, "--dump-outputs", str(tmp_path / "b")))
+    assert a["steps"] == 3 and a["ms_per_step"] > 0 and a["finite"]
+    assert not {"stage_pass", "single_graph_pass", "gaps", "cpu_baseline", "parity"} & set(a)
+    for name in ("f", "grad", "trainRMSE", "trainLL"):
+        x, y = np.load(tmp_path / "a" / (name + ".npy")), np.load(tmp_path / "b" / (name + ".npy"))
+        assert x.dtype == np.float64 and np.array_equal(x, y), name
+    assert float(np.load(tmp_path / "a" / "f.npy")[0]).hex() == a["check"]["f_last"]
+    assert float(np.sum(np.load(tmp_path / "a" / "grad.npy"))).hex() == a["check"]["g_sum"]
+    full = line_of(run_bench(*common, "--full"))
+    assert full["check"] == a["check"]
+    assert {"stage_pass", "single_graph_pass", "gaps", "cpu_baseline", "parity"} <= set(full)
+    assert "rel_g_max" in full["parity"] and "tail_small" in full["kernels"]["stage_ms_per_eval"]
+
+
+def test_dump_outputs_stays_within_its_budget(tmp_path):
+    """bench.dump_outputs: float64 .npy files; a gradient beyond the 64 MB budget is written as a fixed, seeded sample."""
+    sys.path.insert(0, ROOT)
+    import bench
+    g = np.arange(10.0)
+    bench.dump_outputs(str(tmp_path / "s"), 1.5, g, {"trainRMSE": 0.25})
+    assert np.array_equal(np.load(tmp_path / "s" / "grad.npy"), g) and np.load(tmp_path / "s" / "f.npy").tolist() == [1.5]
+    assert np.load(tmp_path / "s" / "trainRMSE.npy").dtype == np.float64
+    big = np.random.default_rng(1).standard_normal(bench.DUMP_LIMIT_BYTES // 8)
+    for d in ("l1", "l2"):
+        bench.dump_outputs(str(tmp_path / d), 0.0, big, {})
+    files = sorted(os.listdir(tmp_path / "l1"))
+    assert files == ["f.npy", "grad_index.npy", "grad_sample.npy"]
+    assert sum(os.path.getsize(tmp_path / "l1" / f) for f in files) <= bench.DUMP_LIMIT_BYTES
+    idx = np.load(tmp_path / "l1" / "grad_index.npy")
+    assert np.array_equal(idx, np.load(tmp_path / "l2" / "grad_index.npy"))
+    assert np.array_equal(np.load(tmp_path / "l1" / "grad_sample.npy"), big[idx.astype(np.int64)])
 
 
 # ---- the first multi-GPU line cannot pass unverified (VERDICT r05 item 4) ---------------------------------------------------------

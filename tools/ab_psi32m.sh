@@ -11,7 +11,7 @@ for v in "$@"; do
   i=$((i+1))
   hipcc $FLAGS $v -c gpz_amd/csrc/k_psi32m.hip -o build/k_psi32m.o 2> $O/v$i.build.err || { echo "variant $i failed to build"; continue; }
   hipcc --offload-arch=gfx950 -shared -fPIC $objs build/k_psi32m.o -ldl -lpthread -o gpz_amd/lib/libgpz_hip.so
-  python bench.py --config c5 --rows 250000 --steps 3 --warmup 1 --no-cpu-baseline > $O/v$i.json 2> $O/v$i.err
+  python bench.py --full --config c5 --rows 250000 --steps 3 --warmup 1 --no-cpu-baseline > $O/v$i.json 2> $O/v$i.err
   echo "variant $i [$v]: $(python - <<PY
 import json
 d=json.load(open("$O/v$i.json"))

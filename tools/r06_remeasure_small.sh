@@ -7,13 +7,13 @@ cd $R
 python tools/pmc_summary.py gpurun_out/$tag/pmc_c2 gpurun_out/$tag/pmc_c2_summary.txt "--config c2 --steps 5 --warmup 3 --no-cpu-baseline --timed-events none
 # (c2, 1 x MI355X" --constants profiles/pmc_constants.json --config c2 > /dev/null 2>&1 || true
 cp profiles/pmc_constants.json gpurun_out/$tag/pmc_c2_summary.txt $O/ 2> /dev/null   # (the bench lines below read the constants of THIS pass)
-python bench.py --config c2 --timed-events none > $O/c2.json 2> $O/c2.err
-python bench.py --config c2 > $O/c2_events.json 2> $O/c2_events.err
-python bench.py --config c2 --validation 0.15 --timed-events none > $O/c2_validation15.json 2> $O/c2_validation15.err
-python bench.py --config c3 --timed-events none > $O/c3.json 2> $O/c3.err   # (c3 shares k_ltl_small and the launch merges, not the two big kernels)
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_c2 -- python bench.py --config c2 --timed-events none --no-cpu-baseline --steps 50 > /dev/null 2>&1
+python bench.py --full --config c2 --timed-events none > $O/c2.json 2> $O/c2.err
+python bench.py --full --config c2 > $O/c2_events.json 2> $O/c2_events.err
+python bench.py --full --config c2 --validation 0.15 --timed-events none > $O/c2_validation15.json 2> $O/c2_validation15.err
+python bench.py --full --config c3 --timed-events none > $O/c3.json 2> $O/c3.err   # (c3 shares k_ltl_small and the launch merges, not the two big kernels)
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_c2 -- python bench.py --full --config c2 --timed-events none --no-cpu-baseline --steps 50 > /dev/null 2>&1
 find $O/prof_c2 -name "*kernel_stats.csv" -exec cp {} $O/kernel_stats_c2.csv \; ; rm -rf $O/prof_c2
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_c3 -- python bench.py --config c3 --timed-events none --no-cpu-baseline --steps 50 > /dev/null 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_c3 -- python bench.py --full --config c3 --timed-events none --no-cpu-baseline --steps 50 > /dev/null 2>&1
 find $O/prof_c3 -name "*kernel_stats.csv" -exec cp {} $O/kernel_stats_c3.csv \; ; rm -rf $O/prof_c3
 hipcc --offload-arch=gfx950 -O3 -std=c++17 -Iinclude -Igpz_amd/csrc tools/small_trace.hip -o build/small_trace 2> /dev/null && (build/small_trace 100000 200 10 1 2; build/small_trace 100000 200 10 1 1) > $O/small_tail_timeline.txt 2>&1
 tools/r06_small_ab.sh c2 > $O/small_tail_ab.txt 2>&1

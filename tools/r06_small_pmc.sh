@@ -1,7 +1,7 @@
 #!/bin/bash
 # SQ counters of k_small_tail at a configuration (two rocprofv3 --pmc passes; run through gpurun)
 R=${GRAFT_REPO_ROOT:-$(pwd)}; O=$R/gpurun_out/small_pmc; mkdir -p $O; export TMPDIR=/tmp; cd /tmp
-ARGS="--config ${1:-c2} --steps 5 --warmup 3 --no-cpu-baseline --timed-events none"
+ARGS="--full --config ${1:-c2} --steps 5 --warmup 3 --no-cpu-baseline --timed-events none"
 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_VALU_MFMA_BUSY_CYCLES SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE --kernel-trace --output-format csv -d $O/sq -o p -- python $R/bench.py $ARGS > /dev/null 2>&1
 rocprofv3 --pmc GRBM_GUI_ACTIVE SQ_INSTS_VALU_MFMA_MOPS_F64 SQ_INSTS_MFMA SQ_INSTS_VALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_WAIT_INST_LDS --kernel-trace --output-format csv -d $O/sq2 -o p -- python $R/bench.py $ARGS > /dev/null 2>&1
 cd $R
