@@ -620,6 +620,186 @@ def predict(X, model, whichSet="best", Psi=None, selection=None, device=0, n_gpu
     return mu, sigma, nu, beta_i, gamma, PHI, w, iS
 
 
+GPZ_PREDICT_FORCE_TILES = 1   # gpz_predictor_create flags (include/gpz_hip.h)
+
+
+class Predictor:
+    """A trained model held on one GPU for prediction over any number of rows (gpz_predictor_*).
+
+        with gpz_amd.Predictor(model, whichSet="best", device=0) as p:
+            mu, sigma, nu, beta_i, gamma = p.predict(X, Psi=None, selection=None)
+            mu, sigma, nu, beta_i, gamma, PHI = p.predict(X, Psi=Psi, return_phi=True)
+
+    The same results as ``predict`` (normalisation, ``selection``, fixPsi, sigma = nu + beta_i + gamma, + muY), but the model's
+    once-per-model work is done once and rows stream through tile-sized device buffers, so device memory does not grow with the
+    number of rows and PHI only leaves the device when asked for.  Complete rows go through the handle (a fused kernel where
+    ceil16(m + 2k) <= 256 and d <= 20, else the PHI kernel + T-GEMM per tile; rows with Psi per tile through predictNoisy); rows with
+    missing values are grouped by NaN pattern and go to gpz_predict_missing as in ``predict``.  Shapes are checked before the GPU is
+    touched; the handle itself is created on first use.  ``route`` / ``info`` (tile rows, device bytes held, route 0 fused / 1 tiles,
+    runs) describe it."""
+
+    def __init__(self, model, whichSet="best", device=0, tile_rows=None, force_tiles=False):
+        if whichSet not in getattr(model, "sets", {}):
+            raise ValueError(f"whichSet {whichSet!r} is not one of the model's sets {sorted(getattr(model, 'sets', {}))}")
+        m, d, k = int(model.m), int(model.d), int(model.k)
+        method = str(model.method)
+        if method not in ("GL", "VL", "GD", "VD", "GC", "VC"):
+            raise ValueError(f"unknown method {method!r}")
+        st = model.sets[whichSet]
+        g_dim = {"GL": 1, "VL": m, "GD": d, "VD": m * d, "GC": d * d, "VC": d * d * m}[method]
+        p = m * d + g_dim + m * k + k + (2 * m * k if model.heteroscedastic else 0)
+        self._theta = np.ascontiguousarray(np.asarray(st["theta"], dtype=np.float64).ravel())
+        if self._theta.size != p:
+            raise ValueError(f"theta has {self._theta.size} entries, the model needs {p}")
+        self._w = _f64(st["w"], 2)
+        if self._w.shape != (m, k):
+            raise ValueError(f"w must be {m} x {k}")
+        iS = np.asarray(st["iSigma_w"], dtype=np.float64)
+        if iS.size != m * m * k:
+            raise ValueError(f"iSigma_w must be {m} x {m} x {k}")
+        self._iS = np.asfortranarray(iS.reshape(m, m, k))
+        pri = st.get("priors")
+        self._priors = np.full(m, 1.0 / m) if pri is None else np.ascontiguousarray(np.asarray(pri, dtype=np.float64).ravel())
+        if tile_rows is not None and (int(tile_rows) != tile_rows or tile_rows < 1):
+            raise ValueError("tile_rows must be a positive integer or None")
+        self.model, self.whichSet, self.device = model, whichSet, int(device)
+        self._m, self._d, self._k, self._method = m, d, k, method
+        self._tile_rows = 0 if tile_rows is None else int(tile_rows)
+        self._flags = GPZ_PREDICT_FORCE_TILES if force_tiles else 0
+        self._h = None
+        self._closed = False
+        self._lib = None
+
+    def _handle(self):
+        if self._closed:
+            raise RuntimeError("Predictor is closed")
+        if self._h is None:
+            self._lib = _lib.load()
+            ds = _desc(self.model, self.device)
+            h = C.c_void_p()
+            _lib.check(self._lib.gpz_predictor_create(C.byref(ds), _lib.dptr(self._theta), _lib.dptr(self._w), _lib.dptr(self._iS),
+                                                      self._tile_rows, self._flags, C.byref(h)))
+            self._h = h
+        return self._h
+
+    def close(self):
+        if self._h is not None:
+            self._lib.gpz_predictor_destroy(self._h)
+            self._h = None
+        self._closed = True
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def route(self):
+        """Which kernels the handle runs (gpz_predictor_route), as one line of text."""
+        h = self._handle()
+        buf = C.create_string_buffer(256)
+        self._lib.gpz_predictor_route(h, buf, 256)
+        return buf.value.decode()
+
+    @property
+    def info(self):
+        """(tile rows, device bytes held, route: 0 fused / 1 tiles, runs) of gpz_predictor_info."""
+        h = self._handle()
+        out = (C.c_int64 * 4)()
+        _lib.check(self._lib.gpz_predictor_info(h, out))
+        return tuple(int(v) for v in out)
+
+    def _check_inputs(self, X, Psi, selection):
+        d = self._d
+        X = np.asarray(X, dtype=np.float64)
+        if X.ndim == 1 and d == 1:
+            X = X[:, None]
+        if X.ndim != 2 or X.shape[1] != d:
+            raise ValueError(f"X must be n x {d}, got shape {X.shape}")
+        n = X.shape[0]
+        psi = None
+        if Psi is not None:
+            psi = np.asarray(Psi, dtype=np.float64)
+            ok = ((psi.ndim == 1 and psi.shape[0] == n) or (psi.ndim == 2 and psi.shape[0] == n and psi.shape[1] in (1, d))
+                  or (psi.ndim == 3 and psi.shape == (d, d, n)))
+            if not ok:
+                raise ValueError(f"Psi must be n x d, n x 1 or d x d x n (n = {n}, d = {d}), got shape {psi.shape}")
+        if selection is not None:
+            sel = np.asarray(selection)
+            if sel.shape != (n,):
+                raise ValueError(f"selection must be a mask of length {n}")
+            sel = sel.astype(bool)
+            X = X[sel]                                                   # predict.m:25
+            if psi is not None:                                          # predict.m:27-33
+                psi = psi[:, :, sel] if psi.ndim == 3 else psi[sel]
+        return X, psi
+
+    def _run(self, Xg, Pg, cube, want_phi):
+        ng, k, m = Xg.shape[0], self._k, self._m
+        o = [np.empty((ng, k), order="F") for _ in range(4)]
+        ph = np.empty((ng, m), order="F") if want_phi else None
+        _lib.check(self._lib.gpz_predictor_run(self._h, _lib.dptr(Xg), ng, _lib.dptr(Pg), 0 if Pg is None else (2 if cube else 1),
+                                               *(_lib.dptr(a) for a in o), _lib.dptr(ph)))
+        return o[0], o[1], o[2], o[3], ph
+
+    def predict(self, X, Psi=None, selection=None, return_phi=False):
+        """mu, sigma, nu, beta_i, gamma [, PHI] of ``predict`` (predict.m:1) for the rows of X (n x d, not normalised)."""
+        if self._closed:
+            raise RuntimeError("Predictor is closed")
+        model, k, m = self.model, self._k, self._m
+        X, psi = self._check_inputs(X, Psi, selection)
+        Xn = np.empty(X.shape, order="F")                                # predict.m:35-36, one pass into the column-major layout
+        np.subtract(X, model.muX, out=Xn)
+        np.divide(Xn, model.sdX, out=Xn)
+        ns = Xn.shape[0]
+        psin = None
+        if psi is not None:
+            from .host import fixPsi
+            psin = np.asfortranarray(fixPsi(psi, ns, model.sdX, model.method))   # predict.m:43
+        cube = psin is not None and psin.ndim == 3
+        if ns == 0:
+            z = np.zeros((0, k))
+            out = (z + model.muY, z.copy(), z.copy(), z.copy(), z.copy())
+            return out + (np.zeros((0, m)),) if return_phi else out
+        self._handle()
+        if np.isnan(Xn.sum()) and np.isnan(Xn).any():                    # predict.m:45-57: groups of identical NaN patterns
+            gid, n_groups = nan_groups(Xn, self.device)
+            order = np.argsort(gid, kind="stable")
+            bounds = np.concatenate(([0], np.cumsum(np.bincount(gid, minlength=n_groups))))
+            groups = [order[bounds[g]:bounds[g + 1]] for g in range(n_groups)]
+            mu = np.zeros((ns, k)); nu = np.zeros((ns, k)); beta_i = np.zeros((ns, k)); gamma = np.zeros((ns, k))
+            PHI = np.zeros((ns, m)) if return_phi else None
+            ds = _desc(model, self.device)
+            for idx in groups:
+                Xg = _f64(Xn[idx], 2)
+                Pg = None if psin is None else np.asfortranarray(psin[:, :, idx] if cube else psin[idx])
+                if not np.isnan(Xg[0]).any():
+                    r = self._run(Xg, Pg, cube, return_phi)
+                else:
+                    ng = Xg.shape[0]
+                    r = [np.empty((ng, k), order="F") for _ in range(4)] + [np.empty((ng, m), order="F")]
+                    _lib.check(self._lib.gpz_predict_missing(C.byref(ds), _lib.dptr(self._theta), _lib.dptr(self._w),
+                                                             _lib.dptr(self._iS), _lib.dptr(self._priors), _lib.dptr(Xg), ng,
+                                                             _lib.dptr(Pg), 0 if Pg is None else (2 if cube else 1),
+                                                             *(_lib.dptr(a) for a in r)))
+                mu[idx] = r[0]; nu[idx] = r[1]; beta_i[idx] = r[2]; gamma[idx] = r[3]
+                if return_phi:
+                    PHI[idx] = r[4]
+        else:                                                            # complete rows: no gather copy
+            mu, nu, beta_i, gamma, PHI = self._run(Xn, psin, cube, return_phi)
+        sigma = nu + beta_i + gamma                                      # predict.m:72
+        mu = mu + model.muY                                              # predict.m:73
+        out = (mu, sigma, nu, beta_i, gamma)
+        return out + (PHI,) if return_phi else out
+
+
 def getPrior(X, Psi, theta, model, selection=None, device=0, return_iterations=False):
     """prior = getPrior(X,Sx,theta,model,set)   (getPrior.m:1); X / Psi already normalised as train.m passes them."""
     lib = _lib.load()

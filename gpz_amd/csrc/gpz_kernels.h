@@ -118,6 +118,21 @@ void launch_small_finish(hipStream_t st, const double *slab, const double *parti
                          const double *P, const double *xmu, int nm, int mp, double *mom, double *cols,
                          double *scal, int accumulate, int cols_only = 0);   // cols_only: records without raw sums (nf = 0)   // the workgroups' records -> moments, column sums, scalar sums (one launch)
 int gpz_cu_count();         // compute units of the current device (k_gemm.hip)
+// ---- predictFull for few basis functions as one kernel (k_predict_small.hip; the streaming predictor, gpz_predictor.hip) -----------
+// fits: an instantiated d (phi_is_wide false) and ceil16(m + 2k) <= 256.  Xc: de x ldx column layout (dimensions >= d zero), n rows;
+// B: k blocks (stride bstride) of ceil16(m) x ldb row-major [inv(Sigma_o) | w | v | 0], ldb = ceil16(m + 2k); out: [3k][ldo] = mu, nu, beta;
+// phi (optional): [m][ldphi].  Returns -1 when the launch failed.
+bool predict_small_fits(int de, int m, int k);
+size_t predict_small_lds(int de);
+int launch_predict_small(hipStream_t st, int kind, int de, const double *Xc, long ldx, int n, int m, int k, const double *P,
+                         const double *G, const double *B, int ldb, long bstride, const double *bvec, double *out, long ldo,
+                         double *phi, long ldphi);
+// B (rows x ld row-major) <- [iS (m x m column-major) | nw columns of W from column wcol | nv columns of V (nullptr: 0) from vcol | 0]
+void launch_pred_fill_b(hipStream_t st, const double *iS, const double *W, int nw, int wcol, const double *V, int nv, int vcol, int m,
+                        int rows, int ld, double *B);
+// tile route: out [3k][ldo] = [phiw | sum of the nslots nu partials (stride ldn, output stride ostride) | exp(lnbeta)]
+void launch_pred_tile_finish(hipStream_t st, const double *phiw, const double *nupart, int nslots, long ldn, long ostride,
+                             const double *lnbeta, long ldt, int n, int k, double *out, long ldo);
 // nupart (optional): [gpz_gemm_wave_cols()*ceil(mp/128)][n_pad] per-wave-column partial sums of PHI.*T over columns < m; phiw: column mcol of T
 void launch_tgemm(hipStream_t st, const double *Phi, int ld, const double *B, int ldb, double *T, int n_pad, int mp,
                   double *nupart, double *phiw, int m, int mcol, bool f32_operands = false, int kdim = 0, int ldt = 0,

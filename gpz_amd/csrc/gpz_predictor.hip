@@ -1,0 +1,371 @@
+// Host side of libgpz_hip.so: the persistent streaming predictor (gpz_predictor_*, include/gpz_hip.h).
+//
+// gpz_predict_full is a one-shot: per call it builds a context, uploads and scans all rows, transposes inv(Sigma_o) on the host, and holds
+// PHI and T for every row on the device.  A predictor does the once-per-model work once (theta unpacked, the QR factors of the covariance
+// kinds, B_o = [inv(Sigma_o) | w | v] laid out for the product) and then streams any number of rows through tile-sized buffers:
+//   * route 0, fused: ceil16(m + 2k) <= 256 and an instantiated d - k_predict_small writes mu, nu and beta only (PHI and T never exist);
+//   * route 1, tiles: the existing k_phi_* + k_tgemm (nu and PHI w from its epilogue) on one tile of rows at a time, k_pred_tile_finish.
+// Rows with input noise go through gpz_predict_noisy one tile at a time.  Device memory does not depend on the number of rows: the
+// buffers are sized by the tile at creation (PHI's own tile buffers are added on the first call that asks for PHI).
+//
+// Pipeline of gpz_predictor_run (full branch): three streams - copies in, compute, copies out - and two slots of pinned staging and device
+// buffers.  Tile t's upload, tile t-1's kernels and tile t-2's download are in flight together while the host thread stages tile t+1's
+// rows and scatters tile t-2's results into the caller's column-major arrays.
+#include "gpz_ctx.h"
+
+#define GPZ_PREDICTOR_TILE_FUSED (1L << 17)   // default rows per tile, fused route: 4096 blocks of 32 rows = 8 rounds of 512 workgroups
+
+struct gpz_predictor {
+    gpz_desc desc;
+    gpz_options opt = gpz_options_load();
+    int mid = 0, kind = 0, d = 0, de = 0, m = 0, k = 1, hetero = 0, mp = 0;
+    long p = 0;
+    int device = 0;
+    int route = 0;                 // 0 fused, 1 tiles
+    int64_t tile_rows = 0, tile_pad = 0, runs = 0;
+    int nk = 0, ldb = 0;           // fused: B_o is nk x ldb
+    int nslots = 0;                // tiles: nu partial slots per output
+    Arena ar;
+    hipStream_t s_in = nullptr, s_cmp = nullptr, s_out = nullptr;
+    hipEvent_t ev_in[2] = {}, ev_cmp[2] = {}, ev_out[2] = {};
+    double *theta_d = nullptr, *iS_d = nullptr, *w_d = nullptr, *prep_ws = nullptr;
+    GpzParams pr{};
+    double *B = nullptr;           // fused: k x [nk][ldb];  tiles: k x [mp][mp]
+    double *Xc[2] = {}, *out[2] = {}, *phi_d[2] = {};
+    double *Phi = nullptr, *T = nullptr, *nupart = nullptr, *phiw = nullptr, *lnbeta = nullptr;   // tiles
+    double *hin[2] = {}, *hout[2] = {}, *hphi[2] = {};   // pinned
+    std::vector<double> theta_h, w_h, iS_h;              // the model, for the input-noise branch (gpz_predict_noisy per tile)
+};
+
+namespace gpzi {
+static void predictor_free(gpz_predictor *p) {
+    if (!p) return;
+    if (p->s_cmp) (void)hipSetDevice(p->device);
+    for (hipStream_t s : {p->s_in, p->s_cmp, p->s_out})
+        if (s) (void)hipStreamSynchronize(s);
+    for (int s = 0; s < 2; ++s) {
+        if (p->hin[s]) (void)hipHostFree(p->hin[s]);
+        if (p->hout[s]) (void)hipHostFree(p->hout[s]);
+        if (p->hphi[s]) (void)hipHostFree(p->hphi[s]);
+        if (p->ev_in[s]) (void)hipEventDestroy(p->ev_in[s]);
+        if (p->ev_cmp[s]) (void)hipEventDestroy(p->ev_cmp[s]);
+        if (p->ev_out[s]) (void)hipEventDestroy(p->ev_out[s]);
+    }
+    p->ar.release();
+    for (hipStream_t s : {p->s_in, p->s_cmp, p->s_out})
+        if (s) (void)hipStreamDestroy(s);
+    delete p;
+}
+
+static int predictor_setup(gpz_predictor *p, const double *theta, const double *w, const double *iSigma_w, int64_t tile_rows,
+                           int32_t flags) {
+    const size_t m = p->m, de = p->de, k = p->k;
+    HIPCHK(hipSetDevice(p->device));
+    HIPCHK(hipStreamCreateWithFlags(&p->s_in, hipStreamNonBlocking));
+    HIPCHK(hipStreamCreateWithFlags(&p->s_cmp, hipStreamNonBlocking));
+    HIPCHK(hipStreamCreateWithFlags(&p->s_out, hipStreamNonBlocking));
+    for (int s = 0; s < 2; ++s) {
+        HIPCHK(hipEventCreateWithFlags(&p->ev_in[s], hipEventDisableTiming));
+        HIPCHK(hipEventCreateWithFlags(&p->ev_cmp[s], hipEventDisableTiming));
+        HIPCHK(hipEventCreateWithFlags(&p->ev_out[s], hipEventDisableTiming));
+        HIPCHK(hipEventRecord(p->ev_cmp[s], p->s_cmp));   // recorded once, so that the first waits of gpz_predictor_run have an event
+        HIPCHK(hipEventRecord(p->ev_out[s], p->s_out));
+    }
+    p->route = (!(flags & GPZ_PREDICT_FORCE_TILES) && predict_small_fits(p->de, p->m, p->k)) ? 0 : 1;
+    if (tile_rows <= 0) {
+        if (p->route == 0) tile_rows = GPZ_PREDICTOR_TILE_FUSED;
+        else {   // PHI + T of a tile within about 1 GiB
+            tile_rows = (1L << 30) / (16L * p->mp);
+            tile_rows = std::max<int64_t>(1024, std::min<int64_t>(GPZ_PREDICTOR_TILE_FUSED, tile_rows / 1024 * 1024));
+        }
+    }
+    if (tile_rows > (1L << 24)) return gpz_fail(GPZ_ERR_ARG, "gpz_predictor_create: tile_rows %lld above 2^24", (long long)tile_rows);
+    p->tile_rows = tile_rows;
+    p->tile_pad = rup(tile_rows, 1024);
+    const size_t tp = (size_t)p->tile_pad;
+    // ---- parameters: k_unpack (+ the QR factors of the covariance kinds), as run_phi_only does
+    auto &ar = p->ar;
+    int rc = 0;
+    if ((rc = ar.alloc(&p->theta_d, (size_t)p->p))) return rc;
+    if ((rc = ar.alloc(&p->pr.P, m * de))) return rc;
+    if ((rc = ar.alloc(&p->pr.G, p->kind == GPZ_KIND_COV ? m * de * de : m * de))) return rc;
+    if ((rc = ar.alloc(&p->pr.G2, m * de))) return rc;
+    if ((rc = ar.alloc(&p->pr.Rc, m * (de * (de + 1) / 2 + de)))) return rc;
+    if (const size_t wl = p->kind == GPZ_KIND_COV ? prep_cov_ws_len(p->m, p->de) : 0)
+        if ((rc = ar.alloc(&p->prep_ws, wl))) return rc;
+    if ((rc = ar.alloc(&p->pr.lnAlpha, m * k))) return rc;
+    if ((rc = ar.alloc(&p->pr.alpha, m * k))) return rc;
+    if ((rc = ar.alloc(&p->pr.b, k))) return rc;
+    if ((rc = ar.alloc(&p->pr.v, m * k))) return rc;
+    if ((rc = ar.alloc(&p->pr.lnTau, m * k))) return rc;
+    if ((rc = ar.alloc(&p->pr.tau, m * k))) return rc;
+    if ((rc = ar.alloc(&p->iS_d, m * m * k))) return rc;
+    if ((rc = ar.alloc(&p->w_d, m * k))) return rc;
+    hipStream_t st = p->s_cmp;
+    HIPCHK(hipMemcpyAsync(p->theta_d, theta, (size_t)p->p * sizeof(double), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(p->iS_d, iSigma_w, m * m * k * sizeof(double), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(p->w_d, w, m * k * sizeof(double), hipMemcpyHostToDevice, st));
+    launch_unpack(st, p->theta_d, p->mid, p->m, p->d, p->de, p->k, p->hetero, p->pr);
+    if (p->kind == GPZ_KIND_COV) launch_prep_cov(st, p->pr.G, p->pr.P, p->m, p->de, p->pr.Rc, p->prep_ws);
+    // ---- B_o and the tile buffers
+    for (int s = 0; s < 2; ++s) {
+        if ((rc = ar.alloc(&p->Xc[s], de * tp))) return rc;
+        if ((rc = ar.alloc(&p->out[s], 3 * k * tp))) return rc;
+        HIPCHK(hipMemsetAsync(p->Xc[s], 0, de * tp * sizeof(double), st));   // dimensions d .. de - 1 stay zero
+    }
+    const double *vsrc = p->hetero ? p->pr.v : nullptr;
+    if (p->route == 0) {
+        p->nk = rup(p->m, 16);
+        p->ldb = rup(p->m + 2 * p->k, 16);
+        const size_t bs = (size_t)p->nk * p->ldb;
+        if ((rc = ar.alloc(&p->B, bs * k))) return rc;
+        for (int o = 0; o < p->k; ++o)   // [inv(Sigma_o) | w | v]: mu_o = T(:, m + o), ln beta_o - b_o = T(:, m + k + o)
+            launch_pred_fill_b(st, p->iS_d + (size_t)o * m * m, p->w_d, p->k, p->m, vsrc, p->k, p->m + p->k, p->m, p->nk, p->ldb,
+                               p->B + (size_t)o * bs);
+    } else {
+        const size_t mp = (size_t)p->mp, bs = mp * mp;
+        p->nslots = gpz_gemm_wave_cols() * (int)((mp + 127) / 128);
+        if ((rc = ar.alloc(&p->B, bs * k))) return rc;
+        for (int o = 0; o < p->k; ++o)   // gpz_predict_full's Bext: [inv(Sigma_o) | 0 .. w_o at column m + o .. 0]
+            launch_pred_fill_b(st, p->iS_d + (size_t)o * m * m, p->w_d + (size_t)o * m, 1, p->m + o, nullptr, 0, 0, p->m, p->mp, p->mp,
+                               p->B + (size_t)o * bs);
+        if ((rc = ar.alloc(&p->Phi, tp * mp))) return rc;
+        if ((rc = ar.alloc(&p->T, tp * mp))) return rc;
+        if ((rc = ar.alloc(&p->nupart, (size_t)p->nslots * k * tp))) return rc;
+        if ((rc = ar.alloc(&p->phiw, k * tp))) return rc;
+        if ((rc = ar.alloc(&p->lnbeta, k * tp))) return rc;
+    }
+    for (int s = 0; s < 2; ++s) {
+        HIPCHK(hipHostMalloc((void **)&p->hin[s], (size_t)p->d * tp * sizeof(double), hipHostMallocDefault));
+        HIPCHK(hipHostMalloc((void **)&p->hout[s], 3 * k * tp * sizeof(double), hipHostMallocDefault));
+        memset(p->hin[s], 0, (size_t)p->d * tp * sizeof(double));
+    }
+    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(hipGetLastError());
+    p->theta_h.assign(theta, theta + p->p);
+    p->w_h.assign(w, w + m * k);
+    p->iS_h.assign(iSigma_w, iSigma_w + m * m * k);
+    return 0;
+}
+
+// the kernels of one tile of nt rows: Xc[s] -> out[s] ([3k][nt]) and, when asked, phi_d[s] ([m][nt])
+static int predictor_tile(gpz_predictor *p, int s, int nt, bool want_phi) {
+    hipStream_t st = p->s_cmp;
+    const int k = p->k;
+    if (p->route == 0) {
+        if (launch_predict_small(st, p->kind, p->de, p->Xc[s], p->tile_pad, nt, p->m, k, p->pr.P,
+                                 p->kind == GPZ_KIND_COV ? p->pr.Rc : p->pr.G2, p->B, p->ldb, (long)p->nk * p->ldb, p->pr.b, p->out[s],
+                                 nt, want_phi ? p->phi_d[s] : nullptr, nt))
+            return gpz_fail(GPZ_ERR_HIP, "gpz_predictor_run: k_predict_small launch failed");
+        return 0;
+    }
+    const long np = rup(nt, 1024);
+    PhiArgs a{};
+    a.Xc = p->Xc[s]; a.ldx = p->tile_pad; a.n = nt; a.n_pad = (int)np;
+    a.m = p->m; a.mp = p->mp; a.d = p->de; a.k = k; a.kind = p->kind;
+    a.P = p->pr.P; a.G = p->kind == GPZ_KIND_COV ? p->pr.Rc : p->pr.G2;
+    a.v = p->hetero ? p->pr.v : nullptr; a.b = p->pr.b;
+    a.Phi = p->Phi; a.lnbeta = p->lnbeta;
+    if (launch_phi(st, a)) return gpz_fail(GPZ_ERR_UNSUPPORTED, "gpz_predictor_run: PHI kernel not instantiated for d=%d", p->de);
+    const size_t mp = (size_t)p->mp;
+    for (int o = 0; o < k; ++o)
+        launch_tgemm(st, p->Phi, p->mp, p->B + (size_t)o * mp * mp, p->mp, p->T, (int)np, p->mp,
+                     p->nupart + (size_t)o * p->nslots * p->tile_pad, p->phiw + (size_t)o * p->tile_pad, p->m, p->m + o);
+    launch_pred_tile_finish(st, p->phiw, p->nupart, p->nslots, np, (long)p->nslots * p->tile_pad, p->lnbeta, p->tile_pad, nt, k,
+                            p->out[s], nt);
+    if (want_phi) launch_transpose_out(st, p->Phi, p->mp, nt, p->m, p->phi_d[s]);
+    if (hipGetLastError() != hipSuccess) return gpz_fail(GPZ_ERR_HIP, "gpz_predictor_run: kernel launch failed");
+    return 0;
+}
+
+static int predictor_want_phi(gpz_predictor *p) {
+    if (p->phi_d[0]) return 0;
+    const size_t n = (size_t)p->m * p->tile_pad;
+    for (int s = 0; s < 2; ++s) {
+        if (int rc = p->ar.alloc(&p->phi_d[s], n)) return rc;
+        HIPCHK(hipHostMalloc((void **)&p->hphi[s], n * sizeof(double), hipHostMallocDefault));
+    }
+    return 0;
+}
+
+static int predictor_run_full(gpz_predictor *p, const double *Xs, int64_t ns, double *mu, double *nu, double *beta_i, double *PHI) {
+    const int k = p->k, d = p->d, m = p->m;
+    const int64_t T = p->tile_rows, ntiles = (ns + T - 1) / T;
+    const size_t tp = (size_t)p->tile_pad;
+    int rc = 0;
+    int64_t nt_of[2] = {0, 0}, r0_of[2] = {0, 0};
+    auto scatter = [&](int s) {
+        const int64_t nt = nt_of[s], r0 = r0_of[s];
+        double *dst[3] = {mu, nu, beta_i};
+        for (int q = 0; q < 3; ++q)
+            for (int o = 0; o < k; ++o) memcpy(dst[q] + (size_t)o * ns + r0, p->hout[s] + (size_t)(q * k + o) * nt, (size_t)nt * sizeof(double));
+        if (PHI)
+            for (int j = 0; j < m; ++j) memcpy(PHI + (size_t)j * ns + r0, p->hphi[s] + (size_t)j * nt, (size_t)nt * sizeof(double));
+    };
+    for (int64_t t = 0; t < ntiles + 2 && !rc; ++t) {
+        const int s = (int)(t & 1);
+        if (t >= 2) {   // tile t - 2 is home: into the caller's arrays (its slot is then free for tile t)
+            if (hipEventSynchronize(p->ev_out[s]) != hipSuccess) { rc = gpz_fail(GPZ_ERR_HIP, "gpz_predictor_run: tile failed"); break; }
+            scatter(s);
+        }
+        if (t >= ntiles) continue;
+        const int64_t r0 = t * T, nt = std::min<int64_t>(T, ns - r0);
+        nt_of[s] = nt; r0_of[s] = r0;
+        // stage the tile's rows ([d][tile_pad], the layout of Xc) and look for missing values on the way
+        bool bad = false;
+        for (int c = 0; c < d; ++c) {
+            const double *src = Xs + (size_t)c * ns + r0;
+            double *dst = p->hin[s] + (size_t)c * tp;
+            int nan = 0;
+            for (int64_t i = 0; i < nt; ++i) { const double v = src[i]; dst[i] = v; nan |= v != v; }
+            bad |= nan != 0;
+        }
+        if (bad) {
+            rc = gpz_fail(GPZ_ERR_UNSUPPORTED, "gpz_predictor_run: the rows have missing values (NaN): group them by pattern and call gpz_predict_missing (predict.m:45-69)");
+            break;
+        }
+        // copy in (after tile t - 2's kernels are done with Xc[s]); kernels (after the copy, and after tile t - 2's download of out[s]);
+        // copy out
+        if (hipStreamWaitEvent(p->s_in, p->ev_cmp[s], 0) != hipSuccess ||
+            hipMemcpy2DAsync(p->Xc[s], tp * sizeof(double), p->hin[s], tp * sizeof(double), (size_t)nt * sizeof(double), d,
+                             hipMemcpyHostToDevice, p->s_in) != hipSuccess ||
+            hipEventRecord(p->ev_in[s], p->s_in) != hipSuccess || hipStreamWaitEvent(p->s_cmp, p->ev_in[s], 0) != hipSuccess ||
+            hipStreamWaitEvent(p->s_cmp, p->ev_out[s], 0) != hipSuccess) {
+            rc = gpz_fail(GPZ_ERR_HIP, "gpz_predictor_run: copy failed");
+            break;
+        }
+        if ((rc = predictor_tile(p, s, (int)nt, PHI != nullptr))) break;
+        if (hipEventRecord(p->ev_cmp[s], p->s_cmp) != hipSuccess || hipStreamWaitEvent(p->s_out, p->ev_cmp[s], 0) != hipSuccess ||
+            hipMemcpyAsync(p->hout[s], p->out[s], 3 * (size_t)k * nt * sizeof(double), hipMemcpyDeviceToHost, p->s_out) != hipSuccess ||
+            (PHI && hipMemcpyAsync(p->hphi[s], p->phi_d[s], (size_t)m * nt * sizeof(double), hipMemcpyDeviceToHost, p->s_out) != hipSuccess) ||
+            hipEventRecord(p->ev_out[s], p->s_out) != hipSuccess) {
+            rc = gpz_fail(GPZ_ERR_HIP, "gpz_predictor_run: copy failed");
+            break;
+        }
+    }
+    for (hipStream_t st : {p->s_in, p->s_cmp, p->s_out})
+        if (hipStreamSynchronize(st) != hipSuccess && !rc) rc = gpz_fail(GPZ_ERR_HIP, "gpz_predictor_run: sync failed");
+    return rc;
+}
+
+// input noise: gpz_predict_noisy on one tile of rows at a time (its buffers are sized by the tile)
+static int predictor_run_noisy(gpz_predictor *p, const double *Xs, int64_t ns, const double *Psi, int32_t psi_kind, double *mu,
+                               double *nu, double *beta_i, double *gamma, double *PHI) {
+    const int k = p->k, d = p->d, m = p->m;
+    const int64_t T = p->tile_rows;
+    const size_t pr = psi_kind == 2 ? (size_t)d * d : (size_t)d;   // Psi doubles per row
+    std::vector<double> xt, pt, o4, ph;
+    for (int64_t r0 = 0; r0 < ns; r0 += T) {
+        const int64_t nt = std::min<int64_t>(T, ns - r0);
+        xt.resize((size_t)nt * d);
+        pt.resize((size_t)nt * pr);
+        o4.resize((size_t)nt * k * 4);
+        for (int c = 0; c < d; ++c) memcpy(xt.data() + (size_t)c * nt, Xs + (size_t)c * ns + r0, (size_t)nt * sizeof(double));
+        if (psi_kind == 2)
+            memcpy(pt.data(), Psi + (size_t)r0 * pr, (size_t)nt * pr * sizeof(double));
+        else
+            for (int c = 0; c < d; ++c) memcpy(pt.data() + (size_t)c * nt, Psi + (size_t)c * ns + r0, (size_t)nt * sizeof(double));
+        if (PHI) ph.resize((size_t)nt * m);
+        double *o = o4.data();
+        const size_t ok = (size_t)nt * k;
+        if (int rc = gpz_predict_noisy(&p->desc, p->theta_h.data(), p->w_h.data(), p->iS_h.data(), xt.data(), nt, pt.data(), psi_kind, o,
+                                       o + ok, o + 2 * ok, o + 3 * ok, PHI ? ph.data() : nullptr))
+            return rc;
+        double *dst[4] = {mu, nu, beta_i, gamma};
+        for (int q = 0; q < 4; ++q)
+            for (int oo = 0; oo < k; ++oo)
+                memcpy(dst[q] + (size_t)oo * ns + r0, o + q * ok + (size_t)oo * nt, (size_t)nt * sizeof(double));
+        if (PHI)
+            for (int j = 0; j < m; ++j) memcpy(PHI + (size_t)j * ns + r0, ph.data() + (size_t)j * nt, (size_t)nt * sizeof(double));
+    }
+    return 0;
+}
+}   // namespace gpzi
+
+extern "C" int gpz_predictor_create(const gpz_desc *desc, const double *theta, const double *w, const double *iSigma_w,
+                                    int64_t tile_rows, int32_t flags, gpz_predictor **out) {
+    if (!out) return gpz_fail(GPZ_ERR_ARG, "gpz_predictor_create: null argument");
+    *out = nullptr;
+    if (!desc || !theta || !w || !iSigma_w) return gpz_fail(GPZ_ERR_ARG, "gpz_predictor_create: null argument");
+    if (desc->dtype != GPZ_F64) return gpz_fail(GPZ_ERR_ARG, "gpz_predictor_create: fp64 only");
+    if (flags & ~GPZ_PREDICT_FORCE_TILES) return gpz_fail(GPZ_ERR_ARG, "gpz_predictor_create: unknown flags %d", (int)flags);
+    gpz_predictor *p = new gpz_predictor();
+    p->desc = *desc;
+    p->desc.world = 1;
+    p->desc.rank = 0;
+    p->mid = method_id_of(desc->method);
+    if (p->mid < 0) { delete p; return gpz_fail(GPZ_ERR_ARG, "unknown method '%.2s'", desc->method); }
+    if (desc->d < 1 || desc->m < 1 || desc->k < 1) { delete p; return gpz_fail(GPZ_ERR_ARG, "d, m, k must be >= 1"); }
+    p->kind = p->mid >= 4 ? GPZ_KIND_COV : GPZ_KIND_DIAG;
+    p->d = desc->d;
+    p->de = pad_dim(desc->d);
+    p->m = desc->m;
+    p->k = desc->k;
+    p->hetero = desc->heteroscedastic ? 1 : 0;
+    p->p = (long)p->m * p->d + g_dim_of(p->mid, p->m, p->d) + (long)p->m * p->k + p->k + (p->hetero ? 2L * p->m * p->k : 0);
+    p->mp = rup(p->m + p->k, 16);
+    p->device = desc->device;
+    int prev = 0;
+    (void)hipGetDevice(&prev);
+    gpz_opts_scope opts_scope(&p->opt);
+    int rc = predictor_setup(p, theta, w, iSigma_w, tile_rows, flags);
+    if (rc) predictor_free(p);
+    else *out = p;
+    (void)hipSetDevice(prev);
+    return rc;
+}
+
+extern "C" void gpz_predictor_destroy(gpz_predictor *p) {
+    if (!p) return;
+    int prev = 0;
+    (void)hipGetDevice(&prev);
+    predictor_free(p);
+    (void)hipSetDevice(prev);
+}
+
+extern "C" int gpz_predictor_run(gpz_predictor *p, const double *Xs, int64_t ns, const double *Psi, int32_t psi_kind, double *mu,
+                                 double *nu, double *beta_i, double *gamma, double *PHI) {
+    if (!p) return gpz_fail(GPZ_ERR_ARG, "gpz_predictor_run: null handle");
+    if (ns < 0) return gpz_fail(GPZ_ERR_ARG, "gpz_predictor_run: ns < 0");
+    if (ns == 0) return 0;
+    if (!Xs || !mu || !nu || !beta_i || !gamma) return gpz_fail(GPZ_ERR_ARG, "gpz_predictor_run: null argument");
+    if (psi_kind < 0 || psi_kind > 3 || (psi_kind != 0) != (Psi != nullptr))
+        return gpz_fail(GPZ_ERR_ARG, "gpz_predictor_run: psi_kind %d does not match Psi", (int)psi_kind);
+    if ((psi_kind == 2 || psi_kind == 3) && p->kind != GPZ_KIND_COV)
+        return gpz_fail(GPZ_ERR_ARG, "gpz_predictor_run: psi_kind %d is for the covariance kinds", (int)psi_kind);
+    int prev = 0;
+    (void)hipGetDevice(&prev);
+    gpz_opts_scope opts_scope(&p->opt);
+    int rc = 0;
+    if (hipSetDevice(p->device) != hipSuccess) rc = gpz_fail(GPZ_ERR_HIP, "gpz_predictor_run: hipSetDevice failed");
+    if (!rc && Psi) {
+        rc = predictor_run_noisy(p, Xs, ns, Psi, psi_kind, mu, nu, beta_i, gamma, PHI);
+    } else if (!rc) {
+        memset(gamma, 0, (size_t)ns * p->k * sizeof(double));   // predictDiag.m:74
+        if (PHI) rc = predictor_want_phi(p);
+        if (!rc) rc = predictor_run_full(p, Xs, ns, mu, nu, beta_i, PHI);
+    }
+    if (!rc) ++p->runs;
+    (void)hipSetDevice(prev);
+    return rc;
+}
+
+extern "C" int gpz_predictor_route(const gpz_predictor *p, char *buf, int cap) {
+    if (!p || !buf || cap < 1) return gpz_fail(GPZ_ERR_ARG, "gpz_predictor_route: null argument");
+    char tmp[160];
+    if (p->route == 0)
+        snprintf(tmp, sizeof tmp, "fused: k_predict_small, %lld-row tiles", (long long)p->tile_rows);
+    else
+        snprintf(tmp, sizeof tmp, "tiles: k_phi + k_tgemm, %lld-row tiles", (long long)p->tile_rows);
+    snprintf(buf, (size_t)cap, "%s", tmp);
+    return (int)strlen(tmp);
+}
+
+extern "C" int gpz_predictor_info(const gpz_predictor *p, int64_t out[4]) {
+    if (!p || !out) return gpz_fail(GPZ_ERR_ARG, "gpz_predictor_info: null argument");
+    out[0] = p->tile_rows;
+    out[1] = (int64_t)p->ar.bytes;
+    out[2] = p->route;
+    out[3] = p->runs;
+    return 0;
+}

@@ -200,6 +200,27 @@ int gpz_predict_missing(const gpz_desc *desc, const double *theta, const double 
                         const double *priors, const double *Xs, int64_t ns, const double *Psi, int32_t psi_kind,
                         double *mu, double *nu, double *beta_i, double *gamma, double *PHI);
 
+/* ---- persistent streaming predictor: predictFull / predictNoisy for any number of rows --------------------------------------------
+ * gpz_predictor_create does the once-per-model work on desc->device (theta unpacked, B_o = [inv(Sigma_o) | w | v] laid out for the
+ * product) and allocates tile-sized buffers only: afterwards device memory does not depend on how many rows are predicted.  theta, w and
+ * iSigma_w as gpz_predict_full takes them; tile_rows = 0 chooses.  Two routes: fused (ceil16(m + 2k) <= 256 and d <= 20, k <= 8: one
+ * kernel writes mu, nu and beta, PHI and T never exist) and tiles (PHI kernel + T-GEMM per tile of rows); GPZ_PREDICT_FORCE_TILES takes
+ * the tile route where the fused kernel fits.  desc->stream is not used: the handle has streams of its own.
+ * gpz_predictor_run: conventions of gpz_predict_full / gpz_predict_noisy - Xs column-major ns x d, normalised; outputs column-major ns x k,
+ * mu without muY; gamma = 0 without Psi (predictDiag.m:74); PHI (ns x m) may be NULL, and then never leaves the device.  Rows with NaN are
+ * refused (GPZ_ERR_UNSUPPORTED; outputs undefined).  Psi / psi_kind (1, 2, 3) as in gpz_predict_noisy: that branch runs per tile.
+ * ns = 0 does nothing.  One thread at a time per handle.
+ * gpz_predictor_route: as gpz_ctx_route (returns the description's full length).  gpz_predictor_info: [tile_rows, device bytes held, route (0 fused, 1 tiles), runs]. */
+typedef struct gpz_predictor gpz_predictor;
+#define GPZ_PREDICT_FORCE_TILES 1   /* flags: take the tile route even where the fused kernel fits (A/B and tests) */
+int gpz_predictor_create(const gpz_desc *desc, const double *theta, const double *w, const double *iSigma_w,
+                         int64_t tile_rows, int32_t flags, gpz_predictor **out);
+void gpz_predictor_destroy(gpz_predictor *p);
+int gpz_predictor_run(gpz_predictor *p, const double *Xs, int64_t ns, const double *Psi, int32_t psi_kind,
+                      double *mu, double *nu, double *beta_i, double *gamma, double *PHI);
+int gpz_predictor_route(const gpz_predictor *p, char *buf, int cap);
+int gpz_predictor_info(const gpz_predictor *p, int64_t out[4]);
+
 /* ---- device-resident L-BFGS memory: minFunc's lbfgsAdd.m / lbfgsProd.m (mex/lbfgsAddC.c, mex/lbfgsProdC.c) ----
  * S and Y (p x corrections) live on the device; all vector arguments are device pointers.
  * gpz_lbfgs_add:        y = g - g_old, s = t*d; skipped (added = 0) when y's <= 1e-10        (lbfgsAdd.m:2-4)
