@@ -621,6 +621,7 @@ def predict(X, model, whichSet="best", Psi=None, selection=None, device=0, n_gpu
 
 
 GPZ_PREDICT_FORCE_TILES = 1   # gpz_predictor_create flags (include/gpz_hip.h)
+GPZ_DRAWS_MAX_COLUMNS = 16384   # n_draws * k per gpz_predictor_draws call (include/gpz_hip.h)
 
 
 class Predictor:
@@ -705,7 +706,10 @@ class Predictor:
         """Which kernels the handle runs (gpz_predictor_route), as one line of text."""
         h = self._handle()
         buf = C.create_string_buffer(256)
-        self._lib.gpz_predictor_route(h, buf, 256)
+        n = self._lib.gpz_predictor_route(h, buf, 256)
+        if n >= 256:                                                     # a long factor list after draws: the whole text
+            buf = C.create_string_buffer(n + 1)
+            self._lib.gpz_predictor_route(h, buf, n + 1)
         return buf.value.decode()
 
     @property
@@ -798,6 +802,51 @@ class Predictor:
         mu = mu + model.muY                                              # predict.m:73
         out = (mu, sigma, nu, beta_i, gamma)
         return out + (PHI,) if return_phi else out
+
+    def draws(self, X, n_draws, seed=0, Z=None, selection=None):
+        """Posterior draws of the predictive mean (gpz_predictor_draws): an array of shape (n_draws, n, k) whose draws[s] has the shape
+        and meaning of ``predict``'s mu (normalisation, ``selection``, + muY) under one draw w_s ~ N(w, iSigma_w) of the weights, the
+        same draw for every row.  The spread of an aggregate of the rows across draws (a bin's mean redshift, a stacked n(z)) is its
+        error from the finite training set, cross-row covariance included; y-draws add sqrt(beta_i) times independent normals per row.
+
+        ``seed`` (an integer in [0, 2^64)) selects the standard normals, generated on the device from Philox4x32-10: draw s of a seed
+        is the same on every call and for every n_draws > s.  ``Z`` (m x n_draws x k, or m x n_draws when k = 1) gives them instead;
+        ``Z = eye(m)`` with n_draws = m makes (draws - mu) an exact square root of the joint covariance of the rows' means.  Complete,
+        noise-free rows only: rows with NaN are refused.  At most n_draws * k = 16384 columns per call."""
+        if self._closed:
+            raise RuntimeError("Predictor is closed")
+        model, k, m = self.model, self._k, self._m
+        X, _ = self._check_inputs(X, None, selection)
+        nbad = int(np.isnan(X).any(axis=1).sum()) if X.size else 0
+        if nbad:
+            raise ValueError(f"X has {nbad} rows with missing values (NaN): draws are for complete rows")
+        if isinstance(n_draws, (bool, np.bool_)) or not isinstance(n_draws, (int, np.integer)) or n_draws < 1:
+            raise ValueError(f"n_draws must be a positive integer, got {n_draws!r}")
+        n_draws = int(n_draws)
+        if n_draws * k > GPZ_DRAWS_MAX_COLUMNS:
+            raise ValueError(f"n_draws * k = {n_draws * k} is over the limit of {GPZ_DRAWS_MAX_COLUMNS} per call")
+        if isinstance(seed, (bool, np.bool_)) or not isinstance(seed, (int, np.integer)) or not 0 <= int(seed) < 2 ** 64:
+            raise ValueError(f"seed must be an integer in [0, 2^64), got {seed!r}")
+        z = None
+        if Z is not None:
+            z = np.asarray(Z, dtype=np.float64)
+            if k == 1 and z.shape == (m, n_draws):
+                z = z[:, :, None]
+            if z.shape != (m, n_draws, k):
+                want = f"({m}, {n_draws}, {k})" + (f" or ({m}, {n_draws})" if k == 1 else "")
+                raise ValueError(f"Z must have shape {want}, got {np.asarray(Z).shape}")
+            z = np.asfortranarray(z)
+        ns = X.shape[0]
+        F = np.empty((ns, k, n_draws), order="F")                        # column-major ns x k x n_draws, as the C entry writes it
+        if ns:
+            Xn = np.empty(X.shape, order="F")                            # predict.m:35-36
+            np.subtract(X, model.muX, out=Xn)
+            np.divide(Xn, model.sdX, out=Xn)
+            h = self._handle()
+            _lib.check(self._lib.gpz_predictor_draws(h, _lib.dptr(Xn), ns, n_draws, int(seed), _lib.dptr(z), _lib.dptr(F)))
+        out = F.transpose(2, 0, 1)                                       # (n_draws, n, k) view
+        out += np.asarray(model.muY, dtype=np.float64).reshape(k)        # predict.m:73
+        return out
 
 
 def getPrior(X, Psi, theta, model, selection=None, device=0, return_iterations=False):

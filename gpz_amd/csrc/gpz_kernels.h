@@ -127,6 +127,21 @@ size_t predict_small_lds(int de);
 int launch_predict_small(hipStream_t st, int kind, int de, const double *Xc, long ldx, int n, int m, int k, const double *P,
                          const double *G, const double *B, int ldb, long bstride, const double *bvec, double *out, long ldo,
                          double *phi, long ldphi);
+// ---- posterior draws of the predictive mean (k_predict_draws.hip; gpz_predictor_draws) -------------------------------------------
+// fits: an instantiated d (phi_is_wide(de, 1) false) and ceil16(m) <= 256.  F = PHI W for the n rows of Xc (as launch_predict_small);
+// W: ceil16(m) x ldw row-major (ldw % 16 == 0, columns >= ncol zero); out: [ncol][ldo].  Returns -1 when the launch failed.
+bool predict_draws_fits(int de, int m);
+size_t predict_draws_lds(int de);
+int launch_predict_draws(hipStream_t st, int kind, int de, const double *Xc, long ldx, int n, int m, const double *P, const double *G,
+                         const double *W, int ldw, int ncol, double *out, long ldo);
+// W (rows x ldw row-major) <- [W_0 | .. | W_{k-1} | 0], W_o(:, s) = w(:, o) + R_o z(:, s, o): z from Z (m x nd x k column-major) or, Z null,
+// Philox4x32-10 of (seed; j, s, o, 0) through Box-Muller.  R: m x m x k column-major.  Rows >= m zero.
+void launch_draws_weights(hipStream_t st, const double *w, const double *R, const double *Z, unsigned long long seed, int m, int nd,
+                          int k, int rows, int ldw, double *W);
+// S (m x m) <- (iS + iS') / 2;  A (mq x mq row-major) <- S, the identity on the padding (the input of launch_chol_step)
+void launch_draws_sym(hipStream_t st, const double *iS, int m, int mq, double *S, double *A);
+// after the Cholesky steps: R (m x m column-major) <- the lower factor in Lm; *ok = 1 unless a pivot failed or min L_jj^2 <= m eps max S_jj
+void launch_draws_chol_check(hipStream_t st, const double *Lm, int mq, const double *S, int m, const int *info, double *R, int *ok);
 // B (rows x ld row-major) <- [iS (m x m column-major) | nw columns of W from column wcol | nv columns of V (nullptr: 0) from vcol | 0]
 void launch_pred_fill_b(hipStream_t st, const double *iS, const double *W, int nw, int wcol, const double *V, int nv, int vcol, int m,
                         int rows, int ld, double *B);
@@ -174,6 +189,10 @@ void launch_cond_flag(hipStream_t st, const double *S, int lds, const double *al
 // Gt, Vt: m x ld work matrices, sbuf: m doubles, word: 8-byte device word.  Returns the sweeps used, -1 on error.
 int run_jacobi_pinv(hipStream_t st, const double *S, int lds, const double *alpha, int m, double *Gt, double *Vt, int ld,
                     double *sbuf, unsigned long long *word, double *Xi, int ldx, double *logdet, double *out3);
+
+// R R' = S (m x m symmetric positive semidefinite, lds) as R = V diag(sqrt(max(lambda, 0))) from the same sweeps; R column-major (ldr)
+int run_jacobi_sqrt(hipStream_t st, const double *S, int lds, int m, double *Gt, double *Vt, int ld, unsigned long long *word, double *R,
+                    int ldr);
 
 void launch_fill_bext(hipStream_t st, const double *Sinv, int ldsi, const double *w, int m, int mp, int out,
                       double *Bext, double *dgi);

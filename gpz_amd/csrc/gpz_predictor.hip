@@ -11,6 +11,16 @@
 // Pipeline of gpz_predictor_run (full branch): three streams - copies in, compute, copies out - and two slots of pinned staging and device
 // buffers.  Tile t's upload, tile t-1's kernels and tile t-2's download are in flight together while the host thread stages tile t+1's
 // rows and scatters tile t-2's results into the caller's column-major arrays.
+//
+// gpz_predictor_draws (posterior draws of the mean, F_s = PHI W_s with W_s = w + R z_s) runs the same pipeline on a tile of its own, sized
+// so that one slot's output is at most 256 MiB.  Its buffers, the factors R_o and W are allocated on the first draws call, so a
+// predict-only handle holds what it held before:
+//   * draws route 0, fused: ceil16(m) <= 256 and an instantiated d - k_predict_draws writes the draws only (PHI never leaves LDS);
+//   * draws route 1, tiles: k_phi_* + k_tgemm with B = W (all n_draws * k columns in one product) + a transpose into the slot.
+// R_o is the Cholesky factor of the symmetric part S_o of iSigma_w(:, :, o) (k_chol_step); where it breaks down (a failed pivot, or
+// min L_jj^2 <= m eps max S_jj) it is V diag(sqrt(max(lambda, 0))) from the one-sided Jacobi sweeps of k_pinv.hip.
+#include <string>
+
 #include "gpz_ctx.h"
 
 #define GPZ_PREDICTOR_TILE_FUSED (1L << 17)   // default rows per tile, fused route: 4096 blocks of 32 rows = 8 rounds of 512 workgroups
@@ -22,6 +32,7 @@ struct gpz_predictor {
     long p = 0;
     int device = 0;
     int route = 0;                 // 0 fused, 1 tiles
+    bool force_tiles = false;      // GPZ_PREDICT_FORCE_TILES
     int64_t tile_rows = 0, tile_pad = 0, runs = 0;
     int nk = 0, ldb = 0;           // fused: B_o is nk x ldb
     int nslots = 0;                // tiles: nu partial slots per output
@@ -35,6 +46,16 @@ struct gpz_predictor {
     double *Phi = nullptr, *T = nullptr, *nupart = nullptr, *phiw = nullptr, *lnbeta = nullptr;   // tiles
     double *hin[2] = {}, *hout[2] = {}, *hphi[2] = {};   // pinned
     std::vector<double> theta_h, w_h, iS_h;              // the model, for the input-noise branch (gpz_predict_noisy per tile)
+    // ---- draws (gpz_predictor_draws): nothing of this exists before the first draws call
+    int droute = -1;               // -1 no draws call yet, 0 fused (k_predict_draws), 1 tiles (k_phi + k_tgemm)
+    std::vector<int> fkind;        // per output: 0 Cholesky, 1 eigendecomposition
+    double *R = nullptr;           // m x m x k column-major: R_o R_o' = S_o
+    double *Wd = nullptr, *Zd = nullptr, *Td = nullptr, *dout[2] = {}, *hdout[2] = {};
+    size_t w_cap = 0, z_cap = 0, t_cap = 0, dout_cap = 0, hdout_cap = 0;   // doubles
+    int64_t dtile = 0;             // rows per draws tile (last call)
+    bool w_seeded = false;         // Wd holds the draws of (w_seed, w_nd)
+    unsigned long long w_seed = 0;
+    int w_nd = 0;
 };
 
 namespace gpzi {
@@ -47,6 +68,7 @@ static void predictor_free(gpz_predictor *p) {
         if (p->hin[s]) (void)hipHostFree(p->hin[s]);
         if (p->hout[s]) (void)hipHostFree(p->hout[s]);
         if (p->hphi[s]) (void)hipHostFree(p->hphi[s]);
+        if (p->hdout[s]) (void)hipHostFree(p->hdout[s]);
         if (p->ev_in[s]) (void)hipEventDestroy(p->ev_in[s]);
         if (p->ev_cmp[s]) (void)hipEventDestroy(p->ev_cmp[s]);
         if (p->ev_out[s]) (void)hipEventDestroy(p->ev_out[s]);
@@ -71,7 +93,8 @@ static int predictor_setup(gpz_predictor *p, const double *theta, const double *
         HIPCHK(hipEventRecord(p->ev_cmp[s], p->s_cmp));   // recorded once, so that the first waits of gpz_predictor_run have an event
         HIPCHK(hipEventRecord(p->ev_out[s], p->s_out));
     }
-    p->route = (!(flags & GPZ_PREDICT_FORCE_TILES) && predict_small_fits(p->de, p->m, p->k)) ? 0 : 1;
+    p->force_tiles = (flags & GPZ_PREDICT_FORCE_TILES) != 0;
+    p->route = (!p->force_tiles && predict_small_fits(p->de, p->m, p->k)) ? 0 : 1;
     if (tile_rows <= 0) {
         if (p->route == 0) tile_rows = GPZ_PREDICTOR_TILE_FUSED;
         else {   // PHI + T of a tile within about 1 GiB
@@ -280,6 +303,177 @@ static int predictor_run_noisy(gpz_predictor *p, const double *Xs, int64_t ns, c
     }
     return 0;
 }
+
+// ---- draws ------------------------------------------------------------------------------------------------------------------------
+// R_o for every output, once per handle: the blocked Cholesky steps of k_chol.hip on S_o (padded to a multiple of 32 with the identity),
+// the eigen-factor of k_pinv.hip's sweeps where that breaks down.
+static int predictor_factor(gpz_predictor *p) {
+    const int m = p->m, k = p->k, mq = rup(m, GPZ_CH_NB);
+    hipStream_t st = p->s_cmp;
+    auto &ar = p->ar;
+    double *S = nullptr, *A = nullptr, *Lm = nullptr, *logdet = nullptr, *Gt = nullptr, *Vt = nullptr;
+    int *info = nullptr;
+    unsigned long long *word = nullptr;
+    int rc = 0;
+    if ((rc = ar.alloc(&p->R, (size_t)m * m * k))) return rc;
+    if ((rc = ar.alloc(&S, (size_t)m * m))) return rc;
+    if ((rc = ar.alloc(&A, (size_t)mq * mq))) return rc;
+    if ((rc = ar.alloc(&Lm, (size_t)mq * mq))) return rc;
+    if ((rc = ar.alloc(&logdet, 1))) return rc;
+    if ((rc = ar.alloc(&info, 4 + (size_t)k))) return rc;   // [pivot failure, -, -, -, ok_0 .. ok_{k-1}]
+    p->fkind.assign(k, 0);
+    for (int o = 0; o < k; ++o) {
+        launch_draws_sym(st, p->iS_d + (size_t)o * m * m, m, mq, S, A);
+        HIPCHK(hipMemsetAsync(info, 0, 4 * sizeof(int), st));
+        for (int k0 = 0; k0 < mq; k0 += GPZ_CH_NB) launch_chol_step(st, A, Lm, nullptr, mq, mq, k0, logdet, info, false);
+        launch_draws_chol_check(st, Lm, mq, S, m, info, p->R + (size_t)o * m * m, info + 4 + o);
+        int ok = 0;
+        HIPCHK(hipMemcpyAsync(&ok, info + 4 + o, sizeof(int), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        if (ok) continue;
+        p->fkind[o] = 1;   // semidefinite (or numerically so): R_o = V diag(sqrt(max(lambda, 0)))
+        if (!Gt) {
+            if ((rc = ar.alloc(&Gt, (size_t)m * m))) return rc;
+            if ((rc = ar.alloc(&Vt, (size_t)m * m))) return rc;
+            if ((rc = ar.alloc(&word, 2))) return rc;
+        }
+        if (run_jacobi_sqrt(st, S, m, m, Gt, Vt, m, word, p->R + (size_t)o * m * m, m) < 0)
+            return gpz_fail(GPZ_ERR_HIP, "gpz_predictor_draws: Jacobi sweeps failed");
+    }
+    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// a device buffer of at least need doubles (a larger request takes a new block; the handle holds its blocks until it is destroyed)
+static int predictor_grow(gpz_predictor *p, double **buf, size_t *cap, size_t need) {
+    if (*buf && *cap >= need) return 0;
+    if (int rc = p->ar.alloc(buf, need)) return rc;
+    *cap = need;
+    return 0;
+}
+
+static int predictor_run_draws(gpz_predictor *p, const double *Xs, int64_t ns, int nd, unsigned long long seed, const double *Z,
+                               double *F) {
+    const int k = p->k, d = p->d, m = p->m, ncol = nd * k, ldw = rup(ncol, 16);
+    const size_t tp = (size_t)p->tile_pad;
+    hipStream_t st = p->s_cmp;
+    int rc = 0;
+    if (p->droute < 0) {
+        const int r = (!p->force_tiles && predict_draws_fits(p->de, p->m)) ? 0 : 1;
+        if (r == 1 && !p->Phi)   // (not reached: a shape outside the fused draws kernel is outside k_predict_small too)
+            return gpz_fail(GPZ_ERR_UNSUPPORTED, "gpz_predictor_draws: no PHI tile buffers on a fused-route handle");
+        if ((rc = predictor_factor(p))) return rc;
+        p->droute = r;
+    }
+    // ---- W = [W_0 | W_1 | ...] for this call (kept while the seed and the number of draws stay the same and Z is NULL)
+    const int wrows = p->droute == 0 ? rup(m, 16) : p->mp;
+    if (Z || !p->w_seeded || p->w_seed != seed || p->w_nd != nd || p->w_cap < (size_t)wrows * ldw) {
+        if ((rc = predictor_grow(p, &p->Wd, &p->w_cap, (size_t)wrows * ldw))) return rc;
+        if (Z) {
+            if ((rc = predictor_grow(p, &p->Zd, &p->z_cap, (size_t)m * ncol))) return rc;
+            HIPCHK(hipMemcpyAsync(p->Zd, Z, (size_t)m * ncol * sizeof(double), hipMemcpyHostToDevice, st));
+        }
+        launch_draws_weights(st, p->w_d, p->R, Z ? p->Zd : nullptr, seed, m, nd, k, wrows, ldw, p->Wd);
+        HIPCHK(hipGetLastError());
+        p->w_seeded = Z == nullptr;
+        p->w_seed = seed;
+        p->w_nd = nd;
+    }
+    // ---- the draws tile: the handle's, shrunk so that a slot's output is <= 256 MiB, in whole granules of the route
+    const int64_t gran = p->droute == 0 ? 32 : 1024;
+    int64_t T = std::min<int64_t>(p->tile_rows, (256L << 20) / (8L * ncol)) / gran * gran;
+    if (T < gran) T = gran;   // <= tile_pad (a multiple of 1024)
+    p->dtile = T;
+    const size_t slot = (size_t)ncol * T;
+    if (p->dout_cap < slot) {
+        for (int s = 0; s < 2; ++s)
+            if ((rc = p->ar.alloc(&p->dout[s], slot))) return rc;
+        p->dout_cap = slot;
+    }
+    if (p->hdout_cap < slot) {
+        for (int s = 0; s < 2; ++s) {
+            if (p->hdout[s]) (void)hipHostFree(p->hdout[s]);
+            p->hdout[s] = nullptr;
+        }
+        p->hdout_cap = 0;
+        for (int s = 0; s < 2; ++s) HIPCHK(hipHostMalloc((void **)&p->hdout[s], slot * sizeof(double), hipHostMallocDefault));
+        p->hdout_cap = slot;
+    }
+    if (p->droute == 1 && (rc = predictor_grow(p, &p->Td, &p->t_cap, (size_t)rup(T, 1024) * ldw))) return rc;
+    // ---- the pipeline of predictor_run_full on tiles of T rows
+    const int64_t ntiles = (ns + T - 1) / T;
+    int64_t nt_of[2] = {0, 0}, r0_of[2] = {0, 0};
+    auto scatter = [&](int s) {   // column c = o nd + s of the slot -> F(:, o, s)
+        const int64_t nt = nt_of[s], r0 = r0_of[s];
+        for (int c = 0; c < ncol; ++c) {
+            const int o = c / nd, q = c % nd;
+            memcpy(F + (size_t)(o + (size_t)k * q) * ns + r0, p->hdout[s] + (size_t)c * nt, (size_t)nt * sizeof(double));
+        }
+    };
+    for (int64_t t = 0; t < ntiles + 2 && !rc; ++t) {
+        const int s = (int)(t & 1);
+        if (t >= 2) {
+            if (hipEventSynchronize(p->ev_out[s]) != hipSuccess) { rc = gpz_fail(GPZ_ERR_HIP, "gpz_predictor_draws: tile failed"); break; }
+            scatter(s);
+        }
+        if (t >= ntiles) continue;
+        const int64_t r0 = t * T, nt = std::min<int64_t>(T, ns - r0);
+        nt_of[s] = nt; r0_of[s] = r0;
+        bool bad = false;
+        for (int c = 0; c < d; ++c) {
+            const double *src = Xs + (size_t)c * ns + r0;
+            double *dst = p->hin[s] + (size_t)c * tp;
+            int nan = 0;
+            for (int64_t i = 0; i < nt; ++i) { const double v = src[i]; dst[i] = v; nan |= v != v; }
+            bad |= nan != 0;
+        }
+        if (bad) {
+            rc = gpz_fail(GPZ_ERR_UNSUPPORTED, "gpz_predictor_draws: the rows have missing values (NaN): draws are for complete rows");
+            break;
+        }
+        if (hipStreamWaitEvent(p->s_in, p->ev_cmp[s], 0) != hipSuccess ||
+            hipMemcpy2DAsync(p->Xc[s], tp * sizeof(double), p->hin[s], tp * sizeof(double), (size_t)nt * sizeof(double), d,
+                             hipMemcpyHostToDevice, p->s_in) != hipSuccess ||
+            hipEventRecord(p->ev_in[s], p->s_in) != hipSuccess || hipStreamWaitEvent(st, p->ev_in[s], 0) != hipSuccess ||
+            hipStreamWaitEvent(st, p->ev_out[s], 0) != hipSuccess) {
+            rc = gpz_fail(GPZ_ERR_HIP, "gpz_predictor_draws: copy failed");
+            break;
+        }
+        const double *G = p->kind == GPZ_KIND_COV ? p->pr.Rc : p->pr.G2;
+        if (p->droute == 0) {
+            if (launch_predict_draws(st, p->kind, p->de, p->Xc[s], p->tile_pad, (int)nt, m, p->pr.P, G, p->Wd, ldw, ncol, p->dout[s], nt)) {
+                rc = gpz_fail(GPZ_ERR_HIP, "gpz_predictor_draws: k_predict_draws launch failed");
+                break;
+            }
+        } else {
+            const long np = rup(nt, 1024);
+            PhiArgs a{};
+            a.Xc = p->Xc[s]; a.ldx = p->tile_pad; a.n = (int)nt; a.n_pad = (int)np;
+            a.m = m; a.mp = p->mp; a.d = p->de; a.k = k; a.kind = p->kind;
+            a.P = p->pr.P; a.G = G;
+            a.v = p->hetero ? p->pr.v : nullptr; a.b = p->pr.b;
+            a.Phi = p->Phi; a.lnbeta = p->lnbeta;
+            if (launch_phi(st, a)) {
+                rc = gpz_fail(GPZ_ERR_UNSUPPORTED, "gpz_predictor_draws: PHI kernel not instantiated for d=%d", p->de);
+                break;
+            }
+            // T = PHI W: K = mp (rows >= m of W are zero), ldw output columns
+            launch_tgemm(st, p->Phi, p->mp, p->Wd, ldw, p->Td, (int)np, ldw, nullptr, nullptr, m, 0, false, p->mp, ldw);
+            launch_transpose_out(st, p->Td, ldw, nt, ncol, p->dout[s]);
+            if (hipGetLastError() != hipSuccess) { rc = gpz_fail(GPZ_ERR_HIP, "gpz_predictor_draws: kernel launch failed"); break; }
+        }
+        if (hipEventRecord(p->ev_cmp[s], st) != hipSuccess || hipStreamWaitEvent(p->s_out, p->ev_cmp[s], 0) != hipSuccess ||
+            hipMemcpyAsync(p->hdout[s], p->dout[s], (size_t)ncol * nt * sizeof(double), hipMemcpyDeviceToHost, p->s_out) != hipSuccess ||
+            hipEventRecord(p->ev_out[s], p->s_out) != hipSuccess) {
+            rc = gpz_fail(GPZ_ERR_HIP, "gpz_predictor_draws: copy failed");
+            break;
+        }
+    }
+    for (hipStream_t q : {p->s_in, p->s_cmp, p->s_out})
+        if (hipStreamSynchronize(q) != hipSuccess && !rc) rc = gpz_fail(GPZ_ERR_HIP, "gpz_predictor_draws: sync failed");
+    return rc;
+}
 }   // namespace gpzi
 
 extern "C" int gpz_predictor_create(const gpz_desc *desc, const double *theta, const double *w, const double *iSigma_w,
@@ -350,6 +544,25 @@ extern "C" int gpz_predictor_run(gpz_predictor *p, const double *Xs, int64_t ns,
     return rc;
 }
 
+extern "C" int gpz_predictor_draws(gpz_predictor *p, const double *Xs, int64_t ns, int32_t ndraws, uint64_t seed, const double *Z,
+                                   double *F) {
+    if (!p) return gpz_fail(GPZ_ERR_ARG, "gpz_predictor_draws: null handle");
+    if (ns < 0) return gpz_fail(GPZ_ERR_ARG, "gpz_predictor_draws: ns < 0");
+    if (ndraws < 1 || (int64_t)ndraws * p->k > GPZ_DRAWS_MAX_COLUMNS)
+        return gpz_fail(GPZ_ERR_ARG, "gpz_predictor_draws: need 1 <= ndraws and ndraws * k <= %d (ndraws %d, k %d)", GPZ_DRAWS_MAX_COLUMNS,
+                        (int)ndraws, p->k);
+    if (ns == 0) return 0;
+    if (!Xs || !F) return gpz_fail(GPZ_ERR_ARG, "gpz_predictor_draws: null argument");
+    int prev = 0;
+    (void)hipGetDevice(&prev);
+    gpz_opts_scope opts_scope(&p->opt);
+    int rc = 0;
+    if (hipSetDevice(p->device) != hipSuccess) rc = gpz_fail(GPZ_ERR_HIP, "gpz_predictor_draws: hipSetDevice failed");
+    if (!rc) rc = predictor_run_draws(p, Xs, ns, (int)ndraws, (unsigned long long)seed, Z, F);
+    (void)hipSetDevice(prev);
+    return rc;
+}
+
 extern "C" int gpz_predictor_route(const gpz_predictor *p, char *buf, int cap) {
     if (!p || !buf || cap < 1) return gpz_fail(GPZ_ERR_ARG, "gpz_predictor_route: null argument");
     char tmp[160];
@@ -357,8 +570,15 @@ extern "C" int gpz_predictor_route(const gpz_predictor *p, char *buf, int cap) {
         snprintf(tmp, sizeof tmp, "fused: k_predict_small, %lld-row tiles", (long long)p->tile_rows);
     else
         snprintf(tmp, sizeof tmp, "tiles: k_phi + k_tgemm, %lld-row tiles", (long long)p->tile_rows);
-    snprintf(buf, (size_t)cap, "%s", tmp);
-    return (int)strlen(tmp);
+    std::string r = tmp;
+    if (p->droute >= 0) {   // after a draws call: its route and each output's factor
+        snprintf(tmp, sizeof tmp, "; draws: %s, %lld-row tiles, factors:", p->droute == 0 ? "fused k_predict_draws" : "tiles k_phi + k_tgemm",
+                 (long long)p->dtile);
+        r += tmp;
+        for (size_t o = 0; o < p->fkind.size(); ++o) r += p->fkind[o] ? " eigen" : " cholesky";
+    }
+    snprintf(buf, (size_t)cap, "%s", r.c_str());
+    return (int)r.size();
 }
 
 extern "C" int gpz_predictor_info(const gpz_predictor *p, int64_t out[4]) {

@@ -219,12 +219,9 @@ void launch_cond_flag(hipStream_t st, const double *S, int lds, const double *al
     hipLaunchKernelGGL(k_cond_norms, dim3(m >= 512 ? COND_NWG : 64), dim3(256), 0, st, S, lds, alpha, Sinv, ldsi, m, part, info, (unsigned *)(info + 2));
 }
 
-// Pseudo-inverse of SIGMA = S + diag(alpha) (alpha may be nullptr) into Xi, ln-det of the kept part into *logdet.
-// Gt, Vt: m x ld work matrices; sbuf: m doubles; word: two 8-byte device words; out3 (optional, device): [logdet, rank, max s].
-// Synchronises the stream once per sweep.  Returns the number of sweeps, or -1 on a HIP error.
-int run_jacobi_pinv(hipStream_t st, const double *S, int lds, const double *alpha, int m, double *Gt, double *Vt, int ld,
-                    double *sbuf, unsigned long long *word, double *Xi, int ldx, double *logdet, double *out3) {
-    hipLaunchKernelGGL(k_jacobi_init, dim3((m + 255) / 256, m), dim3(256), 0, st, S, lds, alpha, m, Gt, Vt, ld);
+// The tournament sweeps on Gt / Vt until the columns are orthogonal (at most 60; the host reads one convergence word per sweep).
+// Returns the number of sweeps, or -1 on a HIP error.
+static int jacobi_sweeps(hipStream_t st, int m, double *Gt, double *Vt, int ld, unsigned long long *word) {
     const int M = (m + 1) & ~1;
     const double conv = 4.0 * sqrt((double)m) * 2.220446049250313e-16;
     int sweep = 0;
@@ -248,8 +245,44 @@ int run_jacobi_pinv(hipStream_t st, const double *S, int lds, const double *alph
             if (!(rel > conv)) break;
         }
     }
+    return sweep > 60 ? 60 : sweep;
+}
+
+// Pseudo-inverse of SIGMA = S + diag(alpha) (alpha may be nullptr) into Xi, ln-det of the kept part into *logdet.
+// Gt, Vt: m x ld work matrices; sbuf: m doubles; word: two 8-byte device words; out3 (optional, device): [logdet, rank, max s].
+// Synchronises the stream once per sweep.  Returns the number of sweeps, or -1 on a HIP error.
+int run_jacobi_pinv(hipStream_t st, const double *S, int lds, const double *alpha, int m, double *Gt, double *Vt, int ld,
+                    double *sbuf, unsigned long long *word, double *Xi, int ldx, double *logdet, double *out3) {
+    hipLaunchKernelGGL(k_jacobi_init, dim3((m + 255) / 256, m), dim3(256), 0, st, S, lds, alpha, m, Gt, Vt, ld);
+    const int sweeps = jacobi_sweeps(st, m, Gt, Vt, ld, word);
+    if (sweeps < 0) return -1;
     hipLaunchKernelGGL(k_jacobi_norms, dim3(m), dim3(256), 0, st, Gt, ld, m, sbuf);
     hipLaunchKernelGGL(k_jacobi_truncate, dim3(1), dim3(256), 0, st, sbuf, m, logdet, out3);
     hipLaunchKernelGGL(k_jacobi_pinv, dim3((m + 63) / 64, (m + 63) / 64), dim3(256), 0, st, Vt, Gt, ld, sbuf, m, Xi, ldx);
-    return sweep > 60 ? 60 : sweep;
+    return sweeps;
+}
+
+// Square-root factor of a symmetric S from the converged sweeps: G = S V, so lambda_j = v_j' g_j is the eigenvalue of v_j (with its
+// sign, which |g_j| would lose), and R(:, j) = v_j sqrt(max(lambda_j, 0)) (R: m x m column-major, ldr).  One workgroup per j.
+__global__ __launch_bounds__(256) void k_jacobi_sqrt(const double *__restrict__ Gt, const double *__restrict__ Vt, int ld, int m,
+                                                     double *__restrict__ R, int ldr) {
+    __shared__ double sh4[4];
+    const int j = blockIdx.x, tid = threadIdx.x;
+    const double *g = Gt + (size_t)j * ld, *v = Vt + (size_t)j * ld;
+    double a = 0.0;
+    for (int e = tid; e < m; e += 256) a = fma(v[e], g[e], a);
+    a = block_sum_256(a, sh4);
+    const double sc = sqrt(fmax(a, 0.0));
+    for (int e = tid; e < m; e += 256) R[(size_t)e + (size_t)ldr * j] = v[e] * sc;
+}
+
+// R R' = S for a symmetric positive SEMIdefinite S (m x m, lds): S = V diag(lambda) V' by the one-sided Jacobi sweeps above,
+// R = V diag(sqrt(max(lambda, 0))).  Gt, Vt: m x ld work matrices; word: two 8-byte device words.  Returns the sweeps used, -1 on error.
+int run_jacobi_sqrt(hipStream_t st, const double *S, int lds, int m, double *Gt, double *Vt, int ld, unsigned long long *word, double *R,
+                    int ldr) {
+    hipLaunchKernelGGL(k_jacobi_init, dim3((m + 255) / 256, m), dim3(256), 0, st, S, lds, (const double *)nullptr, m, Gt, Vt, ld);
+    const int sweeps = jacobi_sweeps(st, m, Gt, Vt, ld, word);
+    if (sweeps < 0) return -1;
+    hipLaunchKernelGGL(k_jacobi_sqrt, dim3(m), dim3(256), 0, st, Gt, Vt, ld, m, R, ldr);
+    return sweeps;
 }

@@ -22,6 +22,7 @@
 #include "gpz_kernels.h"
 
 #define PS_LDA 262   // row stride of the PHI block in LDS (doubles): 2 (mod 4) - the 16 rows of an A-operand read start 4 banks apart
+#include "k_predict_phi.h"
 
 struct PredSmallArgs {
     const double *Xc; long ldx;   // de x ldx column layout (the tile's rows; dimensions >= d are zero)
@@ -69,64 +70,17 @@ __global__ __launch_bounds__(256, 2) void k_predict_small(PredSmallArgs a) {
     const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int m = a.m, k = a.k, nk = a.nk, nb = a.nb;
     const int nblocks = (a.n + 31) >> 5;
-    // PHI build mapping: column j = tid % nk, rows g, g + ngr, ... (ngr = 256 / nk row groups; threads past them idle)
-    const int jc = tid % nk, grp = tid / nk, ngr = 256 / nk;
-    const bool builder = grp < ngr;
+    // PHI build (k_predict_phi.h): thread (column j, row group g) keeps the parameters of basis function j in registers for the whole launch
+    const PsPhiBuilder<D, COV> phi(a.P, a.G, m, nk, tid);
     // this wave's column blocks: gb = wv + 4 q, q < nqw
     const int nqw = (nb - wv + 3) >> 2;
-    // parameters of basis function jc (diagonal kinds): centre and gamma^2 in registers for the whole launch
-    double pj[COV ? 1 : D], gj[COV ? 1 : D];
-    if constexpr (!COV) {
-        const int jj = jc < m ? jc : 0;
-#pragma unroll
-        for (int c = 0; c < D; ++c) { pj[c] = a.P[(size_t)jj * D + c]; gj[c] = a.G[(size_t)jj * D + c]; }
-    }
     const int ks_n = nk >> 2;   // K steps of 4
     for (int blk = blockIdx.x; blk < nblocks; blk += gridDim.x) {
         const long i0 = (long)blk * 32;
         __syncthreads();   // the previous block's epilogue is done with sA / sX / sNu
-        for (int e = tid; e < 32 * D; e += 256) {
-            const int r = e / D, c = e % D;
-            sX[e] = (i0 + r < a.n) ? a.Xc[(size_t)c * a.ldx + i0 + r] : 0.0;
-        }
+        ps_load_x<D>(a.Xc, a.ldx, a.n, i0, sX, tid);
         __syncthreads();
-        // ---- PHI of the block -> sA
-        if (builder) {
-            if constexpr (!COV) {
-                for (int r = grp; r < 32; r += ngr) {
-                    double q = 0.0;
-#pragma unroll
-                    for (int c = 0; c < D; ++c) {
-                        const double dl = sX[r * D + c] - pj[c];
-                        q = fma(dl * dl, gj[c], q);                        // getPHI.m:97  Delta.^2 ./ Sigma
-                    }
-                    sA[r * PS_LDA + jc] = (jc < m && i0 + r < a.n) ? exp(-0.5 * q) : 0.0;   // getPHI.m:113
-                }
-            } else {
-                constexpr int NT = D * (D + 1) / 2;
-                const double *rj = a.G + (size_t)(jc < m ? jc : 0) * (NT + D);
-                // |R_j x - c_j|^2 row of R_j by row: the row's D - a entries in registers, the running sum in sA (k_phi_cov's order per element)
-#pragma unroll
-                for (int aa = 0; aa < D; ++aa) {
-                    double ra[D];
-                    const int off = aa * D - aa * (aa - 1) / 2;
-#pragma unroll
-                    for (int b = aa; b < D; ++b) ra[b] = rj[off + (b - aa)];
-                    const double ca = rj[NT + aa];
-                    for (int r = grp; r < 32; r += ngr) {
-                        double s = -ca;
-#pragma unroll
-                        for (int b = aa; b < D; ++b) s = fma(ra[b], sX[r * D + b], s);
-                        const double q = aa == 0 ? 0.0 : sA[r * PS_LDA + jc];
-                        sA[r * PS_LDA + jc] = fma(s, s, q);                 // getPHI.m:73,76
-                    }
-                }
-                for (int r = grp; r < 32; r += ngr) {
-                    const double q = sA[r * PS_LDA + jc];
-                    sA[r * PS_LDA + jc] = (jc < m && i0 + r < a.n) ? exp(-0.5 * q) : 0.0;
-                }
-            }
-        }
+        phi.build(sA, sX, i0, a.n);   // PHI of the block -> sA
         __syncthreads();
         if (a.phi) {   // PHI requested: 32 consecutive rows of a column per 32 lanes
             for (int e = tid; e < 32 * m; e += 256) {
@@ -196,11 +150,7 @@ __global__ __launch_bounds__(256, 2) void k_predict_small(PredSmallArgs a) {
 size_t predict_small_lds(int de) { return ((size_t)32 * PS_LDA + 32 * (size_t)de + 4 * 32) * sizeof(double); }
 
 bool predict_small_fits(int de, int m, int k) {
-    if (phi_is_wide(de, k)) return false;
-    switch (de) {
-        case 1: case 2: case 3: case 4: case 5: case 6: case 8: case 10: case 12: case 16: case 20: break;
-        default: return false;
-    }
+    if (phi_is_wide(de, k) || !ps_width_instantiated(de)) return false;
     return ((m + 2 * k + 15) / 16) * 16 <= 256 && predict_small_lds(de) <= 80 * 1024;
 }
 

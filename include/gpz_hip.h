@@ -221,6 +221,22 @@ int gpz_predictor_run(gpz_predictor *p, const double *Xs, int64_t ns, const doub
 int gpz_predictor_route(const gpz_predictor *p, char *buf, int cap);
 int gpz_predictor_info(const gpz_predictor *p, int64_t out[4]);
 
+/* ---- posterior draws of the predictive mean through a predictor handle ---------------------------------------------------------
+ * F(i, o, s) = PHI(i, :) (w(:, o) + R_o z(:, s, o)) for the complete rows of Xs: draw s is one realisation of the model's weights
+ * w_s ~ N(w, iSigma_w) over the whole catalogue, so the spread of an aggregate across draws is its error from the finite training set.
+ * R_o R_o' = (iSigma_w(:,:,o) + iSigma_w(:,:,o)') / 2: its Cholesky factor, or V diag(sqrt(max(lambda, 0))) from its eigendecomposition
+ * where the Cholesky breaks down (a failed pivot, or min L_jj^2 <= m eps max S_jj).  z: the caller's Z (m x ndraws x k, column-major) or,
+ * Z = NULL, z[j, s, o] = sqrt(-2 ln u1) cos(2 pi u2) from (x0, x1, x2, x3) = Philox4x32-10(counter (j, s, o, 0), key (seed & 0xffffffff,
+ * seed >> 32)), u1 = (((x1 << 32 | x0) >> 11) + 1) 2^-53, u2 = ((x3 << 32 | x2) >> 11) 2^-53: draw s of a seed is the same on every call
+ * and for every ndraws > s.  A row's draws have the same bits for any tile size, row order or split of the rows into calls.
+ * Xs: column-major ns x d, normalised (as gpz_predictor_run); ns = 0 does nothing.  F: column-major ns x k x ndraws, without muY.
+ * 1 <= ndraws, ndraws * k <= GPZ_DRAWS_MAX_COLUMNS, else GPZ_ERR_ARG; rows with NaN are refused (GPZ_ERR_UNSUPPORTED).  The factors
+ * are formed on the device on the first call; the draws buffers are allocated then too (gpz_predictor_info's bytes include them, its
+ * runs count gpz_predictor_run calls only), and gpz_predictor_route appends the draws route and each output's factor (cholesky / eigen). */
+#define GPZ_DRAWS_MAX_COLUMNS 16384
+int gpz_predictor_draws(gpz_predictor *p, const double *Xs, int64_t ns, int32_t ndraws, uint64_t seed,
+                        const double *Z /* NULL or m x ndraws x k */, double *F /* ns x k x ndraws, column-major */);
+
 /* ---- device-resident L-BFGS memory: minFunc's lbfgsAdd.m / lbfgsProd.m (mex/lbfgsAddC.c, mex/lbfgsProdC.c) ----
  * S and Y (p x corrections) live on the device; all vector arguments are device pointers.
  * gpz_lbfgs_add:        y = g - g_old, s = t*d; skipped (added = 0) when y's <= 1e-10        (lbfgsAdd.m:2-4)
