@@ -234,6 +234,8 @@ struct gpz_ctx {
     bool small_tail_dp = false;   // diagonal kinds + input noise, mp <= 256, k = 1: k_small_tail writes dPHI (into T's buffer), k_moments_diag sums it
     bool small_tail = false;   // mp <= 256, k = 1, no Psi / missing values / row tiles: T-GEMM + row scalars + moments as ONE kernel (k_small.hip), T never allocated
     int st_nwg = 0, st_nf = 0;
+    bool mom_ring = false;     // GC / VC, mp > 256, d = 8 / 10, no Psi / missing values: the moment sums by k_moments_ring (PHI, T through an LDS ring), records of mom_nv values
+    int mom_nv = 0;            // values per chunk record of mom_slab: nm + 2, on the ring route nf + 2
     double *st_slab = nullptr;
     bool fused = true;   // dPHI formed on the fly, output by output (no dPHI / dL matrices): k == 1, or k > 1 on the tuned kernels
     double *phipart = nullptr;   // PHI-build column-group partial sums (small row counts)

@@ -602,7 +602,12 @@ extern "C" int gpz_ctx_create_sharded(const gpz_desc *desc, int64_t n_tot, const
         if ((rc = c->ar.alloc(&c->frec, (size_t)m * (c->nm + 2)))) return bail(rc);
     }
     {
-        const int ncg = (c->m + 255) / 256;
+        // covariance kinds with many basis functions: PHI and T reach the moment sums through an LDS ring (k_moments_ring.hip); its raw sums
+        // about the column means need one value more per record, and the rows [1 | x - mu | 0] of Xs (row tiles and shards included)
+        c->mom_ring = c->fused && !c->gen && !c->has_psi && !c->has_missing && !c->small_tail && !c->small_tail_dp && c->tr.Xs &&
+                      c->tr.xs_ld == c->de + 2 && moments_ring_fits(c->kind, c->de, c->mp) && !c->opt.moments_ring_off;
+        // (the ring kernel's workgroups are moments_ring_cols() = 128 basis functions wide: whole rounds of 512 of THEM)
+        const int ncg = c->mom_ring ? (c->m + moments_ring_cols() - 1) / moments_ring_cols() : (c->m + 255) / 256;
         // chunks of rows per basis-function group: every chunk writes (and k_slab_sum re-reads) m x nm sums, so few enough that the
         // slab stays small beside Phi and T, many enough to fill 256 CUs (tools/mom_nc_sweep.sh: c2 768, c3/c4 512 chunks)
         const int nc_env = c->opt.mom_nc;   // (developer tuning)
@@ -635,7 +640,8 @@ extern "C" int gpz_ctx_create_sharded(const gpz_desc *desc, int64_t n_tot, const
             c->tile_nchunk = (c->tile_rows + c->tile_rpc - 1) / c->tile_rpc;
             c->nchunk = c->ntiles * c->tile_nchunk;
         }
-        if ((rc = c->ar.alloc(&c->mom_slab, (size_t)c->nchunk * m * (c->nm + 2)))) return bail(rc);
+        c->mom_nv = c->mom_ring ? moments_ring_features(c->de) + 2 : c->nm + 2;
+        if ((rc = c->ar.alloc(&c->mom_slab, (size_t)c->nchunk * m * c->mom_nv))) return bail(rc);
     }
     if ((rc = c->ar.alloc(&c->partial, (size_t)GPZ_ROWSCAL_MAX_NWG * gpz_ns(c->k)))) return bail(rc);
     static_assert(GPZ_ROWSCAL_MAX_NWG >= GPZ_SMALL_NWG, "partial record buffer");
@@ -782,11 +788,12 @@ extern "C" int gpz_ctx_route(const gpz_ctx *c, char *buf, int cap) {
     char rows[96];
     if (c->tile_rows) snprintf(rows, sizeof rows, "; rows: streamed, %d tiles of %d (PHI built twice per evaluation)", c->ntiles, c->tile_rows);
     else rows[0] = 0;
-    return snprintf(buf, (size_t)cap, "pair/PHI kernels: %s%s; contractions: %s MFMA%s%s; evaluation graph: %s%s", phi, why,
+    return snprintf(buf, (size_t)cap, "pair/PHI kernels: %s%s; contractions: %s MFMA%s%s; evaluation graph: %s%s%s", phi, why,
                     f32mm ? "fp32-operand (fp64 master sums)" : "fp64",
                     c->syrk_small ? ", PHI' W PHI with the whole triangle in one workgroup (k_syrk_small)" : "",
                     c->small_tail ? ", T-GEMM + row scalars + moments in one kernel (k_small_tail: T stays in registers)" :
-                    c->small_tail_dp ? ", T-GEMM + row scalars + dPHI in one kernel (k_small_tail; moment sums with input noise by k_moments_diag)" : "", gs, rows);
+                    c->small_tail_dp ? ", T-GEMM + row scalars + dPHI in one kernel (k_small_tail; moment sums with input noise by k_moments_diag)" : "", gs, rows,
+                    c->mom_ring ? "; moments: k_moments_ring (PHI, T through an LDS ring)" : "");
 }
 namespace gpzi {
 

@@ -366,6 +366,15 @@ int eval_tail(gpz_ctx *c, bool pinv) {
                     launch_slab_sum(c->st, c->partial, row_scalars_nwg(rt.rows), GPZ_NS, c->tile_rstats + (size_t)t * GPZ_NS);
                 }
                 Stage s(c, "moments");
+                if (c->mom_ring) {
+                    RingMomentArgs ra{};
+                    ra.Phi = c->Phi; ra.T = c->T; ra.ld = c->mp; ra.Xs = c->tr.Xs + r0 * c->tr.xs_ld; ra.rowscal = c->rowscal + 4 * r0;
+                    ra.n = rt.rows; ra.m = c->m; ra.d = c->de; ra.w = c->w + (size_t)o * m; ra.v = c->hetero ? c->pr.v + (size_t)o * m : nullptr;
+                    ra.rows_per_chunk = c->tile_rpc; ra.nchunk = (rt.rows + c->tile_rpc - 1) / c->tile_rpc;
+                    ra.slab = c->mom_slab + (size_t)t * c->tile_nchunk * m * c->mom_nv;
+                    if (launch_moments_ring(c->st, ra)) return gpz_fail(GPZ_ERR_HIP, "k_moments_ring launch failed (d=%d)", c->de);
+                    continue;
+                }
                 FusedMomentArgs a{};
                 a.Phi = c->Phi; a.T = c->T; a.ld = c->mp; a.Xr = c->tr.Xr + r0 * c->de; a.rowscal = c->rowscal + 4 * r0; a.n = rt.rows;
                 a.m = c->m; a.d = c->de; a.kind = c->kind; a.P = c->pr.P; a.w = c->w + (size_t)o * m;
@@ -381,6 +390,10 @@ int eval_tail(gpz_ctx *c, bool pinv) {
             HIPCHK(hipMemcpyAsync(scal + (size_t)o * 4, c->rstats, 4 * sizeof(double), hipMemcpyDeviceToDevice, c->st));
             const RowTile last = row_tile(c, c->ntiles - 1);
             const int nch = (c->ntiles - 1) * c->tile_nchunk + (last.rows + c->tile_rpc - 1) / c->tile_rpc;   // the last tile's chunks end the slab
+            if (c->mom_ring) {
+                launch_ring_finish(c->st, c->mom_slab, nch, c->m, c->de, c->pr.P, c->tr.xmu, c->nm, c->mp, mom, cols + (size_t)o * 2 * mp, o > 0 ? 1 : 0);
+                continue;
+            }
             launch_slab_sum(c->st, c->mom_slab, nch, m * (c->nm + 2), c->frec);
             launch_split_fused(c->st, c->frec, c->m, c->nm, c->mp, mom, cols + (size_t)o * 2 * mp, o > 0 ? 1 : 0);
             continue;
@@ -513,6 +526,15 @@ int eval_tail(gpz_ctx *c, bool pinv) {
                                        nr, c->pat_d, c->m, c->d, c->de, c->pr.P, c->Sig, nch, rpc, c->gen_slab, c->nrec, c->gen_ws);
                     launch_slab_sum(c->st, c->gen_slab, nch, m * c->nrec, recs_g);
                 }
+                continue;
+            }
+            if (c->mom_ring) {   // GC / VC, mp > 256: PHI and T through an LDS ring, raw sums about the column means (k_moments_ring.hip)
+                RingMomentArgs ra{};
+                ra.Phi = c->Phi; ra.T = c->T; ra.ld = c->mp; ra.Xs = c->tr.Xs; ra.rowscal = c->rowscal; ra.n = c->tr.n; ra.m = c->m; ra.d = c->de;
+                ra.w = c->w + (size_t)o * m; ra.v = c->hetero ? c->pr.v + (size_t)o * m : nullptr;
+                ra.nchunk = c->nchunk; ra.rows_per_chunk = c->rows_per_chunk; ra.slab = c->mom_slab;
+                if (launch_moments_ring(c->st, ra)) return gpz_fail(GPZ_ERR_HIP, "k_moments_ring launch failed (d=%d)", c->de);
+                launch_ring_finish(c->st, c->mom_slab, c->nchunk, c->m, c->de, c->pr.P, c->tr.xmu, c->nm, c->mp, mom, cols + (size_t)o * 2 * mp, o > 0 ? 1 : 0);
                 continue;
             }
             FusedMomentArgs a{};

@@ -250,6 +250,25 @@ struct FusedMomentArgs {
     const int *chunktab;            // as in MomentArgs
 };
 int launch_moments_fused(hipStream_t st, const FusedMomentArgs &a);
+// k_moments_ring.hip: the same sums for GC / VC with mp > 256 and d = 8 / 10 (no input noise, no missing values), PHI and T streamed
+// through an LDS ring by LDS-DMA; raw sums about the rows' column means, records [chunk][m][nf + 2] = [features | PHI'c | PHI'dbeta]
+struct RingMomentArgs {
+    const double *Phi, *T; int ld;
+    const double *Xs;          // n x (d + 2) rows [1 | x - mu | 0]
+    const double *rowscal;     // [n][4]: omega beta, c, dbeta, -
+    int n, m, d;
+    const double *w, *v;       // v may be nullptr
+    int nchunk, rows_per_chunk;
+    double *slab;
+};
+bool moments_ring_fits(int kind, int de, int mp);
+int moments_ring_cols();                                        // basis functions per workgroup (the chunk count is sized by it)
+int moments_ring_features(int de);                              // nf = 1 + d + d(d+1)/2
+int launch_moments_ring(hipStream_t st, const RingMomentArgs &a);   // 0, or -1 when the launch failed
+// the chunk records summed in a fixed order, converted to the sums about the basis centres (mom [m][nm], accumulated over outputs) and
+// split off the column sums (cols [2][mp]): what launch_slab_sum + launch_split_fused do for k_moments_fused's records
+void launch_ring_finish(hipStream_t st, const double *slab, int nrec, int m, int d, const double *P, const double *xmu, int nm, int mp,
+                        double *mom, double *cols, int accumulate);
 int launch_moments_wide(hipStream_t st, const MomentArgs &a);
 int launch_moments_fused_wide(hipStream_t st, const FusedMomentArgs &a);   // overwrites a.T with dPHI
 // split the reduced [m][nm+2] records into mom [m][nm] and cols [2][mp]

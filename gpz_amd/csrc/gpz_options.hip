@@ -43,6 +43,7 @@ gpz_options gpz_options_load() {
     o.syrk_small_off = env_set("GPZ_SYRK_SMALL_OFF");
     o.chol_rowinv_off = env_set("GPZ_CHOL_ROWINV_OFF");
     o.small_stagger = (int)env_long("GPZ_SMALL_STAGGER", 0);
+    o.moments_ring_off = env_set("GPZ_MOMENTS_RING_OFF");
 #endif
     return o;
 }

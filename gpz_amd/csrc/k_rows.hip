@@ -567,7 +567,9 @@ __global__ __launch_bounds__(256) void k_moments_fused(const double *__restrict_
 }
 
 #ifndef GPZ_MOM_UR
-#define GPZ_MOM_UR 4    // rows per register set (two sets; 6 or 8 drop the kernel to one wave per SIMD: 8.1 ms vs 4.8 ms at c4)
+#define GPZ_MOM_UR 4    // rows per register set (two sets; 6 or 8 drop the kernel to one wave per SIMD: 8.1 ms vs 4.8 ms at c4).  The registers that hold
+                        // the prefetch are the ones occupancy is paid in: 32 KB requested per CU = 4.0 TB/s at ~2.1 us.  GC / VC with mp > 256 and
+                        // d = 8 / 10 therefore take k_moments_ring.hip (rows through an LDS ring); this kernel serves every other shape
 #endif
 #ifndef GPZ_MOM_UR_DIAG
 #define GPZ_MOM_UR_DIAG 2   // diagonal kinds do ~4d flops per row: short row chunks, so a short pipeline (c2: 0.27 -> 0.20 ms)
