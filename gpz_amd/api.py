@@ -16,6 +16,7 @@ Everything numeric happens in libgpz_hip.so on the GPU; this file only marshals 
 from __future__ import annotations
 
 import ctypes as C
+from collections import namedtuple
 from dataclasses import dataclass, field
 from typing import Optional
 
@@ -622,6 +623,9 @@ def predict(X, model, whichSet="best", Psi=None, selection=None, device=0, n_gpu
 
 GPZ_PREDICT_FORCE_TILES = 1   # gpz_predictor_create flags (include/gpz_hip.h)
 GPZ_DRAWS_MAX_COLUMNS = 16384   # n_draws * k per gpz_predictor_draws call (include/gpz_hip.h)
+GPZ_STACK_MAX_GROUP_BINS = 4096   # n_groups * n_bins per gpz_predictor_stack call (include/gpz_hip.h)
+
+StackResult = namedtuple("StackResult", ["hist", "sum_w", "sum_mu", "sum_mu2", "edges"])
 
 
 class Predictor:
@@ -847,6 +851,110 @@ class Predictor:
         out = F.transpose(2, 0, 1)                                       # (n_draws, n, k) view
         out += np.asarray(model.muY, dtype=np.float64).reshape(k)        # predict.m:73
         return out
+
+
+    def stack(self, X, edges, n_draws=0, seed=0, Z=None, groups=None, n_groups=None, weights=None, selection=None):
+        """Stacked predictive densities on the device (gpz_predictor_stack): the n(z) of every group of rows under the posterior-mean
+        weights and under each of ``n_draws`` weight draws, without any per-row result leaving the GPU.
+
+        ``edges`` (B + 1 strictly increasing values in the units of y, the same for every output) are the bins; ``groups`` an integer
+        label per row in [-1, n_groups) (-1 leaves the row out; default: one group; ``n_groups`` defaults to max label + 1);
+        ``weights`` a weight >= 0 per row (default 1).  Column 0 uses ``predict``'s mu and sigma, column 1 + s uses ``draws``' draw s
+        (same ``seed`` / ``Z``) with the noise variance beta_i as its width.  Returns a StackResult:
+
+            hist     (1 + n_draws, G, k, B)   sum over the group's rows of weight * (normal mass of the row in the bin)
+            sum_w    (G,)                     sum of the weights
+            sum_mu   (1 + n_draws, G, k)      sum of weight * mu        (mu with muY, as ``predict`` returns it)
+            sum_mu2  (1 + n_draws, G, k)      sum of weight * mu^2
+            edges    (B + 1,)
+
+        ``sum_mu / sum_w`` is a group's mean under a column, and the spread of ``hist[1:]`` or of that mean over the draws is the error
+        from the finite training set.  Mass outside [edges[0], edges[-1]] is not counted.  Normalisation and ``selection`` (applied
+        to the rows, labels and weights alike) as in ``predict``.  Complete, noise-free rows only.  Every field but ``edges`` is a plain
+        sum over rows, so the results of several calls add: a catalogue read in chunks is a loop over ``stack`` and a ``+=`` per field.
+        The same call on the same handle returns the same bits every time; another ``tile_rows`` may change the last ones."""
+        if self._closed:
+            raise RuntimeError("Predictor is closed")
+        model, k, m = self.model, self._k, self._m
+        n_all = np.asarray(X).shape[0] if np.ndim(X) else 0             # rows before the selection: labels and weights go with them
+        X, _ = self._check_inputs(X, None, selection)
+        sel = None if selection is None else np.asarray(selection).astype(bool)
+        nbad = int(np.isnan(X).any(axis=1).sum()) if X.size else 0
+        if nbad:
+            raise ValueError(f"X has {nbad} rows with missing values (NaN): stacks are for complete rows")
+        e = np.asarray(edges, dtype=np.float64)
+        if e.ndim != 1 or e.size < 2:
+            raise ValueError(f"edges must be a vector of at least 2 values, got shape {e.shape}")
+        if not np.all(np.isfinite(e)) or not np.all(np.diff(e) > 0):
+            raise ValueError("edges must be finite and strictly increasing")
+        B = e.size - 1
+        if isinstance(n_draws, (bool, np.bool_)) or not isinstance(n_draws, (int, np.integer)) or n_draws < 0:
+            raise ValueError(f"n_draws must be a non-negative integer, got {n_draws!r}")
+        n_draws = int(n_draws)
+        if (1 + n_draws) * k > GPZ_DRAWS_MAX_COLUMNS:
+            raise ValueError(f"(1 + n_draws) * k = {(1 + n_draws) * k} is over the limit of {GPZ_DRAWS_MAX_COLUMNS} per call")
+        if isinstance(seed, (bool, np.bool_)) or not isinstance(seed, (int, np.integer)) or not 0 <= int(seed) < 2 ** 64:
+            raise ValueError(f"seed must be an integer in [0, 2^64), got {seed!r}")
+        z = None
+        if Z is not None:
+            if n_draws == 0:
+                raise ValueError("Z must be None when n_draws is 0")
+            z = np.asarray(Z, dtype=np.float64)
+            if k == 1 and z.shape == (m, n_draws):
+                z = z[:, :, None]
+            if z.shape != (m, n_draws, k):
+                want = f"({m}, {n_draws}, {k})" + (f" or ({m}, {n_draws})" if k == 1 else "")
+                raise ValueError(f"Z must have shape {want}, got {np.asarray(Z).shape}")
+            z = np.asfortranarray(z)
+        ns = X.shape[0]
+        lab = None
+        if groups is not None:
+            ga = np.asarray(groups)
+            if ga.shape != (n_all,) or ga.dtype.kind not in "iu":
+                raise ValueError(f"groups must be {n_all} integer labels")
+            if sel is not None:
+                ga = ga[sel]
+            top = int(ga.max()) + 1 if ga.size else 0
+            if n_groups is None:
+                n_groups = max(top, 1)
+            if ga.size and int(ga.min()) < -1:
+                raise ValueError("groups must be labels in [-1, n_groups)")
+        elif n_groups is None:
+            n_groups = 1
+        if isinstance(n_groups, (bool, np.bool_)) or not isinstance(n_groups, (int, np.integer)) or n_groups < 1:
+            raise ValueError(f"n_groups must be a positive integer, got {n_groups!r}")
+        G = int(n_groups)
+        if groups is not None:
+            if ga.size and int(ga.max()) >= G:
+                raise ValueError(f"groups must be labels in [-1, n_groups) with n_groups = {G}, got {int(ga.max())}")
+            lab = np.ascontiguousarray(ga, dtype=np.int32)
+        wt = None
+        if weights is not None:
+            wa = np.asarray(weights, dtype=np.float64)
+            if wa.shape != (n_all,):
+                raise ValueError(f"weights must be {n_all} values")
+            if sel is not None:
+                wa = wa[sel]
+            if not np.all(np.isfinite(wa)) or np.any(wa < 0):
+                raise ValueError("weights must be finite and >= 0")
+            wt = np.ascontiguousarray(wa)
+        if G * B > GPZ_STACK_MAX_GROUP_BINS:
+            raise ValueError(f"n_groups * bins = {G * B} is over the limit of {GPZ_STACK_MAX_GROUP_BINS} per call")
+        C_ = 1 + n_draws
+        muY = np.asarray(model.muY, dtype=np.float64).reshape(-1)
+        muY = np.broadcast_to(muY, (k,)) if muY.size == 1 else muY.reshape(k)
+        hist = np.zeros((C_, G, k, B)); sum_w = np.zeros(G); sum_mu = np.zeros((C_, G, k)); sum_mu2 = np.zeros((C_, G, k))
+        if ns:
+            Xn = np.empty(X.shape, order="F")                            # predict.m:35-36
+            np.subtract(X, model.muX, out=Xn)
+            np.divide(Xn, model.sdX, out=Xn)
+            es = np.ascontiguousarray(e[None, :] - muY[:, None])         # k x (B + 1): the entry's mu is without muY
+            h = self._handle()
+            _lib.check(self._lib.gpz_predictor_stack(h, _lib.dptr(Xn), ns, n_draws, int(seed), _lib.dptr(z), _lib.dptr(es), B,
+                                                     None if lab is None else lab.ctypes.data_as(_lib.c_int32_p), G, _lib.dptr(wt),
+                                                     _lib.dptr(hist), _lib.dptr(sum_w), _lib.dptr(sum_mu), _lib.dptr(sum_mu2),
+                                                     _lib.dptr(np.ascontiguousarray(muY))))   # predict.m:73 inside the sums
+        return StackResult(hist, sum_w, sum_mu, sum_mu2, e.copy())
 
 
 def getPrior(X, Psi, theta, model, selection=None, device=0, return_iterations=False):

@@ -142,6 +142,17 @@ void launch_draws_weights(hipStream_t st, const double *w, const double *R, cons
 void launch_draws_sym(hipStream_t st, const double *iS, int m, int mq, double *S, double *A);
 // after the Cholesky steps: R (m x m column-major) <- the lower factor in Lm; *ok = 1 unless a pivot failed or min L_jj^2 <= m eps max S_jj
 void launch_draws_chol_check(hipStream_t st, const double *Lm, int mq, const double *S, int m, const int *info, double *R, int *ok);
+// ---- stacked predictive densities per group and per column (k_predict_stack.hip; gpz_predictor_stack) ---------------------------
+// One tile: out [3k][nt] (mu, nu, beta) and dout [nd k][nt] (draw s of output o in row o nd + s) as the kernels above leave them, lab
+// (nt labels in [-1, G), nullptr: all 0), wt (nt weights, nullptr: all 1), edges [k][B + 1].  Column-output q = c k + o < (1 + nd) k:
+// c = 0 the posterior-mean weights (width^2 = nu + beta), c = 1 + s draw s (width^2 = beta).  Every one of the R row slabs writes a
+// record of G B bin masses + [G][3] sums of omega, omega y, omega y^2 with y = mu + shift[o] per q: slab [R][(1 + nd) k][G B + 3 G].  launch_stack_accum adds
+// the R slabs (count doubles each) to acc in slab order.  Both return -1 when the launch failed.
+size_t predict_stack_lds(int G, int B);
+int predict_stack_slabs(long Q, long rec, long T);   // R: a function of the column count, the record length and the tile rows only
+int launch_stack_tile(hipStream_t st, const double *out, const double *dout, const int *lab, const double *wt, const double *edges,
+                      const double *shift, long nt, int k, int nd, int B, int G, int R, double *slab);
+int launch_stack_accum(hipStream_t st, const double *slab, int R, size_t count, double *acc);
 // B (rows x ld row-major) <- [iS (m x m column-major) | nw columns of W from column wcol | nv columns of V (nullptr: 0) from vcol | 0]
 void launch_pred_fill_b(hipStream_t st, const double *iS, const double *W, int nw, int wcol, const double *V, int nv, int vcol, int m,
                         int rows, int ld, double *B);

@@ -17,6 +17,9 @@
 // predict-only handle holds what it held before:
 //   * draws route 0, fused: ceil16(m) <= 256 and an instantiated d - k_predict_draws writes the draws only (PHI never leaves LDS);
 //   * draws route 1, tiles: k_phi_* + k_tgemm with B = W (all n_draws * k columns in one product) + a transpose into the slot.
+// gpz_predictor_stack (stacked predictive densities per group, for the posterior-mean weights and per draw) runs predictor_tile and, with
+// draws, their kernels on the draws tile without any download, then k_stack_tile / k_stack_accum (k_predict_stack.hip); the accumulators
+// come home once at the end.  Its buffers (labels, weights, edges, accumulators, slabs) are allocated on the first stack call.
 // R_o is the Cholesky factor of the symmetric part S_o of iSigma_w(:, :, o) (k_chol_step); where it breaks down (a failed pivot, or
 // min L_jj^2 <= m eps max S_jj) it is V diag(sqrt(max(lambda, 0))) from the one-sided Jacobi sweeps of k_pinv.hip.
 #include <string>
@@ -56,6 +59,13 @@ struct gpz_predictor {
     bool w_seeded = false;         // Wd holds the draws of (w_seed, w_nd)
     unsigned long long w_seed = 0;
     int w_nd = 0;
+    // ---- stack (gpz_predictor_stack): nothing of this exists before the first stack call
+    int *lab_d[2] = {}, *hlab[2] = {};      // the tile's labels: device, pinned
+    double *wt_d[2] = {}, *hwt[2] = {};     // the tile's weights
+    double *edges_d = nullptr, *acc_d = nullptr, *slab_d = nullptr;
+    size_t edges_cap = 0, acc_cap = 0, slab_cap = 0;   // doubles
+    int64_t stile = 0;             // rows per stack tile (last call; 0: no stack call yet)
+    int sslabs = 0;                // row slabs per tile (last call)
 };
 
 namespace gpzi {
@@ -69,6 +79,8 @@ static void predictor_free(gpz_predictor *p) {
         if (p->hout[s]) (void)hipHostFree(p->hout[s]);
         if (p->hphi[s]) (void)hipHostFree(p->hphi[s]);
         if (p->hdout[s]) (void)hipHostFree(p->hdout[s]);
+        if (p->hlab[s]) (void)hipHostFree(p->hlab[s]);
+        if (p->hwt[s]) (void)hipHostFree(p->hwt[s]);
         if (p->ev_in[s]) (void)hipEventDestroy(p->ev_in[s]);
         if (p->ev_cmp[s]) (void)hipEventDestroy(p->ev_cmp[s]);
         if (p->ev_out[s]) (void)hipEventDestroy(p->ev_out[s]);
@@ -345,7 +357,8 @@ static int predictor_factor(gpz_predictor *p) {
     return 0;
 }
 
-// a device buffer of at least need doubles (a larger request takes a new block; the handle holds its blocks until it is destroyed)
+// a device buffer of at least need doubles (a larger request takes a new block; the handle holds its blocks until it is destroyed, the
+// outgrown one too: calls with ever larger shapes keep every earlier block, and the stack's accumulators and slabs can be 128 MiB each)
 static int predictor_grow(gpz_predictor *p, double **buf, size_t *cap, size_t need) {
     if (*buf && *cap >= need) return 0;
     if (int rc = p->ar.alloc(buf, need)) return rc;
@@ -353,10 +366,10 @@ static int predictor_grow(gpz_predictor *p, double **buf, size_t *cap, size_t ne
     return 0;
 }
 
-static int predictor_run_draws(gpz_predictor *p, const double *Xs, int64_t ns, int nd, unsigned long long seed, const double *Z,
-                               double *F) {
-    const int k = p->k, d = p->d, m = p->m, ncol = nd * k, ldw = rup(ncol, 16);
-    const size_t tp = (size_t)p->tile_pad;
+// what a call with nd draws needs before its first tile: the factors (once per handle), W for (seed, Z), the draws tile *Tout and the
+// device buffers of that tile; the pinned slots too when the draws themselves go home (pinned)
+static int predictor_draws_prepare(gpz_predictor *p, int nd, unsigned long long seed, const double *Z, bool pinned, int64_t *Tout) {
+    const int k = p->k, m = p->m, ncol = nd * k, ldw = rup(ncol, 16);
     hipStream_t st = p->s_cmp;
     int rc = 0;
     if (p->droute < 0) {
@@ -391,7 +404,7 @@ static int predictor_run_draws(gpz_predictor *p, const double *Xs, int64_t ns, i
             if ((rc = p->ar.alloc(&p->dout[s], slot))) return rc;
         p->dout_cap = slot;
     }
-    if (p->hdout_cap < slot) {
+    if (pinned && p->hdout_cap < slot) {
         for (int s = 0; s < 2; ++s) {
             if (p->hdout[s]) (void)hipHostFree(p->hdout[s]);
             p->hdout[s] = nullptr;
@@ -401,6 +414,45 @@ static int predictor_run_draws(gpz_predictor *p, const double *Xs, int64_t ns, i
         p->hdout_cap = slot;
     }
     if (p->droute == 1 && (rc = predictor_grow(p, &p->Td, &p->t_cap, (size_t)rup(T, 1024) * ldw))) return rc;
+    *Tout = T;
+    return 0;
+}
+
+// the draws kernels of one tile of nt rows: Xc[s] -> dout[s] ([nd k][nt]).  phi_built: predictor_tile has just run on the same slot and
+// rows on the tile route, so p->Phi already holds this tile's PHI (the same launch_phi with the same arguments; launch_tgemm only reads it)
+static int predictor_draws_tile(gpz_predictor *p, int s, int64_t nt, int ncol, int ldw, bool phi_built = false) {
+    const int k = p->k, m = p->m;
+    hipStream_t st = p->s_cmp;
+    const double *G = p->kind == GPZ_KIND_COV ? p->pr.Rc : p->pr.G2;
+    if (p->droute == 0) {
+        if (launch_predict_draws(st, p->kind, p->de, p->Xc[s], p->tile_pad, (int)nt, m, p->pr.P, G, p->Wd, ldw, ncol, p->dout[s], nt))
+            return gpz_fail(GPZ_ERR_HIP, "gpz_predictor_draws: k_predict_draws launch failed");
+        return 0;
+    }
+    const long np = rup(nt, 1024);
+    PhiArgs a{};
+    a.Xc = p->Xc[s]; a.ldx = p->tile_pad; a.n = (int)nt; a.n_pad = (int)np;
+    a.m = m; a.mp = p->mp; a.d = p->de; a.k = k; a.kind = p->kind;
+    a.P = p->pr.P; a.G = G;
+    a.v = p->hetero ? p->pr.v : nullptr; a.b = p->pr.b;
+    a.Phi = p->Phi; a.lnbeta = p->lnbeta;
+    if (!phi_built && launch_phi(st, a))
+        return gpz_fail(GPZ_ERR_UNSUPPORTED, "gpz_predictor_draws: PHI kernel not instantiated for d=%d", p->de);
+    // T = PHI W: K = mp (rows >= m of W are zero), ldw output columns
+    launch_tgemm(st, p->Phi, p->mp, p->Wd, ldw, p->Td, (int)np, ldw, nullptr, nullptr, m, 0, false, p->mp, ldw);
+    launch_transpose_out(st, p->Td, ldw, nt, ncol, p->dout[s]);
+    if (hipGetLastError() != hipSuccess) return gpz_fail(GPZ_ERR_HIP, "gpz_predictor_draws: kernel launch failed");
+    return 0;
+}
+
+static int predictor_run_draws(gpz_predictor *p, const double *Xs, int64_t ns, int nd, unsigned long long seed, const double *Z,
+                               double *F) {
+    const int k = p->k, d = p->d, ncol = nd * k, ldw = rup(ncol, 16);
+    const size_t tp = (size_t)p->tile_pad;
+    hipStream_t st = p->s_cmp;
+    int rc = 0;
+    int64_t T = 0;
+    if ((rc = predictor_draws_prepare(p, nd, seed, Z, true, &T))) return rc;
     // ---- the pipeline of predictor_run_full on tiles of T rows
     const int64_t ntiles = (ns + T - 1) / T;
     int64_t nt_of[2] = {0, 0}, r0_of[2] = {0, 0};
@@ -440,29 +492,7 @@ static int predictor_run_draws(gpz_predictor *p, const double *Xs, int64_t ns, i
             rc = gpz_fail(GPZ_ERR_HIP, "gpz_predictor_draws: copy failed");
             break;
         }
-        const double *G = p->kind == GPZ_KIND_COV ? p->pr.Rc : p->pr.G2;
-        if (p->droute == 0) {
-            if (launch_predict_draws(st, p->kind, p->de, p->Xc[s], p->tile_pad, (int)nt, m, p->pr.P, G, p->Wd, ldw, ncol, p->dout[s], nt)) {
-                rc = gpz_fail(GPZ_ERR_HIP, "gpz_predictor_draws: k_predict_draws launch failed");
-                break;
-            }
-        } else {
-            const long np = rup(nt, 1024);
-            PhiArgs a{};
-            a.Xc = p->Xc[s]; a.ldx = p->tile_pad; a.n = (int)nt; a.n_pad = (int)np;
-            a.m = m; a.mp = p->mp; a.d = p->de; a.k = k; a.kind = p->kind;
-            a.P = p->pr.P; a.G = G;
-            a.v = p->hetero ? p->pr.v : nullptr; a.b = p->pr.b;
-            a.Phi = p->Phi; a.lnbeta = p->lnbeta;
-            if (launch_phi(st, a)) {
-                rc = gpz_fail(GPZ_ERR_UNSUPPORTED, "gpz_predictor_draws: PHI kernel not instantiated for d=%d", p->de);
-                break;
-            }
-            // T = PHI W: K = mp (rows >= m of W are zero), ldw output columns
-            launch_tgemm(st, p->Phi, p->mp, p->Wd, ldw, p->Td, (int)np, ldw, nullptr, nullptr, m, 0, false, p->mp, ldw);
-            launch_transpose_out(st, p->Td, ldw, nt, ncol, p->dout[s]);
-            if (hipGetLastError() != hipSuccess) { rc = gpz_fail(GPZ_ERR_HIP, "gpz_predictor_draws: kernel launch failed"); break; }
-        }
+        if ((rc = predictor_draws_tile(p, s, nt, ncol, ldw))) break;
         if (hipEventRecord(p->ev_cmp[s], st) != hipSuccess || hipStreamWaitEvent(p->s_out, p->ev_cmp[s], 0) != hipSuccess ||
             hipMemcpyAsync(p->hdout[s], p->dout[s], (size_t)ncol * nt * sizeof(double), hipMemcpyDeviceToHost, p->s_out) != hipSuccess ||
             hipEventRecord(p->ev_out[s], p->s_out) != hipSuccess) {
@@ -472,6 +502,86 @@ static int predictor_run_draws(gpz_predictor *p, const double *Xs, int64_t ns, i
     }
     for (hipStream_t q : {p->s_in, p->s_cmp, p->s_out})
         if (hipStreamSynchronize(q) != hipSuccess && !rc) rc = gpz_fail(GPZ_ERR_HIP, "gpz_predictor_draws: sync failed");
+    return rc;
+}
+
+// ---- stack ------------------------------------------------------------------------------------------------------------------------
+// Per tile: rows, labels and weights up; predictor_tile (mu, nu, beta stay in out[s]); with draws, their kernels (F stays in dout[s]);
+// k_stack_tile writes the tile's row slabs and k_stack_accum adds them to the running accumulators, all on the compute stream, so the
+// tiles add in their order.  Nothing comes back before the accumulators at the end.  Both kernels run on the draws tile, so that out[s]
+// and dout[s] describe the same rows.  res: (1 + nd) k records of G B + 3 G doubles (k_predict_stack.hip).
+static int predictor_run_stack(gpz_predictor *p, const double *Xs, int64_t ns, int nd, unsigned long long seed, const double *Z,
+                               const double *edges, const double *shift, int B, const int32_t *group, int G, const double *weight,
+                               double *res) {
+    const int k = p->k, d = p->d, ncol = nd * k, ldw = rup(ncol, 16), Q = (1 + nd) * k;
+    const size_t tp = (size_t)p->tile_pad, rec = (size_t)G * B + 3 * (size_t)G, count = (size_t)Q * rec;
+    hipStream_t st = p->s_cmp;
+    int rc = 0;
+    int64_t T = p->tile_rows;
+    if (nd > 0 && (rc = predictor_draws_prepare(p, nd, seed, Z, false, &T))) return rc;
+    for (int s = 0; s < 2; ++s) {   // each one where it is missing: a call that failed half-way here leaves the next one its rest
+        if (!p->lab_d[s] && (rc = p->ar.alloc(&p->lab_d[s], tp))) return rc;
+        if (!p->wt_d[s] && (rc = p->ar.alloc(&p->wt_d[s], tp))) return rc;
+        if (!p->hlab[s]) HIPCHK(hipHostMalloc((void **)&p->hlab[s], tp * sizeof(int), hipHostMallocDefault));
+        if (!p->hwt[s]) HIPCHK(hipHostMalloc((void **)&p->hwt[s], tp * sizeof(double), hipHostMallocDefault));
+    }
+    const int R = predict_stack_slabs(Q, (long)rec, T);
+    const size_t ne = (size_t)k * (B + 1);   // the edges, then the k shifts of the sums
+    if ((rc = predictor_grow(p, &p->edges_d, &p->edges_cap, ne + k))) return rc;
+    if ((rc = predictor_grow(p, &p->acc_d, &p->acc_cap, count))) return rc;
+    if ((rc = predictor_grow(p, &p->slab_d, &p->slab_cap, count * R))) return rc;
+    p->stile = T;
+    p->sslabs = R;
+    // from here on every failure leaves through the synchronisation of the three streams below: copies from the caller's memory are in flight
+    if (hipMemcpyAsync(p->edges_d, edges, ne * sizeof(double), hipMemcpyHostToDevice, st) != hipSuccess ||
+        (shift ? hipMemcpyAsync(p->edges_d + ne, shift, (size_t)k * sizeof(double), hipMemcpyHostToDevice, st)
+               : hipMemsetAsync(p->edges_d + ne, 0, (size_t)k * sizeof(double), st)) != hipSuccess ||
+        hipMemsetAsync(p->acc_d, 0, count * sizeof(double), st) != hipSuccess)
+        rc = gpz_fail(GPZ_ERR_HIP, "gpz_predictor_stack: copy failed");
+    const int64_t ntiles = rc ? 0 : (ns + T - 1) / T;
+    for (int64_t t = 0; t < ntiles && !rc; ++t) {
+        const int s = (int)(t & 1);
+        // tile t - 2's upload has left the pinned slot
+        if (t >= 2 && hipEventSynchronize(p->ev_in[s]) != hipSuccess) { rc = gpz_fail(GPZ_ERR_HIP, "gpz_predictor_stack: tile failed"); break; }
+        const int64_t r0 = t * T, nt = std::min<int64_t>(T, ns - r0);
+        bool bad = false;
+        for (int c = 0; c < d; ++c) {
+            const double *src = Xs + (size_t)c * ns + r0;
+            double *dst = p->hin[s] + (size_t)c * tp;
+            int nan = 0;
+            for (int64_t i = 0; i < nt; ++i) { const double v = src[i]; dst[i] = v; nan |= v != v; }
+            bad |= nan != 0;
+        }
+        if (bad) {
+            rc = gpz_fail(GPZ_ERR_UNSUPPORTED, "gpz_predictor_stack: the rows have missing values (NaN): stacks are for complete rows");
+            break;
+        }
+        if (group) memcpy(p->hlab[s], group + r0, (size_t)nt * sizeof(int));
+        if (weight) memcpy(p->hwt[s], weight + r0, (size_t)nt * sizeof(double));
+        // copies in (after tile t - 2's kernels are done with the slot); kernels (after the copies)
+        if (hipStreamWaitEvent(p->s_in, p->ev_cmp[s], 0) != hipSuccess ||
+            hipMemcpy2DAsync(p->Xc[s], tp * sizeof(double), p->hin[s], tp * sizeof(double), (size_t)nt * sizeof(double), d,
+                             hipMemcpyHostToDevice, p->s_in) != hipSuccess ||
+            (group && hipMemcpyAsync(p->lab_d[s], p->hlab[s], (size_t)nt * sizeof(int), hipMemcpyHostToDevice, p->s_in) != hipSuccess) ||
+            (weight && hipMemcpyAsync(p->wt_d[s], p->hwt[s], (size_t)nt * sizeof(double), hipMemcpyHostToDevice, p->s_in) != hipSuccess) ||
+            hipEventRecord(p->ev_in[s], p->s_in) != hipSuccess || hipStreamWaitEvent(st, p->ev_in[s], 0) != hipSuccess) {
+            rc = gpz_fail(GPZ_ERR_HIP, "gpz_predictor_stack: copy failed");
+            break;
+        }
+        if ((rc = predictor_tile(p, s, (int)nt, false))) break;
+        if (nd > 0 && (rc = predictor_draws_tile(p, s, nt, ncol, ldw, p->route == 1))) break;
+        if (launch_stack_tile(st, p->out[s], nd > 0 ? p->dout[s] : nullptr, group ? p->lab_d[s] : nullptr, weight ? p->wt_d[s] : nullptr,
+                              p->edges_d, p->edges_d + ne, nt, k, nd, B, G, R, p->slab_d) ||
+            launch_stack_accum(st, p->slab_d, R, count, p->acc_d)) {
+            rc = gpz_fail(GPZ_ERR_HIP, "gpz_predictor_stack: k_stack_tile launch failed");
+            break;
+        }
+        if (hipEventRecord(p->ev_cmp[s], st) != hipSuccess) { rc = gpz_fail(GPZ_ERR_HIP, "gpz_predictor_stack: event failed"); break; }
+    }
+    if (!rc && hipMemcpyAsync(res, p->acc_d, count * sizeof(double), hipMemcpyDeviceToHost, st) != hipSuccess)
+        rc = gpz_fail(GPZ_ERR_HIP, "gpz_predictor_stack: copy failed");
+    for (hipStream_t q : {p->s_in, p->s_cmp, p->s_out})
+        if (hipStreamSynchronize(q) != hipSuccess && !rc) rc = gpz_fail(GPZ_ERR_HIP, "gpz_predictor_stack: sync failed");
     return rc;
 }
 }   // namespace gpzi
@@ -563,6 +673,68 @@ extern "C" int gpz_predictor_draws(gpz_predictor *p, const double *Xs, int64_t n
     return rc;
 }
 
+extern "C" int gpz_predictor_stack(gpz_predictor *p, const double *Xs, int64_t ns, int32_t ndraws, uint64_t seed, const double *Z,
+                                   const double *edges, int32_t nbins, const int32_t *group, int32_t ngroups, const double *weight,
+                                   double *hist, double *sum_w, double *sum_mu, double *sum_mu2, const double *mu_shift) {
+    if (!p) return gpz_fail(GPZ_ERR_ARG, "gpz_predictor_stack: null handle");
+    if (ns < 0) return gpz_fail(GPZ_ERR_ARG, "gpz_predictor_stack: ns < 0");
+    if (ndraws < 0 || (1 + (int64_t)ndraws) * p->k > GPZ_DRAWS_MAX_COLUMNS)
+        return gpz_fail(GPZ_ERR_ARG, "gpz_predictor_stack: need 0 <= ndraws and (1 + ndraws) * k <= %d (ndraws %d, k %d)",
+                        GPZ_DRAWS_MAX_COLUMNS, (int)ndraws, p->k);
+    if (nbins < 1 || ngroups < 1) return gpz_fail(GPZ_ERR_ARG, "gpz_predictor_stack: need nbins >= 1 and ngroups >= 1");
+    if ((int64_t)nbins * ngroups > GPZ_STACK_MAX_GROUP_BINS)
+        return gpz_fail(GPZ_ERR_ARG, "gpz_predictor_stack: ngroups * nbins = %lld is over GPZ_STACK_MAX_GROUP_BINS = %d",
+                        (long long)nbins * ngroups, GPZ_STACK_MAX_GROUP_BINS);
+    const int k = p->k, B = nbins, G = ngroups, C = 1 + ndraws;
+    if (!edges || !hist || !sum_w || !sum_mu || !sum_mu2) return gpz_fail(GPZ_ERR_ARG, "gpz_predictor_stack: null argument");
+    for (int o = 0; o < k; ++o)
+        for (int j = 0; j <= B; ++j) {
+            const double e = edges[(size_t)o * (B + 1) + j];
+            if (!std::isfinite(e) || (j > 0 && !(e > edges[(size_t)o * (B + 1) + j - 1])))
+                return gpz_fail(GPZ_ERR_ARG, "gpz_predictor_stack: the edges must be finite and strictly increasing (output %d, edge %d)", o, j);
+        }
+    if (ns > 0 && !Xs) return gpz_fail(GPZ_ERR_ARG, "gpz_predictor_stack: null argument");
+    if (group)
+        for (int64_t i = 0; i < ns; ++i)
+            if (group[i] < -1 || group[i] >= G)
+                return gpz_fail(GPZ_ERR_ARG, "gpz_predictor_stack: label %d of row %lld is outside [-1, %d)", (int)group[i], (long long)i, G);
+    if (mu_shift)
+        for (int o = 0; o < k; ++o)
+            if (!std::isfinite(mu_shift[o])) return gpz_fail(GPZ_ERR_ARG, "gpz_predictor_stack: mu_shift must be finite");
+    if (weight)
+        for (int64_t i = 0; i < ns; ++i)
+            if (!(weight[i] >= 0.0) || !std::isfinite(weight[i]))
+                return gpz_fail(GPZ_ERR_ARG, "gpz_predictor_stack: the weight of row %lld is negative or not finite", (long long)i);
+    const size_t GB = (size_t)G * B, rec = GB + 3 * (size_t)G, Q = (size_t)C * k;
+    memset(hist, 0, Q * GB * sizeof(double));
+    memset(sum_w, 0, (size_t)G * sizeof(double));
+    memset(sum_mu, 0, Q * G * sizeof(double));
+    memset(sum_mu2, 0, Q * G * sizeof(double));
+    if (ns == 0) return 0;
+    std::vector<double> res(Q * rec);
+    int prev = 0;
+    (void)hipGetDevice(&prev);
+    gpz_opts_scope opts_scope(&p->opt);
+    int rc = 0;
+    if (hipSetDevice(p->device) != hipSuccess) rc = gpz_fail(GPZ_ERR_HIP, "gpz_predictor_stack: hipSetDevice failed");
+    if (!rc) rc = predictor_run_stack(p, Xs, ns, (int)ndraws, (unsigned long long)seed, Z, edges, mu_shift, B, group, G, weight, res.data());
+    (void)hipSetDevice(prev);
+    if (rc) return rc;
+    // records [c][o][G B + 3 G] -> hist [c][g][o][B], sums [c][g][o]; the sum of the weights is the same in every record
+    for (int c = 0; c < C; ++c)
+        for (int o = 0; o < k; ++o) {
+            const double *r = res.data() + ((size_t)c * k + o) * rec;
+            for (int g = 0; g < G; ++g) {
+                const size_t at = ((size_t)c * G + g) * k + o;
+                memcpy(hist + at * B, r + (size_t)g * B, (size_t)B * sizeof(double));
+                sum_mu[at] = r[GB + 3 * (size_t)g + 1];
+                sum_mu2[at] = r[GB + 3 * (size_t)g + 2];
+                if (c == 0 && o == 0) sum_w[g] = r[GB + 3 * (size_t)g];
+            }
+        }
+    return 0;
+}
+
 extern "C" int gpz_predictor_route(const gpz_predictor *p, char *buf, int cap) {
     if (!p || !buf || cap < 1) return gpz_fail(GPZ_ERR_ARG, "gpz_predictor_route: null argument");
     char tmp[160];
@@ -576,6 +748,10 @@ extern "C" int gpz_predictor_route(const gpz_predictor *p, char *buf, int cap) {
                  (long long)p->dtile);
         r += tmp;
         for (size_t o = 0; o < p->fkind.size(); ++o) r += p->fkind[o] ? " eigen" : " cholesky";
+    }
+    if (p->stile > 0) {   // after a stack call
+        snprintf(tmp, sizeof tmp, "; stack: k_stack_tile + k_stack_accum, %lld-row tiles, %d row slabs", (long long)p->stile, p->sslabs);
+        r += tmp;
     }
     snprintf(buf, (size_t)cap, "%s", r.c_str());
     return (int)r.size();

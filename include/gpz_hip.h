@@ -237,6 +237,36 @@ int gpz_predictor_info(const gpz_predictor *p, int64_t out[4]);
 int gpz_predictor_draws(gpz_predictor *p, const double *Xs, int64_t ns, int32_t ndraws, uint64_t seed,
                         const double *Z /* NULL or m x ndraws x k */, double *F /* ns x k x ndraws, column-major */);
 
+/* ---- stacked predictive densities through a predictor handle: n(z) per group, for the posterior-mean weights and per draw --------
+ * Rows i of Xs (complete, noise-free, as for gpz_predictor_draws), outputs o < k, edges e_0 < .. < e_nbins per output, a label
+ * g_i in {-1, 0 .. ngroups-1} per row (-1: the row is left out; group = NULL: every row in group 0), a weight omega_i >= 0 per row
+ * (weight = NULL: 1).  Columns c = 0 .. ndraws:
+ *   c = 0      mu = gpz_predictor_run's mu, width^2 = nu + beta_i (the predictive variance, gamma = 0 for these rows);
+ *   c = 1 + s  mu = gpz_predictor_draws' F(i, o, s) for the same seed / Z, width^2 = beta_i (the weight uncertainty is in the draw).
+ *   hist[c, g, o, j]  = sum over the rows of group g of omega_i (Phi((e_{j+1} - mu) / width) - Phi((e_j - mu) / width))
+ *   sum_w[g]          = sum omega_i      sum_mu[c, g, o] = sum omega_i mu      sum_mu2[c, g, o] = sum omega_i mu^2
+ * edges: k x (nbins + 1), output o's edges at edges[o * (nbins + 1) ..], in the units of mu as this entry sees it: WITHOUT muY, so a
+ * caller with edges in the units of y passes e - muY[o]; sum_mu and sum_mu2 are sums of that mu (without muY) too when mu_shift is
+ * NULL.  mu_shift (k values, the caller's muY) is added to every mu before it enters sum_mu and sum_mu2, and to nothing else: shifting
+ * the finished sums instead (sum mu^2 + 2 muY sum mu + muY^2 sum omega) cancels where a group's mu + muY is small against muY, and a
+ * group of a few rows then loses digits that the sums of mu + muY keep.  Mass outside
+ * [e_0, e_nbins] is not counted, and a bin further than 9 widths from a row's mu gets none of that row (less than 1.2e-19 omega_i).
+ * Layouts, the last index fastest: hist [1 + ndraws][ngroups][k][nbins], sum_w [ngroups], sum_mu and sum_mu2 [1 + ndraws][ngroups][k].
+ * Per-row results never leave the device; what comes back does not depend on ns, and the results of several calls add.  The same
+ * call on the same handle gives the same bits every time (partial sums per slab of rows, added in a fixed order); another tile size
+ * may change the last bits.  ns = 0 returns zeros.
+ * GPZ_ERR_ARG: edges not finite or not strictly increasing, nbins < 1, ngroups < 1, a label outside [-1, ngroups), a negative or
+ * non-finite weight, ndraws < 0, (1 + ndraws) * k > GPZ_DRAWS_MAX_COLUMNS, ngroups * nbins > GPZ_STACK_MAX_GROUP_BINS (the histogram
+ * of one column lives in one workgroup's LDS; with the column limit that is at most 2^26 cells per call).  Rows with NaN:
+ * GPZ_ERR_UNSUPPORTED.  ndraws = 0 forms no factors and allocates no draws buffer; the stack buffers are allocated on the first call
+ * (gpz_predictor_info's bytes include them) and gpz_predictor_route then appends a stack clause.  A call with a larger shape takes
+ * larger accumulator and slab blocks and the handle keeps the outgrown ones until it is destroyed. */
+#define GPZ_STACK_MAX_GROUP_BINS 4096
+int gpz_predictor_stack(gpz_predictor *p, const double *Xs, int64_t ns, int32_t ndraws, uint64_t seed,
+                        const double *Z /* NULL or m x ndraws x k */, const double *edges /* k x (nbins + 1), muY already subtracted */,
+                        int32_t nbins, const int32_t *group /* ns or NULL */, int32_t ngroups, const double *weight /* ns or NULL */,
+                        double *hist, double *sum_w, double *sum_mu, double *sum_mu2, const double *mu_shift /* k or NULL */);
+
 /* ---- device-resident L-BFGS memory: minFunc's lbfgsAdd.m / lbfgsProd.m (mex/lbfgsAddC.c, mex/lbfgsProdC.c) ----
  * S and Y (p x corrections) live on the device; all vector arguments are device pointers.
  * gpz_lbfgs_add:        y = g - g_old, s = t*d; skipped (added = 0) when y's <= 1e-10        (lbfgsAdd.m:2-4)
