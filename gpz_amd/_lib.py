@@ -83,6 +83,14 @@ SYMBOLS = {
     "gpz_predictor_draws": (C.c_int, [C.c_void_p, c_double_p, C.c_int64, C.c_int32, C.c_uint64, c_double_p, c_double_p]),
     "gpz_predictor_stack": (C.c_int, [C.c_void_p, c_double_p, C.c_int64, C.c_int32, C.c_uint64, c_double_p, c_double_p, C.c_int32,
                                       c_int32_p, C.c_int32, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p]),
+    # device-resident entries: X_d and every *_d argument are device addresses (void*), strides in elements, the last one a hipStream_t
+    "gpz_predictor_run_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int64, c_double_p, c_double_p,
+                                        c_double_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gpz_predictor_draws_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int64, c_double_p, c_double_p,
+                                          c_double_p, C.c_int32, C.c_uint64, c_double_p, C.c_void_p, C.c_void_p]),
+    "gpz_predictor_stack_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int64, c_double_p, c_double_p,
+                                          C.c_int32, C.c_uint64, c_double_p, c_double_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p,
+                                          c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, C.c_void_p]),
     "gpz_prior": (C.c_int, [C.POINTER(gpz_desc), c_double_p, c_double_p, C.c_int64, c_double_p, C.c_int32, c_double_p,
                             c_int32_p]),
     "gpz_inv_logdet": (C.c_int, [c_double_p, C.c_int32, C.c_int32, c_double_p, c_double_p, c_int32_p]),

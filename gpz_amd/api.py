@@ -956,6 +956,187 @@ class Predictor:
                                                      _lib.dptr(np.ascontiguousarray(muY))))   # predict.m:73 inside the sums
         return StackResult(hist, sum_w, sum_mu, sum_mu2, e.copy())
 
+    # ---- device-resident entries: the catalogue is a torch tensor on the handle's GPU, per-row results stay there -------------------
+    def _check_dev_rows(self, X, selection, what):
+        """X (and the mask) of a *_dev call by type, dtype and shape; nothing here touches a GPU.  Returns X as n x d."""
+        import torch
+        d = self._d
+        if isinstance(X, np.ndarray):
+            raise TypeError(f"{what}_dev takes a torch tensor on cuda:{self.device}; a NumPy array goes to Predictor.{what}")
+        if not isinstance(X, torch.Tensor):
+            raise TypeError(f"X must be a torch.Tensor on cuda:{self.device}, got {type(X).__name__}")
+        if X.dtype not in (torch.float64, torch.float32):
+            raise TypeError(f"X must be float64 or float32, got {X.dtype}")
+        if X.dim() == 1 and d == 1:
+            X = X[:, None]
+        if X.dim() != 2 or X.shape[1] != d:
+            raise ValueError(f"X must be n x {d}, got shape {tuple(X.shape)}")
+        if selection is not None:
+            if not isinstance(selection, torch.Tensor) or selection.dtype != torch.bool:
+                raise TypeError("selection must be a bool torch tensor on the same device as X")
+            if tuple(selection.shape) != (X.shape[0],):
+                raise ValueError(f"selection must be a mask of length {X.shape[0]}")
+        return X
+
+    def _check_dev_device(self, **tensors):
+        """Every tensor of a *_dev call lives on cuda:<self.device> (checked after the shapes and before the GPU is touched)."""
+        for name, t in tensors.items():
+            if t is None:
+                continue
+            if not t.is_cuda:
+                raise ValueError(f"{name} must be on cuda:{self.device}, it is on {t.device}: the host methods take host arrays")
+            if t.device.index != self.device:
+                raise ValueError(f"{name} is on {t.device}, the predictor on cuda:{self.device}")
+
+    def _check_draw_args(self, n_draws, seed, Z, least):
+        k, m = self._k, self._m
+        if isinstance(n_draws, (bool, np.bool_)) or not isinstance(n_draws, (int, np.integer)) or n_draws < least:
+            raise ValueError(f"n_draws must be a {'positive' if least else 'non-negative'} integer, got {n_draws!r}")
+        n_draws = int(n_draws)
+        if (1 - least + n_draws) * k > GPZ_DRAWS_MAX_COLUMNS:
+            raise ValueError(f"{'n_draws' if least else '(1 + n_draws)'} * k = {(1 - least + n_draws) * k} is over the limit of "
+                             f"{GPZ_DRAWS_MAX_COLUMNS} per call")
+        if isinstance(seed, (bool, np.bool_)) or not isinstance(seed, (int, np.integer)) or not 0 <= int(seed) < 2 ** 64:
+            raise ValueError(f"seed must be an integer in [0, 2^64), got {seed!r}")
+        z = None
+        if Z is not None:
+            if n_draws == 0:
+                raise ValueError("Z must be None when n_draws is 0")
+            z = np.asarray(Z, dtype=np.float64)
+            if k == 1 and z.shape == (m, n_draws):
+                z = z[:, :, None]
+            if z.shape != (m, n_draws, k):
+                want = f"({m}, {n_draws}, {k})" + (f" or ({m}, {n_draws})" if k == 1 else "")
+                raise ValueError(f"Z must have shape {want}, got {np.asarray(Z).shape}")
+            z = np.asfortranarray(z)
+        return n_draws, z
+
+    def _norm_vectors(self):
+        """model.muX, model.sdX (d values each) and model.muY (k values) as contiguous float64 host vectors."""
+        def vec(a, n):
+            a = np.asarray(a, dtype=np.float64).reshape(-1)
+            return np.ascontiguousarray(np.broadcast_to(a, (n,)) if a.size == 1 else a.reshape(n))
+        return vec(self.model.muX, self._d), vec(self.model.sdX, self._d), vec(self.model.muY, self._k)
+
+    @staticmethod
+    def _x_args(X):
+        """(address, element type, rows, row stride, column stride) of gpz_predictor_*_dev: the tensor as it lies, never copied."""
+        import torch
+        return X.data_ptr(), 1 if X.dtype == torch.float32 else 0, X.shape[0], X.stride(0), X.stride(1)
+
+    def predict_dev(self, X, selection=None, return_phi=False):
+        """``predict`` for a catalogue that is on the GPU already (gpz_predictor_run_dev): X is a float64 or float32 torch tensor of
+        shape (n, d) on cuda:<device> with any strides (row-major as torch makes it, a transposed or sliced view: it is read as it lies,
+        never copied), ``selection`` a bool tensor there.  Returns mu, sigma, nu, beta_i, gamma [, PHI] as float64 tensors of shape
+        (n, k) [(n, m)] on the same device, column-major (``.T`` of a contiguous (k, n) tensor).  Same meaning and, for the same rows,
+        the same bits as ``predict``: normalisation by model.muX / sdX, + muY, sigma = nu + beta_i + gamma.  No row and no result
+        crosses to the host.  The call is ordered after the work queued on torch's current stream of that device (no synchronise is
+        needed before it) and is complete when it returns.  Complete, noise-free rows only: rows with NaN are refused (GpzError).
+        Type, dtype and shape are checked first, the device last, all before the GPU is touched."""
+        import torch
+        if self._closed:
+            raise RuntimeError("Predictor is closed")
+        k, m = self._k, self._m
+        X = self._check_dev_rows(X, selection, "predict")
+        self._check_dev_device(X=X, selection=selection)
+        if selection is not None:
+            X = X[selection]                                             # predict.m:25
+        n = X.shape[0]
+        # the tensors are referenced by this frame for the whole call, which returns when the device is done: no record_stream needed
+        out = [torch.empty((k, n), dtype=torch.float64, device=X.device).T for _ in range(5)]
+        PHI = torch.empty((m, n), dtype=torch.float64, device=X.device).T if return_phi else None
+        if n:
+            muX, sdX, muY = self._norm_vectors()
+            h = self._handle()
+            _lib.check(self._lib.gpz_predictor_run_dev(h, *self._x_args(X), _lib.dptr(muX), _lib.dptr(sdX), _lib.dptr(muY),
+                                                       *(t.data_ptr() for t in out), None if PHI is None else PHI.data_ptr(),
+                                                       torch.cuda.current_stream(X.device).cuda_stream))
+        return tuple(out) + (PHI,) if return_phi else tuple(out)
+
+    def draws_dev(self, X, n_draws, seed=0, Z=None, selection=None):
+        """``draws`` for a catalogue on the GPU (gpz_predictor_draws_dev): X and ``selection`` as for ``predict_dev``, ``n_draws``,
+        ``seed`` and ``Z`` (a host array: it is m x n_draws x k) as for ``draws``.  Returns a float64 tensor of shape (n_draws, n, k) on
+        the device, a view of the column-major n x k x n_draws buffer, with the bits of ``draws`` for the same rows.  Any statistic of
+        the draws is then a torch reduction over it; nothing comes to the host unless asked."""
+        import torch
+        if self._closed:
+            raise RuntimeError("Predictor is closed")
+        k = self._k
+        X = self._check_dev_rows(X, selection, "draws")
+        n_draws, z = self._check_draw_args(n_draws, seed, Z, 1)
+        self._check_dev_device(X=X, selection=selection)
+        if selection is not None:
+            X = X[selection]
+        n = X.shape[0]
+        # referenced by this frame for the whole (host-synchronous) call: no record_stream needed
+        F = torch.empty((n_draws, k, n), dtype=torch.float64, device=X.device)   # column-major n x k x n_draws, as the C entry writes it
+        if n:
+            muX, sdX, muY = self._norm_vectors()
+            h = self._handle()
+            _lib.check(self._lib.gpz_predictor_draws_dev(h, *self._x_args(X), _lib.dptr(muX), _lib.dptr(sdX), _lib.dptr(muY), n_draws,
+                                                         int(seed), _lib.dptr(z), F.data_ptr(),
+                                                         torch.cuda.current_stream(X.device).cuda_stream))
+        return F.permute(0, 2, 1)                                        # (n_draws, n, k) view
+
+    def stack_dev(self, X, edges, n_draws=0, seed=0, Z=None, groups=None, n_groups=None, weights=None, selection=None):
+        """``stack`` for a catalogue on the GPU (gpz_predictor_stack_dev): X and ``selection`` as for ``predict_dev``; ``groups`` an
+        integer tensor and ``weights`` a float tensor on the same device (converted there to int32 / float64), one value per row of X
+        before the selection; everything else as for ``stack``.  Returns the same NumPy StackResult, with the bits of ``stack`` on the
+        same handle and rows.  ``n_groups`` defaults to ``groups.max() + 1`` (one scalar read back).  Labels outside [-1, n_groups)
+        and negative or non-finite weights are found on the device and refused with a GpzError, as rows with NaN are."""
+        import torch
+        if self._closed:
+            raise RuntimeError("Predictor is closed")
+        k = self._k
+        X = self._check_dev_rows(X, selection, "stack")
+        n_all = X.shape[0]
+        e = np.asarray(edges, dtype=np.float64)
+        if e.ndim != 1 or e.size < 2:
+            raise ValueError(f"edges must be a vector of at least 2 values, got shape {e.shape}")
+        if not np.all(np.isfinite(e)) or not np.all(np.diff(e) > 0):
+            raise ValueError("edges must be finite and strictly increasing")
+        B = e.size - 1
+        n_draws, z = self._check_draw_args(n_draws, seed, Z, 0)
+        if groups is not None:
+            if not isinstance(groups, torch.Tensor) or groups.dtype.is_floating_point or groups.dtype.is_complex or \
+                    groups.dtype == torch.bool or tuple(groups.shape) != (n_all,):
+                raise ValueError(f"groups must be a tensor of {n_all} integer labels")
+        if weights is not None:
+            if not isinstance(weights, torch.Tensor) or not weights.dtype.is_floating_point or tuple(weights.shape) != (n_all,):
+                raise ValueError(f"weights must be a float tensor of {n_all} values")
+        if n_groups is not None and (isinstance(n_groups, (bool, np.bool_)) or not isinstance(n_groups, (int, np.integer))
+                                     or n_groups < 1):
+            raise ValueError(f"n_groups must be a positive integer, got {n_groups!r}")
+        if n_groups is not None and int(n_groups) * B > GPZ_STACK_MAX_GROUP_BINS:
+            raise ValueError(f"n_groups * bins = {int(n_groups) * B} is over the limit of {GPZ_STACK_MAX_GROUP_BINS} per call")
+        self._check_dev_device(X=X, selection=selection, groups=groups, weights=weights)
+        lab = wt = None
+        if selection is not None:
+            X = X[selection]
+        if groups is not None:
+            lab = (groups if selection is None else groups[selection]).to(torch.int32).contiguous()
+        if weights is not None:
+            wt = (weights if selection is None else weights[selection]).to(torch.float64).contiguous()
+        if n_groups is None:
+            n_groups = max(int(lab.max()) + 1, 1) if lab is not None and lab.numel() else 1
+            if n_groups * B > GPZ_STACK_MAX_GROUP_BINS:
+                raise ValueError(f"n_groups * bins = {n_groups * B} is over the limit of {GPZ_STACK_MAX_GROUP_BINS} per call")
+        G = int(n_groups)
+        n = X.shape[0]
+        C_ = 1 + n_draws
+        hist = np.zeros((C_, G, k, B)); sum_w = np.zeros(G); sum_mu = np.zeros((C_, G, k)); sum_mu2 = np.zeros((C_, G, k))
+        if n:
+            muX, sdX, muY = self._norm_vectors()
+            es = np.ascontiguousarray(e[None, :] - muY[:, None])         # k x (B + 1): the entry's mu is without muY
+            h = self._handle()
+            # X, lab and wt are referenced by this frame for the whole (host-synchronous) call: no record_stream needed
+            _lib.check(self._lib.gpz_predictor_stack_dev(h, *self._x_args(X), _lib.dptr(muX), _lib.dptr(sdX), n_draws, int(seed),
+                                                         _lib.dptr(z), _lib.dptr(es), B, None if lab is None else lab.data_ptr(), G,
+                                                         None if wt is None else wt.data_ptr(), _lib.dptr(hist), _lib.dptr(sum_w),
+                                                         _lib.dptr(sum_mu), _lib.dptr(sum_mu2), _lib.dptr(muY),
+                                                         torch.cuda.current_stream(X.device).cuda_stream))
+        return StackResult(hist, sum_w, sum_mu, sum_mu2, e.copy())
+
 
 def getPrior(X, Psi, theta, model, selection=None, device=0, return_iterations=False):
     """prior = getPrior(X,Sx,theta,model,set)   (getPrior.m:1); X / Psi already normalised as train.m passes them."""

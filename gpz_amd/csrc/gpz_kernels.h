@@ -153,6 +153,21 @@ int predict_stack_slabs(long Q, long rec, long T);   // R: a function of the col
 int launch_stack_tile(hipStream_t st, const double *out, const double *dout, const int *lab, const double *wt, const double *edges,
                       const double *shift, long nt, int k, int nd, int B, int G, int R, double *slab);
 int launch_stack_accum(hipStream_t st, const double *slab, int R, size_t count, double *acc);
+// ---- device-resident entries of the streaming predictor (k_predict_dev.hip; gpz_predictor_*_dev) ----------------------------------
+// X: the caller's rows on the device, f64 or f32 (f32 != 0), element (i, c) at X[i rs + c cs].  check: rec[0] |= 1 when an element of
+// the ns rows is NaN, rec[1] when a label (lab, ns values or nullptr) is outside [-1, G), rec[2] when a weight (wt, ns values or nullptr)
+// is negative or not finite.  stage: rows r0 .. r0 + nt - 1 -> Xc [d][ldx] as (x - muX[c]) / sdX[c] (muX nullptr: x itself).
+// finish: out [3k][nt] -> column-major ns x k arrays at row r0 (mu + muY[o], sigma = nu + beta + gamma; sigma and gamma may be nullptr).
+// phi: [m][nt] -> column-major ns x m at row r0.  draws finish: dout [nd k][nt] -> F column-major ns x k x nd, + muY[o].  muY may be
+// nullptr.  All return -1 when the launch failed.
+int launch_pred_check_dev(hipStream_t st, const void *X, int f32, long ns, int d, long rs, long cs, const int *lab, int G,
+                          const double *wt, unsigned *rec);
+int launch_pred_stage(hipStream_t st, const void *X, int f32, long rs, long cs, long r0, int nt, int d, const double *muX,
+                      const double *sdX, double *Xc, long ldx);
+int launch_pred_finish_dev(hipStream_t st, const double *out, int nt, int k, const double *muY, long ns, long r0, double *mu,
+                           double *sigma, double *nu, double *beta, double *gamma);
+int launch_pred_phi_dev(hipStream_t st, const double *phi, int nt, int m, long ns, long r0, double *PHI);
+int launch_draws_finish_dev(hipStream_t st, const double *dout, int nt, int k, int nd, const double *muY, long ns, long r0, double *F);
 // B (rows x ld row-major) <- [iS (m x m column-major) | nw columns of W from column wcol | nv columns of V (nullptr: 0) from vcol | 0]
 void launch_pred_fill_b(hipStream_t st, const double *iS, const double *W, int nw, int wcol, const double *V, int nv, int vcol, int m,
                         int rows, int ld, double *B);

@@ -22,6 +22,10 @@
 // come home once at the end.  Its buffers (labels, weights, edges, accumulators, slabs) are allocated on the first stack call.
 // R_o is the Cholesky factor of the symmetric part S_o of iSigma_w(:, :, o) (k_chol_step); where it breaks down (a failed pivot, or
 // min L_jj^2 <= m eps max S_jj) it is V diag(sqrt(max(lambda, 0))) from the one-sided Jacobi sweeps of k_pinv.hip.
+// The device-resident entries (gpz_predictor_run_dev / _draws_dev / _stack_dev) take the rows from the caller's device memory and leave
+// the per-row results there: per tile k_pred_stage -> the same predictor_tile / predictor_draws_tile / k_stack_tile -> a finish kernel
+// (k_predict_dev.hip), all on the compute stream, which waits for an event on the caller's stream first.  No pinned slot, no copy
+// stream; one scan of all rows (k_pred_check_dev) before the first tile stands for the host entries' NaN, label and weight loops.
 #include <string>
 
 #include "gpz_ctx.h"
@@ -66,6 +70,10 @@ struct gpz_predictor {
     size_t edges_cap = 0, acc_cap = 0, slab_cap = 0;   // doubles
     int64_t stile = 0;             // rows per stack tile (last call; 0: no stack call yet)
     int sslabs = 0;                // row slabs per tile (last call)
+    // ---- device-resident entries: nothing of this exists before the first of their calls
+    double *par_d = nullptr;       // [muX d | sdX d | muY k | the record of k_pred_check_dev, 4 words]
+    hipEvent_t ev_dev = nullptr;   // recorded on the caller's stream, waited for by s_cmp
+    bool dev_used = false;
 };
 
 namespace gpzi {
@@ -85,6 +93,7 @@ static void predictor_free(gpz_predictor *p) {
         if (p->ev_cmp[s]) (void)hipEventDestroy(p->ev_cmp[s]);
         if (p->ev_out[s]) (void)hipEventDestroy(p->ev_out[s]);
     }
+    if (p->ev_dev) (void)hipEventDestroy(p->ev_dev);
     p->ar.release();
     for (hipStream_t s : {p->s_in, p->s_cmp, p->s_out})
         if (s) (void)hipStreamDestroy(s);
@@ -213,12 +222,13 @@ static int predictor_tile(gpz_predictor *p, int s, int nt, bool want_phi) {
     return 0;
 }
 
-static int predictor_want_phi(gpz_predictor *p) {
-    if (p->phi_d[0]) return 0;
+// PHI's tile buffers, each one where it is missing; the pinned ones only for a call that takes PHI home (pinned)
+static int predictor_want_phi(gpz_predictor *p, bool pinned = true) {
     const size_t n = (size_t)p->m * p->tile_pad;
     for (int s = 0; s < 2; ++s) {
-        if (int rc = p->ar.alloc(&p->phi_d[s], n)) return rc;
-        HIPCHK(hipHostMalloc((void **)&p->hphi[s], n * sizeof(double), hipHostMallocDefault));
+        if (!p->phi_d[s])
+            if (int rc = p->ar.alloc(&p->phi_d[s], n)) return rc;
+        if (pinned && !p->hphi[s]) HIPCHK(hipHostMalloc((void **)&p->hphi[s], n * sizeof(double), hipHostMallocDefault));
     }
     return 0;
 }
@@ -584,6 +594,189 @@ static int predictor_run_stack(gpz_predictor *p, const double *Xs, int64_t ns, i
         if (hipStreamSynchronize(q) != hipSuccess && !rc) rc = gpz_fail(GPZ_ERR_HIP, "gpz_predictor_stack: sync failed");
     return rc;
 }
+// ---- device-resident entries -------------------------------------------------------------------------------------------------------
+// the caller's rows: element (i, c) at X[i rs + c cs], f64 or f32
+struct DevRows {
+    const void *X;
+    int f32;
+    int64_t ns, rs, cs;
+};
+
+static int predictor_dev_args(const char *who, const gpz_predictor *p, const void *X_d, int32_t x_type, int64_t ns, int64_t rs, int64_t cs,
+                              const double *muX, const double *sdX) {
+    if (x_type != GPZ_X_F64 && x_type != GPZ_X_F32) return gpz_fail(GPZ_ERR_ARG, "%s: x_type %d is neither GPZ_X_F64 nor GPZ_X_F32", who, (int)x_type);
+    if ((muX != nullptr) != (sdX != nullptr)) return gpz_fail(GPZ_ERR_ARG, "%s: muX and sdX go together (both or neither)", who);
+    if (ns > 0 && !X_d) return gpz_fail(GPZ_ERR_ARG, "%s: null argument", who);
+    if (rs < 0 || cs < 0 || (ns > 1 && (rs == 0 || (cs == 0 && p->d > 1))))
+        return gpz_fail(GPZ_ERR_ARG, "%s: strides (%lld, %lld) of %lld rows: a stride must be positive", who, (long long)rs, (long long)cs,
+                        (long long)ns);
+    return 0;
+}
+
+// What a device call does before its first tile: the parameter buffer (once per handle), muX, sdX and muY up, the compute stream after
+// everything queued on the caller's stream, and k_pred_check_dev over all rows with its verdict.  nan_text: the host entry's refusal.
+static int predictor_dev_begin(gpz_predictor *p, const char *who, const DevRows &x, const double *muX, const double *sdX, const double *muY,
+                               const int *lab, int G, const double *wt, void *stream, const char *nan_text, const double **muX_d,
+                               const double **sdX_d, const double **muY_d) {
+    const size_t d = p->d, k = p->k;
+    hipStream_t st = p->s_cmp;
+    if (!p->par_d)
+        if (int rc = p->ar.alloc(&p->par_d, 2 * d + k + 2)) return rc;
+    if (!p->ev_dev) HIPCHK(hipEventCreateWithFlags(&p->ev_dev, hipEventDisableTiming));
+    p->dev_used = true;
+    unsigned *rec = (unsigned *)(p->par_d + 2 * d + k);
+    unsigned verdict[4] = {0, 0, 0, 0};
+    int rc = 0;
+    // from here on every failure leaves through the synchronisation below: copies from the caller's memory may be in flight
+    if (hipEventRecord(p->ev_dev, (hipStream_t)stream) != hipSuccess || hipStreamWaitEvent(st, p->ev_dev, 0) != hipSuccess)
+        rc = gpz_fail(GPZ_ERR_HIP, "%s: cannot order the call after the caller's stream", who);
+    if (!rc &&
+        ((muX && (hipMemcpyAsync(p->par_d, muX, d * sizeof(double), hipMemcpyHostToDevice, st) != hipSuccess ||
+                  hipMemcpyAsync(p->par_d + d, sdX, d * sizeof(double), hipMemcpyHostToDevice, st) != hipSuccess)) ||
+         (muY && hipMemcpyAsync(p->par_d + 2 * d, muY, k * sizeof(double), hipMemcpyHostToDevice, st) != hipSuccess) ||
+         hipMemsetAsync(rec, 0, 4 * sizeof(unsigned), st) != hipSuccess))
+        rc = gpz_fail(GPZ_ERR_HIP, "%s: copy failed", who);
+    if (!rc && launch_pred_check_dev(st, x.X, x.f32, x.ns, p->d, x.rs, x.cs, lab, G, wt, rec))
+        rc = gpz_fail(GPZ_ERR_HIP, "%s: k_pred_check_dev launch failed", who);
+    if (!rc && hipMemcpyAsync(verdict, rec, sizeof verdict, hipMemcpyDeviceToHost, st) != hipSuccess)
+        rc = gpz_fail(GPZ_ERR_HIP, "%s: copy failed", who);
+    if (hipStreamSynchronize(st) != hipSuccess && !rc) rc = gpz_fail(GPZ_ERR_HIP, "%s: sync failed", who);
+    if (rc) return rc;
+    if (verdict[1]) return gpz_fail(GPZ_ERR_ARG, "%s: a label is outside [-1, %d)", who, G);
+    if (verdict[2]) return gpz_fail(GPZ_ERR_ARG, "%s: a weight is negative or not finite", who);
+    if (verdict[0]) return gpz_fail(GPZ_ERR_UNSUPPORTED, "%s: %s", who, nan_text);
+    *muX_d = muX ? p->par_d : nullptr;
+    *sdX_d = muX ? p->par_d + d : nullptr;
+    *muY_d = muY ? p->par_d + 2 * d : nullptr;
+    return 0;
+}
+
+static int predictor_run_dev(gpz_predictor *p, const DevRows &x, const double *muX_d, const double *sdX_d, const double *muY_d, double *mu,
+                             double *sigma, double *nu, double *beta, double *gamma, double *PHI) {
+    const int64_t T = p->tile_rows, ns = x.ns;
+    hipStream_t st = p->s_cmp;
+    int rc = 0;
+    for (int64_t r0 = 0, t = 0; r0 < ns && !rc; r0 += T, ++t) {
+        const int s = (int)(t & 1), nt = (int)std::min<int64_t>(T, ns - r0);
+        if (launch_pred_stage(st, x.X, x.f32, x.rs, x.cs, r0, nt, p->d, muX_d, sdX_d, p->Xc[s], p->tile_pad)) {
+            rc = gpz_fail(GPZ_ERR_HIP, "gpz_predictor_run_dev: k_pred_stage launch failed");
+            break;
+        }
+        if ((rc = predictor_tile(p, s, nt, PHI != nullptr))) break;
+        if (launch_pred_finish_dev(st, p->out[s], nt, p->k, muY_d, ns, r0, mu, sigma, nu, beta, gamma) ||
+            (PHI && launch_pred_phi_dev(st, p->phi_d[s], nt, p->m, ns, r0, PHI)))
+            rc = gpz_fail(GPZ_ERR_HIP, "gpz_predictor_run_dev: finish kernel launch failed");
+    }
+    if (hipStreamSynchronize(st) != hipSuccess && !rc) rc = gpz_fail(GPZ_ERR_HIP, "gpz_predictor_run_dev: sync failed");
+    return rc;
+}
+
+static int predictor_run_draws_dev(gpz_predictor *p, const DevRows &x, const double *muX_d, const double *sdX_d, const double *muY_d, int nd,
+                                   unsigned long long seed, const double *Z, double *F) {
+    const int ncol = nd * p->k, ldw = rup(ncol, 16);
+    const int64_t ns = x.ns;
+    hipStream_t st = p->s_cmp;
+    int64_t T = 0;
+    int rc = predictor_draws_prepare(p, nd, seed, Z, false, &T);
+    for (int64_t r0 = 0, t = 0; r0 < ns && !rc; r0 += T, ++t) {
+        const int s = (int)(t & 1), nt = (int)std::min<int64_t>(T, ns - r0);
+        if (launch_pred_stage(st, x.X, x.f32, x.rs, x.cs, r0, nt, p->d, muX_d, sdX_d, p->Xc[s], p->tile_pad)) {
+            rc = gpz_fail(GPZ_ERR_HIP, "gpz_predictor_draws_dev: k_pred_stage launch failed");
+            break;
+        }
+        if ((rc = predictor_draws_tile(p, s, nt, ncol, ldw))) break;
+        if (launch_draws_finish_dev(st, p->dout[s], nt, p->k, nd, muY_d, ns, r0, F))
+            rc = gpz_fail(GPZ_ERR_HIP, "gpz_predictor_draws_dev: k_draws_finish_dev launch failed");
+    }
+    if (hipStreamSynchronize(st) != hipSuccess && !rc) rc = gpz_fail(GPZ_ERR_HIP, "gpz_predictor_draws_dev: sync failed");   // Z may be in flight
+    return rc;
+}
+
+// predictor_run_stack with the rows, labels and weights where the caller has them: the tile kernels read lab + r0 and wt + r0 directly
+static int predictor_run_stack_dev(gpz_predictor *p, const DevRows &x, const double *muX_d, const double *sdX_d, int nd,
+                                   unsigned long long seed, const double *Z, const double *edges, const double *shift, int B,
+                                   const int32_t *group, int G, const double *weight, double *res) {
+    const int k = p->k, ncol = nd * k, ldw = rup(ncol, 16), Q = (1 + nd) * k;
+    const size_t rec = (size_t)G * B + 3 * (size_t)G, count = (size_t)Q * rec;
+    const int64_t ns = x.ns;
+    hipStream_t st = p->s_cmp;
+    int rc = 0;
+    int64_t T = p->tile_rows;
+    if (nd > 0) rc = predictor_draws_prepare(p, nd, seed, Z, false, &T);
+    const int R = predict_stack_slabs(Q, (long)rec, T);
+    const size_t ne = (size_t)k * (B + 1);
+    if (!rc) rc = predictor_grow(p, &p->edges_d, &p->edges_cap, ne + k);
+    if (!rc) rc = predictor_grow(p, &p->acc_d, &p->acc_cap, count);
+    if (!rc) rc = predictor_grow(p, &p->slab_d, &p->slab_cap, count * R);
+    if (!rc) {
+        p->stile = T;
+        p->sslabs = R;
+        if (hipMemcpyAsync(p->edges_d, edges, ne * sizeof(double), hipMemcpyHostToDevice, st) != hipSuccess ||
+            (shift ? hipMemcpyAsync(p->edges_d + ne, shift, (size_t)k * sizeof(double), hipMemcpyHostToDevice, st)
+                   : hipMemsetAsync(p->edges_d + ne, 0, (size_t)k * sizeof(double), st)) != hipSuccess ||
+            hipMemsetAsync(p->acc_d, 0, count * sizeof(double), st) != hipSuccess)
+            rc = gpz_fail(GPZ_ERR_HIP, "gpz_predictor_stack_dev: copy failed");
+    }
+    for (int64_t r0 = 0, t = 0; r0 < ns && !rc; r0 += T, ++t) {
+        const int s = (int)(t & 1);
+        const int64_t nt = std::min<int64_t>(T, ns - r0);
+        if (launch_pred_stage(st, x.X, x.f32, x.rs, x.cs, r0, (int)nt, p->d, muX_d, sdX_d, p->Xc[s], p->tile_pad)) {
+            rc = gpz_fail(GPZ_ERR_HIP, "gpz_predictor_stack_dev: k_pred_stage launch failed");
+            break;
+        }
+        if ((rc = predictor_tile(p, s, (int)nt, false))) break;
+        if (nd > 0 && (rc = predictor_draws_tile(p, s, nt, ncol, ldw, p->route == 1))) break;
+        if (launch_stack_tile(st, p->out[s], nd > 0 ? p->dout[s] : nullptr, group ? group + r0 : nullptr, weight ? weight + r0 : nullptr,
+                              p->edges_d, p->edges_d + ne, nt, k, nd, B, G, R, p->slab_d) ||
+            launch_stack_accum(st, p->slab_d, R, count, p->acc_d))
+            rc = gpz_fail(GPZ_ERR_HIP, "gpz_predictor_stack_dev: k_stack_tile launch failed");
+    }
+    if (!rc && hipMemcpyAsync(res, p->acc_d, count * sizeof(double), hipMemcpyDeviceToHost, st) != hipSuccess)
+        rc = gpz_fail(GPZ_ERR_HIP, "gpz_predictor_stack_dev: copy failed");
+    if (hipStreamSynchronize(st) != hipSuccess && !rc) rc = gpz_fail(GPZ_ERR_HIP, "gpz_predictor_stack_dev: sync failed");
+    return rc;
+}
+
+// the shape checks of a stack call, in the order gpz_predictor_stack has always made them (who: the entry's name in the message)
+static int stack_check_shape(const char *who, const gpz_predictor *p, int64_t ns, int32_t ndraws, int32_t nbins, int32_t ngroups,
+                             const double *edges, const double *hist, const double *sum_w, const double *sum_mu, const double *sum_mu2,
+                             const void *Xs) {
+    if (!p) return gpz_fail(GPZ_ERR_ARG, "%s: null handle", who);
+    if (ns < 0) return gpz_fail(GPZ_ERR_ARG, "%s: ns < 0", who);
+    if (ndraws < 0 || (1 + (int64_t)ndraws) * p->k > GPZ_DRAWS_MAX_COLUMNS)
+        return gpz_fail(GPZ_ERR_ARG, "%s: need 0 <= ndraws and (1 + ndraws) * k <= %d (ndraws %d, k %d)", who, GPZ_DRAWS_MAX_COLUMNS,
+                        (int)ndraws, p->k);
+    if (nbins < 1 || ngroups < 1) return gpz_fail(GPZ_ERR_ARG, "%s: need nbins >= 1 and ngroups >= 1", who);
+    if ((int64_t)nbins * ngroups > GPZ_STACK_MAX_GROUP_BINS)
+        return gpz_fail(GPZ_ERR_ARG, "%s: ngroups * nbins = %lld is over GPZ_STACK_MAX_GROUP_BINS = %d", who, (long long)nbins * ngroups,
+                        GPZ_STACK_MAX_GROUP_BINS);
+    const int k = p->k, B = nbins;
+    if (!edges || !hist || !sum_w || !sum_mu || !sum_mu2) return gpz_fail(GPZ_ERR_ARG, "%s: null argument", who);
+    for (int o = 0; o < k; ++o)
+        for (int j = 0; j <= B; ++j) {
+            const double e = edges[(size_t)o * (B + 1) + j];
+            if (!std::isfinite(e) || (j > 0 && !(e > edges[(size_t)o * (B + 1) + j - 1])))
+                return gpz_fail(GPZ_ERR_ARG, "%s: the edges must be finite and strictly increasing (output %d, edge %d)", who, o, j);
+        }
+    if (ns > 0 && !Xs) return gpz_fail(GPZ_ERR_ARG, "%s: null argument", who);
+    return 0;
+}
+
+// records [c][o][G B + 3 G] -> hist [c][g][o][B], sums [c][g][o]; the sum of the weights is the same in every record
+static void stack_unpack(const double *res, int C, int k, int G, int B, double *hist, double *sum_w, double *sum_mu, double *sum_mu2) {
+    const size_t GB = (size_t)G * B, rec = GB + 3 * (size_t)G;
+    for (int c = 0; c < C; ++c)
+        for (int o = 0; o < k; ++o) {
+            const double *r = res + ((size_t)c * k + o) * rec;
+            for (int g = 0; g < G; ++g) {
+                const size_t at = ((size_t)c * G + g) * k + o;
+                memcpy(hist + at * B, r + (size_t)g * B, (size_t)B * sizeof(double));
+                sum_mu[at] = r[GB + 3 * (size_t)g + 1];
+                sum_mu2[at] = r[GB + 3 * (size_t)g + 2];
+                if (c == 0 && o == 0) sum_w[g] = r[GB + 3 * (size_t)g];
+            }
+        }
+}
 }   // namespace gpzi
 
 extern "C" int gpz_predictor_create(const gpz_desc *desc, const double *theta, const double *w, const double *iSigma_w,
@@ -676,24 +869,8 @@ extern "C" int gpz_predictor_draws(gpz_predictor *p, const double *Xs, int64_t n
 extern "C" int gpz_predictor_stack(gpz_predictor *p, const double *Xs, int64_t ns, int32_t ndraws, uint64_t seed, const double *Z,
                                    const double *edges, int32_t nbins, const int32_t *group, int32_t ngroups, const double *weight,
                                    double *hist, double *sum_w, double *sum_mu, double *sum_mu2, const double *mu_shift) {
-    if (!p) return gpz_fail(GPZ_ERR_ARG, "gpz_predictor_stack: null handle");
-    if (ns < 0) return gpz_fail(GPZ_ERR_ARG, "gpz_predictor_stack: ns < 0");
-    if (ndraws < 0 || (1 + (int64_t)ndraws) * p->k > GPZ_DRAWS_MAX_COLUMNS)
-        return gpz_fail(GPZ_ERR_ARG, "gpz_predictor_stack: need 0 <= ndraws and (1 + ndraws) * k <= %d (ndraws %d, k %d)",
-                        GPZ_DRAWS_MAX_COLUMNS, (int)ndraws, p->k);
-    if (nbins < 1 || ngroups < 1) return gpz_fail(GPZ_ERR_ARG, "gpz_predictor_stack: need nbins >= 1 and ngroups >= 1");
-    if ((int64_t)nbins * ngroups > GPZ_STACK_MAX_GROUP_BINS)
-        return gpz_fail(GPZ_ERR_ARG, "gpz_predictor_stack: ngroups * nbins = %lld is over GPZ_STACK_MAX_GROUP_BINS = %d",
-                        (long long)nbins * ngroups, GPZ_STACK_MAX_GROUP_BINS);
+    if (int rc = stack_check_shape("gpz_predictor_stack", p, ns, ndraws, nbins, ngroups, edges, hist, sum_w, sum_mu, sum_mu2, Xs)) return rc;
     const int k = p->k, B = nbins, G = ngroups, C = 1 + ndraws;
-    if (!edges || !hist || !sum_w || !sum_mu || !sum_mu2) return gpz_fail(GPZ_ERR_ARG, "gpz_predictor_stack: null argument");
-    for (int o = 0; o < k; ++o)
-        for (int j = 0; j <= B; ++j) {
-            const double e = edges[(size_t)o * (B + 1) + j];
-            if (!std::isfinite(e) || (j > 0 && !(e > edges[(size_t)o * (B + 1) + j - 1])))
-                return gpz_fail(GPZ_ERR_ARG, "gpz_predictor_stack: the edges must be finite and strictly increasing (output %d, edge %d)", o, j);
-        }
-    if (ns > 0 && !Xs) return gpz_fail(GPZ_ERR_ARG, "gpz_predictor_stack: null argument");
     if (group)
         for (int64_t i = 0; i < ns; ++i)
             if (group[i] < -1 || group[i] >= G)
@@ -720,18 +897,101 @@ extern "C" int gpz_predictor_stack(gpz_predictor *p, const double *Xs, int64_t n
     if (!rc) rc = predictor_run_stack(p, Xs, ns, (int)ndraws, (unsigned long long)seed, Z, edges, mu_shift, B, group, G, weight, res.data());
     (void)hipSetDevice(prev);
     if (rc) return rc;
-    // records [c][o][G B + 3 G] -> hist [c][g][o][B], sums [c][g][o]; the sum of the weights is the same in every record
-    for (int c = 0; c < C; ++c)
-        for (int o = 0; o < k; ++o) {
-            const double *r = res.data() + ((size_t)c * k + o) * rec;
-            for (int g = 0; g < G; ++g) {
-                const size_t at = ((size_t)c * G + g) * k + o;
-                memcpy(hist + at * B, r + (size_t)g * B, (size_t)B * sizeof(double));
-                sum_mu[at] = r[GB + 3 * (size_t)g + 1];
-                sum_mu2[at] = r[GB + 3 * (size_t)g + 2];
-                if (c == 0 && o == 0) sum_w[g] = r[GB + 3 * (size_t)g];
-            }
-        }
+    stack_unpack(res.data(), C, k, G, B, hist, sum_w, sum_mu, sum_mu2);
+    return 0;
+}
+
+extern "C" int gpz_predictor_run_dev(gpz_predictor *p, const void *X_d, int32_t x_type, int64_t ns, int64_t row_stride, int64_t col_stride,
+                                     const double *muX, const double *sdX, const double *muY, double *mu_d, double *sigma_d, double *nu_d,
+                                     double *beta_d, double *gamma_d, double *PHI_d, void *stream) {
+    const char *who = "gpz_predictor_run_dev";
+    if (!p) return gpz_fail(GPZ_ERR_ARG, "%s: null handle", who);
+    if (ns < 0) return gpz_fail(GPZ_ERR_ARG, "%s: ns < 0", who);
+    if (int rc = predictor_dev_args(who, p, X_d, x_type, ns, row_stride, col_stride, muX, sdX)) return rc;
+    if (ns == 0) return 0;
+    if (!mu_d || !nu_d || !beta_d) return gpz_fail(GPZ_ERR_ARG, "%s: null argument", who);
+    const DevRows x{X_d, x_type == GPZ_X_F32, ns, row_stride, col_stride};
+    const double *mx = nullptr, *sx = nullptr, *my = nullptr;
+    int prev = 0;
+    (void)hipGetDevice(&prev);
+    gpz_opts_scope opts_scope(&p->opt);
+    int rc = 0;
+    if (hipSetDevice(p->device) != hipSuccess) rc = gpz_fail(GPZ_ERR_HIP, "%s: hipSetDevice failed", who);
+    if (!rc && PHI_d) rc = predictor_want_phi(p, false);
+    if (!rc)
+        rc = predictor_dev_begin(p, who, x, muX, sdX, muY, nullptr, 0, nullptr, stream,
+                                 "the rows have missing values (NaN): group them by pattern and call gpz_predict_missing (predict.m:45-69)",
+                                 &mx, &sx, &my);
+    if (!rc) rc = predictor_run_dev(p, x, mx, sx, my, mu_d, sigma_d, nu_d, beta_d, gamma_d, PHI_d);
+    if (!rc) ++p->runs;
+    (void)hipSetDevice(prev);
+    return rc;
+}
+
+extern "C" int gpz_predictor_draws_dev(gpz_predictor *p, const void *X_d, int32_t x_type, int64_t ns, int64_t row_stride,
+                                       int64_t col_stride, const double *muX, const double *sdX, const double *muY, int32_t ndraws,
+                                       uint64_t seed, const double *Z, double *F_d, void *stream) {
+    const char *who = "gpz_predictor_draws_dev";
+    if (!p) return gpz_fail(GPZ_ERR_ARG, "%s: null handle", who);
+    if (ns < 0) return gpz_fail(GPZ_ERR_ARG, "%s: ns < 0", who);
+    if (ndraws < 1 || (int64_t)ndraws * p->k > GPZ_DRAWS_MAX_COLUMNS)
+        return gpz_fail(GPZ_ERR_ARG, "%s: need 1 <= ndraws and ndraws * k <= %d (ndraws %d, k %d)", who, GPZ_DRAWS_MAX_COLUMNS, (int)ndraws,
+                        p->k);
+    if (int rc = predictor_dev_args(who, p, X_d, x_type, ns, row_stride, col_stride, muX, sdX)) return rc;
+    if (ns == 0) return 0;
+    if (!F_d) return gpz_fail(GPZ_ERR_ARG, "%s: null argument", who);
+    const DevRows x{X_d, x_type == GPZ_X_F32, ns, row_stride, col_stride};
+    const double *mx = nullptr, *sx = nullptr, *my = nullptr;
+    int prev = 0;
+    (void)hipGetDevice(&prev);
+    gpz_opts_scope opts_scope(&p->opt);
+    int rc = 0;
+    if (hipSetDevice(p->device) != hipSuccess) rc = gpz_fail(GPZ_ERR_HIP, "%s: hipSetDevice failed", who);
+    if (!rc)
+        rc = predictor_dev_begin(p, who, x, muX, sdX, muY, nullptr, 0, nullptr, stream,
+                                 "the rows have missing values (NaN): draws are for complete rows", &mx, &sx, &my);
+    if (!rc) rc = predictor_run_draws_dev(p, x, mx, sx, my, (int)ndraws, (unsigned long long)seed, Z, F_d);
+    (void)hipSetDevice(prev);
+    return rc;
+}
+
+extern "C" int gpz_predictor_stack_dev(gpz_predictor *p, const void *X_d, int32_t x_type, int64_t ns, int64_t row_stride,
+                                       int64_t col_stride, const double *muX, const double *sdX, int32_t ndraws, uint64_t seed,
+                                       const double *Z, const double *edges, int32_t nbins, const int32_t *group_d, int32_t ngroups,
+                                       const double *weight_d, double *hist, double *sum_w, double *sum_mu, double *sum_mu2,
+                                       const double *mu_shift, void *stream) {
+    const char *who = "gpz_predictor_stack_dev";
+    if (int rc = stack_check_shape(who, p, ns, ndraws, nbins, ngroups, edges, hist, sum_w, sum_mu, sum_mu2, X_d)) return rc;
+    if (int rc = predictor_dev_args(who, p, X_d, x_type, ns, row_stride, col_stride, muX, sdX)) return rc;
+    const int k = p->k, B = nbins, G = ngroups, C = 1 + ndraws;
+    if (mu_shift)
+        for (int o = 0; o < k; ++o)
+            if (!std::isfinite(mu_shift[o])) return gpz_fail(GPZ_ERR_ARG, "%s: mu_shift must be finite", who);
+    if (ns == 0) {
+        const size_t GB = (size_t)G * B, Q = (size_t)C * k;
+        memset(hist, 0, Q * GB * sizeof(double));
+        memset(sum_w, 0, (size_t)G * sizeof(double));
+        memset(sum_mu, 0, Q * G * sizeof(double));
+        memset(sum_mu2, 0, Q * G * sizeof(double));
+        return 0;
+    }
+    const DevRows x{X_d, x_type == GPZ_X_F32, ns, row_stride, col_stride};
+    const double *mx = nullptr, *sx = nullptr, *my = nullptr;
+    std::vector<double> res((size_t)C * k * ((size_t)G * B + 3 * (size_t)G));
+    int prev = 0;
+    (void)hipGetDevice(&prev);
+    gpz_opts_scope opts_scope(&p->opt);
+    int rc = 0;
+    if (hipSetDevice(p->device) != hipSuccess) rc = gpz_fail(GPZ_ERR_HIP, "%s: hipSetDevice failed", who);
+    if (!rc)   // the refusals of the host entry's loops over labels and weights, and of its staging loop over the rows, before any tile
+        rc = predictor_dev_begin(p, who, x, muX, sdX, nullptr, group_d, G, weight_d, stream,
+                                 "the rows have missing values (NaN): stacks are for complete rows", &mx, &sx, &my);
+    if (!rc)
+        rc = predictor_run_stack_dev(p, x, mx, sx, (int)ndraws, (unsigned long long)seed, Z, edges, mu_shift, B, group_d, G, weight_d,
+                                     res.data());
+    (void)hipSetDevice(prev);
+    if (rc) return rc;   // the outputs are untouched
+    stack_unpack(res.data(), C, k, G, B, hist, sum_w, sum_mu, sum_mu2);
     return 0;
 }
 
@@ -753,6 +1013,7 @@ extern "C" int gpz_predictor_route(const gpz_predictor *p, char *buf, int cap) {
         snprintf(tmp, sizeof tmp, "; stack: k_stack_tile + k_stack_accum, %lld-row tiles, %d row slabs", (long long)p->stile, p->sslabs);
         r += tmp;
     }
+    if (p->dev_used) r += "; device entries: k_pred_stage";
     snprintf(buf, (size_t)cap, "%s", r.c_str());
     return (int)r.size();
 }

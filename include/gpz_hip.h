@@ -267,6 +267,42 @@ int gpz_predictor_stack(gpz_predictor *p, const double *Xs, int64_t ns, int32_t 
                         int32_t nbins, const int32_t *group /* ns or NULL */, int32_t ngroups, const double *weight /* ns or NULL */,
                         double *hist, double *sum_w, double *sum_mu, double *sum_mu2, const double *mu_shift /* k or NULL */);
 
+/* ---- device-resident entries of the predictor handle: the catalogue is read from device memory, per-row results stay there ---------
+ * The three entries above with the rows, and every per-row result, in the caller's memory on the handle's device: no row and no
+ * per-row result crosses the bus.  X_d: element (i, c) of the ns x d rows at X_d[i * row_stride + c * col_stride], strides in elements
+ * (a row-major array has (d, 1), a column-major one (1, ns), any view of either its own), x_type GPZ_X_F64 or GPZ_X_F32 (converted to
+ * f64, exactly).  muX, sdX (host, d values each): the rows enter the kernels as (x - muX[c]) / sdX[c], one f64 subtraction and one f64
+ * division (the bits of the host's normalisation); both NULL: the rows are normalised already.  muY (host, k values or NULL) is added
+ * to mu and to the draws.  Every *_d argument is a device pointer; everything else is host memory.
+ * gpz_predictor_run_dev: mu_d, nu_d, beta_d (required), sigma_d = nu + beta + gamma, gamma_d = 0 (both optional): column-major ns x k;
+ * PHI_d: column-major ns x m or NULL.  gpz_predictor_draws_dev: F_d column-major ns x k x ndraws (with muY when given); Z stays a host
+ * array.  gpz_predictor_stack_dev: group_d (ns int32 labels or NULL) and weight_d (ns doubles or NULL) on the device, edges, mu_shift and
+ * the results in host memory exactly as gpz_predictor_stack takes and returns them.
+ * stream: the caller's hipStream_t (NULL: the legacy default stream).  The call is ordered after everything queued on it so far (an
+ * event, not a host synchronisation), runs on the handle's compute stream and returns when its results are complete.  The tile length is
+ * the host entry's, and the tile kernels are the host entries' own: the results have the bits of the host entry on the same rows.
+ * Before its first tile a call scans all rows (and labels and weights) on the device: rows with NaN -> GPZ_ERR_UNSUPPORTED, a label
+ * outside [-1, ngroups) or a negative or non-finite weight -> GPZ_ERR_ARG, in both cases with the outputs untouched.  The argument
+ * checks of the host entries apply unchanged; x_type outside {0, 1}, a stride of 0 with ns > 1, or only one of muX / sdX ->
+ * GPZ_ERR_ARG.  Input noise is not part of these entries.  gpz_predictor_info's runs count gpz_predictor_run_dev calls too; its bytes
+ * grow by one small parameter buffer on the first device call and never with ns; gpz_predictor_route then appends
+ * "; device entries: k_pred_stage". */
+#define GPZ_X_F64 0
+#define GPZ_X_F32 1
+int gpz_predictor_run_dev(gpz_predictor *p, const void *X_d, int32_t x_type, int64_t ns, int64_t row_stride, int64_t col_stride,
+                          const double *muX, const double *sdX, const double *muY /* k or NULL */,
+                          double *mu_d, double *sigma_d, double *nu_d, double *beta_d, double *gamma_d, double *PHI_d, void *stream);
+int gpz_predictor_draws_dev(gpz_predictor *p, const void *X_d, int32_t x_type, int64_t ns, int64_t row_stride, int64_t col_stride,
+                            const double *muX, const double *sdX, const double *muY /* k or NULL */,
+                            int32_t ndraws, uint64_t seed, const double *Z /* host: NULL or m x ndraws x k */,
+                            double *F_d /* ns x k x ndraws, column-major */, void *stream);
+int gpz_predictor_stack_dev(gpz_predictor *p, const void *X_d, int32_t x_type, int64_t ns, int64_t row_stride, int64_t col_stride,
+                            const double *muX, const double *sdX,
+                            int32_t ndraws, uint64_t seed, const double *Z, const double *edges, int32_t nbins,
+                            const int32_t *group_d /* ns or NULL */, int32_t ngroups, const double *weight_d /* ns or NULL */,
+                            double *hist, double *sum_w, double *sum_mu, double *sum_mu2, const double *mu_shift /* k or NULL */,
+                            void *stream);
+
 /* ---- device-resident L-BFGS memory: minFunc's lbfgsAdd.m / lbfgsProd.m (mex/lbfgsAddC.c, mex/lbfgsProdC.c) ----
  * S and Y (p x corrections) live on the device; all vector arguments are device pointers.
  * gpz_lbfgs_add:        y = g - g_old, s = t*d; skipped (added = 0) when y's <= 1e-10        (lbfgsAdd.m:2-4)
