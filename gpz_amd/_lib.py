@@ -91,6 +91,14 @@ SYMBOLS = {
     "gpz_predictor_stack_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int64, c_double_p, c_double_p,
                                           C.c_int32, C.c_uint64, c_double_p, c_double_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p,
                                           c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, C.c_void_p]),
+    # rows with input noise on the handle: Psi_d a device address with its own element type and strides, sd2 = sdX ** 2 (host)
+    "gpz_predictor_run_noisy_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_int32,
+                                              C.c_int64, C.c_int64, c_double_p, c_double_p, c_double_p, c_double_p, C.c_void_p,
+                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gpz_predictor_draws_noisy_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_int32,
+                                                C.c_int64, C.c_int64, c_double_p, c_double_p, c_double_p, c_double_p, C.c_int32,
+                                                C.c_uint64, c_double_p, C.c_void_p, C.c_void_p]),
+    "gpz_predictor_draws_noisy": (C.c_int, [C.c_void_p, c_double_p, C.c_int64, c_double_p, C.c_int32, C.c_uint64, c_double_p, c_double_p]),
     "gpz_prior": (C.c_int, [C.POINTER(gpz_desc), c_double_p, c_double_p, C.c_int64, c_double_p, C.c_int32, c_double_p,
                             c_int32_p]),
     "gpz_inv_logdet": (C.c_int, [c_double_p, C.c_int32, C.c_int32, c_double_p, c_double_p, c_int32_p]),

@@ -638,7 +638,8 @@ class Predictor:
     The same results as ``predict`` (normalisation, ``selection``, fixPsi, sigma = nu + beta_i + gamma, + muY), but the model's
     once-per-model work is done once and rows stream through tile-sized device buffers, so device memory does not grow with the
     number of rows and PHI only leaves the device when asked for.  Complete rows go through the handle (a fused kernel where
-    ceil16(m + 2k) <= 256 and d <= 20, else the PHI kernel + T-GEMM per tile; rows with Psi per tile through predictNoisy); rows with
+    ceil16(m + 2k) <= 256 and d <= 20, else the PHI kernel + T-GEMM per tile; rows with Psi per tile through predictNoisy, and on the
+    handle's own tiles from ``predict_dev`` / ``draws`` / ``draws_dev`` with ``Psi=`` for a diagonal kind, d <= 20, k <= 8, m <= 256); rows with
     missing values are grouped by NaN pattern and go to gpz_predict_missing as in ``predict``.  Shapes are checked before the GPU is
     touched; the handle itself is created on first use.  ``route`` / ``info`` (tile rows, device bytes held, route 0 fused / 1 tiles,
     runs) describe it."""
@@ -807,23 +808,30 @@ class Predictor:
         out = (mu, sigma, nu, beta_i, gamma)
         return out + (PHI,) if return_phi else out
 
-    def draws(self, X, n_draws, seed=0, Z=None, selection=None):
+    def draws(self, X, n_draws, seed=0, Z=None, selection=None, Psi=None):
         """Posterior draws of the predictive mean (gpz_predictor_draws): an array of shape (n_draws, n, k) whose draws[s] has the shape
         and meaning of ``predict``'s mu (normalisation, ``selection``, + muY) under one draw w_s ~ N(w, iSigma_w) of the weights, the
         same draw for every row.  The spread of an aggregate of the rows across draws (a bin's mean redshift, a stacked n(z)) is its
         error from the finite training set, cross-row covariance included; y-draws add sqrt(beta_i) times independent normals per row.
+        With ``Psi`` (a host array as ``predict`` takes it; gpz_predictor_draws_noisy) draws[s] is ``predict(X, Psi=Psi)``'s mu under draw
+        s, E_x[PHI] w_s + muY: the mean is linear in the weights, so this is exact.  Psi needs a model inside predict_noisy_fits (a
+        diagonal kind, d <= 20, k <= 8, m <= 256), else ValueError.
 
         ``seed`` (an integer in [0, 2^64)) selects the standard normals, generated on the device from Philox4x32-10: draw s of a seed
         is the same on every call and for every n_draws > s.  ``Z`` (m x n_draws x k, or m x n_draws when k = 1) gives them instead;
-        ``Z = eye(m)`` with n_draws = m makes (draws - mu) an exact square root of the joint covariance of the rows' means.  Complete,
-        noise-free rows only: rows with NaN are refused.  At most n_draws * k = 16384 columns per call."""
+        ``Z = eye(m)`` with n_draws = m makes (draws - mu) an exact square root of the joint covariance of the rows' means.  Complete
+        rows only: rows with NaN are refused.  At most n_draws * k = 16384 columns per call."""
         if self._closed:
             raise RuntimeError("Predictor is closed")
         model, k, m = self.model, self._k, self._m
-        X, _ = self._check_inputs(X, None, selection)
+        X, psi = self._check_inputs(X, Psi, selection)
         nbad = int(np.isnan(X).any(axis=1).sum()) if X.size else 0
         if nbad:
             raise ValueError(f"X has {nbad} rows with missing values (NaN): draws are for complete rows")
+        if psi is not None:
+            self._check_noisy_model("draws", draws=True)
+            if not np.all(np.isfinite(psi)) or np.any(psi < 0):
+                raise ValueError("Psi must be finite and >= 0")
         if isinstance(n_draws, (bool, np.bool_)) or not isinstance(n_draws, (int, np.integer)) or n_draws < 1:
             raise ValueError(f"n_draws must be a positive integer, got {n_draws!r}")
         n_draws = int(n_draws)
@@ -846,8 +854,16 @@ class Predictor:
             Xn = np.empty(X.shape, order="F")                            # predict.m:35-36
             np.subtract(X, model.muX, out=Xn)
             np.divide(Xn, model.sdX, out=Xn)
+            psin = None
+            if psi is not None:
+                from .host import fixPsi
+                psin = np.asfortranarray(fixPsi(psi, ns, model.sdX, model.method))   # predict.m:43: n x d for a diagonal kind
             h = self._handle()
-            _lib.check(self._lib.gpz_predictor_draws(h, _lib.dptr(Xn), ns, n_draws, int(seed), _lib.dptr(z), _lib.dptr(F)))
+            if psin is None:
+                _lib.check(self._lib.gpz_predictor_draws(h, _lib.dptr(Xn), ns, n_draws, int(seed), _lib.dptr(z), _lib.dptr(F)))
+            else:
+                _lib.check(self._lib.gpz_predictor_draws_noisy(h, _lib.dptr(Xn), ns, _lib.dptr(psin), n_draws, int(seed), _lib.dptr(z),
+                                                               _lib.dptr(F)))
         out = F.transpose(2, 0, 1)                                       # (n_draws, n, k) view
         out += np.asarray(model.muY, dtype=np.float64).reshape(k)        # predict.m:73
         return out
@@ -978,6 +994,31 @@ class Predictor:
                 raise ValueError(f"selection must be a mask of length {X.shape[0]}")
         return X
 
+    def _check_noisy_model(self, what, draws=False):
+        """predict_noisy_fits (k_predict_noisy.hip) for this model, before the GPU is touched."""
+        if self._method[1] == "C" or self._d > 20 or self._k > 8 or self._m > 256:
+            raise ValueError(f"{what} with Psi needs a model inside predict_noisy_fits: a diagonal kind (GL, VL, GD, VD), d <= 20, "
+                             f"k <= 8 and m <= 256; this one is {self._method} with d = {self._d}, m = {self._m}, k = {self._k} "
+                             "(Predictor.predict takes Psi for every shape)")
+        if draws and self._flags & GPZ_PREDICT_FORCE_TILES:
+            raise ValueError(f"{what} with Psi needs the fused draws route: the predictor was made with force_tiles=True")
+
+    def _check_dev_psi(self, Psi, n, what):
+        """Psi of a *_dev call by type, dtype and shape ((n, d), (n, 1) or (n,)); nothing here touches a GPU.  Returns it as n x 1 or n x d."""
+        import torch
+        d = self._d
+        if isinstance(Psi, np.ndarray):
+            raise TypeError(f"{what}_dev takes Psi as a torch tensor on cuda:{self.device}; a NumPy array goes to Predictor.{what}")
+        if not isinstance(Psi, torch.Tensor):
+            raise TypeError(f"Psi must be a torch.Tensor on cuda:{self.device}, got {type(Psi).__name__}")
+        if Psi.dtype not in (torch.float64, torch.float32):
+            raise TypeError(f"Psi must be float64 or float32, got {Psi.dtype}")
+        if Psi.dim() == 1:
+            Psi = Psi[:, None]
+        if Psi.dim() != 2 or Psi.shape[0] != n or Psi.shape[1] not in (1, d):
+            raise ValueError(f"Psi must be n x d, n x 1 or n (n = {n}, d = {d}), got shape {tuple(Psi.shape)}")
+        return Psi
+
     def _check_dev_device(self, **tensors):
         """Every tensor of a *_dev call lives on cuda:<self.device> (checked after the shapes and before the GPU is touched)."""
         for name, t in tensors.items():
@@ -1024,23 +1065,41 @@ class Predictor:
         import torch
         return X.data_ptr(), 1 if X.dtype == torch.float32 else 0, X.shape[0], X.stride(0), X.stride(1)
 
-    def predict_dev(self, X, selection=None, return_phi=False):
+    def _psi_args(self, Psi, n):
+        """(address, element type, row stride, column stride) of Psi for gpz_predictor_*_noisy_dev: n x 1 is broadcast by a stride of 0."""
+        import torch
+        P = Psi.expand(n, self._d)                                       # a view: never a copy
+        return P.data_ptr(), 1 if P.dtype == torch.float32 else 0, P.stride(0), P.stride(1)
+
+    def predict_dev(self, X, selection=None, return_phi=False, Psi=None):
         """``predict`` for a catalogue that is on the GPU already (gpz_predictor_run_dev): X is a float64 or float32 torch tensor of
         shape (n, d) on cuda:<device> with any strides (row-major as torch makes it, a transposed or sliced view: it is read as it lies,
         never copied), ``selection`` a bool tensor there.  Returns mu, sigma, nu, beta_i, gamma [, PHI] as float64 tensors of shape
         (n, k) [(n, m)] on the same device, column-major (``.T`` of a contiguous (k, n) tensor).  Same meaning and, for the same rows,
         the same bits as ``predict``: normalisation by model.muX / sdX, + muY, sigma = nu + beta_i + gamma.  No row and no result
         crosses to the host.  The call is ordered after the work queued on torch's current stream of that device (no synchronise is
-        needed before it) and is complete when it returns.  Complete, noise-free rows only: rows with NaN are refused (GpzError).
+        needed before it) and is complete when it returns.  Complete rows only: rows with NaN are refused (GpzError).
+        ``Psi`` (gpz_predictor_run_noisy_dev): the rows' input-noise variances as a float64 or float32 tensor on the same device, of
+        shape (n, d), (n, 1) or (n,), with any strides (read as it lies; one variance per row is broadcast, not copied).  The five
+        tensors are then ``predict(X, Psi=Psi)``'s, gamma no longer zero, computed on the handle's tiles by k_predict_noisy_small; a
+        row's results do not depend on the tile size or the row order.  It needs a model inside predict_noisy_fits (a diagonal kind,
+        d <= 20, k <= 8, m <= 256) and does not return PHI; an element of Psi that is NaN, infinite or negative is refused (GpzError).
         Type, dtype and shape are checked first, the device last, all before the GPU is touched."""
         import torch
         if self._closed:
             raise RuntimeError("Predictor is closed")
         k, m = self._k, self._m
         X = self._check_dev_rows(X, selection, "predict")
-        self._check_dev_device(X=X, selection=selection)
+        if Psi is not None:
+            Psi = self._check_dev_psi(Psi, X.shape[0], "predict")
+            if return_phi:
+                raise ValueError("return_phi=True is not available with Psi on the device: Predictor.predict returns PHI for noisy rows")
+            self._check_noisy_model("predict_dev")
+        self._check_dev_device(X=X, selection=selection, Psi=Psi)
         if selection is not None:
             X = X[selection]                                             # predict.m:25
+            if Psi is not None:
+                Psi = Psi[selection]                                     # predict.m:27-33
         n = X.shape[0]
         # the tensors are referenced by this frame for the whole call, which returns when the device is done: no record_stream needed
         out = [torch.empty((k, n), dtype=torch.float64, device=X.device).T for _ in range(5)]
@@ -1048,34 +1107,54 @@ class Predictor:
         if n:
             muX, sdX, muY = self._norm_vectors()
             h = self._handle()
-            _lib.check(self._lib.gpz_predictor_run_dev(h, *self._x_args(X), _lib.dptr(muX), _lib.dptr(sdX), _lib.dptr(muY),
-                                                       *(t.data_ptr() for t in out), None if PHI is None else PHI.data_ptr(),
-                                                       torch.cuda.current_stream(X.device).cuda_stream))
+            if Psi is None:
+                _lib.check(self._lib.gpz_predictor_run_dev(h, *self._x_args(X), _lib.dptr(muX), _lib.dptr(sdX), _lib.dptr(muY),
+                                                           *(t.data_ptr() for t in out), None if PHI is None else PHI.data_ptr(),
+                                                           torch.cuda.current_stream(X.device).cuda_stream))
+            else:
+                sd2 = np.ascontiguousarray(sdX ** 2)                     # fixPsi.m: Psi ./ sdX.^2
+                _lib.check(self._lib.gpz_predictor_run_noisy_dev(h, *self._x_args(X), *self._psi_args(Psi, n), _lib.dptr(muX),
+                                                                 _lib.dptr(sdX), _lib.dptr(sd2), _lib.dptr(muY),
+                                                                 *(t.data_ptr() for t in out),
+                                                                 torch.cuda.current_stream(X.device).cuda_stream))
         return tuple(out) + (PHI,) if return_phi else tuple(out)
 
-    def draws_dev(self, X, n_draws, seed=0, Z=None, selection=None):
+    def draws_dev(self, X, n_draws, seed=0, Z=None, selection=None, Psi=None):
         """``draws`` for a catalogue on the GPU (gpz_predictor_draws_dev): X and ``selection`` as for ``predict_dev``, ``n_draws``,
         ``seed`` and ``Z`` (a host array: it is m x n_draws x k) as for ``draws``.  Returns a float64 tensor of shape (n_draws, n, k) on
         the device, a view of the column-major n x k x n_draws buffer, with the bits of ``draws`` for the same rows.  Any statistic of
-        the draws is then a torch reduction over it; nothing comes to the host unless asked."""
+        the draws is then a torch reduction over it; nothing comes to the host unless asked.  ``Psi`` as for ``predict_dev``
+        (gpz_predictor_draws_noisy_dev): the draws of ``predict(X, Psi=Psi)``'s mu, with the bits of ``draws(X, ..., Psi=Psi)``."""
         import torch
         if self._closed:
             raise RuntimeError("Predictor is closed")
         k = self._k
         X = self._check_dev_rows(X, selection, "draws")
         n_draws, z = self._check_draw_args(n_draws, seed, Z, 1)
-        self._check_dev_device(X=X, selection=selection)
+        if Psi is not None:
+            Psi = self._check_dev_psi(Psi, X.shape[0], "draws")
+            self._check_noisy_model("draws_dev", draws=True)
+        self._check_dev_device(X=X, selection=selection, Psi=Psi)
         if selection is not None:
             X = X[selection]
+            if Psi is not None:
+                Psi = Psi[selection]
         n = X.shape[0]
         # referenced by this frame for the whole (host-synchronous) call: no record_stream needed
         F = torch.empty((n_draws, k, n), dtype=torch.float64, device=X.device)   # column-major n x k x n_draws, as the C entry writes it
         if n:
             muX, sdX, muY = self._norm_vectors()
             h = self._handle()
-            _lib.check(self._lib.gpz_predictor_draws_dev(h, *self._x_args(X), _lib.dptr(muX), _lib.dptr(sdX), _lib.dptr(muY), n_draws,
-                                                         int(seed), _lib.dptr(z), F.data_ptr(),
-                                                         torch.cuda.current_stream(X.device).cuda_stream))
+            if Psi is None:
+                _lib.check(self._lib.gpz_predictor_draws_dev(h, *self._x_args(X), _lib.dptr(muX), _lib.dptr(sdX), _lib.dptr(muY), n_draws,
+                                                             int(seed), _lib.dptr(z), F.data_ptr(),
+                                                             torch.cuda.current_stream(X.device).cuda_stream))
+            else:
+                sd2 = np.ascontiguousarray(sdX ** 2)                     # fixPsi.m: Psi ./ sdX.^2
+                _lib.check(self._lib.gpz_predictor_draws_noisy_dev(h, *self._x_args(X), *self._psi_args(Psi, n), _lib.dptr(muX),
+                                                                   _lib.dptr(sdX), _lib.dptr(sd2), _lib.dptr(muY), n_draws, int(seed),
+                                                                   _lib.dptr(z), F.data_ptr(),
+                                                                   torch.cuda.current_stream(X.device).cuda_stream))
         return F.permute(0, 2, 1)                                        # (n_draws, n, k) view
 
     def stack_dev(self, X, edges, n_draws=0, seed=0, Z=None, groups=None, n_groups=None, weights=None, selection=None):

@@ -168,6 +168,32 @@ int launch_pred_finish_dev(hipStream_t st, const double *out, int nt, int k, con
                            double *sigma, double *nu, double *beta, double *gamma);
 int launch_pred_phi_dev(hipStream_t st, const double *phi, int nt, int m, long ns, long r0, double *PHI);
 int launch_draws_finish_dev(hipStream_t st, const double *dout, int nt, int k, int nd, const double *muY, long ns, long r0, double *F);
+// ---- rows with input noise through the streaming predictor (k_predict_noisy.hip; gpz_predictor_*_noisy*) --------------------------
+// fits: a diagonal kind, an instantiated de <= 20, k <= 8 and ceil16(m) <= 256 (the limit of the fused draws).  Psi: per-dimension
+// variances in the layout of Xc ([d][ldx], dimensions >= d zero).  The pair records are predict_noisy_rec(d, k) = 1 + 2 d + 3 k doubles:
+// launch_pair_table (record stride rec) writes [lnZ | c_ab | C_ab], launch_noisy_pair_coef the 3 k coefficients behind them (iS: m x m x k
+// column-major, read at a >= b only).  launch_predict_noisy_small: part [nchunk][5k][ldp] -> out [4k][n] = mu | nu | beta | gamma.
+// predict_noisy_chunks: the pair chunks, a function of the model's shape only - never of the rows - so that a row's results have the
+// same bits for any tile size, position and row order.  The launchers return -1 when a launch failed.
+bool predict_noisy_fits(int kind, int de, int m, int k);
+int predict_noisy_chunks(int m, int d, int k);
+int predict_noisy_rec(int d, int k);
+int launch_noisy_pair_coef(hipStream_t st, int m, int k, int d, const double *w, const double *v, const double *iS, double *tab, int rec);
+int launch_predict_noisy_small(hipStream_t st, int d, int de, const double *Xc, const double *Psic, long ldx, int n, int m, int k,
+                               const double *P, const double *G2, const double *w, const double *v, const double *bvec,
+                               const double *tab, int nchunk, double *part, long ldp, double *out);
+// launch_predict_draws for rows with Psi (diagonal kinds): 32 * de more doubles of LDS for the block's rows of Psi
+size_t predict_draws_psi_lds(int de);
+int launch_predict_draws_psi(hipStream_t st, int de, const double *Xc, const double *Psic, long ldx, int n, int m, const double *P,
+                             const double *G, const double *W, int ldw, int ncol, double *out, long ldo);
+// check: rec[3] |= 1 when an element of the caller's Psi (as X: f64 or f32, element (i, c) at Psi[i rs + c cs], cs = 0 for n x 1) is NaN,
+// negative, or infinite itself or divided by smin (the smallest sd2; 1 without one).  stage: rows r0 .. r0 + nt - 1 -> Psic [d][ldx] as double(psi) / sd2[c] (sd2 nullptr: psi itself).  finish:
+// out [4k][nt] -> column-major ns x k arrays at row r0 (mu + muY[o], gamma, sigma = (nu + beta) + gamma; sigma and gamma may be nullptr).
+int launch_pred_check_psi(hipStream_t st, const void *Psi, int f32, long ns, int d, long rs, long cs, double smin, unsigned *rec);
+int launch_pred_stage_psi(hipStream_t st, const void *Psi, int f32, long rs, long cs, long r0, int nt, int d, const double *sd2,
+                          double *Psic, long ldx);
+int launch_pred_finish_noisy_dev(hipStream_t st, const double *out, int nt, int k, const double *muY, long ns, long r0, double *mu,
+                                 double *sigma, double *nu, double *beta, double *gamma);
 // B (rows x ld row-major) <- [iS (m x m column-major) | nw columns of W from column wcol | nv columns of V (nullptr: 0) from vcol | 0]
 void launch_pred_fill_b(hipStream_t st, const double *iS, const double *W, int nw, int wcol, const double *V, int nv, int vcol, int m,
                         int rows, int ld, double *B);

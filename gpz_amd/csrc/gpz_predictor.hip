@@ -26,6 +26,11 @@
 // the per-row results there: per tile k_pred_stage -> the same predictor_tile / predictor_draws_tile / k_stack_tile -> a finish kernel
 // (k_predict_dev.hip), all on the compute stream, which waits for an event on the caller's stream first.  No pinned slot, no copy
 // stream; one scan of all rows (k_pred_check_dev) before the first tile stands for the host entries' NaN, label and weight loops.
+// Rows with per-dimension input noise stay on the handle where predict_noisy_fits holds (a diagonal kind, d <= 20, k <= 8, m <= 256):
+// gpz_predictor_run_noisy_dev runs k_predict_noisy_small per tile (predictNoisy as one kernel + a finish, k_predict_noisy.hip), and
+// gpz_predictor_draws_noisy / _draws_noisy_dev the draws kernel behind a PHI block built from X and Psi.  The pair table (which depends on
+// the model only), the Psi slots, the 4k-row outputs and the chunk slab are allocated on the first such call (predictor_noisy_prepare).
+// gpz_predictor_run with Psi keeps the one-shot route above.
 #include <string>
 
 #include "gpz_ctx.h"
@@ -74,6 +79,13 @@ struct gpz_predictor {
     double *par_d = nullptr;       // [muX d | sdX d | muY k | the record of k_pred_check_dev, 4 words]
     hipEvent_t ev_dev = nullptr;   // recorded on the caller's stream, waited for by s_cmp
     bool dev_used = false;
+    // ---- input noise on the handle (gpz_predictor_*_noisy*): nothing of this exists before the first of their calls
+    bool noisy_ready = false;
+    int nchunks = 0, nrec = 0;     // predict_noisy_chunks, predict_noisy_rec of the model
+    double *ptab = nullptr;        // m (m + 1) / 2 pair records
+    double *Psic[2] = {}, *nout[2] = {}, *npart = nullptr;   // Psi in the layout of Xc; [4k][tile_pad]; [nchunks][5k][tile_pad]
+    double *sd2_d = nullptr;       // sdX ** 2 of the device entries
+    double *hpsi[2] = {};          // pinned, gpz_predictor_draws_noisy only
 };
 
 namespace gpzi {
@@ -89,6 +101,7 @@ static void predictor_free(gpz_predictor *p) {
         if (p->hdout[s]) (void)hipHostFree(p->hdout[s]);
         if (p->hlab[s]) (void)hipHostFree(p->hlab[s]);
         if (p->hwt[s]) (void)hipHostFree(p->hwt[s]);
+        if (p->hpsi[s]) (void)hipHostFree(p->hpsi[s]);
         if (p->ev_in[s]) (void)hipEventDestroy(p->ev_in[s]);
         if (p->ev_cmp[s]) (void)hipEventDestroy(p->ev_cmp[s]);
         if (p->ev_out[s]) (void)hipEventDestroy(p->ev_out[s]);
@@ -326,6 +339,62 @@ static int predictor_run_noisy(gpz_predictor *p, const double *Xs, int64_t ns, c
     return 0;
 }
 
+// ---- input noise on the handle ----------------------------------------------------------------------------------------------------
+static int predictor_noisy_check(const char *who, const gpz_predictor *p) {
+    if (!predict_noisy_fits(p->kind, p->de, p->m, p->k))
+        return gpz_fail(GPZ_ERR_UNSUPPORTED,
+                        "%s: input noise on the handle needs predict_noisy_fits: a diagonal kind (GL, VL, GD, VD), d <= 20, k <= 8 and "
+                        "ceil16(m) <= 256 (method %.2s, d %d, m %d, k %d); gpz_predictor_run takes Psi for every shape",
+                        who, p->desc.method, p->d, p->m, p->k);
+    return 0;
+}
+
+// What every call with Psi needs, the draws included: Psic[2] and sd2.  Each one where it is missing.
+static int predictor_psi_slots(gpz_predictor *p) {
+    const size_t tp = (size_t)p->tile_pad;
+    int rc = 0;
+    for (int s = 0; s < 2; ++s)
+        if (!p->Psic[s]) {
+            if ((rc = p->ar.alloc(&p->Psic[s], (size_t)p->de * tp))) return rc;
+            HIPCHK(hipMemsetAsync(p->Psic[s], 0, (size_t)p->de * tp * sizeof(double), p->s_cmp));   // dimensions d .. de - 1 stay zero
+        }
+    if (!p->sd2_d && (rc = p->ar.alloc(&p->sd2_d, (size_t)p->d))) return rc;
+    return 0;
+}
+
+// What the first predictNoisy call adds to the handle beyond that: the pair table [lnZ | c_ab | C_ab | coefficients] (the model's alone:
+// launch_pair_table needs only pr.P and pr.G for a diagonal kind), the 4k-row output slots and the chunk slab.  The draws read none of
+// these and do not come here.
+static int predictor_noisy_prepare(gpz_predictor *p) {
+    if (p->noisy_ready) return 0;
+    const size_t m = p->m, k = p->k, tp = (size_t)p->tile_pad, npair = m * (m + 1) / 2;
+    hipStream_t st = p->s_cmp;
+    auto &ar = p->ar;
+    int rc = 0;
+    if ((rc = predictor_psi_slots(p))) return rc;
+    p->nchunks = predict_noisy_chunks(p->m, p->d, p->k);
+    p->nrec = predict_noisy_rec(p->d, p->k);
+    if (!p->ptab && (rc = ar.alloc(&p->ptab, npair * p->nrec))) return rc;
+    for (int s = 0; s < 2; ++s)
+        if (!p->nout[s] && (rc = ar.alloc(&p->nout[s], 4 * k * tp))) return rc;
+    if (!p->npart && (rc = ar.alloc(&p->npart, (size_t)p->nchunks * 5 * k * tp))) return rc;
+    launch_pair_table(st, GPZ_KIND_DIAG, p->m, p->d, p->de, p->pr.P, p->pr.G, nullptr, nullptr, p->ptab, p->nrec, nullptr);
+    if (hipGetLastError() != hipSuccess ||
+        launch_noisy_pair_coef(st, p->m, p->k, p->d, p->w_d, p->hetero ? p->pr.v : nullptr, p->iS_d, p->ptab, p->nrec))
+        return gpz_fail(GPZ_ERR_HIP, "gpz_predictor: pair table launch failed");
+    HIPCHK(hipStreamSynchronize(st));
+    p->noisy_ready = true;
+    return 0;
+}
+
+// predictNoisy of one tile of nt rows: Xc[s], Psic[s] -> nout[s] ([4k][nt] = mu | nu | beta | gamma)
+static int predictor_noisy_tile(gpz_predictor *p, int s, int nt) {
+    if (launch_predict_noisy_small(p->s_cmp, p->d, p->de, p->Xc[s], p->Psic[s], p->tile_pad, nt, p->m, p->k, p->pr.P, p->pr.G2, p->w_d,
+                                   p->hetero ? p->pr.v : nullptr, p->pr.b, p->ptab, p->nchunks, p->npart, p->tile_pad, p->nout[s]))
+        return gpz_fail(GPZ_ERR_HIP, "gpz_predictor_run_noisy_dev: k_predict_noisy_small launch failed");
+    return 0;
+}
+
 // ---- draws ------------------------------------------------------------------------------------------------------------------------
 // R_o for every output, once per handle: the blocked Cholesky steps of k_chol.hip on S_o (padded to a multiple of 32 with the identity),
 // the eigen-factor of k_pinv.hip's sweeps where that breaks down.
@@ -430,10 +499,18 @@ static int predictor_draws_prepare(gpz_predictor *p, int nd, unsigned long long 
 
 // the draws kernels of one tile of nt rows: Xc[s] -> dout[s] ([nd k][nt]).  phi_built: predictor_tile has just run on the same slot and
 // rows on the tile route, so p->Phi already holds this tile's PHI (the same launch_phi with the same arguments; launch_tgemm only reads it)
-static int predictor_draws_tile(gpz_predictor *p, int s, int64_t nt, int ncol, int ldw, bool phi_built = false) {
+// Psic: the tile's Psi slot for rows with input noise (fused route, diagonal kinds), else nullptr
+static int predictor_draws_tile(gpz_predictor *p, int s, int64_t nt, int ncol, int ldw, bool phi_built = false,
+                                const double *Psic = nullptr) {
     const int k = p->k, m = p->m;
     hipStream_t st = p->s_cmp;
     const double *G = p->kind == GPZ_KIND_COV ? p->pr.Rc : p->pr.G2;
+    if (Psic) {
+        if (p->droute != 0) return gpz_fail(GPZ_ERR_UNSUPPORTED, "gpz_predictor_draws: input noise needs the fused draws route");
+        if (launch_predict_draws_psi(st, p->de, p->Xc[s], Psic, p->tile_pad, (int)nt, m, p->pr.P, G, p->Wd, ldw, ncol, p->dout[s], nt))
+            return gpz_fail(GPZ_ERR_HIP, "gpz_predictor_draws: k_predict_draws_psi launch failed");
+        return 0;
+    }
     if (p->droute == 0) {
         if (launch_predict_draws(st, p->kind, p->de, p->Xc[s], p->tile_pad, (int)nt, m, p->pr.P, G, p->Wd, ldw, ncol, p->dout[s], nt))
             return gpz_fail(GPZ_ERR_HIP, "gpz_predictor_draws: k_predict_draws launch failed");
@@ -455,14 +532,22 @@ static int predictor_draws_tile(gpz_predictor *p, int s, int64_t nt, int ncol, i
     return 0;
 }
 
+// Psi (gpz_predictor_draws_noisy; nullptr: noise-free rows): normalised ns x d column-major, staged into a second pair of pinned slots
+// and uploaded with X's tile
 static int predictor_run_draws(gpz_predictor *p, const double *Xs, int64_t ns, int nd, unsigned long long seed, const double *Z,
-                               double *F) {
+                               double *F, const double *Psi = nullptr) {
     const int k = p->k, d = p->d, ncol = nd * k, ldw = rup(ncol, 16);
     const size_t tp = (size_t)p->tile_pad;
     hipStream_t st = p->s_cmp;
     int rc = 0;
     int64_t T = 0;
+    if (Psi) {
+        if ((rc = predictor_psi_slots(p))) return rc;
+        for (int s = 0; s < 2; ++s)
+            if (!p->hpsi[s]) HIPCHK(hipHostMalloc((void **)&p->hpsi[s], (size_t)d * tp * sizeof(double), hipHostMallocDefault));
+    }
     if ((rc = predictor_draws_prepare(p, nd, seed, Z, true, &T))) return rc;
+    if (Psi && p->droute != 0) return gpz_fail(GPZ_ERR_UNSUPPORTED, "gpz_predictor_draws_noisy: input noise needs the fused draws route");
     // ---- the pipeline of predictor_run_full on tiles of T rows
     const int64_t ntiles = (ns + T - 1) / T;
     int64_t nt_of[2] = {0, 0}, r0_of[2] = {0, 0};
@@ -494,15 +579,30 @@ static int predictor_run_draws(gpz_predictor *p, const double *Xs, int64_t ns, i
             rc = gpz_fail(GPZ_ERR_UNSUPPORTED, "gpz_predictor_draws: the rows have missing values (NaN): draws are for complete rows");
             break;
         }
+        if (Psi) {
+            for (int c = 0; c < d; ++c) {
+                const double *src = Psi + (size_t)c * ns + r0;
+                double *dst = p->hpsi[s] + (size_t)c * tp;
+                int neg = 0;
+                for (int64_t i = 0; i < nt; ++i) { const double v = src[i]; dst[i] = v; neg |= !(v >= 0.0) || !(v <= 1.7976931348623157e308); }
+                bad |= neg != 0;
+            }
+            if (bad) {
+                rc = gpz_fail(GPZ_ERR_ARG, "gpz_predictor_draws_noisy: Psi has an element that is NaN, infinite or negative");
+                break;
+            }
+        }
         if (hipStreamWaitEvent(p->s_in, p->ev_cmp[s], 0) != hipSuccess ||
             hipMemcpy2DAsync(p->Xc[s], tp * sizeof(double), p->hin[s], tp * sizeof(double), (size_t)nt * sizeof(double), d,
                              hipMemcpyHostToDevice, p->s_in) != hipSuccess ||
+            (Psi && hipMemcpy2DAsync(p->Psic[s], tp * sizeof(double), p->hpsi[s], tp * sizeof(double), (size_t)nt * sizeof(double), d,
+                                     hipMemcpyHostToDevice, p->s_in) != hipSuccess) ||
             hipEventRecord(p->ev_in[s], p->s_in) != hipSuccess || hipStreamWaitEvent(st, p->ev_in[s], 0) != hipSuccess ||
             hipStreamWaitEvent(st, p->ev_out[s], 0) != hipSuccess) {
             rc = gpz_fail(GPZ_ERR_HIP, "gpz_predictor_draws: copy failed");
             break;
         }
-        if ((rc = predictor_draws_tile(p, s, nt, ncol, ldw))) break;
+        if ((rc = predictor_draws_tile(p, s, nt, ncol, ldw, false, Psi ? p->Psic[s] : nullptr))) break;
         if (hipEventRecord(p->ev_cmp[s], st) != hipSuccess || hipStreamWaitEvent(p->s_out, p->ev_cmp[s], 0) != hipSuccess ||
             hipMemcpyAsync(p->hdout[s], p->dout[s], (size_t)ncol * nt * sizeof(double), hipMemcpyDeviceToHost, p->s_out) != hipSuccess ||
             hipEventRecord(p->ev_out[s], p->s_out) != hipSuccess) {
@@ -613,11 +713,25 @@ static int predictor_dev_args(const char *who, const gpz_predictor *p, const voi
     return 0;
 }
 
+// the caller's Psi: as X, and a column stride of 0 broadcasts an n x 1 Psi
+static int predictor_dev_psi_args(const char *who, const gpz_predictor *p, const void *Psi_d, int32_t psi_type, int64_t ns, int64_t rs,
+                                  int64_t cs, const double *sdX, const double *sd2) {
+    if (psi_type != GPZ_X_F64 && psi_type != GPZ_X_F32)
+        return gpz_fail(GPZ_ERR_ARG, "%s: psi_type %d is neither GPZ_X_F64 nor GPZ_X_F32", who, (int)psi_type);
+    if ((sdX != nullptr) != (sd2 != nullptr)) return gpz_fail(GPZ_ERR_ARG, "%s: sdX and sd2 go together (both or neither)", who);
+    if (ns > 0 && !Psi_d) return gpz_fail(GPZ_ERR_ARG, "%s: null Psi", who);
+    if (rs < 0 || cs < 0 || (ns > 1 && rs == 0))
+        return gpz_fail(GPZ_ERR_ARG, "%s: Psi strides (%lld, %lld) of %lld rows: the row stride must be positive", who, (long long)rs,
+                        (long long)cs, (long long)ns);
+    (void)p;
+    return 0;
+}
+
 // What a device call does before its first tile: the parameter buffer (once per handle), muX, sdX and muY up, the compute stream after
 // everything queued on the caller's stream, and k_pred_check_dev over all rows with its verdict.  nan_text: the host entry's refusal.
 static int predictor_dev_begin(gpz_predictor *p, const char *who, const DevRows &x, const double *muX, const double *sdX, const double *muY,
                                const int *lab, int G, const double *wt, void *stream, const char *nan_text, const double **muX_d,
-                               const double **sdX_d, const double **muY_d) {
+                               const double **sdX_d, const double **muY_d, const DevRows *psi = nullptr, const double *sd2 = nullptr) {
     const size_t d = p->d, k = p->k;
     hipStream_t st = p->s_cmp;
     if (!p->par_d)
@@ -638,6 +752,10 @@ static int predictor_dev_begin(gpz_predictor *p, const char *who, const DevRows 
         rc = gpz_fail(GPZ_ERR_HIP, "%s: copy failed", who);
     if (!rc && launch_pred_check_dev(st, x.X, x.f32, x.ns, p->d, x.rs, x.cs, lab, G, wt, rec))
         rc = gpz_fail(GPZ_ERR_HIP, "%s: k_pred_check_dev launch failed", who);
+    if (!rc && psi &&   // (predictor_psi_slots has run: sd2_d exists)
+        ((sd2 && hipMemcpyAsync(p->sd2_d, sd2, d * sizeof(double), hipMemcpyHostToDevice, st) != hipSuccess) ||
+         launch_pred_check_psi(st, psi->X, psi->f32, psi->ns, p->d, psi->rs, psi->cs, sd2 ? *std::min_element(sd2, sd2 + d) : 1.0, rec)))
+        rc = gpz_fail(GPZ_ERR_HIP, "%s: k_pred_check_psi launch failed", who);
     if (!rc && hipMemcpyAsync(verdict, rec, sizeof verdict, hipMemcpyDeviceToHost, st) != hipSuccess)
         rc = gpz_fail(GPZ_ERR_HIP, "%s: copy failed", who);
     if (hipStreamSynchronize(st) != hipSuccess && !rc) rc = gpz_fail(GPZ_ERR_HIP, "%s: sync failed", who);
@@ -645,6 +763,7 @@ static int predictor_dev_begin(gpz_predictor *p, const char *who, const DevRows 
     if (verdict[1]) return gpz_fail(GPZ_ERR_ARG, "%s: a label is outside [-1, %d)", who, G);
     if (verdict[2]) return gpz_fail(GPZ_ERR_ARG, "%s: a weight is negative or not finite", who);
     if (verdict[0]) return gpz_fail(GPZ_ERR_UNSUPPORTED, "%s: %s", who, nan_text);
+    if (verdict[3]) return gpz_fail(GPZ_ERR_ARG, "%s: Psi has an element that is NaN, infinite or negative", who);
     *muX_d = muX ? p->par_d : nullptr;
     *sdX_d = muX ? p->par_d + d : nullptr;
     *muY_d = muY ? p->par_d + 2 * d : nullptr;
@@ -671,8 +790,32 @@ static int predictor_run_dev(gpz_predictor *p, const DevRows &x, const double *m
     return rc;
 }
 
+// gpz_predictor_run_noisy_dev's tiles: both stage kernels, predictNoisy, the finish into the caller's arrays
+static int predictor_run_noisy_dev(gpz_predictor *p, const DevRows &x, const DevRows &psi, const double *muX_d, const double *sdX_d,
+                                   const double *sd2_d, const double *muY_d, double *mu, double *sigma, double *nu, double *beta,
+                                   double *gamma) {
+    const int64_t T = p->tile_rows, ns = x.ns;
+    hipStream_t st = p->s_cmp;
+    int rc = 0;
+    for (int64_t r0 = 0, t = 0; r0 < ns && !rc; r0 += T, ++t) {
+        const int s = (int)(t & 1), nt = (int)std::min<int64_t>(T, ns - r0);
+        if (launch_pred_stage(st, x.X, x.f32, x.rs, x.cs, r0, nt, p->d, muX_d, sdX_d, p->Xc[s], p->tile_pad) ||
+            launch_pred_stage_psi(st, psi.X, psi.f32, psi.rs, psi.cs, r0, nt, p->d, sd2_d, p->Psic[s], p->tile_pad)) {
+            rc = gpz_fail(GPZ_ERR_HIP, "gpz_predictor_run_noisy_dev: stage kernel launch failed");
+            break;
+        }
+        if ((rc = predictor_noisy_tile(p, s, nt))) break;
+        if (launch_pred_finish_noisy_dev(st, p->nout[s], nt, p->k, muY_d, ns, r0, mu, sigma, nu, beta, gamma))
+            rc = gpz_fail(GPZ_ERR_HIP, "gpz_predictor_run_noisy_dev: finish kernel launch failed");
+    }
+    if (hipStreamSynchronize(st) != hipSuccess && !rc) rc = gpz_fail(GPZ_ERR_HIP, "gpz_predictor_run_noisy_dev: sync failed");
+    return rc;
+}
+
+// psi (gpz_predictor_draws_noisy_dev; nullptr: noise-free rows) with sd2_d
 static int predictor_run_draws_dev(gpz_predictor *p, const DevRows &x, const double *muX_d, const double *sdX_d, const double *muY_d, int nd,
-                                   unsigned long long seed, const double *Z, double *F) {
+                                   unsigned long long seed, const double *Z, double *F, const DevRows *psi = nullptr,
+                                   const double *sd2_d = nullptr) {
     const int ncol = nd * p->k, ldw = rup(ncol, 16);
     const int64_t ns = x.ns;
     hipStream_t st = p->s_cmp;
@@ -684,7 +827,11 @@ static int predictor_run_draws_dev(gpz_predictor *p, const DevRows &x, const dou
             rc = gpz_fail(GPZ_ERR_HIP, "gpz_predictor_draws_dev: k_pred_stage launch failed");
             break;
         }
-        if ((rc = predictor_draws_tile(p, s, nt, ncol, ldw))) break;
+        if (psi && launch_pred_stage_psi(st, psi->X, psi->f32, psi->rs, psi->cs, r0, nt, p->d, sd2_d, p->Psic[s], p->tile_pad)) {
+            rc = gpz_fail(GPZ_ERR_HIP, "gpz_predictor_draws_noisy_dev: k_pred_stage_psi launch failed");
+            break;
+        }
+        if ((rc = predictor_draws_tile(p, s, nt, ncol, ldw, false, psi ? p->Psic[s] : nullptr))) break;
         if (launch_draws_finish_dev(st, p->dout[s], nt, p->k, nd, muY_d, ns, r0, F))
             rc = gpz_fail(GPZ_ERR_HIP, "gpz_predictor_draws_dev: k_draws_finish_dev launch failed");
     }
@@ -955,6 +1102,95 @@ extern "C" int gpz_predictor_draws_dev(gpz_predictor *p, const void *X_d, int32_
     return rc;
 }
 
+extern "C" int gpz_predictor_run_noisy_dev(gpz_predictor *p, const void *X_d, int32_t x_type, int64_t ns, int64_t row_stride,
+                                           int64_t col_stride, const void *Psi_d, int32_t psi_type, int64_t psi_row_stride,
+                                           int64_t psi_col_stride, const double *muX, const double *sdX, const double *sd2,
+                                           const double *muY, double *mu_d, double *sigma_d, double *nu_d, double *beta_d,
+                                           double *gamma_d, void *stream) {
+    const char *who = "gpz_predictor_run_noisy_dev";
+    if (!p) return gpz_fail(GPZ_ERR_ARG, "%s: null handle", who);
+    if (ns < 0) return gpz_fail(GPZ_ERR_ARG, "%s: ns < 0", who);
+    if (int rc = predictor_noisy_check(who, p)) return rc;
+    if (int rc = predictor_dev_args(who, p, X_d, x_type, ns, row_stride, col_stride, muX, sdX)) return rc;
+    if (int rc = predictor_dev_psi_args(who, p, Psi_d, psi_type, ns, psi_row_stride, psi_col_stride, sdX, sd2)) return rc;
+    if (ns == 0) return 0;
+    if (!mu_d || !nu_d || !beta_d) return gpz_fail(GPZ_ERR_ARG, "%s: null argument", who);
+    const DevRows x{X_d, x_type == GPZ_X_F32, ns, row_stride, col_stride};
+    const DevRows psi{Psi_d, psi_type == GPZ_X_F32, ns, psi_row_stride, psi_col_stride};
+    const double *mx = nullptr, *sx = nullptr, *my = nullptr;
+    int prev = 0;
+    (void)hipGetDevice(&prev);
+    gpz_opts_scope opts_scope(&p->opt);
+    int rc = 0;
+    if (hipSetDevice(p->device) != hipSuccess) rc = gpz_fail(GPZ_ERR_HIP, "%s: hipSetDevice failed", who);
+    if (!rc) rc = predictor_noisy_prepare(p);
+    if (!rc)
+        rc = predictor_dev_begin(p, who, x, muX, sdX, muY, nullptr, 0, nullptr, stream,
+                                 "the rows have missing values (NaN): input noise on the handle is for complete rows", &mx, &sx, &my, &psi,
+                                 sd2);
+    if (!rc) rc = predictor_run_noisy_dev(p, x, psi, mx, sx, sd2 ? p->sd2_d : nullptr, my, mu_d, sigma_d, nu_d, beta_d, gamma_d);
+    if (!rc) ++p->runs;
+    (void)hipSetDevice(prev);
+    return rc;
+}
+
+extern "C" int gpz_predictor_draws_noisy_dev(gpz_predictor *p, const void *X_d, int32_t x_type, int64_t ns, int64_t row_stride,
+                                             int64_t col_stride, const void *Psi_d, int32_t psi_type, int64_t psi_row_stride,
+                                             int64_t psi_col_stride, const double *muX, const double *sdX, const double *sd2,
+                                             const double *muY, int32_t ndraws, uint64_t seed, const double *Z, double *F_d,
+                                             void *stream) {
+    const char *who = "gpz_predictor_draws_noisy_dev";
+    if (!p) return gpz_fail(GPZ_ERR_ARG, "%s: null handle", who);
+    if (ns < 0) return gpz_fail(GPZ_ERR_ARG, "%s: ns < 0", who);
+    if (ndraws < 1 || (int64_t)ndraws * p->k > GPZ_DRAWS_MAX_COLUMNS)
+        return gpz_fail(GPZ_ERR_ARG, "%s: need 1 <= ndraws and ndraws * k <= %d (ndraws %d, k %d)", who, GPZ_DRAWS_MAX_COLUMNS, (int)ndraws,
+                        p->k);
+    if (int rc = predictor_noisy_check(who, p)) return rc;
+    if (p->force_tiles) return gpz_fail(GPZ_ERR_UNSUPPORTED, "%s: input noise needs the fused draws route (GPZ_PREDICT_FORCE_TILES is set)", who);
+    if (int rc = predictor_dev_args(who, p, X_d, x_type, ns, row_stride, col_stride, muX, sdX)) return rc;
+    if (int rc = predictor_dev_psi_args(who, p, Psi_d, psi_type, ns, psi_row_stride, psi_col_stride, sdX, sd2)) return rc;
+    if (ns == 0) return 0;
+    if (!F_d) return gpz_fail(GPZ_ERR_ARG, "%s: null argument", who);
+    const DevRows x{X_d, x_type == GPZ_X_F32, ns, row_stride, col_stride};
+    const DevRows psi{Psi_d, psi_type == GPZ_X_F32, ns, psi_row_stride, psi_col_stride};
+    const double *mx = nullptr, *sx = nullptr, *my = nullptr;
+    int prev = 0;
+    (void)hipGetDevice(&prev);
+    gpz_opts_scope opts_scope(&p->opt);
+    int rc = 0;
+    if (hipSetDevice(p->device) != hipSuccess) rc = gpz_fail(GPZ_ERR_HIP, "%s: hipSetDevice failed", who);
+    if (!rc) rc = predictor_psi_slots(p);
+    if (!rc)
+        rc = predictor_dev_begin(p, who, x, muX, sdX, muY, nullptr, 0, nullptr, stream,
+                                 "the rows have missing values (NaN): draws are for complete rows", &mx, &sx, &my, &psi, sd2);
+    if (!rc)
+        rc = predictor_run_draws_dev(p, x, mx, sx, my, (int)ndraws, (unsigned long long)seed, Z, F_d, &psi, sd2 ? p->sd2_d : nullptr);
+    (void)hipSetDevice(prev);
+    return rc;
+}
+
+extern "C" int gpz_predictor_draws_noisy(gpz_predictor *p, const double *Xs, int64_t ns, const double *Psi, int32_t ndraws, uint64_t seed,
+                                         const double *Z, double *F) {
+    const char *who = "gpz_predictor_draws_noisy";
+    if (!p) return gpz_fail(GPZ_ERR_ARG, "%s: null handle", who);
+    if (ns < 0) return gpz_fail(GPZ_ERR_ARG, "%s: ns < 0", who);
+    if (ndraws < 1 || (int64_t)ndraws * p->k > GPZ_DRAWS_MAX_COLUMNS)
+        return gpz_fail(GPZ_ERR_ARG, "%s: need 1 <= ndraws and ndraws * k <= %d (ndraws %d, k %d)", who, GPZ_DRAWS_MAX_COLUMNS, (int)ndraws,
+                        p->k);
+    if (int rc = predictor_noisy_check(who, p)) return rc;
+    if (p->force_tiles) return gpz_fail(GPZ_ERR_UNSUPPORTED, "%s: input noise needs the fused draws route (GPZ_PREDICT_FORCE_TILES is set)", who);
+    if (ns == 0) return 0;
+    if (!Xs || !Psi || !F) return gpz_fail(GPZ_ERR_ARG, "%s: null argument", who);
+    int prev = 0;
+    (void)hipGetDevice(&prev);
+    gpz_opts_scope opts_scope(&p->opt);
+    int rc = 0;
+    if (hipSetDevice(p->device) != hipSuccess) rc = gpz_fail(GPZ_ERR_HIP, "%s: hipSetDevice failed", who);
+    if (!rc) rc = predictor_run_draws(p, Xs, ns, (int)ndraws, (unsigned long long)seed, Z, F, Psi);
+    (void)hipSetDevice(prev);
+    return rc;
+}
+
 extern "C" int gpz_predictor_stack_dev(gpz_predictor *p, const void *X_d, int32_t x_type, int64_t ns, int64_t row_stride,
                                        int64_t col_stride, const double *muX, const double *sdX, int32_t ndraws, uint64_t seed,
                                        const double *Z, const double *edges, int32_t nbins, const int32_t *group_d, int32_t ngroups,
@@ -1014,6 +1250,10 @@ extern "C" int gpz_predictor_route(const gpz_predictor *p, char *buf, int cap) {
         r += tmp;
     }
     if (p->dev_used) r += "; device entries: k_pred_stage";
+    if (p->noisy_ready) {   // after the first call with input noise on the handle
+        snprintf(tmp, sizeof tmp, "; noise: k_predict_noisy_small (%d pair chunks)", p->nchunks);
+        r += tmp;
+    }
     snprintf(buf, (size_t)cap, "%s", r.c_str());
     return (int)r.size();
 }

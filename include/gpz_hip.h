@@ -284,7 +284,7 @@ int gpz_predictor_stack(gpz_predictor *p, const double *Xs, int64_t ns, int32_t 
  * Before its first tile a call scans all rows (and labels and weights) on the device: rows with NaN -> GPZ_ERR_UNSUPPORTED, a label
  * outside [-1, ngroups) or a negative or non-finite weight -> GPZ_ERR_ARG, in both cases with the outputs untouched.  The argument
  * checks of the host entries apply unchanged; x_type outside {0, 1}, a stride of 0 with ns > 1, or only one of muX / sdX ->
- * GPZ_ERR_ARG.  Input noise is not part of these entries.  gpz_predictor_info's runs count gpz_predictor_run_dev calls too; its bytes
+ * GPZ_ERR_ARG.  Input noise has entries of its own below.  gpz_predictor_info's runs count gpz_predictor_run_dev calls too; its bytes
  * grow by one small parameter buffer on the first device call and never with ns; gpz_predictor_route then appends
  * "; device entries: k_pred_stage". */
 #define GPZ_X_F64 0
@@ -302,6 +302,35 @@ int gpz_predictor_stack_dev(gpz_predictor *p, const void *X_d, int32_t x_type, i
                             const int32_t *group_d /* ns or NULL */, int32_t ngroups, const double *weight_d /* ns or NULL */,
                             double *hist, double *sum_w, double *sum_mu, double *sum_mu2, const double *mu_shift /* k or NULL */,
                             void *stream);
+
+/* ---- rows with input noise on the predictor handle --------------------------------------------------------------------------------
+ * predictNoisy (predictDiag.m:75-125) and the draws for rows with a variance per input dimension, on the handle's own tiles, where
+ * predict_noisy_fits holds: a diagonal kind (GL, VL, GD, VD), d <= 20, k <= 8 and ceil16(m) <= 256.  Any other shape returns
+ * GPZ_ERR_UNSUPPORTED and names the condition; gpz_predictor_run takes Psi for every shape on its one-shot route.  Complete rows only.
+ * The device entries take what gpz_predictor_run_dev / _draws_dev take, plus Psi_d: element (i, c) of the ns x d variances at
+ * Psi_d[i * psi_row_stride + c * psi_col_stride], psi_type GPZ_X_F64 or GPZ_X_F32, a column stride of 0 for one variance per row; and
+ * sd2 (host, d values, = sdX squared; NULL with sdX): Psi enters the kernels as double(psi) / sd2[c], one f64 division (the bits of
+ * fixPsi).  gpz_predictor_run_noisy_dev: mu_d, nu_d, beta_d (required), gamma_d, sigma_d = (nu + beta) + gamma (optional); there is no
+ * PHI argument.  nu reads the lower triangle of iSigma_w(:,:,o) only, as the reference does.  A NaN in the rows -> GPZ_ERR_UNSUPPORTED,
+ * an element of Psi that is NaN, negative or (itself or divided by sd2) infinite -> GPZ_ERR_ARG, both found by the scan before the first tile, outputs untouched.
+ * gpz_predictor_draws_noisy (host): F(i, o, s) = E_x[PHI](i, :) (w(:, o) + R_o z(:, s, o)), the predictive mean of predictNoisy under
+ * weight draw s (it is linear in w); Xs and Psi column-major ns x d, normalised; everything else as gpz_predictor_draws.
+ * A row's results have the same bits for any tile size, row order or split of the rows into calls: the pair sum is cut into
+ * chunks by the model's shape alone.  The first call with Psi allocates the Psi slots; the first gpz_predictor_run_noisy_dev the pair
+ * table (m (m + 1) / 2 records of 1 + 2 d + 3 k doubles), the output slots and the chunk slab (gpz_predictor_info's bytes; a handle that never sees Psi holds what it held), and
+ * gpz_predictor_route then ends in "; noise: k_predict_noisy_small (C pair chunks)". */
+int gpz_predictor_run_noisy_dev(gpz_predictor *p, const void *X_d, int32_t x_type, int64_t ns, int64_t row_stride, int64_t col_stride,
+                                const void *Psi_d, int32_t psi_type, int64_t psi_row_stride, int64_t psi_col_stride,
+                                const double *muX, const double *sdX, const double *sd2, const double *muY /* k or NULL */,
+                                double *mu_d, double *sigma_d, double *nu_d, double *beta_d, double *gamma_d, void *stream);
+int gpz_predictor_draws_noisy_dev(gpz_predictor *p, const void *X_d, int32_t x_type, int64_t ns, int64_t row_stride, int64_t col_stride,
+                                  const void *Psi_d, int32_t psi_type, int64_t psi_row_stride, int64_t psi_col_stride,
+                                  const double *muX, const double *sdX, const double *sd2, const double *muY /* k or NULL */,
+                                  int32_t ndraws, uint64_t seed, const double *Z /* host: NULL or m x ndraws x k */,
+                                  double *F_d /* ns x k x ndraws, column-major */, void *stream);
+int gpz_predictor_draws_noisy(gpz_predictor *p, const double *Xs, int64_t ns, const double *Psi /* ns x d, normalised */,
+                              int32_t ndraws, uint64_t seed, const double *Z /* NULL or m x ndraws x k */,
+                              double *F /* ns x k x ndraws, column-major */);
 
 /* ---- device-resident L-BFGS memory: minFunc's lbfgsAdd.m / lbfgsProd.m (mex/lbfgsAddC.c, mex/lbfgsProdC.c) ----
  * S and Y (p x corrections) live on the device; all vector arguments are device pointers.
