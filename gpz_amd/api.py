@@ -676,9 +676,12 @@ class Predictor:
         self._closed = False
         self._lib = None
 
-    def _handle(self):
+    def _check_open(self):
         if self._closed:
             raise RuntimeError("Predictor is closed")
+
+    def _handle(self):
+        self._check_open()
         if self._h is None:
             self._lib = _lib.load()
             ds = _desc(self.model, self.device)
@@ -750,6 +753,13 @@ class Predictor:
                 psi = psi[:, :, sel] if psi.ndim == 3 else psi[sel]
         return X, psi
 
+    def _normalised(self, X):
+        """(X - muX) / sdX (predict.m:35-36), one pass into the column-major layout."""
+        Xn = np.empty(X.shape, order="F")
+        np.subtract(X, self.model.muX, out=Xn)
+        np.divide(Xn, self.model.sdX, out=Xn)
+        return Xn
+
     def _run(self, Xg, Pg, cube, want_phi):
         ng, k, m = Xg.shape[0], self._k, self._m
         o = [np.empty((ng, k), order="F") for _ in range(4)]
@@ -760,13 +770,10 @@ class Predictor:
 
     def predict(self, X, Psi=None, selection=None, return_phi=False):
         """mu, sigma, nu, beta_i, gamma [, PHI] of ``predict`` (predict.m:1) for the rows of X (n x d, not normalised)."""
-        if self._closed:
-            raise RuntimeError("Predictor is closed")
+        self._check_open()
         model, k, m = self.model, self._k, self._m
         X, psi = self._check_inputs(X, Psi, selection)
-        Xn = np.empty(X.shape, order="F")                                # predict.m:35-36, one pass into the column-major layout
-        np.subtract(X, model.muX, out=Xn)
-        np.divide(Xn, model.sdX, out=Xn)
+        Xn = self._normalised(X)
         ns = Xn.shape[0]
         psin = None
         if psi is not None:
@@ -821,9 +828,8 @@ class Predictor:
         is the same on every call and for every n_draws > s.  ``Z`` (m x n_draws x k, or m x n_draws when k = 1) gives them instead;
         ``Z = eye(m)`` with n_draws = m makes (draws - mu) an exact square root of the joint covariance of the rows' means.  Complete
         rows only: rows with NaN are refused.  At most n_draws * k = 16384 columns per call."""
-        if self._closed:
-            raise RuntimeError("Predictor is closed")
-        model, k, m = self.model, self._k, self._m
+        self._check_open()
+        model, k = self.model, self._k
         X, psi = self._check_inputs(X, Psi, selection)
         nbad = int(np.isnan(X).any(axis=1).sum()) if X.size else 0
         if nbad:
@@ -832,28 +838,11 @@ class Predictor:
             self._check_noisy_model("draws", draws=True)
             if not np.all(np.isfinite(psi)) or np.any(psi < 0):
                 raise ValueError("Psi must be finite and >= 0")
-        if isinstance(n_draws, (bool, np.bool_)) or not isinstance(n_draws, (int, np.integer)) or n_draws < 1:
-            raise ValueError(f"n_draws must be a positive integer, got {n_draws!r}")
-        n_draws = int(n_draws)
-        if n_draws * k > GPZ_DRAWS_MAX_COLUMNS:
-            raise ValueError(f"n_draws * k = {n_draws * k} is over the limit of {GPZ_DRAWS_MAX_COLUMNS} per call")
-        if isinstance(seed, (bool, np.bool_)) or not isinstance(seed, (int, np.integer)) or not 0 <= int(seed) < 2 ** 64:
-            raise ValueError(f"seed must be an integer in [0, 2^64), got {seed!r}")
-        z = None
-        if Z is not None:
-            z = np.asarray(Z, dtype=np.float64)
-            if k == 1 and z.shape == (m, n_draws):
-                z = z[:, :, None]
-            if z.shape != (m, n_draws, k):
-                want = f"({m}, {n_draws}, {k})" + (f" or ({m}, {n_draws})" if k == 1 else "")
-                raise ValueError(f"Z must have shape {want}, got {np.asarray(Z).shape}")
-            z = np.asfortranarray(z)
+        n_draws, z = self._check_draw_args(n_draws, seed, Z, 1)
         ns = X.shape[0]
         F = np.empty((ns, k, n_draws), order="F")                        # column-major ns x k x n_draws, as the C entry writes it
         if ns:
-            Xn = np.empty(X.shape, order="F")                            # predict.m:35-36
-            np.subtract(X, model.muX, out=Xn)
-            np.divide(Xn, model.sdX, out=Xn)
+            Xn = self._normalised(X)
             psin = None
             if psi is not None:
                 from .host import fixPsi
@@ -867,7 +856,6 @@ class Predictor:
         out = F.transpose(2, 0, 1)                                       # (n_draws, n, k) view
         out += np.asarray(model.muY, dtype=np.float64).reshape(k)        # predict.m:73
         return out
-
 
     def stack(self, X, edges, n_draws=0, seed=0, Z=None, groups=None, n_groups=None, weights=None, selection=None):
         """Stacked predictive densities on the device (gpz_predictor_stack): the n(z) of every group of rows under the posterior-mean
@@ -889,39 +877,15 @@ class Predictor:
         to the rows, labels and weights alike) as in ``predict``.  Complete, noise-free rows only.  Every field but ``edges`` is a plain
         sum over rows, so the results of several calls add: a catalogue read in chunks is a loop over ``stack`` and a ``+=`` per field.
         The same call on the same handle returns the same bits every time; another ``tile_rows`` may change the last ones."""
-        if self._closed:
-            raise RuntimeError("Predictor is closed")
-        model, k, m = self.model, self._k, self._m
+        self._check_open()
         n_all = np.asarray(X).shape[0] if np.ndim(X) else 0             # rows before the selection: labels and weights go with them
         X, _ = self._check_inputs(X, None, selection)
         sel = None if selection is None else np.asarray(selection).astype(bool)
         nbad = int(np.isnan(X).any(axis=1).sum()) if X.size else 0
         if nbad:
             raise ValueError(f"X has {nbad} rows with missing values (NaN): stacks are for complete rows")
-        e = np.asarray(edges, dtype=np.float64)
-        if e.ndim != 1 or e.size < 2:
-            raise ValueError(f"edges must be a vector of at least 2 values, got shape {e.shape}")
-        if not np.all(np.isfinite(e)) or not np.all(np.diff(e) > 0):
-            raise ValueError("edges must be finite and strictly increasing")
-        B = e.size - 1
-        if isinstance(n_draws, (bool, np.bool_)) or not isinstance(n_draws, (int, np.integer)) or n_draws < 0:
-            raise ValueError(f"n_draws must be a non-negative integer, got {n_draws!r}")
-        n_draws = int(n_draws)
-        if (1 + n_draws) * k > GPZ_DRAWS_MAX_COLUMNS:
-            raise ValueError(f"(1 + n_draws) * k = {(1 + n_draws) * k} is over the limit of {GPZ_DRAWS_MAX_COLUMNS} per call")
-        if isinstance(seed, (bool, np.bool_)) or not isinstance(seed, (int, np.integer)) or not 0 <= int(seed) < 2 ** 64:
-            raise ValueError(f"seed must be an integer in [0, 2^64), got {seed!r}")
-        z = None
-        if Z is not None:
-            if n_draws == 0:
-                raise ValueError("Z must be None when n_draws is 0")
-            z = np.asarray(Z, dtype=np.float64)
-            if k == 1 and z.shape == (m, n_draws):
-                z = z[:, :, None]
-            if z.shape != (m, n_draws, k):
-                want = f"({m}, {n_draws}, {k})" + (f" or ({m}, {n_draws})" if k == 1 else "")
-                raise ValueError(f"Z must have shape {want}, got {np.asarray(Z).shape}")
-            z = np.asfortranarray(z)
+        e, B = self._check_edges(edges)
+        n_draws, z = self._check_draw_args(n_draws, seed, Z, 0)
         ns = X.shape[0]
         lab = None
         if groups is not None:
@@ -956,20 +920,16 @@ class Predictor:
             wt = np.ascontiguousarray(wa)
         if G * B > GPZ_STACK_MAX_GROUP_BINS:
             raise ValueError(f"n_groups * bins = {G * B} is over the limit of {GPZ_STACK_MAX_GROUP_BINS} per call")
-        C_ = 1 + n_draws
-        muY = np.asarray(model.muY, dtype=np.float64).reshape(-1)
-        muY = np.broadcast_to(muY, (k,)) if muY.size == 1 else muY.reshape(k)
-        hist = np.zeros((C_, G, k, B)); sum_w = np.zeros(G); sum_mu = np.zeros((C_, G, k)); sum_mu2 = np.zeros((C_, G, k))
+        hist, sum_w, sum_mu, sum_mu2 = self._stack_arrays(n_draws, G, B)
         if ns:
-            Xn = np.empty(X.shape, order="F")                            # predict.m:35-36
-            np.subtract(X, model.muX, out=Xn)
-            np.divide(Xn, model.sdX, out=Xn)
-            es = np.ascontiguousarray(e[None, :] - muY[:, None])         # k x (B + 1): the entry's mu is without muY
+            Xn = self._normalised(X)
+            muY = self._norm_vectors()[2]
+            es = self._stack_edges(e, muY)
             h = self._handle()
             _lib.check(self._lib.gpz_predictor_stack(h, _lib.dptr(Xn), ns, n_draws, int(seed), _lib.dptr(z), _lib.dptr(es), B,
                                                      None if lab is None else lab.ctypes.data_as(_lib.c_int32_p), G, _lib.dptr(wt),
                                                      _lib.dptr(hist), _lib.dptr(sum_w), _lib.dptr(sum_mu), _lib.dptr(sum_mu2),
-                                                     _lib.dptr(np.ascontiguousarray(muY))))   # predict.m:73 inside the sums
+                                                     _lib.dptr(muY)))          # predict.m:73 inside the sums
         return StackResult(hist, sum_w, sum_mu, sum_mu2, e.copy())
 
     # ---- device-resident entries: the catalogue is a torch tensor on the handle's GPU, per-row results stay there -------------------
@@ -1052,6 +1012,26 @@ class Predictor:
             z = np.asfortranarray(z)
         return n_draws, z
 
+    @staticmethod
+    def _check_edges(edges):
+        """The bin edges of a stack call as a float64 vector, and the number of bins."""
+        e = np.asarray(edges, dtype=np.float64)
+        if e.ndim != 1 or e.size < 2:
+            raise ValueError(f"edges must be a vector of at least 2 values, got shape {e.shape}")
+        if not np.all(np.isfinite(e)) or not np.all(np.diff(e) > 0):
+            raise ValueError("edges must be finite and strictly increasing")
+        return e, e.size - 1
+
+    def _stack_arrays(self, n_draws, G, B):
+        """The zeroed fields of a StackResult: hist, sum_w, sum_mu, sum_mu2."""
+        C_, k = 1 + n_draws, self._k
+        return np.zeros((C_, G, k, B)), np.zeros(G), np.zeros((C_, G, k)), np.zeros((C_, G, k))
+
+    @staticmethod
+    def _stack_edges(e, muY):
+        """The edges as the entry takes them: k x (B + 1), without muY as the entry's mu is."""
+        return np.ascontiguousarray(e[None, :] - muY[:, None])
+
     def _norm_vectors(self):
         """model.muX, model.sdX (d values each) and model.muY (k values) as contiguous float64 host vectors."""
         def vec(a, n):
@@ -1086,8 +1066,7 @@ class Predictor:
         d <= 20, k <= 8, m <= 256) and does not return PHI; an element of Psi that is NaN, infinite or negative is refused (GpzError).
         Type, dtype and shape are checked first, the device last, all before the GPU is touched."""
         import torch
-        if self._closed:
-            raise RuntimeError("Predictor is closed")
+        self._check_open()
         k, m = self._k, self._m
         X = self._check_dev_rows(X, selection, "predict")
         if Psi is not None:
@@ -1126,8 +1105,7 @@ class Predictor:
         the draws is then a torch reduction over it; nothing comes to the host unless asked.  ``Psi`` as for ``predict_dev``
         (gpz_predictor_draws_noisy_dev): the draws of ``predict(X, Psi=Psi)``'s mu, with the bits of ``draws(X, ..., Psi=Psi)``."""
         import torch
-        if self._closed:
-            raise RuntimeError("Predictor is closed")
+        self._check_open()
         k = self._k
         X = self._check_dev_rows(X, selection, "draws")
         n_draws, z = self._check_draw_args(n_draws, seed, Z, 1)
@@ -1164,17 +1142,10 @@ class Predictor:
         same handle and rows.  ``n_groups`` defaults to ``groups.max() + 1`` (one scalar read back).  Labels outside [-1, n_groups)
         and negative or non-finite weights are found on the device and refused with a GpzError, as rows with NaN are."""
         import torch
-        if self._closed:
-            raise RuntimeError("Predictor is closed")
-        k = self._k
+        self._check_open()
         X = self._check_dev_rows(X, selection, "stack")
         n_all = X.shape[0]
-        e = np.asarray(edges, dtype=np.float64)
-        if e.ndim != 1 or e.size < 2:
-            raise ValueError(f"edges must be a vector of at least 2 values, got shape {e.shape}")
-        if not np.all(np.isfinite(e)) or not np.all(np.diff(e) > 0):
-            raise ValueError("edges must be finite and strictly increasing")
-        B = e.size - 1
+        e, B = self._check_edges(edges)
         n_draws, z = self._check_draw_args(n_draws, seed, Z, 0)
         if groups is not None:
             if not isinstance(groups, torch.Tensor) or groups.dtype.is_floating_point or groups.dtype.is_complex or \
@@ -1202,11 +1173,10 @@ class Predictor:
                 raise ValueError(f"n_groups * bins = {n_groups * B} is over the limit of {GPZ_STACK_MAX_GROUP_BINS} per call")
         G = int(n_groups)
         n = X.shape[0]
-        C_ = 1 + n_draws
-        hist = np.zeros((C_, G, k, B)); sum_w = np.zeros(G); sum_mu = np.zeros((C_, G, k)); sum_mu2 = np.zeros((C_, G, k))
+        hist, sum_w, sum_mu, sum_mu2 = self._stack_arrays(n_draws, G, B)
         if n:
             muX, sdX, muY = self._norm_vectors()
-            es = np.ascontiguousarray(e[None, :] - muY[:, None])         # k x (B + 1): the entry's mu is without muY
+            es = self._stack_edges(e, muY)
             h = self._handle()
             # X, lab and wt are referenced by this frame for the whole (host-synchronous) call: no record_stream needed
             _lib.check(self._lib.gpz_predictor_stack_dev(h, *self._x_args(X), _lib.dptr(muX), _lib.dptr(sdX), n_draws, int(seed),

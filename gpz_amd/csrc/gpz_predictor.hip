@@ -205,6 +205,17 @@ static int predictor_setup(gpz_predictor *p, const double *theta, const double *
     return 0;
 }
 
+// launch_phi's arguments for the nt rows in Xc[s] on the tile route: PHI into p->Phi, ln beta into p->lnbeta
+static PhiArgs predictor_phi_args(const gpz_predictor *p, int s, int nt) {
+    PhiArgs a{};
+    a.Xc = p->Xc[s]; a.ldx = p->tile_pad; a.n = nt; a.n_pad = (int)rup(nt, 1024);
+    a.m = p->m; a.mp = p->mp; a.d = p->de; a.k = p->k; a.kind = p->kind;
+    a.P = p->pr.P; a.G = p->kind == GPZ_KIND_COV ? p->pr.Rc : p->pr.G2;
+    a.v = p->hetero ? p->pr.v : nullptr; a.b = p->pr.b;
+    a.Phi = p->Phi; a.lnbeta = p->lnbeta;
+    return a;
+}
+
 // the kernels of one tile of nt rows: Xc[s] -> out[s] ([3k][nt]) and, when asked, phi_d[s] ([m][nt])
 static int predictor_tile(gpz_predictor *p, int s, int nt, bool want_phi) {
     hipStream_t st = p->s_cmp;
@@ -217,13 +228,8 @@ static int predictor_tile(gpz_predictor *p, int s, int nt, bool want_phi) {
         return 0;
     }
     const long np = rup(nt, 1024);
-    PhiArgs a{};
-    a.Xc = p->Xc[s]; a.ldx = p->tile_pad; a.n = nt; a.n_pad = (int)np;
-    a.m = p->m; a.mp = p->mp; a.d = p->de; a.k = k; a.kind = p->kind;
-    a.P = p->pr.P; a.G = p->kind == GPZ_KIND_COV ? p->pr.Rc : p->pr.G2;
-    a.v = p->hetero ? p->pr.v : nullptr; a.b = p->pr.b;
-    a.Phi = p->Phi; a.lnbeta = p->lnbeta;
-    if (launch_phi(st, a)) return gpz_fail(GPZ_ERR_UNSUPPORTED, "gpz_predictor_run: PHI kernel not instantiated for d=%d", p->de);
+    if (launch_phi(st, predictor_phi_args(p, s, nt)))
+        return gpz_fail(GPZ_ERR_UNSUPPORTED, "gpz_predictor_run: PHI kernel not instantiated for d=%d", p->de);
     const size_t mp = (size_t)p->mp;
     for (int o = 0; o < k; ++o)
         launch_tgemm(st, p->Phi, p->mp, p->B + (size_t)o * mp * mp, p->mp, p->T, (int)np, p->mp,
@@ -246,64 +252,104 @@ static int predictor_want_phi(gpz_predictor *p, bool pinned = true) {
     return 0;
 }
 
-static int predictor_run_full(gpz_predictor *p, const double *Xs, int64_t ns, double *mu, double *nu, double *beta_i, double *PHI) {
-    const int k = p->k, d = p->d, m = p->m;
-    const int64_t T = p->tile_rows, ntiles = (ns + T - 1) / T;
+// ---- the host pipeline --------------------------------------------------------------------------------------------------------------
+// columns [r0, r0 + nt) of the column-major ns x d array A into a pinned slot ([d][tp], the layout of Xc); true if hit(v) held for an element
+template <class Hit>
+static bool predictor_stage(const double *A, int64_t ns, int d, int64_t r0, int64_t nt, double *slot, size_t tp, Hit hit) {
+    bool bad = false;
+    for (int c = 0; c < d; ++c) {
+        const double *src = A + (size_t)c * ns + r0;
+        double *dst = slot + (size_t)c * tp;
+        int any = 0;
+        for (int64_t i = 0; i < nt; ++i) { const double v = src[i]; dst[i] = v; any |= hit(v); }
+        bad |= any != 0;
+    }
+    return bad;
+}
+
+// The tiles of a host entry: three streams - copies in, compute, copies out - and the two slots.  The driver owns the loop and every event
+// and stream call; a job says what one tile in slot s (nt rows from row r0, T rows per tile) is made of:
+//   who, nan_text     the entry's name in the messages, and its refusal of rows with missing values
+//   downloads         false: nothing comes home per tile (the stack), so there is no work on s_out and no tile to wait for at the end
+//   stage(s, r0, nt)  what goes into the pinned slots beside the rows: 0, or the refusal
+//   upload(s, nt)     the copies that ride s_in behind the rows; true: one failed (so too download)
+//   kernels(s, nt)    the tile's kernels on s_cmp: 0, or the failure
+//   download(s, nt)   the copies home on s_out;  scatter(s, r0, nt): the pinned results into the caller's arrays, two tiles later
+// Failures return at once: the caller drains the streams (predictor_drain) whatever the result.
+template <class Job>
+static int predictor_pipeline(gpz_predictor *p, const double *Xs, int64_t ns, int64_t T, Job &job) {
     const size_t tp = (size_t)p->tile_pad;
-    int rc = 0;
+    const int64_t ntiles = (ns + T - 1) / T;
     int64_t nt_of[2] = {0, 0}, r0_of[2] = {0, 0};
-    auto scatter = [&](int s) {
-        const int64_t nt = nt_of[s], r0 = r0_of[s];
-        double *dst[3] = {mu, nu, beta_i};
-        for (int q = 0; q < 3; ++q)
-            for (int o = 0; o < k; ++o) memcpy(dst[q] + (size_t)o * ns + r0, p->hout[s] + (size_t)(q * k + o) * nt, (size_t)nt * sizeof(double));
-        if (PHI)
-            for (int j = 0; j < m; ++j) memcpy(PHI + (size_t)j * ns + r0, p->hphi[s] + (size_t)j * nt, (size_t)nt * sizeof(double));
-    };
-    for (int64_t t = 0; t < ntiles + 2 && !rc; ++t) {
+    for (int64_t t = 0; t < ntiles + (Job::downloads ? 2 : 0); ++t) {
         const int s = (int)(t & 1);
-        if (t >= 2) {   // tile t - 2 is home: into the caller's arrays (its slot is then free for tile t)
-            if (hipEventSynchronize(p->ev_out[s]) != hipSuccess) { rc = gpz_fail(GPZ_ERR_HIP, "gpz_predictor_run: tile failed"); break; }
-            scatter(s);
+        if (t >= 2) {   // slot s is free for tile t: tile t - 2 is home (into the caller's arrays) or, with no download, its upload has left the pinned slot
+            if (hipEventSynchronize(Job::downloads ? p->ev_out[s] : p->ev_in[s]) != hipSuccess)
+                return gpz_fail(GPZ_ERR_HIP, "%s: tile failed", job.who);
+            if constexpr (Job::downloads) job.scatter(s, r0_of[s], nt_of[s]);
         }
         if (t >= ntiles) continue;
         const int64_t r0 = t * T, nt = std::min<int64_t>(T, ns - r0);
         nt_of[s] = nt; r0_of[s] = r0;
-        // stage the tile's rows ([d][tile_pad], the layout of Xc) and look for missing values on the way
-        bool bad = false;
-        for (int c = 0; c < d; ++c) {
-            const double *src = Xs + (size_t)c * ns + r0;
-            double *dst = p->hin[s] + (size_t)c * tp;
-            int nan = 0;
-            for (int64_t i = 0; i < nt; ++i) { const double v = src[i]; dst[i] = v; nan |= v != v; }
-            bad |= nan != 0;
-        }
-        if (bad) {
-            rc = gpz_fail(GPZ_ERR_UNSUPPORTED, "gpz_predictor_run: the rows have missing values (NaN): group them by pattern and call gpz_predict_missing (predict.m:45-69)");
-            break;
-        }
-        // copy in (after tile t - 2's kernels are done with Xc[s]); kernels (after the copy, and after tile t - 2's download of out[s]);
-        // copy out
+        // stage the tile's rows and look for missing values on the way
+        if (predictor_stage(Xs, ns, p->d, r0, nt, p->hin[s], tp, [](double v) { return v != v; }))
+            return gpz_fail(GPZ_ERR_UNSUPPORTED, "%s: %s", job.who, job.nan_text);
+        if (int rc = job.stage(s, r0, nt)) return rc;
+        // copies in (after tile t - 2's kernels are done with the slot); kernels (after the copies, and after tile t - 2's download of the
+        // slot's outputs); copies out
         if (hipStreamWaitEvent(p->s_in, p->ev_cmp[s], 0) != hipSuccess ||
-            hipMemcpy2DAsync(p->Xc[s], tp * sizeof(double), p->hin[s], tp * sizeof(double), (size_t)nt * sizeof(double), d,
+            hipMemcpy2DAsync(p->Xc[s], tp * sizeof(double), p->hin[s], tp * sizeof(double), (size_t)nt * sizeof(double), p->d,
                              hipMemcpyHostToDevice, p->s_in) != hipSuccess ||
-            hipEventRecord(p->ev_in[s], p->s_in) != hipSuccess || hipStreamWaitEvent(p->s_cmp, p->ev_in[s], 0) != hipSuccess ||
-            hipStreamWaitEvent(p->s_cmp, p->ev_out[s], 0) != hipSuccess) {
-            rc = gpz_fail(GPZ_ERR_HIP, "gpz_predictor_run: copy failed");
-            break;
-        }
-        if ((rc = predictor_tile(p, s, (int)nt, PHI != nullptr))) break;
-        if (hipEventRecord(p->ev_cmp[s], p->s_cmp) != hipSuccess || hipStreamWaitEvent(p->s_out, p->ev_cmp[s], 0) != hipSuccess ||
-            hipMemcpyAsync(p->hout[s], p->out[s], 3 * (size_t)k * nt * sizeof(double), hipMemcpyDeviceToHost, p->s_out) != hipSuccess ||
-            (PHI && hipMemcpyAsync(p->hphi[s], p->phi_d[s], (size_t)m * nt * sizeof(double), hipMemcpyDeviceToHost, p->s_out) != hipSuccess) ||
-            hipEventRecord(p->ev_out[s], p->s_out) != hipSuccess) {
-            rc = gpz_fail(GPZ_ERR_HIP, "gpz_predictor_run: copy failed");
-            break;
-        }
+            job.upload(s, nt) || hipEventRecord(p->ev_in[s], p->s_in) != hipSuccess ||
+            hipStreamWaitEvent(p->s_cmp, p->ev_in[s], 0) != hipSuccess ||
+            (Job::downloads && hipStreamWaitEvent(p->s_cmp, p->ev_out[s], 0) != hipSuccess))
+            return gpz_fail(GPZ_ERR_HIP, "%s: copy failed", job.who);
+        if (int rc = job.kernels(s, nt)) return rc;
+        if (hipEventRecord(p->ev_cmp[s], p->s_cmp) != hipSuccess)
+            return gpz_fail(GPZ_ERR_HIP, "%s: %s failed", job.who, Job::downloads ? "copy" : "event");
+        if constexpr (Job::downloads)
+            if (hipStreamWaitEvent(p->s_out, p->ev_cmp[s], 0) != hipSuccess || job.download(s, nt) ||
+                hipEventRecord(p->ev_out[s], p->s_out) != hipSuccess)
+                return gpz_fail(GPZ_ERR_HIP, "%s: copy failed", job.who);
     }
+    return 0;
+}
+
+// the end of every host entry, failed or not: nothing of the call is in flight when it returns
+static int predictor_drain(gpz_predictor *p, const char *who, int rc) {
     for (hipStream_t st : {p->s_in, p->s_cmp, p->s_out})
-        if (hipStreamSynchronize(st) != hipSuccess && !rc) rc = gpz_fail(GPZ_ERR_HIP, "gpz_predictor_run: sync failed");
+        if (hipStreamSynchronize(st) != hipSuccess && !rc) rc = gpz_fail(GPZ_ERR_HIP, "%s: sync failed", who);
     return rc;
+}
+
+// gpz_predictor_run (full branch): mu, nu, beta and, when asked, PHI of every tile come home
+struct RunJob {
+    gpz_predictor *p;
+    int64_t ns;
+    double *mu, *nu, *beta_i, *PHI;
+    const char *who = "gpz_predictor_run";
+    const char *nan_text = "the rows have missing values (NaN): group them by pattern and call gpz_predict_missing (predict.m:45-69)";
+    static constexpr bool downloads = true;
+    int stage(int, int64_t, int64_t) { return 0; }
+    bool upload(int, int64_t) { return false; }
+    int kernels(int s, int64_t nt) { return predictor_tile(p, s, (int)nt, PHI != nullptr); }
+    bool download(int s, int64_t nt) {
+        return hipMemcpyAsync(p->hout[s], p->out[s], 3 * (size_t)p->k * nt * sizeof(double), hipMemcpyDeviceToHost, p->s_out) != hipSuccess ||
+               (PHI && hipMemcpyAsync(p->hphi[s], p->phi_d[s], (size_t)p->m * nt * sizeof(double), hipMemcpyDeviceToHost, p->s_out) != hipSuccess);
+    }
+    void scatter(int s, int64_t r0, int64_t nt) {
+        double *dst[3] = {mu, nu, beta_i};
+        for (int q = 0; q < 3; ++q)
+            for (int o = 0; o < p->k; ++o)
+                memcpy(dst[q] + (size_t)o * ns + r0, p->hout[s] + (size_t)(q * p->k + o) * nt, (size_t)nt * sizeof(double));
+        if (PHI)
+            for (int j = 0; j < p->m; ++j) memcpy(PHI + (size_t)j * ns + r0, p->hphi[s] + (size_t)j * nt, (size_t)nt * sizeof(double));
+    }
+};
+
+static int predictor_run_full(gpz_predictor *p, const double *Xs, int64_t ns, double *mu, double *nu, double *beta_i, double *PHI) {
+    RunJob job{p, ns, mu, nu, beta_i, PHI};
+    return predictor_drain(p, job.who, predictor_pipeline(p, Xs, ns, p->tile_rows, job));
 }
 
 // input noise: gpz_predict_noisy on one tile of rows at a time (its buffers are sized by the tile)
@@ -502,7 +548,7 @@ static int predictor_draws_prepare(gpz_predictor *p, int nd, unsigned long long 
 // Psic: the tile's Psi slot for rows with input noise (fused route, diagonal kinds), else nullptr
 static int predictor_draws_tile(gpz_predictor *p, int s, int64_t nt, int ncol, int ldw, bool phi_built = false,
                                 const double *Psic = nullptr) {
-    const int k = p->k, m = p->m;
+    const int m = p->m;
     hipStream_t st = p->s_cmp;
     const double *G = p->kind == GPZ_KIND_COV ? p->pr.Rc : p->pr.G2;
     if (Psic) {
@@ -517,13 +563,7 @@ static int predictor_draws_tile(gpz_predictor *p, int s, int64_t nt, int ncol, i
         return 0;
     }
     const long np = rup(nt, 1024);
-    PhiArgs a{};
-    a.Xc = p->Xc[s]; a.ldx = p->tile_pad; a.n = (int)nt; a.n_pad = (int)np;
-    a.m = m; a.mp = p->mp; a.d = p->de; a.k = k; a.kind = p->kind;
-    a.P = p->pr.P; a.G = G;
-    a.v = p->hetero ? p->pr.v : nullptr; a.b = p->pr.b;
-    a.Phi = p->Phi; a.lnbeta = p->lnbeta;
-    if (!phi_built && launch_phi(st, a))
+    if (!phi_built && launch_phi(st, predictor_phi_args(p, s, (int)nt)))
         return gpz_fail(GPZ_ERR_UNSUPPORTED, "gpz_predictor_draws: PHI kernel not instantiated for d=%d", p->de);
     // T = PHI W: K = mp (rows >= m of W are zero), ldw output columns
     launch_tgemm(st, p->Phi, p->mp, p->Wd, ldw, p->Td, (int)np, ldw, nullptr, nullptr, m, 0, false, p->mp, ldw);
@@ -532,87 +572,54 @@ static int predictor_draws_tile(gpz_predictor *p, int s, int64_t nt, int ncol, i
     return 0;
 }
 
-// Psi (gpz_predictor_draws_noisy; nullptr: noise-free rows): normalised ns x d column-major, staged into a second pair of pinned slots
-// and uploaded with X's tile
+// gpz_predictor_draws: the draws of every tile come home.  Psi (gpz_predictor_draws_noisy; nullptr: noise-free rows): normalised ns x d
+// column-major, staged into a second pair of pinned slots and uploaded with X's tile
+struct DrawsJob {
+    gpz_predictor *p;
+    int64_t ns;
+    int nd, ncol, ldw;
+    const double *Psi;
+    double *F;
+    const char *who = "gpz_predictor_draws";
+    const char *nan_text = "the rows have missing values (NaN): draws are for complete rows";
+    static constexpr bool downloads = true;
+    int stage(int s, int64_t r0, int64_t nt) {
+        if (Psi && predictor_stage(Psi, ns, p->d, r0, nt, p->hpsi[s], (size_t)p->tile_pad,
+                                   [](double v) { return !(v >= 0.0) || !(v <= 1.7976931348623157e308); }))
+            return gpz_fail(GPZ_ERR_ARG, "gpz_predictor_draws_noisy: Psi has an element that is NaN, infinite or negative");
+        return 0;
+    }
+    bool upload(int s, int64_t nt) {
+        const size_t tp = (size_t)p->tile_pad;
+        return Psi && hipMemcpy2DAsync(p->Psic[s], tp * sizeof(double), p->hpsi[s], tp * sizeof(double), (size_t)nt * sizeof(double), p->d,
+                                       hipMemcpyHostToDevice, p->s_in) != hipSuccess;
+    }
+    int kernels(int s, int64_t nt) { return predictor_draws_tile(p, s, nt, ncol, ldw, false, Psi ? p->Psic[s] : nullptr); }
+    bool download(int s, int64_t nt) {
+        return hipMemcpyAsync(p->hdout[s], p->dout[s], (size_t)ncol * nt * sizeof(double), hipMemcpyDeviceToHost, p->s_out) != hipSuccess;
+    }
+    void scatter(int s, int64_t r0, int64_t nt) {   // column c = o nd + q of the slot -> F(:, o, q)
+        for (int c = 0; c < ncol; ++c) {
+            const int o = c / nd, q = c % nd;
+            memcpy(F + (size_t)(o + (size_t)p->k * q) * ns + r0, p->hdout[s] + (size_t)c * nt, (size_t)nt * sizeof(double));
+        }
+    }
+};
+
 static int predictor_run_draws(gpz_predictor *p, const double *Xs, int64_t ns, int nd, unsigned long long seed, const double *Z,
-                               double *F, const double *Psi = nullptr) {
-    const int k = p->k, d = p->d, ncol = nd * k, ldw = rup(ncol, 16);
-    const size_t tp = (size_t)p->tile_pad;
-    hipStream_t st = p->s_cmp;
+                               double *F, const double *Psi) {
     int rc = 0;
     int64_t T = 0;
     if (Psi) {
         if ((rc = predictor_psi_slots(p))) return rc;
         for (int s = 0; s < 2; ++s)
-            if (!p->hpsi[s]) HIPCHK(hipHostMalloc((void **)&p->hpsi[s], (size_t)d * tp * sizeof(double), hipHostMallocDefault));
+            if (!p->hpsi[s])
+                HIPCHK(hipHostMalloc((void **)&p->hpsi[s], (size_t)p->d * p->tile_pad * sizeof(double), hipHostMallocDefault));
     }
     if ((rc = predictor_draws_prepare(p, nd, seed, Z, true, &T))) return rc;
     if (Psi && p->droute != 0) return gpz_fail(GPZ_ERR_UNSUPPORTED, "gpz_predictor_draws_noisy: input noise needs the fused draws route");
-    // ---- the pipeline of predictor_run_full on tiles of T rows
-    const int64_t ntiles = (ns + T - 1) / T;
-    int64_t nt_of[2] = {0, 0}, r0_of[2] = {0, 0};
-    auto scatter = [&](int s) {   // column c = o nd + s of the slot -> F(:, o, s)
-        const int64_t nt = nt_of[s], r0 = r0_of[s];
-        for (int c = 0; c < ncol; ++c) {
-            const int o = c / nd, q = c % nd;
-            memcpy(F + (size_t)(o + (size_t)k * q) * ns + r0, p->hdout[s] + (size_t)c * nt, (size_t)nt * sizeof(double));
-        }
-    };
-    for (int64_t t = 0; t < ntiles + 2 && !rc; ++t) {
-        const int s = (int)(t & 1);
-        if (t >= 2) {
-            if (hipEventSynchronize(p->ev_out[s]) != hipSuccess) { rc = gpz_fail(GPZ_ERR_HIP, "gpz_predictor_draws: tile failed"); break; }
-            scatter(s);
-        }
-        if (t >= ntiles) continue;
-        const int64_t r0 = t * T, nt = std::min<int64_t>(T, ns - r0);
-        nt_of[s] = nt; r0_of[s] = r0;
-        bool bad = false;
-        for (int c = 0; c < d; ++c) {
-            const double *src = Xs + (size_t)c * ns + r0;
-            double *dst = p->hin[s] + (size_t)c * tp;
-            int nan = 0;
-            for (int64_t i = 0; i < nt; ++i) { const double v = src[i]; dst[i] = v; nan |= v != v; }
-            bad |= nan != 0;
-        }
-        if (bad) {
-            rc = gpz_fail(GPZ_ERR_UNSUPPORTED, "gpz_predictor_draws: the rows have missing values (NaN): draws are for complete rows");
-            break;
-        }
-        if (Psi) {
-            for (int c = 0; c < d; ++c) {
-                const double *src = Psi + (size_t)c * ns + r0;
-                double *dst = p->hpsi[s] + (size_t)c * tp;
-                int neg = 0;
-                for (int64_t i = 0; i < nt; ++i) { const double v = src[i]; dst[i] = v; neg |= !(v >= 0.0) || !(v <= 1.7976931348623157e308); }
-                bad |= neg != 0;
-            }
-            if (bad) {
-                rc = gpz_fail(GPZ_ERR_ARG, "gpz_predictor_draws_noisy: Psi has an element that is NaN, infinite or negative");
-                break;
-            }
-        }
-        if (hipStreamWaitEvent(p->s_in, p->ev_cmp[s], 0) != hipSuccess ||
-            hipMemcpy2DAsync(p->Xc[s], tp * sizeof(double), p->hin[s], tp * sizeof(double), (size_t)nt * sizeof(double), d,
-                             hipMemcpyHostToDevice, p->s_in) != hipSuccess ||
-            (Psi && hipMemcpy2DAsync(p->Psic[s], tp * sizeof(double), p->hpsi[s], tp * sizeof(double), (size_t)nt * sizeof(double), d,
-                                     hipMemcpyHostToDevice, p->s_in) != hipSuccess) ||
-            hipEventRecord(p->ev_in[s], p->s_in) != hipSuccess || hipStreamWaitEvent(st, p->ev_in[s], 0) != hipSuccess ||
-            hipStreamWaitEvent(st, p->ev_out[s], 0) != hipSuccess) {
-            rc = gpz_fail(GPZ_ERR_HIP, "gpz_predictor_draws: copy failed");
-            break;
-        }
-        if ((rc = predictor_draws_tile(p, s, nt, ncol, ldw, false, Psi ? p->Psic[s] : nullptr))) break;
-        if (hipEventRecord(p->ev_cmp[s], st) != hipSuccess || hipStreamWaitEvent(p->s_out, p->ev_cmp[s], 0) != hipSuccess ||
-            hipMemcpyAsync(p->hdout[s], p->dout[s], (size_t)ncol * nt * sizeof(double), hipMemcpyDeviceToHost, p->s_out) != hipSuccess ||
-            hipEventRecord(p->ev_out[s], p->s_out) != hipSuccess) {
-            rc = gpz_fail(GPZ_ERR_HIP, "gpz_predictor_draws: copy failed");
-            break;
-        }
-    }
-    for (hipStream_t q : {p->s_in, p->s_cmp, p->s_out})
-        if (hipStreamSynchronize(q) != hipSuccess && !rc) rc = gpz_fail(GPZ_ERR_HIP, "gpz_predictor_draws: sync failed");
-    return rc;
+    DrawsJob job{p, ns, nd, nd * p->k, rup(nd * p->k, 16), Psi, F};
+    return predictor_drain(p, job.who, predictor_pipeline(p, Xs, ns, T, job));   // on tiles of T rows
 }
 
 // ---- stack ------------------------------------------------------------------------------------------------------------------------
@@ -620,110 +627,128 @@ static int predictor_run_draws(gpz_predictor *p, const double *Xs, int64_t ns, i
 // k_stack_tile writes the tile's row slabs and k_stack_accum adds them to the running accumulators, all on the compute stream, so the
 // tiles add in their order.  Nothing comes back before the accumulators at the end.  Both kernels run on the draws tile, so that out[s]
 // and dout[s] describe the same rows.  res: (1 + nd) k records of G B + 3 G doubles (k_predict_stack.hip).
-static int predictor_run_stack(gpz_predictor *p, const double *Xs, int64_t ns, int nd, unsigned long long seed, const double *Z,
-                               const double *edges, const double *shift, int B, const int32_t *group, int G, const double *weight,
-                               double *res) {
-    const int k = p->k, d = p->d, ncol = nd * k, ldw = rup(ncol, 16), Q = (1 + nd) * k;
-    const size_t tp = (size_t)p->tile_pad, rec = (size_t)G * B + 3 * (size_t)G, count = (size_t)Q * rec;
+struct StackCall {
+    int nd, B, G, ncol, ldw;
+    int R;           // row slabs per tile
+    size_t ne;       // the edges; behind them in edges_d, the k shifts of the sums
+    size_t count;    // doubles in the accumulators
+    int64_t T;       // rows per tile
+};
+
+// What a stack call does before its first tile: with draws, what they need; the label and weight slots of the host entry (pinned); the
+// edges, accumulators and slabs; then the edges and shifts go up and the accumulators are cleared.  Once this has been called the entry
+// leaves through its stream synchronisation, failed or not: copies from the caller's memory may be in flight.
+static int predictor_stack_prepare(gpz_predictor *p, const char *who, int nd, unsigned long long seed, const double *Z, const double *edges,
+                         const double *shift, int B, int G, bool pinned, StackCall *c) {
+    const int k = p->k, Q = (1 + nd) * k;
+    const size_t tp = (size_t)p->tile_pad, rec = (size_t)G * B + 3 * (size_t)G;
     hipStream_t st = p->s_cmp;
     int rc = 0;
     int64_t T = p->tile_rows;
     if (nd > 0 && (rc = predictor_draws_prepare(p, nd, seed, Z, false, &T))) return rc;
-    for (int s = 0; s < 2; ++s) {   // each one where it is missing: a call that failed half-way here leaves the next one its rest
+    for (int s = 0; s < 2 && pinned; ++s) {   // each one where it is missing: a call that failed half-way here leaves the next one its rest
         if (!p->lab_d[s] && (rc = p->ar.alloc(&p->lab_d[s], tp))) return rc;
         if (!p->wt_d[s] && (rc = p->ar.alloc(&p->wt_d[s], tp))) return rc;
         if (!p->hlab[s]) HIPCHK(hipHostMalloc((void **)&p->hlab[s], tp * sizeof(int), hipHostMallocDefault));
         if (!p->hwt[s]) HIPCHK(hipHostMalloc((void **)&p->hwt[s], tp * sizeof(double), hipHostMallocDefault));
     }
-    const int R = predict_stack_slabs(Q, (long)rec, T);
-    const size_t ne = (size_t)k * (B + 1);   // the edges, then the k shifts of the sums
-    if ((rc = predictor_grow(p, &p->edges_d, &p->edges_cap, ne + k))) return rc;
-    if ((rc = predictor_grow(p, &p->acc_d, &p->acc_cap, count))) return rc;
-    if ((rc = predictor_grow(p, &p->slab_d, &p->slab_cap, count * R))) return rc;
+    *c = StackCall{nd, B, G, nd * k, rup(nd * k, 16), predict_stack_slabs(Q, (long)rec, T), (size_t)k * (B + 1), (size_t)Q * rec, T};
+    if ((rc = predictor_grow(p, &p->edges_d, &p->edges_cap, c->ne + k))) return rc;
+    if ((rc = predictor_grow(p, &p->acc_d, &p->acc_cap, c->count))) return rc;
+    if ((rc = predictor_grow(p, &p->slab_d, &p->slab_cap, c->count * c->R))) return rc;
     p->stile = T;
-    p->sslabs = R;
-    // from here on every failure leaves through the synchronisation of the three streams below: copies from the caller's memory are in flight
-    if (hipMemcpyAsync(p->edges_d, edges, ne * sizeof(double), hipMemcpyHostToDevice, st) != hipSuccess ||
-        (shift ? hipMemcpyAsync(p->edges_d + ne, shift, (size_t)k * sizeof(double), hipMemcpyHostToDevice, st)
-               : hipMemsetAsync(p->edges_d + ne, 0, (size_t)k * sizeof(double), st)) != hipSuccess ||
-        hipMemsetAsync(p->acc_d, 0, count * sizeof(double), st) != hipSuccess)
-        rc = gpz_fail(GPZ_ERR_HIP, "gpz_predictor_stack: copy failed");
-    const int64_t ntiles = rc ? 0 : (ns + T - 1) / T;
-    for (int64_t t = 0; t < ntiles && !rc; ++t) {
-        const int s = (int)(t & 1);
-        // tile t - 2's upload has left the pinned slot
-        if (t >= 2 && hipEventSynchronize(p->ev_in[s]) != hipSuccess) { rc = gpz_fail(GPZ_ERR_HIP, "gpz_predictor_stack: tile failed"); break; }
-        const int64_t r0 = t * T, nt = std::min<int64_t>(T, ns - r0);
-        bool bad = false;
-        for (int c = 0; c < d; ++c) {
-            const double *src = Xs + (size_t)c * ns + r0;
-            double *dst = p->hin[s] + (size_t)c * tp;
-            int nan = 0;
-            for (int64_t i = 0; i < nt; ++i) { const double v = src[i]; dst[i] = v; nan |= v != v; }
-            bad |= nan != 0;
-        }
-        if (bad) {
-            rc = gpz_fail(GPZ_ERR_UNSUPPORTED, "gpz_predictor_stack: the rows have missing values (NaN): stacks are for complete rows");
-            break;
-        }
+    p->sslabs = c->R;
+    if (hipMemcpyAsync(p->edges_d, edges, c->ne * sizeof(double), hipMemcpyHostToDevice, st) != hipSuccess ||
+        (shift ? hipMemcpyAsync(p->edges_d + c->ne, shift, (size_t)k * sizeof(double), hipMemcpyHostToDevice, st)
+               : hipMemsetAsync(p->edges_d + c->ne, 0, (size_t)k * sizeof(double), st)) != hipSuccess ||
+        hipMemsetAsync(p->acc_d, 0, c->count * sizeof(double), st) != hipSuccess)
+        return gpz_fail(GPZ_ERR_HIP, "%s: copy failed", who);
+    return 0;
+}
+
+// the kernels of one stack tile of nt rows in slot s; lab, wt: the tile's labels and weights on the device (nullptr: one group, weight 1)
+static int predictor_stack_tile(gpz_predictor *p, const char *who, const StackCall &c, int s, int64_t nt, const int *lab, const double *wt) {
+    int rc = 0;
+    if ((rc = predictor_tile(p, s, (int)nt, false))) return rc;
+    if (c.nd > 0 && (rc = predictor_draws_tile(p, s, nt, c.ncol, c.ldw, p->route == 1))) return rc;
+    if (launch_stack_tile(p->s_cmp, p->out[s], c.nd > 0 ? p->dout[s] : nullptr, lab, wt, p->edges_d, p->edges_d + c.ne, nt, p->k, c.nd, c.B,
+                          c.G, c.R, p->slab_d) ||
+        launch_stack_accum(p->s_cmp, p->slab_d, c.R, c.count, p->acc_d))
+        return gpz_fail(GPZ_ERR_HIP, "%s: k_stack_tile launch failed", who);
+    return 0;
+}
+
+// the accumulators come home behind the last tile
+static int predictor_stack_result(gpz_predictor *p, const char *who, const StackCall &c, double *res) {
+    if (hipMemcpyAsync(res, p->acc_d, c.count * sizeof(double), hipMemcpyDeviceToHost, p->s_cmp) != hipSuccess)
+        return gpz_fail(GPZ_ERR_HIP, "%s: copy failed", who);
+    return 0;
+}
+
+// gpz_predictor_stack: the tile's labels and weights ride up with its rows, nothing comes home
+struct StackJob {
+    gpz_predictor *p;
+    const StackCall &c;
+    const int32_t *group;
+    const double *weight;
+    const char *who = "gpz_predictor_stack";
+    const char *nan_text = "the rows have missing values (NaN): stacks are for complete rows";
+    static constexpr bool downloads = false;
+    int stage(int s, int64_t r0, int64_t nt) {
         if (group) memcpy(p->hlab[s], group + r0, (size_t)nt * sizeof(int));
         if (weight) memcpy(p->hwt[s], weight + r0, (size_t)nt * sizeof(double));
-        // copies in (after tile t - 2's kernels are done with the slot); kernels (after the copies)
-        if (hipStreamWaitEvent(p->s_in, p->ev_cmp[s], 0) != hipSuccess ||
-            hipMemcpy2DAsync(p->Xc[s], tp * sizeof(double), p->hin[s], tp * sizeof(double), (size_t)nt * sizeof(double), d,
-                             hipMemcpyHostToDevice, p->s_in) != hipSuccess ||
-            (group && hipMemcpyAsync(p->lab_d[s], p->hlab[s], (size_t)nt * sizeof(int), hipMemcpyHostToDevice, p->s_in) != hipSuccess) ||
-            (weight && hipMemcpyAsync(p->wt_d[s], p->hwt[s], (size_t)nt * sizeof(double), hipMemcpyHostToDevice, p->s_in) != hipSuccess) ||
-            hipEventRecord(p->ev_in[s], p->s_in) != hipSuccess || hipStreamWaitEvent(st, p->ev_in[s], 0) != hipSuccess) {
-            rc = gpz_fail(GPZ_ERR_HIP, "gpz_predictor_stack: copy failed");
-            break;
-        }
-        if ((rc = predictor_tile(p, s, (int)nt, false))) break;
-        if (nd > 0 && (rc = predictor_draws_tile(p, s, nt, ncol, ldw, p->route == 1))) break;
-        if (launch_stack_tile(st, p->out[s], nd > 0 ? p->dout[s] : nullptr, group ? p->lab_d[s] : nullptr, weight ? p->wt_d[s] : nullptr,
-                              p->edges_d, p->edges_d + ne, nt, k, nd, B, G, R, p->slab_d) ||
-            launch_stack_accum(st, p->slab_d, R, count, p->acc_d)) {
-            rc = gpz_fail(GPZ_ERR_HIP, "gpz_predictor_stack: k_stack_tile launch failed");
-            break;
-        }
-        if (hipEventRecord(p->ev_cmp[s], st) != hipSuccess) { rc = gpz_fail(GPZ_ERR_HIP, "gpz_predictor_stack: event failed"); break; }
+        return 0;
     }
-    if (!rc && hipMemcpyAsync(res, p->acc_d, count * sizeof(double), hipMemcpyDeviceToHost, st) != hipSuccess)
-        rc = gpz_fail(GPZ_ERR_HIP, "gpz_predictor_stack: copy failed");
-    for (hipStream_t q : {p->s_in, p->s_cmp, p->s_out})
-        if (hipStreamSynchronize(q) != hipSuccess && !rc) rc = gpz_fail(GPZ_ERR_HIP, "gpz_predictor_stack: sync failed");
-    return rc;
-}
-// ---- device-resident entries -------------------------------------------------------------------------------------------------------
-// the caller's rows: element (i, c) at X[i rs + c cs], f64 or f32
-struct DevRows {
-    const void *X;
-    int f32;
-    int64_t ns, rs, cs;
+    bool upload(int s, int64_t nt) {
+        return (group && hipMemcpyAsync(p->lab_d[s], p->hlab[s], (size_t)nt * sizeof(int), hipMemcpyHostToDevice, p->s_in) != hipSuccess) ||
+               (weight && hipMemcpyAsync(p->wt_d[s], p->hwt[s], (size_t)nt * sizeof(double), hipMemcpyHostToDevice, p->s_in) != hipSuccess);
+    }
+    int kernels(int s, int64_t nt) { return predictor_stack_tile(p, who, c, s, nt, group ? p->lab_d[s] : nullptr, weight ? p->wt_d[s] : nullptr); }
 };
 
-static int predictor_dev_args(const char *who, const gpz_predictor *p, const void *X_d, int32_t x_type, int64_t ns, int64_t rs, int64_t cs,
-                              const double *muX, const double *sdX) {
-    if (x_type != GPZ_X_F64 && x_type != GPZ_X_F32) return gpz_fail(GPZ_ERR_ARG, "%s: x_type %d is neither GPZ_X_F64 nor GPZ_X_F32", who, (int)x_type);
+static int predictor_run_stack(gpz_predictor *p, const double *Xs, int64_t ns, int nd, unsigned long long seed, const double *Z,
+                               const double *edges, const double *shift, int B, const int32_t *group, int G, const double *weight,
+                               double *res) {
+    const char *who = "gpz_predictor_stack";
+    StackCall c{};
+    int rc = predictor_stack_prepare(p, who, nd, seed, Z, edges, shift, B, G, true, &c);
+    if (!rc) {
+        StackJob job{p, c, group, weight};
+        rc = predictor_pipeline(p, Xs, ns, c.T, job);
+    }
+    if (!rc) rc = predictor_stack_result(p, who, c, res);
+    return predictor_drain(p, who, rc);
+}
+
+// ---- device-resident entries -------------------------------------------------------------------------------------------------------
+// the caller's rows: element (i, c) at X[i rs + c cs], type GPZ_X_F64 or GPZ_X_F32
+struct DevRows {
+    const void *X;
+    int32_t type;
+    int64_t ns, rs, cs;
+    int f32() const { return type == GPZ_X_F32; }
+};
+
+static int predictor_dev_args(const char *who, const gpz_predictor *p, const DevRows &x, const double *muX, const double *sdX) {
+    if (x.type != GPZ_X_F64 && x.type != GPZ_X_F32)
+        return gpz_fail(GPZ_ERR_ARG, "%s: x_type %d is neither GPZ_X_F64 nor GPZ_X_F32", who, (int)x.type);
     if ((muX != nullptr) != (sdX != nullptr)) return gpz_fail(GPZ_ERR_ARG, "%s: muX and sdX go together (both or neither)", who);
-    if (ns > 0 && !X_d) return gpz_fail(GPZ_ERR_ARG, "%s: null argument", who);
-    if (rs < 0 || cs < 0 || (ns > 1 && (rs == 0 || (cs == 0 && p->d > 1))))
-        return gpz_fail(GPZ_ERR_ARG, "%s: strides (%lld, %lld) of %lld rows: a stride must be positive", who, (long long)rs, (long long)cs,
-                        (long long)ns);
+    if (x.ns > 0 && !x.X) return gpz_fail(GPZ_ERR_ARG, "%s: null argument", who);
+    if (x.rs < 0 || x.cs < 0 || (x.ns > 1 && (x.rs == 0 || (x.cs == 0 && p->d > 1))))
+        return gpz_fail(GPZ_ERR_ARG, "%s: strides (%lld, %lld) of %lld rows: a stride must be positive", who, (long long)x.rs,
+                        (long long)x.cs, (long long)x.ns);
     return 0;
 }
 
 // the caller's Psi: as X, and a column stride of 0 broadcasts an n x 1 Psi
-static int predictor_dev_psi_args(const char *who, const gpz_predictor *p, const void *Psi_d, int32_t psi_type, int64_t ns, int64_t rs,
-                                  int64_t cs, const double *sdX, const double *sd2) {
-    if (psi_type != GPZ_X_F64 && psi_type != GPZ_X_F32)
-        return gpz_fail(GPZ_ERR_ARG, "%s: psi_type %d is neither GPZ_X_F64 nor GPZ_X_F32", who, (int)psi_type);
+static int predictor_dev_psi_args(const char *who, const DevRows &psi, const double *sdX, const double *sd2) {
+    if (psi.type != GPZ_X_F64 && psi.type != GPZ_X_F32)
+        return gpz_fail(GPZ_ERR_ARG, "%s: psi_type %d is neither GPZ_X_F64 nor GPZ_X_F32", who, (int)psi.type);
     if ((sdX != nullptr) != (sd2 != nullptr)) return gpz_fail(GPZ_ERR_ARG, "%s: sdX and sd2 go together (both or neither)", who);
-    if (ns > 0 && !Psi_d) return gpz_fail(GPZ_ERR_ARG, "%s: null Psi", who);
-    if (rs < 0 || cs < 0 || (ns > 1 && rs == 0))
-        return gpz_fail(GPZ_ERR_ARG, "%s: Psi strides (%lld, %lld) of %lld rows: the row stride must be positive", who, (long long)rs,
-                        (long long)cs, (long long)ns);
-    (void)p;
+    if (psi.ns > 0 && !psi.X) return gpz_fail(GPZ_ERR_ARG, "%s: null Psi", who);
+    if (psi.rs < 0 || psi.cs < 0 || (psi.ns > 1 && psi.rs == 0))
+        return gpz_fail(GPZ_ERR_ARG, "%s: Psi strides (%lld, %lld) of %lld rows: the row stride must be positive", who, (long long)psi.rs,
+                        (long long)psi.cs, (long long)psi.ns);
     return 0;
 }
 
@@ -750,11 +775,11 @@ static int predictor_dev_begin(gpz_predictor *p, const char *who, const DevRows 
          (muY && hipMemcpyAsync(p->par_d + 2 * d, muY, k * sizeof(double), hipMemcpyHostToDevice, st) != hipSuccess) ||
          hipMemsetAsync(rec, 0, 4 * sizeof(unsigned), st) != hipSuccess))
         rc = gpz_fail(GPZ_ERR_HIP, "%s: copy failed", who);
-    if (!rc && launch_pred_check_dev(st, x.X, x.f32, x.ns, p->d, x.rs, x.cs, lab, G, wt, rec))
+    if (!rc && launch_pred_check_dev(st, x.X, x.f32(), x.ns, p->d, x.rs, x.cs, lab, G, wt, rec))
         rc = gpz_fail(GPZ_ERR_HIP, "%s: k_pred_check_dev launch failed", who);
     if (!rc && psi &&   // (predictor_psi_slots has run: sd2_d exists)
         ((sd2 && hipMemcpyAsync(p->sd2_d, sd2, d * sizeof(double), hipMemcpyHostToDevice, st) != hipSuccess) ||
-         launch_pred_check_psi(st, psi->X, psi->f32, psi->ns, p->d, psi->rs, psi->cs, sd2 ? *std::min_element(sd2, sd2 + d) : 1.0, rec)))
+         launch_pred_check_psi(st, psi->X, psi->f32(), psi->ns, p->d, psi->rs, psi->cs, sd2 ? *std::min_element(sd2, sd2 + d) : 1.0, rec)))
         rc = gpz_fail(GPZ_ERR_HIP, "%s: k_pred_check_psi launch failed", who);
     if (!rc && hipMemcpyAsync(verdict, rec, sizeof verdict, hipMemcpyDeviceToHost, st) != hipSuccess)
         rc = gpz_fail(GPZ_ERR_HIP, "%s: copy failed", who);
@@ -770,117 +795,121 @@ static int predictor_dev_begin(gpz_predictor *p, const char *who, const DevRows 
     return 0;
 }
 
-static int predictor_run_dev(gpz_predictor *p, const DevRows &x, const double *muX_d, const double *sdX_d, const double *muY_d, double *mu,
-                             double *sigma, double *nu, double *beta, double *gamma, double *PHI) {
-    const int64_t T = p->tile_rows, ns = x.ns;
+// The tiles of a device entry, all on the compute stream: k_pred_stage (and, with psi, k_pred_stage_psi into Psic[s]) from the caller's
+// memory into slot s, then body(s, r0, nt), the entry's kernels down to the one that writes into the caller's arrays.
+template <class Body>
+static int predictor_dev_tiles(gpz_predictor *p, const char *who, const DevRows &x, const double *muX_d, const double *sdX_d,
+                               const DevRows *psi, const double *sd2_d, int64_t T, Body body) {
     hipStream_t st = p->s_cmp;
-    int rc = 0;
-    for (int64_t r0 = 0, t = 0; r0 < ns && !rc; r0 += T, ++t) {
-        const int s = (int)(t & 1), nt = (int)std::min<int64_t>(T, ns - r0);
-        if (launch_pred_stage(st, x.X, x.f32, x.rs, x.cs, r0, nt, p->d, muX_d, sdX_d, p->Xc[s], p->tile_pad)) {
-            rc = gpz_fail(GPZ_ERR_HIP, "gpz_predictor_run_dev: k_pred_stage launch failed");
-            break;
-        }
-        if ((rc = predictor_tile(p, s, nt, PHI != nullptr))) break;
-        if (launch_pred_finish_dev(st, p->out[s], nt, p->k, muY_d, ns, r0, mu, sigma, nu, beta, gamma) ||
-            (PHI && launch_pred_phi_dev(st, p->phi_d[s], nt, p->m, ns, r0, PHI)))
-            rc = gpz_fail(GPZ_ERR_HIP, "gpz_predictor_run_dev: finish kernel launch failed");
+    for (int64_t r0 = 0, t = 0; r0 < x.ns; r0 += T, ++t) {
+        const int s = (int)(t & 1), nt = (int)std::min<int64_t>(T, x.ns - r0);
+        if (launch_pred_stage(st, x.X, x.f32(), x.rs, x.cs, r0, nt, p->d, muX_d, sdX_d, p->Xc[s], p->tile_pad))
+            return gpz_fail(GPZ_ERR_HIP, "%s: k_pred_stage launch failed", who);
+        if (psi && launch_pred_stage_psi(st, psi->X, psi->f32(), psi->rs, psi->cs, r0, nt, p->d, sd2_d, p->Psic[s], p->tile_pad))
+            return gpz_fail(GPZ_ERR_HIP, "%s: k_pred_stage_psi launch failed", who);
+        if (int rc = body(s, r0, nt)) return rc;
     }
-    if (hipStreamSynchronize(st) != hipSuccess && !rc) rc = gpz_fail(GPZ_ERR_HIP, "gpz_predictor_run_dev: sync failed");
+    return 0;
+}
+
+// the end of every device entry once it has prepared anything after predictor_dev_begin, failed or not: copies from the caller's memory
+// (Z, the edges) may be in flight
+static int predictor_dev_sync(gpz_predictor *p, const char *who, int rc) {
+    if (hipStreamSynchronize(p->s_cmp) != hipSuccess && !rc) rc = gpz_fail(GPZ_ERR_HIP, "%s: sync failed", who);
     return rc;
 }
 
-// gpz_predictor_run_noisy_dev's tiles: both stage kernels, predictNoisy, the finish into the caller's arrays
-static int predictor_run_noisy_dev(gpz_predictor *p, const DevRows &x, const DevRows &psi, const double *muX_d, const double *sdX_d,
-                                   const double *sd2_d, const double *muY_d, double *mu, double *sigma, double *nu, double *beta,
-                                   double *gamma) {
-    const int64_t T = p->tile_rows, ns = x.ns;
+// gpz_predictor_run_dev and, with psi, gpz_predictor_run_noisy_dev (predictNoisy per tile: Xc[s], Psic[s] -> nout[s]), each with its
+// finish kernel into the caller's arrays
+static int predictor_run_dev(gpz_predictor *p, const char *who, const DevRows &x, const DevRows *psi, const double *muX_d,
+                             const double *sdX_d, const double *sd2_d, const double *muY_d, double *mu, double *sigma, double *nu,
+                             double *beta, double *gamma, double *PHI) {
     hipStream_t st = p->s_cmp;
+    const int64_t ns = x.ns;
     int rc = 0;
-    for (int64_t r0 = 0, t = 0; r0 < ns && !rc; r0 += T, ++t) {
-        const int s = (int)(t & 1), nt = (int)std::min<int64_t>(T, ns - r0);
-        if (launch_pred_stage(st, x.X, x.f32, x.rs, x.cs, r0, nt, p->d, muX_d, sdX_d, p->Xc[s], p->tile_pad) ||
-            launch_pred_stage_psi(st, psi.X, psi.f32, psi.rs, psi.cs, r0, nt, p->d, sd2_d, p->Psic[s], p->tile_pad)) {
-            rc = gpz_fail(GPZ_ERR_HIP, "gpz_predictor_run_noisy_dev: stage kernel launch failed");
-            break;
-        }
-        if ((rc = predictor_noisy_tile(p, s, nt))) break;
-        if (launch_pred_finish_noisy_dev(st, p->nout[s], nt, p->k, muY_d, ns, r0, mu, sigma, nu, beta, gamma))
-            rc = gpz_fail(GPZ_ERR_HIP, "gpz_predictor_run_noisy_dev: finish kernel launch failed");
-    }
-    if (hipStreamSynchronize(st) != hipSuccess && !rc) rc = gpz_fail(GPZ_ERR_HIP, "gpz_predictor_run_noisy_dev: sync failed");
-    return rc;
+    if (psi)
+        rc = predictor_dev_tiles(p, who, x, muX_d, sdX_d, psi, sd2_d, p->tile_rows, [&](int s, int64_t r0, int nt) {
+            if (int rc = predictor_noisy_tile(p, s, nt)) return rc;
+            if (launch_pred_finish_noisy_dev(st, p->nout[s], nt, p->k, muY_d, ns, r0, mu, sigma, nu, beta, gamma))
+                return gpz_fail(GPZ_ERR_HIP, "%s: finish kernel launch failed", who);
+            return 0;
+        });
+    else
+        rc = predictor_dev_tiles(p, who, x, muX_d, sdX_d, nullptr, nullptr, p->tile_rows, [&](int s, int64_t r0, int nt) {
+            if (int rc = predictor_tile(p, s, nt, PHI != nullptr)) return rc;
+            if (launch_pred_finish_dev(st, p->out[s], nt, p->k, muY_d, ns, r0, mu, sigma, nu, beta, gamma) ||
+                (PHI && launch_pred_phi_dev(st, p->phi_d[s], nt, p->m, ns, r0, PHI)))
+                return gpz_fail(GPZ_ERR_HIP, "%s: finish kernel launch failed", who);
+            return 0;
+        });
+    return predictor_dev_sync(p, who, rc);
 }
 
 // psi (gpz_predictor_draws_noisy_dev; nullptr: noise-free rows) with sd2_d
 static int predictor_run_draws_dev(gpz_predictor *p, const DevRows &x, const double *muX_d, const double *sdX_d, const double *muY_d, int nd,
-                                   unsigned long long seed, const double *Z, double *F, const DevRows *psi = nullptr,
-                                   const double *sd2_d = nullptr) {
+                                   unsigned long long seed, const double *Z, double *F, const DevRows *psi, const double *sd2_d) {
+    const char *who = "gpz_predictor_draws_dev";
     const int ncol = nd * p->k, ldw = rup(ncol, 16);
-    const int64_t ns = x.ns;
-    hipStream_t st = p->s_cmp;
     int64_t T = 0;
     int rc = predictor_draws_prepare(p, nd, seed, Z, false, &T);
-    for (int64_t r0 = 0, t = 0; r0 < ns && !rc; r0 += T, ++t) {
-        const int s = (int)(t & 1), nt = (int)std::min<int64_t>(T, ns - r0);
-        if (launch_pred_stage(st, x.X, x.f32, x.rs, x.cs, r0, nt, p->d, muX_d, sdX_d, p->Xc[s], p->tile_pad)) {
-            rc = gpz_fail(GPZ_ERR_HIP, "gpz_predictor_draws_dev: k_pred_stage launch failed");
-            break;
-        }
-        if (psi && launch_pred_stage_psi(st, psi->X, psi->f32, psi->rs, psi->cs, r0, nt, p->d, sd2_d, p->Psic[s], p->tile_pad)) {
-            rc = gpz_fail(GPZ_ERR_HIP, "gpz_predictor_draws_noisy_dev: k_pred_stage_psi launch failed");
-            break;
-        }
-        if ((rc = predictor_draws_tile(p, s, nt, ncol, ldw, false, psi ? p->Psic[s] : nullptr))) break;
-        if (launch_draws_finish_dev(st, p->dout[s], nt, p->k, nd, muY_d, ns, r0, F))
-            rc = gpz_fail(GPZ_ERR_HIP, "gpz_predictor_draws_dev: k_draws_finish_dev launch failed");
-    }
-    if (hipStreamSynchronize(st) != hipSuccess && !rc) rc = gpz_fail(GPZ_ERR_HIP, "gpz_predictor_draws_dev: sync failed");   // Z may be in flight
-    return rc;
+    if (!rc)
+        rc = predictor_dev_tiles(p, who, x, muX_d, sdX_d, psi, sd2_d, T, [&](int s, int64_t r0, int nt) {
+            if (int rc = predictor_draws_tile(p, s, nt, ncol, ldw, false, psi ? p->Psic[s] : nullptr)) return rc;
+            if (launch_draws_finish_dev(p->s_cmp, p->dout[s], nt, p->k, nd, muY_d, x.ns, r0, F))
+                return gpz_fail(GPZ_ERR_HIP, "%s: k_draws_finish_dev launch failed", who);
+            return 0;
+        });
+    return predictor_dev_sync(p, who, rc);
 }
 
 // predictor_run_stack with the rows, labels and weights where the caller has them: the tile kernels read lab + r0 and wt + r0 directly
 static int predictor_run_stack_dev(gpz_predictor *p, const DevRows &x, const double *muX_d, const double *sdX_d, int nd,
                                    unsigned long long seed, const double *Z, const double *edges, const double *shift, int B,
                                    const int32_t *group, int G, const double *weight, double *res) {
-    const int k = p->k, ncol = nd * k, ldw = rup(ncol, 16), Q = (1 + nd) * k;
-    const size_t rec = (size_t)G * B + 3 * (size_t)G, count = (size_t)Q * rec;
-    const int64_t ns = x.ns;
-    hipStream_t st = p->s_cmp;
+    const char *who = "gpz_predictor_stack_dev";
+    StackCall c{};
+    int rc = predictor_stack_prepare(p, who, nd, seed, Z, edges, shift, B, G, false, &c);
+    if (!rc)
+        rc = predictor_dev_tiles(p, who, x, muX_d, sdX_d, nullptr, nullptr, c.T, [&](int s, int64_t r0, int nt) {
+            return predictor_stack_tile(p, who, c, s, nt, group ? group + r0 : nullptr, weight ? weight + r0 : nullptr);
+        });
+    if (!rc) rc = predictor_stack_result(p, who, c, res);
+    return predictor_dev_sync(p, who, rc);
+}
+
+// ---- what the entries share ---------------------------------------------------------------------------------------------------------
+static int predictor_check_call(const char *who, const gpz_predictor *p, int64_t ns) {
+    if (!p) return gpz_fail(GPZ_ERR_ARG, "%s: null handle", who);
+    if (ns < 0) return gpz_fail(GPZ_ERR_ARG, "%s: ns < 0", who);
+    return 0;
+}
+
+// least: 1 for the draws; 0 for the stack, whose column 0 is the posterior mean
+static int predictor_check_ndraws(const char *who, const gpz_predictor *p, int32_t ndraws, int least) {
+    if (ndraws < least || (1 - least + (int64_t)ndraws) * p->k > GPZ_DRAWS_MAX_COLUMNS)
+        return gpz_fail(GPZ_ERR_ARG, "%s: need %d <= ndraws and %s * k <= %d (ndraws %d, k %d)", who, least,
+                        least ? "ndraws" : "(1 + ndraws)", GPZ_DRAWS_MAX_COLUMNS, (int)ndraws, p->k);
+    return 0;
+}
+
+// draws with input noise: a model inside predict_noisy_fits, on the fused draws route
+static int predictor_check_noisy_draws(const char *who, const gpz_predictor *p) {
+    if (int rc = predictor_noisy_check(who, p)) return rc;
+    if (p->force_tiles) return gpz_fail(GPZ_ERR_UNSUPPORTED, "%s: input noise needs the fused draws route (GPZ_PREDICT_FORCE_TILES is set)", who);
+    return 0;
+}
+
+// Every entry after create runs its body through here: the handle's options and device for the length of the call, the caller's device
+// again on every way out.
+template <class Body>
+static int predictor_call(gpz_predictor *p, const char *who, Body body) {
+    int prev = 0;
+    (void)hipGetDevice(&prev);
+    gpz_opts_scope opts_scope(&p->opt);
     int rc = 0;
-    int64_t T = p->tile_rows;
-    if (nd > 0) rc = predictor_draws_prepare(p, nd, seed, Z, false, &T);
-    const int R = predict_stack_slabs(Q, (long)rec, T);
-    const size_t ne = (size_t)k * (B + 1);
-    if (!rc) rc = predictor_grow(p, &p->edges_d, &p->edges_cap, ne + k);
-    if (!rc) rc = predictor_grow(p, &p->acc_d, &p->acc_cap, count);
-    if (!rc) rc = predictor_grow(p, &p->slab_d, &p->slab_cap, count * R);
-    if (!rc) {
-        p->stile = T;
-        p->sslabs = R;
-        if (hipMemcpyAsync(p->edges_d, edges, ne * sizeof(double), hipMemcpyHostToDevice, st) != hipSuccess ||
-            (shift ? hipMemcpyAsync(p->edges_d + ne, shift, (size_t)k * sizeof(double), hipMemcpyHostToDevice, st)
-                   : hipMemsetAsync(p->edges_d + ne, 0, (size_t)k * sizeof(double), st)) != hipSuccess ||
-            hipMemsetAsync(p->acc_d, 0, count * sizeof(double), st) != hipSuccess)
-            rc = gpz_fail(GPZ_ERR_HIP, "gpz_predictor_stack_dev: copy failed");
-    }
-    for (int64_t r0 = 0, t = 0; r0 < ns && !rc; r0 += T, ++t) {
-        const int s = (int)(t & 1);
-        const int64_t nt = std::min<int64_t>(T, ns - r0);
-        if (launch_pred_stage(st, x.X, x.f32, x.rs, x.cs, r0, (int)nt, p->d, muX_d, sdX_d, p->Xc[s], p->tile_pad)) {
-            rc = gpz_fail(GPZ_ERR_HIP, "gpz_predictor_stack_dev: k_pred_stage launch failed");
-            break;
-        }
-        if ((rc = predictor_tile(p, s, (int)nt, false))) break;
-        if (nd > 0 && (rc = predictor_draws_tile(p, s, nt, ncol, ldw, p->route == 1))) break;
-        if (launch_stack_tile(st, p->out[s], nd > 0 ? p->dout[s] : nullptr, group ? group + r0 : nullptr, weight ? weight + r0 : nullptr,
-                              p->edges_d, p->edges_d + ne, nt, k, nd, B, G, R, p->slab_d) ||
-            launch_stack_accum(st, p->slab_d, R, count, p->acc_d))
-            rc = gpz_fail(GPZ_ERR_HIP, "gpz_predictor_stack_dev: k_stack_tile launch failed");
-    }
-    if (!rc && hipMemcpyAsync(res, p->acc_d, count * sizeof(double), hipMemcpyDeviceToHost, st) != hipSuccess)
-        rc = gpz_fail(GPZ_ERR_HIP, "gpz_predictor_stack_dev: copy failed");
-    if (hipStreamSynchronize(st) != hipSuccess && !rc) rc = gpz_fail(GPZ_ERR_HIP, "gpz_predictor_stack_dev: sync failed");
+    if (hipSetDevice(p->device) != hipSuccess) rc = gpz_fail(GPZ_ERR_HIP, "%s: hipSetDevice failed", who);
+    if (!rc) rc = body();
+    (void)hipSetDevice(prev);
     return rc;
 }
 
@@ -888,11 +917,8 @@ static int predictor_run_stack_dev(gpz_predictor *p, const DevRows &x, const dou
 static int stack_check_shape(const char *who, const gpz_predictor *p, int64_t ns, int32_t ndraws, int32_t nbins, int32_t ngroups,
                              const double *edges, const double *hist, const double *sum_w, const double *sum_mu, const double *sum_mu2,
                              const void *Xs) {
-    if (!p) return gpz_fail(GPZ_ERR_ARG, "%s: null handle", who);
-    if (ns < 0) return gpz_fail(GPZ_ERR_ARG, "%s: ns < 0", who);
-    if (ndraws < 0 || (1 + (int64_t)ndraws) * p->k > GPZ_DRAWS_MAX_COLUMNS)
-        return gpz_fail(GPZ_ERR_ARG, "%s: need 0 <= ndraws and (1 + ndraws) * k <= %d (ndraws %d, k %d)", who, GPZ_DRAWS_MAX_COLUMNS,
-                        (int)ndraws, p->k);
+    if (int rc = predictor_check_call(who, p, ns)) return rc;
+    if (int rc = predictor_check_ndraws(who, p, ndraws, 0)) return rc;
     if (nbins < 1 || ngroups < 1) return gpz_fail(GPZ_ERR_ARG, "%s: need nbins >= 1 and ngroups >= 1", who);
     if ((int64_t)nbins * ngroups > GPZ_STACK_MAX_GROUP_BINS)
         return gpz_fail(GPZ_ERR_ARG, "%s: ngroups * nbins = %lld is over GPZ_STACK_MAX_GROUP_BINS = %d", who, (long long)nbins * ngroups,
@@ -923,6 +949,83 @@ static void stack_unpack(const double *res, int C, int k, int G, int B, double *
                 if (c == 0 && o == 0) sum_w[g] = r[GB + 3 * (size_t)g];
             }
         }
+}
+
+static void stack_zero(int C, int k, int G, int B, double *hist, double *sum_w, double *sum_mu, double *sum_mu2) {
+    const size_t Q = (size_t)C * k;
+    memset(hist, 0, Q * G * B * sizeof(double));
+    memset(sum_w, 0, (size_t)G * sizeof(double));
+    memset(sum_mu, 0, Q * G * sizeof(double));
+    memset(sum_mu2, 0, Q * G * sizeof(double));
+}
+
+static int stack_check_shift(const char *who, const gpz_predictor *p, const double *mu_shift) {
+    for (int o = 0; mu_shift && o < p->k; ++o)
+        if (!std::isfinite(mu_shift[o])) return gpz_fail(GPZ_ERR_ARG, "%s: mu_shift must be finite", who);
+    return 0;
+}
+
+// gpz_predictor_draws and, with noisy, gpz_predictor_draws_noisy
+static int draws_entry(const char *who, bool noisy, gpz_predictor *p, const double *Xs, int64_t ns, const double *Psi, int32_t ndraws,
+                       uint64_t seed, const double *Z, double *F) {
+    if (int rc = predictor_check_call(who, p, ns)) return rc;
+    if (int rc = predictor_check_ndraws(who, p, ndraws, 1)) return rc;
+    if (noisy)
+        if (int rc = predictor_check_noisy_draws(who, p)) return rc;
+    if (ns == 0) return 0;
+    if (!Xs || (noisy && !Psi) || !F) return gpz_fail(GPZ_ERR_ARG, "%s: null argument", who);
+    return predictor_call(p, who, [&] { return predictor_run_draws(p, Xs, ns, (int)ndraws, (unsigned long long)seed, Z, F, Psi); });
+}
+
+// gpz_predictor_run_dev and, with psi, gpz_predictor_run_noisy_dev
+static int run_dev_entry(const char *who, gpz_predictor *p, const DevRows &x, const DevRows *psi, const double *muX, const double *sdX,
+                         const double *sd2, const double *muY, double *mu_d, double *sigma_d, double *nu_d, double *beta_d, double *gamma_d,
+                         double *PHI_d, void *stream) {
+    if (int rc = predictor_check_call(who, p, x.ns)) return rc;
+    if (psi)
+        if (int rc = predictor_noisy_check(who, p)) return rc;
+    if (int rc = predictor_dev_args(who, p, x, muX, sdX)) return rc;
+    if (psi)
+        if (int rc = predictor_dev_psi_args(who, *psi, sdX, sd2)) return rc;
+    if (x.ns == 0) return 0;
+    if (!mu_d || !nu_d || !beta_d) return gpz_fail(GPZ_ERR_ARG, "%s: null argument", who);
+    return predictor_call(p, who, [&] {
+        const double *mx = nullptr, *sx = nullptr, *my = nullptr;
+        int rc = psi ? predictor_noisy_prepare(p) : PHI_d ? predictor_want_phi(p, false) : 0;
+        if (!rc)
+            rc = predictor_dev_begin(p, who, x, muX, sdX, muY, nullptr, 0, nullptr, stream,
+                                     psi ? "the rows have missing values (NaN): input noise on the handle is for complete rows"
+                                         : "the rows have missing values (NaN): group them by pattern and call gpz_predict_missing (predict.m:45-69)",
+                                     &mx, &sx, &my, psi, sd2);
+        if (!rc) rc = predictor_run_dev(p, who, x, psi, mx, sx, sd2 ? p->sd2_d : nullptr, my, mu_d, sigma_d, nu_d, beta_d, gamma_d, PHI_d);
+        if (!rc) ++p->runs;
+        return rc;
+    });
+}
+
+// gpz_predictor_draws_dev and, with psi, gpz_predictor_draws_noisy_dev
+static int draws_dev_entry(const char *who, gpz_predictor *p, const DevRows &x, const DevRows *psi, const double *muX, const double *sdX,
+                           const double *sd2, const double *muY, int32_t ndraws, uint64_t seed, const double *Z, double *F_d,
+                           void *stream) {
+    if (int rc = predictor_check_call(who, p, x.ns)) return rc;
+    if (int rc = predictor_check_ndraws(who, p, ndraws, 1)) return rc;
+    if (psi)
+        if (int rc = predictor_check_noisy_draws(who, p)) return rc;
+    if (int rc = predictor_dev_args(who, p, x, muX, sdX)) return rc;
+    if (psi)
+        if (int rc = predictor_dev_psi_args(who, *psi, sdX, sd2)) return rc;
+    if (x.ns == 0) return 0;
+    if (!F_d) return gpz_fail(GPZ_ERR_ARG, "%s: null argument", who);
+    return predictor_call(p, who, [&] {
+        const double *mx = nullptr, *sx = nullptr, *my = nullptr;
+        int rc = psi ? predictor_psi_slots(p) : 0;
+        if (!rc)
+            rc = predictor_dev_begin(p, who, x, muX, sdX, muY, nullptr, 0, nullptr, stream,
+                                     "the rows have missing values (NaN): draws are for complete rows", &mx, &sx, &my, psi, sd2);
+        if (!rc)
+            rc = predictor_run_draws_dev(p, x, mx, sx, my, (int)ndraws, (unsigned long long)seed, Z, F_d, psi, sd2 ? p->sd2_d : nullptr);
+        return rc;
+    });
 }
 }   // namespace gpzi
 
@@ -969,81 +1072,60 @@ extern "C" void gpz_predictor_destroy(gpz_predictor *p) {
 
 extern "C" int gpz_predictor_run(gpz_predictor *p, const double *Xs, int64_t ns, const double *Psi, int32_t psi_kind, double *mu,
                                  double *nu, double *beta_i, double *gamma, double *PHI) {
-    if (!p) return gpz_fail(GPZ_ERR_ARG, "gpz_predictor_run: null handle");
-    if (ns < 0) return gpz_fail(GPZ_ERR_ARG, "gpz_predictor_run: ns < 0");
+    const char *who = "gpz_predictor_run";
+    if (int rc = predictor_check_call(who, p, ns)) return rc;
     if (ns == 0) return 0;
     if (!Xs || !mu || !nu || !beta_i || !gamma) return gpz_fail(GPZ_ERR_ARG, "gpz_predictor_run: null argument");
     if (psi_kind < 0 || psi_kind > 3 || (psi_kind != 0) != (Psi != nullptr))
         return gpz_fail(GPZ_ERR_ARG, "gpz_predictor_run: psi_kind %d does not match Psi", (int)psi_kind);
     if ((psi_kind == 2 || psi_kind == 3) && p->kind != GPZ_KIND_COV)
         return gpz_fail(GPZ_ERR_ARG, "gpz_predictor_run: psi_kind %d is for the covariance kinds", (int)psi_kind);
-    int prev = 0;
-    (void)hipGetDevice(&prev);
-    gpz_opts_scope opts_scope(&p->opt);
-    int rc = 0;
-    if (hipSetDevice(p->device) != hipSuccess) rc = gpz_fail(GPZ_ERR_HIP, "gpz_predictor_run: hipSetDevice failed");
-    if (!rc && Psi) {
-        rc = predictor_run_noisy(p, Xs, ns, Psi, psi_kind, mu, nu, beta_i, gamma, PHI);
-    } else if (!rc) {
-        memset(gamma, 0, (size_t)ns * p->k * sizeof(double));   // predictDiag.m:74
-        if (PHI) rc = predictor_want_phi(p);
-        if (!rc) rc = predictor_run_full(p, Xs, ns, mu, nu, beta_i, PHI);
-    }
-    if (!rc) ++p->runs;
-    (void)hipSetDevice(prev);
-    return rc;
+    return predictor_call(p, who, [&] {
+        int rc = 0;
+        if (Psi) {
+            rc = predictor_run_noisy(p, Xs, ns, Psi, psi_kind, mu, nu, beta_i, gamma, PHI);
+        } else {
+            memset(gamma, 0, (size_t)ns * p->k * sizeof(double));   // predictDiag.m:74
+            if (PHI) rc = predictor_want_phi(p);
+            if (!rc) rc = predictor_run_full(p, Xs, ns, mu, nu, beta_i, PHI);
+        }
+        if (!rc) ++p->runs;
+        return rc;
+    });
 }
 
 extern "C" int gpz_predictor_draws(gpz_predictor *p, const double *Xs, int64_t ns, int32_t ndraws, uint64_t seed, const double *Z,
                                    double *F) {
-    if (!p) return gpz_fail(GPZ_ERR_ARG, "gpz_predictor_draws: null handle");
-    if (ns < 0) return gpz_fail(GPZ_ERR_ARG, "gpz_predictor_draws: ns < 0");
-    if (ndraws < 1 || (int64_t)ndraws * p->k > GPZ_DRAWS_MAX_COLUMNS)
-        return gpz_fail(GPZ_ERR_ARG, "gpz_predictor_draws: need 1 <= ndraws and ndraws * k <= %d (ndraws %d, k %d)", GPZ_DRAWS_MAX_COLUMNS,
-                        (int)ndraws, p->k);
-    if (ns == 0) return 0;
-    if (!Xs || !F) return gpz_fail(GPZ_ERR_ARG, "gpz_predictor_draws: null argument");
-    int prev = 0;
-    (void)hipGetDevice(&prev);
-    gpz_opts_scope opts_scope(&p->opt);
-    int rc = 0;
-    if (hipSetDevice(p->device) != hipSuccess) rc = gpz_fail(GPZ_ERR_HIP, "gpz_predictor_draws: hipSetDevice failed");
-    if (!rc) rc = predictor_run_draws(p, Xs, ns, (int)ndraws, (unsigned long long)seed, Z, F);
-    (void)hipSetDevice(prev);
-    return rc;
+    return draws_entry("gpz_predictor_draws", false, p, Xs, ns, nullptr, ndraws, seed, Z, F);
+}
+
+extern "C" int gpz_predictor_draws_noisy(gpz_predictor *p, const double *Xs, int64_t ns, const double *Psi, int32_t ndraws, uint64_t seed,
+                                         const double *Z, double *F) {
+    return draws_entry("gpz_predictor_draws_noisy", true, p, Xs, ns, Psi, ndraws, seed, Z, F);
 }
 
 extern "C" int gpz_predictor_stack(gpz_predictor *p, const double *Xs, int64_t ns, int32_t ndraws, uint64_t seed, const double *Z,
                                    const double *edges, int32_t nbins, const int32_t *group, int32_t ngroups, const double *weight,
                                    double *hist, double *sum_w, double *sum_mu, double *sum_mu2, const double *mu_shift) {
-    if (int rc = stack_check_shape("gpz_predictor_stack", p, ns, ndraws, nbins, ngroups, edges, hist, sum_w, sum_mu, sum_mu2, Xs)) return rc;
+    const char *who = "gpz_predictor_stack";
+    if (int rc = stack_check_shape(who, p, ns, ndraws, nbins, ngroups, edges, hist, sum_w, sum_mu, sum_mu2, Xs)) return rc;
     const int k = p->k, B = nbins, G = ngroups, C = 1 + ndraws;
     if (group)
         for (int64_t i = 0; i < ns; ++i)
             if (group[i] < -1 || group[i] >= G)
                 return gpz_fail(GPZ_ERR_ARG, "gpz_predictor_stack: label %d of row %lld is outside [-1, %d)", (int)group[i], (long long)i, G);
-    if (mu_shift)
-        for (int o = 0; o < k; ++o)
-            if (!std::isfinite(mu_shift[o])) return gpz_fail(GPZ_ERR_ARG, "gpz_predictor_stack: mu_shift must be finite");
+    if (int rc = stack_check_shift(who, p, mu_shift)) return rc;
     if (weight)
         for (int64_t i = 0; i < ns; ++i)
             if (!(weight[i] >= 0.0) || !std::isfinite(weight[i]))
                 return gpz_fail(GPZ_ERR_ARG, "gpz_predictor_stack: the weight of row %lld is negative or not finite", (long long)i);
-    const size_t GB = (size_t)G * B, rec = GB + 3 * (size_t)G, Q = (size_t)C * k;
-    memset(hist, 0, Q * GB * sizeof(double));
-    memset(sum_w, 0, (size_t)G * sizeof(double));
-    memset(sum_mu, 0, Q * G * sizeof(double));
-    memset(sum_mu2, 0, Q * G * sizeof(double));
+    stack_zero(C, k, G, B, hist, sum_w, sum_mu, sum_mu2);
     if (ns == 0) return 0;
-    std::vector<double> res(Q * rec);
-    int prev = 0;
-    (void)hipGetDevice(&prev);
-    gpz_opts_scope opts_scope(&p->opt);
-    int rc = 0;
-    if (hipSetDevice(p->device) != hipSuccess) rc = gpz_fail(GPZ_ERR_HIP, "gpz_predictor_stack: hipSetDevice failed");
-    if (!rc) rc = predictor_run_stack(p, Xs, ns, (int)ndraws, (unsigned long long)seed, Z, edges, mu_shift, B, group, G, weight, res.data());
-    (void)hipSetDevice(prev);
-    if (rc) return rc;
+    std::vector<double> res((size_t)C * k * ((size_t)G * B + 3 * (size_t)G));
+    if (int rc = predictor_call(p, who, [&] {
+            return predictor_run_stack(p, Xs, ns, (int)ndraws, (unsigned long long)seed, Z, edges, mu_shift, B, group, G, weight, res.data());
+        }))
+        return rc;
     stack_unpack(res.data(), C, k, G, B, hist, sum_w, sum_mu, sum_mu2);
     return 0;
 }
@@ -1051,55 +1133,8 @@ extern "C" int gpz_predictor_stack(gpz_predictor *p, const double *Xs, int64_t n
 extern "C" int gpz_predictor_run_dev(gpz_predictor *p, const void *X_d, int32_t x_type, int64_t ns, int64_t row_stride, int64_t col_stride,
                                      const double *muX, const double *sdX, const double *muY, double *mu_d, double *sigma_d, double *nu_d,
                                      double *beta_d, double *gamma_d, double *PHI_d, void *stream) {
-    const char *who = "gpz_predictor_run_dev";
-    if (!p) return gpz_fail(GPZ_ERR_ARG, "%s: null handle", who);
-    if (ns < 0) return gpz_fail(GPZ_ERR_ARG, "%s: ns < 0", who);
-    if (int rc = predictor_dev_args(who, p, X_d, x_type, ns, row_stride, col_stride, muX, sdX)) return rc;
-    if (ns == 0) return 0;
-    if (!mu_d || !nu_d || !beta_d) return gpz_fail(GPZ_ERR_ARG, "%s: null argument", who);
-    const DevRows x{X_d, x_type == GPZ_X_F32, ns, row_stride, col_stride};
-    const double *mx = nullptr, *sx = nullptr, *my = nullptr;
-    int prev = 0;
-    (void)hipGetDevice(&prev);
-    gpz_opts_scope opts_scope(&p->opt);
-    int rc = 0;
-    if (hipSetDevice(p->device) != hipSuccess) rc = gpz_fail(GPZ_ERR_HIP, "%s: hipSetDevice failed", who);
-    if (!rc && PHI_d) rc = predictor_want_phi(p, false);
-    if (!rc)
-        rc = predictor_dev_begin(p, who, x, muX, sdX, muY, nullptr, 0, nullptr, stream,
-                                 "the rows have missing values (NaN): group them by pattern and call gpz_predict_missing (predict.m:45-69)",
-                                 &mx, &sx, &my);
-    if (!rc) rc = predictor_run_dev(p, x, mx, sx, my, mu_d, sigma_d, nu_d, beta_d, gamma_d, PHI_d);
-    if (!rc) ++p->runs;
-    (void)hipSetDevice(prev);
-    return rc;
-}
-
-extern "C" int gpz_predictor_draws_dev(gpz_predictor *p, const void *X_d, int32_t x_type, int64_t ns, int64_t row_stride,
-                                       int64_t col_stride, const double *muX, const double *sdX, const double *muY, int32_t ndraws,
-                                       uint64_t seed, const double *Z, double *F_d, void *stream) {
-    const char *who = "gpz_predictor_draws_dev";
-    if (!p) return gpz_fail(GPZ_ERR_ARG, "%s: null handle", who);
-    if (ns < 0) return gpz_fail(GPZ_ERR_ARG, "%s: ns < 0", who);
-    if (ndraws < 1 || (int64_t)ndraws * p->k > GPZ_DRAWS_MAX_COLUMNS)
-        return gpz_fail(GPZ_ERR_ARG, "%s: need 1 <= ndraws and ndraws * k <= %d (ndraws %d, k %d)", who, GPZ_DRAWS_MAX_COLUMNS, (int)ndraws,
-                        p->k);
-    if (int rc = predictor_dev_args(who, p, X_d, x_type, ns, row_stride, col_stride, muX, sdX)) return rc;
-    if (ns == 0) return 0;
-    if (!F_d) return gpz_fail(GPZ_ERR_ARG, "%s: null argument", who);
-    const DevRows x{X_d, x_type == GPZ_X_F32, ns, row_stride, col_stride};
-    const double *mx = nullptr, *sx = nullptr, *my = nullptr;
-    int prev = 0;
-    (void)hipGetDevice(&prev);
-    gpz_opts_scope opts_scope(&p->opt);
-    int rc = 0;
-    if (hipSetDevice(p->device) != hipSuccess) rc = gpz_fail(GPZ_ERR_HIP, "%s: hipSetDevice failed", who);
-    if (!rc)
-        rc = predictor_dev_begin(p, who, x, muX, sdX, muY, nullptr, 0, nullptr, stream,
-                                 "the rows have missing values (NaN): draws are for complete rows", &mx, &sx, &my);
-    if (!rc) rc = predictor_run_draws_dev(p, x, mx, sx, my, (int)ndraws, (unsigned long long)seed, Z, F_d);
-    (void)hipSetDevice(prev);
-    return rc;
+    return run_dev_entry("gpz_predictor_run_dev", p, DevRows{X_d, x_type, ns, row_stride, col_stride}, nullptr, muX, sdX, nullptr, muY, mu_d,
+                         sigma_d, nu_d, beta_d, gamma_d, PHI_d, stream);
 }
 
 extern "C" int gpz_predictor_run_noisy_dev(gpz_predictor *p, const void *X_d, int32_t x_type, int64_t ns, int64_t row_stride,
@@ -1107,31 +1142,16 @@ extern "C" int gpz_predictor_run_noisy_dev(gpz_predictor *p, const void *X_d, in
                                            int64_t psi_col_stride, const double *muX, const double *sdX, const double *sd2,
                                            const double *muY, double *mu_d, double *sigma_d, double *nu_d, double *beta_d,
                                            double *gamma_d, void *stream) {
-    const char *who = "gpz_predictor_run_noisy_dev";
-    if (!p) return gpz_fail(GPZ_ERR_ARG, "%s: null handle", who);
-    if (ns < 0) return gpz_fail(GPZ_ERR_ARG, "%s: ns < 0", who);
-    if (int rc = predictor_noisy_check(who, p)) return rc;
-    if (int rc = predictor_dev_args(who, p, X_d, x_type, ns, row_stride, col_stride, muX, sdX)) return rc;
-    if (int rc = predictor_dev_psi_args(who, p, Psi_d, psi_type, ns, psi_row_stride, psi_col_stride, sdX, sd2)) return rc;
-    if (ns == 0) return 0;
-    if (!mu_d || !nu_d || !beta_d) return gpz_fail(GPZ_ERR_ARG, "%s: null argument", who);
-    const DevRows x{X_d, x_type == GPZ_X_F32, ns, row_stride, col_stride};
-    const DevRows psi{Psi_d, psi_type == GPZ_X_F32, ns, psi_row_stride, psi_col_stride};
-    const double *mx = nullptr, *sx = nullptr, *my = nullptr;
-    int prev = 0;
-    (void)hipGetDevice(&prev);
-    gpz_opts_scope opts_scope(&p->opt);
-    int rc = 0;
-    if (hipSetDevice(p->device) != hipSuccess) rc = gpz_fail(GPZ_ERR_HIP, "%s: hipSetDevice failed", who);
-    if (!rc) rc = predictor_noisy_prepare(p);
-    if (!rc)
-        rc = predictor_dev_begin(p, who, x, muX, sdX, muY, nullptr, 0, nullptr, stream,
-                                 "the rows have missing values (NaN): input noise on the handle is for complete rows", &mx, &sx, &my, &psi,
-                                 sd2);
-    if (!rc) rc = predictor_run_noisy_dev(p, x, psi, mx, sx, sd2 ? p->sd2_d : nullptr, my, mu_d, sigma_d, nu_d, beta_d, gamma_d);
-    if (!rc) ++p->runs;
-    (void)hipSetDevice(prev);
-    return rc;
+    const DevRows psi{Psi_d, psi_type, ns, psi_row_stride, psi_col_stride};
+    return run_dev_entry("gpz_predictor_run_noisy_dev", p, DevRows{X_d, x_type, ns, row_stride, col_stride}, &psi, muX, sdX, sd2, muY, mu_d,
+                         sigma_d, nu_d, beta_d, gamma_d, nullptr, stream);
+}
+
+extern "C" int gpz_predictor_draws_dev(gpz_predictor *p, const void *X_d, int32_t x_type, int64_t ns, int64_t row_stride,
+                                       int64_t col_stride, const double *muX, const double *sdX, const double *muY, int32_t ndraws,
+                                       uint64_t seed, const double *Z, double *F_d, void *stream) {
+    return draws_dev_entry("gpz_predictor_draws_dev", p, DevRows{X_d, x_type, ns, row_stride, col_stride}, nullptr, muX, sdX, nullptr, muY,
+                           ndraws, seed, Z, F_d, stream);
 }
 
 extern "C" int gpz_predictor_draws_noisy_dev(gpz_predictor *p, const void *X_d, int32_t x_type, int64_t ns, int64_t row_stride,
@@ -1139,56 +1159,9 @@ extern "C" int gpz_predictor_draws_noisy_dev(gpz_predictor *p, const void *X_d, 
                                              int64_t psi_col_stride, const double *muX, const double *sdX, const double *sd2,
                                              const double *muY, int32_t ndraws, uint64_t seed, const double *Z, double *F_d,
                                              void *stream) {
-    const char *who = "gpz_predictor_draws_noisy_dev";
-    if (!p) return gpz_fail(GPZ_ERR_ARG, "%s: null handle", who);
-    if (ns < 0) return gpz_fail(GPZ_ERR_ARG, "%s: ns < 0", who);
-    if (ndraws < 1 || (int64_t)ndraws * p->k > GPZ_DRAWS_MAX_COLUMNS)
-        return gpz_fail(GPZ_ERR_ARG, "%s: need 1 <= ndraws and ndraws * k <= %d (ndraws %d, k %d)", who, GPZ_DRAWS_MAX_COLUMNS, (int)ndraws,
-                        p->k);
-    if (int rc = predictor_noisy_check(who, p)) return rc;
-    if (p->force_tiles) return gpz_fail(GPZ_ERR_UNSUPPORTED, "%s: input noise needs the fused draws route (GPZ_PREDICT_FORCE_TILES is set)", who);
-    if (int rc = predictor_dev_args(who, p, X_d, x_type, ns, row_stride, col_stride, muX, sdX)) return rc;
-    if (int rc = predictor_dev_psi_args(who, p, Psi_d, psi_type, ns, psi_row_stride, psi_col_stride, sdX, sd2)) return rc;
-    if (ns == 0) return 0;
-    if (!F_d) return gpz_fail(GPZ_ERR_ARG, "%s: null argument", who);
-    const DevRows x{X_d, x_type == GPZ_X_F32, ns, row_stride, col_stride};
-    const DevRows psi{Psi_d, psi_type == GPZ_X_F32, ns, psi_row_stride, psi_col_stride};
-    const double *mx = nullptr, *sx = nullptr, *my = nullptr;
-    int prev = 0;
-    (void)hipGetDevice(&prev);
-    gpz_opts_scope opts_scope(&p->opt);
-    int rc = 0;
-    if (hipSetDevice(p->device) != hipSuccess) rc = gpz_fail(GPZ_ERR_HIP, "%s: hipSetDevice failed", who);
-    if (!rc) rc = predictor_psi_slots(p);
-    if (!rc)
-        rc = predictor_dev_begin(p, who, x, muX, sdX, muY, nullptr, 0, nullptr, stream,
-                                 "the rows have missing values (NaN): draws are for complete rows", &mx, &sx, &my, &psi, sd2);
-    if (!rc)
-        rc = predictor_run_draws_dev(p, x, mx, sx, my, (int)ndraws, (unsigned long long)seed, Z, F_d, &psi, sd2 ? p->sd2_d : nullptr);
-    (void)hipSetDevice(prev);
-    return rc;
-}
-
-extern "C" int gpz_predictor_draws_noisy(gpz_predictor *p, const double *Xs, int64_t ns, const double *Psi, int32_t ndraws, uint64_t seed,
-                                         const double *Z, double *F) {
-    const char *who = "gpz_predictor_draws_noisy";
-    if (!p) return gpz_fail(GPZ_ERR_ARG, "%s: null handle", who);
-    if (ns < 0) return gpz_fail(GPZ_ERR_ARG, "%s: ns < 0", who);
-    if (ndraws < 1 || (int64_t)ndraws * p->k > GPZ_DRAWS_MAX_COLUMNS)
-        return gpz_fail(GPZ_ERR_ARG, "%s: need 1 <= ndraws and ndraws * k <= %d (ndraws %d, k %d)", who, GPZ_DRAWS_MAX_COLUMNS, (int)ndraws,
-                        p->k);
-    if (int rc = predictor_noisy_check(who, p)) return rc;
-    if (p->force_tiles) return gpz_fail(GPZ_ERR_UNSUPPORTED, "%s: input noise needs the fused draws route (GPZ_PREDICT_FORCE_TILES is set)", who);
-    if (ns == 0) return 0;
-    if (!Xs || !Psi || !F) return gpz_fail(GPZ_ERR_ARG, "%s: null argument", who);
-    int prev = 0;
-    (void)hipGetDevice(&prev);
-    gpz_opts_scope opts_scope(&p->opt);
-    int rc = 0;
-    if (hipSetDevice(p->device) != hipSuccess) rc = gpz_fail(GPZ_ERR_HIP, "%s: hipSetDevice failed", who);
-    if (!rc) rc = predictor_run_draws(p, Xs, ns, (int)ndraws, (unsigned long long)seed, Z, F, Psi);
-    (void)hipSetDevice(prev);
-    return rc;
+    const DevRows psi{Psi_d, psi_type, ns, psi_row_stride, psi_col_stride};
+    return draws_dev_entry("gpz_predictor_draws_noisy_dev", p, DevRows{X_d, x_type, ns, row_stride, col_stride}, &psi, muX, sdX, sd2, muY,
+                           ndraws, seed, Z, F_d, stream);
 }
 
 extern "C" int gpz_predictor_stack_dev(gpz_predictor *p, const void *X_d, int32_t x_type, int64_t ns, int64_t row_stride,
@@ -1197,36 +1170,27 @@ extern "C" int gpz_predictor_stack_dev(gpz_predictor *p, const void *X_d, int32_
                                        const double *weight_d, double *hist, double *sum_w, double *sum_mu, double *sum_mu2,
                                        const double *mu_shift, void *stream) {
     const char *who = "gpz_predictor_stack_dev";
+    const DevRows x{X_d, x_type, ns, row_stride, col_stride};
     if (int rc = stack_check_shape(who, p, ns, ndraws, nbins, ngroups, edges, hist, sum_w, sum_mu, sum_mu2, X_d)) return rc;
-    if (int rc = predictor_dev_args(who, p, X_d, x_type, ns, row_stride, col_stride, muX, sdX)) return rc;
+    if (int rc = predictor_dev_args(who, p, x, muX, sdX)) return rc;
+    if (int rc = stack_check_shift(who, p, mu_shift)) return rc;
     const int k = p->k, B = nbins, G = ngroups, C = 1 + ndraws;
-    if (mu_shift)
-        for (int o = 0; o < k; ++o)
-            if (!std::isfinite(mu_shift[o])) return gpz_fail(GPZ_ERR_ARG, "%s: mu_shift must be finite", who);
     if (ns == 0) {
-        const size_t GB = (size_t)G * B, Q = (size_t)C * k;
-        memset(hist, 0, Q * GB * sizeof(double));
-        memset(sum_w, 0, (size_t)G * sizeof(double));
-        memset(sum_mu, 0, Q * G * sizeof(double));
-        memset(sum_mu2, 0, Q * G * sizeof(double));
+        stack_zero(C, k, G, B, hist, sum_w, sum_mu, sum_mu2);
         return 0;
     }
-    const DevRows x{X_d, x_type == GPZ_X_F32, ns, row_stride, col_stride};
-    const double *mx = nullptr, *sx = nullptr, *my = nullptr;
     std::vector<double> res((size_t)C * k * ((size_t)G * B + 3 * (size_t)G));
-    int prev = 0;
-    (void)hipGetDevice(&prev);
-    gpz_opts_scope opts_scope(&p->opt);
-    int rc = 0;
-    if (hipSetDevice(p->device) != hipSuccess) rc = gpz_fail(GPZ_ERR_HIP, "%s: hipSetDevice failed", who);
-    if (!rc)   // the refusals of the host entry's loops over labels and weights, and of its staging loop over the rows, before any tile
-        rc = predictor_dev_begin(p, who, x, muX, sdX, nullptr, group_d, G, weight_d, stream,
-                                 "the rows have missing values (NaN): stacks are for complete rows", &mx, &sx, &my);
-    if (!rc)
-        rc = predictor_run_stack_dev(p, x, mx, sx, (int)ndraws, (unsigned long long)seed, Z, edges, mu_shift, B, group_d, G, weight_d,
-                                     res.data());
-    (void)hipSetDevice(prev);
-    if (rc) return rc;   // the outputs are untouched
+    if (int rc = predictor_call(p, who, [&] {
+            const double *mx = nullptr, *sx = nullptr, *my = nullptr;
+            // the refusals of the host entry's loops over labels and weights, and of its staging loop over the rows, before any tile
+            int rc = predictor_dev_begin(p, who, x, muX, sdX, nullptr, group_d, G, weight_d, stream,
+                                         "the rows have missing values (NaN): stacks are for complete rows", &mx, &sx, &my);
+            if (!rc)
+                rc = predictor_run_stack_dev(p, x, mx, sx, (int)ndraws, (unsigned long long)seed, Z, edges, mu_shift, B, group_d, G,
+                                             weight_d, res.data());
+            return rc;
+        }))
+        return rc;   // the outputs are untouched
     stack_unpack(res.data(), C, k, G, B, hist, sum_w, sum_mu, sum_mu2);
     return 0;
 }
