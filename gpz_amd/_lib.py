@@ -60,6 +60,7 @@ SYMBOLS = {
     "gpz_vec_axpy": (C.c_int, [C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]),
     "gpz_ctx_set_pinv_mode": (C.c_int, [C.c_void_p, C.c_int]),
     "gpz_ctx_last_pinv": (C.c_int, [C.c_void_p, c_double_p]),
+    "gpz_ctx_last_phi": (C.c_int, [C.c_void_p, c_double_p]),
     "gpz_ctx_enable_timing": (C.c_int, [C.c_void_p, C.c_int]),
     "gpz_ctx_timings": (C.c_int, [C.c_void_p, C.POINTER(C.c_char_p), c_double_p, C.POINTER(C.c_int64), C.c_int]),
     "gpz_ctx_route": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int]),

@@ -108,6 +108,12 @@ def _mask(a, n):
     return a
 
 
+def _last_phi(lib, h):
+    out = (C.c_double * 2)()
+    _lib.check(lib.gpz_ctx_last_phi(h, out))
+    return bool(out[0]), float(out[1])
+
+
 class GPzContext:
     """The closure ``f = @(theta) GPz(theta,model,X,Y,Psi,omega,training,validation)`` (train.m:40) with the data
     resident on the GPU.  ``X`` must already be normalised and ``Y`` centred, as train.m:30-33 does before
@@ -229,6 +235,11 @@ class GPzContext:
         out = (C.c_double * 4)()
         _lib.check(self._lib.gpz_ctx_last_pinv(self._h, out))
         return bool(out[0]), int(out[1]), float(out[2]), int(out[3])
+
+    def last_phi(self):
+        """(fell back, bound) of the last eval: whether the covariance-kind PHI build left the f64 MFMA route (k_phi_quad) for
+        k_phi_cov because the bound on its rounding error, max_j B_j, exceeded 2^-33.  (False, 0.0) on every other route."""
+        return _last_phi(self._lib, self._h)
 
     def phi(self):
         """PHI (n_train x m) of the last eval/solve — the 5th output of GPz.m:1."""
@@ -368,6 +379,10 @@ class GPzMulti:
         buf = C.create_string_buffer(512)
         self._lib.gpz_ctx_route(self._lib.gpz_mgpu_ctx(self._h, int(rank)), buf, 512)
         return buf.value.decode()
+
+    def last_phi(self, rank=0):
+        """GPzContext.last_phi of one rank (every rank bounds the rounding error over its own rows)."""
+        return _last_phi(self._lib, self._lib.gpz_mgpu_ctx(self._h, int(rank)))
 
     def enable_timing(self, on=True):
         for c in self._each():

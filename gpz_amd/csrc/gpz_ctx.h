@@ -139,6 +139,7 @@ struct RowSet {          // a device-resident row selection of the data
     double *xmu = nullptr;  // de: column means of the rows (missing entries count as 0): centre of k_small_tail's feature expansion
     double *Xs = nullptr;   // n_pad x xs_ld: rows [1 | x - xmu | 0], or [1 | (x - xmu) mk | mk | 0] with missing values (zero rows past n)
     int xs_ld = 0;          // (k_small_tail builds its features from these rows)
+    double *fmax = nullptr; // covariance kinds, plain Xs, de = 8 / 10: max over the rows of |F_if|, F_i = [1 | x' | x'_a x'_b (a <= b)] (k_phi_quad_coef's bound)
     long om_ld = 0;         // omega of output o, row i: om[o*om_ld + i]; 0 = one column for every output (GPz.m:48)
     // diagonal kinds only: input-noise variances and the observed-dimension mask (nullptr => absent)
     double *Psic = nullptr, *Psir = nullptr;   // de x n_pad, n_pad x de (0 where the input is missing)
@@ -236,6 +237,12 @@ struct gpz_ctx {
     int st_nwg = 0, st_nf = 0;
     bool mom_ring = false;     // GC / VC, mp > 256, d = 8 / 10, no Psi / missing values: the moment sums by k_moments_ring (PHI, T through an LDS ring), records of mom_nv values
     int mom_nv = 0;            // values per chunk record of mom_slab: nm + 2, on the ring route nf + 2
+    // GC / VC, mp > 256, d = 8 / 10, k = 1, no Psi / missing values: PHI by k_phi_quad (f64 MFMA over centred row features) whenever the
+    // evaluation's rounding bound allows, else by k_phi_cov - both launched, the route word decides on the device (k_phi_quad.hip)
+    bool phi_quad = false;
+    double *phi_Cq = nullptr, *phi_bound = nullptr, *phi_blockmax = nullptr;   // [mp][phi_quad_stride], max_j B_j, scratch
+    int *phi_route = nullptr;            // [route word, ticket of k_phi_quad_coef]
+    double phi_last[2] = {0, 0};         // [fell back to k_phi_cov, max_j B_j] of the last evaluation
     double *st_slab = nullptr;
     bool fused = true;   // dPHI formed on the fly, output by output (no dPHI / dL matrices): k == 1, or k > 1 on the tuned kernels
     double *phipart = nullptr;   // PHI-build column-group partial sums (small row counts)

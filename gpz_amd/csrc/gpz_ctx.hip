@@ -98,6 +98,21 @@ static int upload_rowset(gpz_ctx *c, RowSet &rs, int64_t n_tot, const double *X,
             }
             if (int e = c->ar.alloc(&rs.Xs, np * xl)) return e;
             HIPCHK(hipMemcpy(rs.Xs, xs.data(), xs.size() * sizeof(double), hipMemcpyHostToDevice));
+            if (!masked && c->kind == GPZ_KIND_COV && (de == 8 || de == 10)) {   // the widths of k_phi_quad: feature maxima for its rounding bound
+                const int nf = 1 + de + de * (de + 1) / 2;
+                std::vector<double> fm((size_t)nf, 0.0);
+                fm[0] = 1.0;
+                for (size_t r = 0; r < idx.size(); ++r) {
+                    const double *x = xs.data() + r * xl + 1;
+                    int f = 1 + de;
+                    for (int a = 0; a < de; ++a) {
+                        fm[1 + a] = std::max(fm[1 + a], fabs(x[a]));
+                        for (int b = a; b < de; ++b, ++f) fm[f] = std::max(fm[f], fabs(x[a] * x[b]));
+                    }
+                }
+                if (int e = c->ar.alloc(&rs.fmax, (size_t)nf)) return e;
+                HIPCHK(hipMemcpy(rs.fmax, fm.data(), (size_t)nf * sizeof(double), hipMemcpyHostToDevice));
+            }
         }
     }
     if (any_missing || c->has_missing) {
@@ -640,6 +655,17 @@ extern "C" int gpz_ctx_create_sharded(const gpz_desc *desc, int64_t n_tot, const
             c->tile_nchunk = (c->tile_rows + c->tile_rpc - 1) / c->tile_rpc;
             c->nchunk = c->ntiles * c->tile_nchunk;
         }
+        // ... and PHI itself is a product of the same row features (k_phi_quad.hip).  Independent of the moment route.
+        c->phi_quad = !c->gen && !c->has_psi && !c->has_missing && c->tr.Xs && c->tr.fmax && c->tr.xs_ld == c->de + 2 &&
+                      phi_quad_fits(c->kind, c->de, c->mp, c->k) && !c->opt.phi_quad_off;
+        if (c->phi_quad) {
+            if ((rc = c->ar.alloc(&c->phi_Cq, (size_t)c->mp * phi_quad_stride(c->de)))) return bail(rc);
+            if ((rc = c->ar.alloc(&c->phi_bound, 1))) return bail(rc);
+            if ((rc = c->ar.alloc(&c->phi_blockmax, (size_t)(c->mp + 63) / 64))) return bail(rc);
+            if ((rc = c->ar.alloc(&c->phi_route, 2))) return bail(rc);
+            if (hipMemset(c->phi_route, 0, 2 * sizeof(int)) != hipSuccess || hipMemset(c->phi_bound, 0, sizeof(double)) != hipSuccess)
+                return bail(gpz_fail(GPZ_ERR_HIP, "memset failed"));
+        }
         c->mom_nv = c->mom_ring ? moments_ring_features(c->de) + 2 : c->nm + 2;
         if ((rc = c->ar.alloc(&c->mom_slab, (size_t)c->nchunk * m * c->mom_nv))) return bail(rc);
     }
@@ -730,6 +756,12 @@ extern "C" int gpz_ctx_last_pinv(const gpz_ctx *c, double out[4]) {
 namespace gpzi {
 
 }   // namespace gpzi
+extern "C" int gpz_ctx_last_phi(const gpz_ctx *c, double out[2]) {
+    if (!c || !out) return gpz_fail(GPZ_ERR_ARG, "null argument");
+    out[0] = c->phi_last[0];
+    out[1] = c->phi_last[1];
+    return GPZ_OK;
+}
 extern "C" int gpz_ctx_enable_timing(gpz_ctx *c, int enable) {
     if (!c) return gpz_fail(GPZ_ERR_ARG, "null context");
     c->timing = enable < 0 ? 0 : enable > 2 ? 2 : enable;   // 0 off, 1 every stage (eager launches), 2 the dominant stages (graph segments)
@@ -788,12 +820,13 @@ extern "C" int gpz_ctx_route(const gpz_ctx *c, char *buf, int cap) {
     char rows[96];
     if (c->tile_rows) snprintf(rows, sizeof rows, "; rows: streamed, %d tiles of %d (PHI built twice per evaluation)", c->ntiles, c->tile_rows);
     else rows[0] = 0;
-    return snprintf(buf, (size_t)cap, "pair/PHI kernels: %s%s; contractions: %s MFMA%s%s; evaluation graph: %s%s%s", phi, why,
+    return snprintf(buf, (size_t)cap, "pair/PHI kernels: %s%s; contractions: %s MFMA%s%s; evaluation graph: %s%s%s%s", phi, why,
                     f32mm ? "fp32-operand (fp64 master sums)" : "fp64",
                     c->syrk_small ? ", PHI' W PHI with the whole triangle in one workgroup (k_syrk_small)" : "",
                     c->small_tail ? ", T-GEMM + row scalars + moments in one kernel (k_small_tail: T stays in registers)" :
                     c->small_tail_dp ? ", T-GEMM + row scalars + dPHI in one kernel (k_small_tail; moment sums with input noise by k_moments_diag)" : "", gs, rows,
-                    c->mom_ring ? "; moments: k_moments_ring (PHI, T through an LDS ring)" : "");
+                    c->mom_ring ? "; moments: k_moments_ring (PHI, T through an LDS ring)" : "",
+                    c->phi_quad ? "; PHI: k_phi_quad (f64 MFMA over centred row features; k_phi_cov when the rounding bound exceeds 2^-33)" : "");
 }
 namespace gpzi {
 

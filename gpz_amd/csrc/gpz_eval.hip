@@ -122,6 +122,15 @@ static int moments_by_pattern(gpz_ctx *c, bool fused, double *mom) {
     return 0;
 }
 
+// Contexts on the k_phi_quad route: that kernel for the training rows a describes (r0: their offset in the row set), and a's own launch
+// marked as the fallback.  Both are launched; this evaluation's route word (launch_phi_quad_coef, stage_a) says which one runs.
+static int phi_quad_first(gpz_ctx *c, PhiArgs &a, long r0) {
+    if (!c->phi_quad) return 0;
+    a.route = c->phi_route; a.route_want = GPZ_PHI_ROUTE_EXACT;
+    if (launch_phi_quad(c->st, a, c->tr.Xs + (size_t)r0 * c->tr.xs_ld, c->phi_Cq)) return gpz_fail(GPZ_ERR_HIP, "k_phi_quad launch failed (d=%d)", c->de);
+    return 0;
+}
+
 // PHI, ln beta and omega*beta of the training row set from the unpacked parameters (getPHI.m:60-125, GPz.m:43-48).
 int build_phi(gpz_ctx *c) {
     if (c->gen) {
@@ -171,6 +180,7 @@ int build_phi(gpz_ctx *c) {
         a.Phi = c->Phi; a.lnbeta = c->lnbeta; a.wbeta = c->wbeta; a.w = nullptr; a.phiw = nullptr;
         a.Psic = c->tr.Psic; a.Mc = c->tr.Mc; a.ucnt = c->tr.ucnt;
         a.part = a.n_pad <= c->phipart_rows ? c->phipart : nullptr; a.part_groups = c->phipart_groups;
+        if (int e = phi_quad_first(c, a, 0)) return e;
         if (launch_phi(c->st, a)) return gpz_fail(GPZ_ERR_UNSUPPORTED, "PHI kernel not instantiated for d=%d", c->de);
     }
     return 0;
@@ -197,6 +207,7 @@ static int phi_tile(gpz_ctx *c, const RowTile &rt) {
     a.Psic = c->tr.Psic ? c->tr.Psic + r0 : nullptr; a.Mc = c->tr.Mc ? c->tr.Mc + r0 : nullptr;
     a.ucnt = c->tr.ucnt ? c->tr.ucnt + r0 : nullptr;
     a.part = a.n_pad <= c->phipart_rows ? c->phipart : nullptr; a.part_groups = c->phipart_groups;   // (row-indexed from the tile's base, stride = the tile's rows)
+    if (int e = phi_quad_first(c, a, r0)) return e;
     if (launch_phi(c->st, a)) return gpz_fail(GPZ_ERR_UNSUPPORTED, "PHI kernel not instantiated for d=%d", c->de);
     return 0;
 }
@@ -244,6 +255,9 @@ int stage_a(gpz_ctx *c, const double *theta, const double *theta_dev) {
         double *vsums0 = c->va.n_pad > 0 ? nullptr : c->comm2 + (size_t)c->m * c->nm + (size_t)c->k * 2 * c->mp + (size_t)c->k * 4;
         launch_unpack(c->st, c->theta_d, c->mid, c->m, c->d, c->de, c->k, c->hetero, c->pr, c->info, vsums0, gpz_ns(c->k));
         if (c->kind == GPZ_KIND_COV) launch_prep_cov(c->st, c->pr.G, c->pr.P, c->m, c->de, c->pr.Rc, c->prep_ws);
+        if (c->phi_quad && launch_phi_quad_coef(c->st, c->pr.Rc, c->pr.P, c->tr.xmu, c->tr.fmax, c->m, c->mp, c->de, c->phi_Cq, c->phi_blockmax,
+                                                (unsigned *)(c->phi_route + 1), c->phi_bound, c->phi_route))
+            return gpz_fail(GPZ_ERR_UNSUPPORTED, "k_phi_quad_coef not instantiated for d=%d", c->de);
     }
     if (int e = psi32_agree(c)) return e;
     if (c->tile_rows) { if (int e = stage_a_tiles(c)) return e; }
@@ -673,6 +687,7 @@ int eval_tail(gpz_ctx *c, bool pinv) {
         a.g_dim = c->g_dim; a.pr = c->pr; a.mom = mom; a.nm = c->nm; a.cols = cols; a.scal = scal;
         a.w = c->w; a.dwda = c->dwda; a.dgi = c->dgi; a.logdet = c->logdet;
         a.sums1 = c->comm1 + k * mp * mp; a.vsums = have_valid ? vsums : nullptr; a.info = c->info;
+        a.phi_bound = c->phi_quad ? c->phi_bound : nullptr;
         a.out = c->out_d; a.dGfull = c->dGfull; a.p = (int)c->p; a.nmp = c->mp; a.de = c->de;
         a.psi = (c->has_psi && !c->gen) ? 1 : 0; a.gen = c->gen ? 1 : 0;
         if (c->gen && c->psi32 && c->tr.psi_diag)   // whitened records: the stable chain through R (k_psi32.hip)

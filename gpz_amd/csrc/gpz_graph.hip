@@ -177,6 +177,9 @@ static int eval_common(gpz_ctx *c, const double *theta, const double *theta_dev,
         if (have_valid) { stats[2] = st[2]; stats[3] = st[3]; }
     }
     if (diag) { diag[0] = st[4]; diag[1] = st[5]; }
+    // k_phi_quad contexts: the bound travels in the result block; the device chose by the same comparison (k_phi_quad_coef)
+    c->phi_last[1] = c->phi_quad ? st[8] : 0.0;
+    c->phi_last[0] = (c->phi_quad && !(st[8] <= GPZ_PHI_QUAD_TAU)) ? 1.0 : 0.0;
     return GPZ_OK;
 }
 

@@ -60,6 +60,10 @@ struct PhiArgs {
     // describe the whole row set.  nullptr = one parameter set for all rows.
     const int *wgtab;
     int nwg_tab;
+    // covariance kinds beside k_phi_quad (k_phi_quad.hip): the evaluation's route word; the launch runs when *route == route_want.
+    // nullptr = the launch always runs.
+    const int *route;
+    int route_want;
 };
 int phi_cov_rows_per_wg(int de, int k);   // rows one workgroup of the cov-kind PHI kernel covers (granularity of wgtab)
 bool phi_is_wide(int de, int k);          // d or k beyond the instantiated kernels: the runtime-d route of k_wide.hip
@@ -70,6 +74,35 @@ size_t prep_cov_ws_len(int m, int de);   // workspace (doubles) the QR needs whe
 int launch_prep_cov_wide(hipStream_t st, const double *G, const double *P, int m, int de, double *Rc, double *ws);
 void launch_prep_cov(hipStream_t st, const double *G, const double *P, int m, int de, double *Rc, double *ws = nullptr);
 int launch_phi(hipStream_t st, const PhiArgs &a);   // returns 0, or -1 if d is not supported
+// column groups of a PHI build with few rows (k_phi.hip), and the kernel that combines their per-row sums ([ngroup][2][k][a.n_pad] in part)
+int phi_pick_groups(int nwg, int mp, int JB, int min_wgs, int prologue_cols, int max_groups);
+void launch_phi_finalize(hipStream_t st, const double *part, int ngroup, const PhiArgs &a, const int *route, int route_want);
+
+// ---- covariance-kind PHI on the f64 MFMA from centred row monomials (k_phi_quad.hip) ---------------------------------------------
+// ln PHI = F C with the row features F_i = [1 | x' | x'_a x'_b] (x' = x - the rows' column means: the rows of Xs) and per-basis
+// coefficients C_j, taken whenever a bound on the product's rounding error over the context's rows stays below GPZ_PHI_QUAD_TAU.
+//
+// The threshold 2^-33 = 1.16e-10 on max_j B_j, B_j = (NF + 2d + 6) 2^-53 sum_f max_i|F_if| Chat_fj:
+//   * B overestimates the observed error of the exponent by about 100 x (long-double comparison on the benchmark's theta and on
+//     Gamma x 10, x 100: DESIGN.md section 8), so it holds the actual |delta q| to about 1e-12, PHI to about 6e-13 relative - four
+//     orders of magnitude under the 1e-8 parity gate;
+//   * it lies 120 x above the bound at the benchmark's starting theta (c4 9.5e-13, c3 8.4e-13, the test problems 3 - 7e-13): an
+//     optimiser can narrow the basis functions tenfold (B grows with |Gamma|^2) before the route changes;
+//   * Gamma x 100 exceeds it by 50 x.
+#define GPZ_PHI_QUAD_TAU 0x1p-33
+#define GPZ_PHI_ROUTE_QUAD 0
+#define GPZ_PHI_ROUTE_EXACT 1
+bool phi_quad_fits(int kind, int de, int mp, int k);   // GC / VC, d = 8 / 10, mp > 256, one output
+int phi_quad_stride(int de);                           // doubles per basis function of Cq: 4 ceil(NF / 4)
+// Cq [mp][stride] from Rc ([R_j | c_j] of launch_prep_cov), P and the rows' means; fmx: max_i |F_if| over the rows (nf values);
+// blockmax: ceil(mp / 64) doubles of scratch, ticket: a device word that is zero before the first launch; *bound = max_j B_j,
+// *route = GPZ_PHI_ROUTE_QUAD / _EXACT.  -1: d not instantiated.
+int launch_phi_quad_coef(hipStream_t st, const double *Rc, const double *P, const double *xmu, const double *fmx, int m, int mp, int de,
+                         double *Cq, double *blockmax, unsigned *ticket, double *bound, int *route);
+// the product for the rows a describes (what the PHI-storing launch_phi(a) delivers: PHI with its [Y | 0] columns and zero rows, ln beta,
+// omega beta, the column-group split; a.w / a.phiw null, a.n_pad a multiple of 128); runs when *a.route == GPZ_PHI_ROUTE_QUAD.
+// Xs: those rows' [1 | x' | 0].  -1: not launched.
+int launch_phi_quad(hipStream_t st, const PhiArgs &a, const double *Xs, const double *Cq);
 
 // ---- MFMA contractions (k_gemm.hip) ------------------------------------------------------------
 // off-diagonal 128-tiles: nsplit row ranges of rows_per_split rows; diagonal tiles: nsplit_d ranges of rows_per_split_d
@@ -341,7 +374,8 @@ struct FinishArgs {
     const double *sums1;                  // [sum omega, sum_i omega_i lnbeta_io (8), n_train]       (GPZ_NS doubles)
     const double *vsums;                  // [sum omega delta^2, sum LL, per-output (8), n_valid, 0]  or nullptr
     const int *info;
-    double *out;                          // [f, grad(p), stats(4), info, n, logdet0, svd-route flag, 0]   (p + 10 doubles)
+    const double *phi_bound;              // k_phi_quad contexts: max_j B_j of this evaluation (nullptr: 0 is reported)
+    double *out;                          // [f, grad(p), stats(4), info, n, logdet0, svd-route flag, PHI rounding bound]   (p + 10 doubles)
     double *dGfull;                       // scratch m*d or m*d*d
     int p;
     int nmp;                              // leading dimension of cols (= mp)

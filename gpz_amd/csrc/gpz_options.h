@@ -43,6 +43,7 @@ struct gpz_options {
     bool syrk_small_off = false;         // GPZ_SYRK_SMALL_OFF        m + k <= 256: k_syrk's 128 x 128 tiles instead of k_syrk_small
     bool small_tail_off = false;         // GPZ_SMALL_TAIL_OFF        m + k <= 256: k_tgemm + k_row_scalars + k_moments_fused instead of k_small_tail
     bool moments_ring_off = false;       // GPZ_MOMENTS_RING_OFF      GC / VC, mp > 256, d = 8 / 10: k_moments_fused (register prefetch) instead of k_moments_ring (LDS ring)
+    bool phi_quad_off = false;           // GPZ_PHI_QUAD_OFF          GC / VC, mp > 256, d = 8 / 10, k = 1: k_phi_cov alone instead of k_phi_quad with its fallback
     int debug_fail_cut = 0;              // GPZ_DEBUG_FAIL_CUT=k      test hook: the k-th segment cut of a graph recording fails after its hipStreamEndCapture
 };
 

@@ -44,6 +44,7 @@ gpz_options gpz_options_load() {
     o.chol_rowinv_off = env_set("GPZ_CHOL_ROWINV_OFF");
     o.small_stagger = (int)env_long("GPZ_SMALL_STAGGER", 0);
     o.moments_ring_off = env_set("GPZ_MOMENTS_RING_OFF");
+    o.phi_quad_off = env_set("GPZ_PHI_QUAD_OFF");
 #endif
     return o;
 }

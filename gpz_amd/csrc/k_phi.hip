@@ -388,7 +388,8 @@ __global__ __launch_bounds__(256, 2) void k_phi_cov(const double *__restrict__ X
                                                   double *__restrict__ Phi, double *__restrict__ lnbeta,
                                                   double *__restrict__ wbeta, const double *__restrict__ wv,
                                                   double *__restrict__ phiw, int jgroup, double *__restrict__ part, long ldp,
-                                                  const int *__restrict__ wgtab) {
+                                                  const int *__restrict__ wgtab, const int *__restrict__ route, int route_want) {
+    if (route && *route != route_want) return;       // this evaluation's PHI is k_phi_quad's (k_phi_quad.hip)
     constexpr int KM = KGEN ? 8 : 1;
     constexpr int NT = D * (D + 1) / 2;
     constexpr int NP = NT + D;                       // doubles per basis function
@@ -588,7 +589,9 @@ __global__ __launch_bounds__(256, 2) void k_phi_cov(const double *__restrict__ X
 // lnbeta = b + sum_g part_v[g], omega*beta, PHI*w from the column-group partial sums (fixed order: repeatable)
 __global__ void k_phi_finalize(const double *__restrict__ part, long ldp, int ngroup, long ldx, long rows, int n, int k,
                                const double *__restrict__ bvec, const double *__restrict__ omega, long om_ld,
-                               double *__restrict__ lnbeta, double *__restrict__ wbeta, double *__restrict__ phiw) {
+                               double *__restrict__ lnbeta, double *__restrict__ wbeta, double *__restrict__ phiw,
+                               const int *__restrict__ route, int route_want) {
+    if (route && *route != route_want) return;       // the sums of the PHI kernel that did not run
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= rows) return;
     for (int o = 0; o < k; ++o) {
@@ -614,7 +617,7 @@ __global__ void k_phi_finalize(const double *__restrict__ part, long ldp, int ng
 // prologue in columns' worth), with at least `min_wgs` workgroups' worth of time per CU (fewer cannot hide the parameter loads).
 // c2 (391 row blocks, 208 columns): g = 1 .. 13 measured 136, 84, 83, 93, 78, -, 75, ..., 74 us and the model ranks them the same
 // ("about 1024 workgroups" chose g = 3).  Among choices within 1 % the largest wins (c4: two groups 4.34 ms, one 4.44).
-static int phi_pick_groups(int nwg, int mp, int JB, int min_wgs, int prologue_cols, int max_groups) {
+int phi_pick_groups(int nwg, int mp, int JB, int min_wgs, int prologue_cols, int max_groups) {
     const int ncu = gpz_cu_count();
     constexpr int MAXG = 64;                                     // (the callers' part_groups is 16: phipart holds that many partial sums per row)
     long cost[MAXG + 1];
@@ -634,6 +637,11 @@ static int phi_pick_groups(int nwg, int mp, int JB, int min_wgs, int prologue_co
     for (int g = 1; g <= max_groups; ++g)
         if (cost[g] >= 0 && cost[g] * 100 <= best_cost * 101) best = g;
     return best;
+}
+
+void launch_phi_finalize(hipStream_t st, const double *part, int ngroup, const PhiArgs &a, const int *route, int route_want) {
+    hipLaunchKernelGGL(k_phi_finalize, dim3((unsigned)((a.n_pad + 255) / 256)), dim3(256), 0, st, part, (long)a.n_pad, ngroup, a.ldx,
+                       (long)a.n_pad, a.n, a.k, a.b, a.omega, a.om_ld, a.lnbeta, a.wbeta, a.phiw, route, route_want);
 }
 
 // 4 rows per thread and 8-wide blocks while [tile | params] fits twice in a CU's LDS; else 2 rows
@@ -668,13 +676,11 @@ static void launch_phi_cov_d(hipStream_t st, const PhiArgs &a) {
     dim3 grid(nwg, ngroup);
 #define PHI_COV(KG, TB) \
     hipLaunchKernelGGL((k_phi_cov<D, KG, R, JB, TB>), grid, dim3(256), 0, st, a.Xc, a.ldx, a.n, a.m, a.mp, a.k, a.G, a.v, \
-                       a.b, a.omega, a.om_ld, a.Y, a.Phi, a.lnbeta, a.wbeta, a.w, a.phiw, jgroup, part, (long)a.n_pad, a.wgtab)
+                       a.b, a.omega, a.om_ld, a.Y, a.Phi, a.lnbeta, a.wbeta, a.w, a.phiw, jgroup, part, (long)a.n_pad, a.wgtab, a.route, a.route_want)
     if (a.wgtab) { if (a.k == 1) PHI_COV(false, true); else PHI_COV(true, true); }
     else { if (a.k == 1) PHI_COV(false, false); else PHI_COV(true, false); }
 #undef PHI_COV
-    if (part)
-        hipLaunchKernelGGL(k_phi_finalize, dim3((unsigned)((a.n_pad + 255) / 256)), dim3(256), 0, st, (const double *)part,
-                           (long)a.n_pad, ngroup, a.ldx, (long)a.n_pad, a.n, a.k, a.b, a.omega, a.om_ld, a.lnbeta, a.wbeta, a.phiw);
+    if (part) launch_phi_finalize(st, part, ngroup, a, a.route, a.route_want);
 }
 
 #ifndef GPZ_PHI_DIAG_RP
@@ -712,9 +718,7 @@ static void launch_phi_kd(hipStream_t st, const PhiArgs &a) {
     else { if (a.Psic) PHI_DIAG(true, true); else PHI_DIAG(true, false); }
 #undef PHI_DIAG
 #undef PHI_DIAG_R
-    if (part)
-        hipLaunchKernelGGL(k_phi_finalize, dim3((unsigned)((a.n_pad + 255) / 256)), dim3(256), 0, st, (const double *)part,
-                           (long)a.n_pad, ngroup, a.ldx, (long)a.n_pad, a.n, a.k, a.b, a.omega, a.om_ld, a.lnbeta, a.wbeta, a.phiw);
+    if (part) launch_phi_finalize(st, part, ngroup, a, nullptr, 0);
 }
 
 template <int KIND>

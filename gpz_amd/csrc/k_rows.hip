@@ -786,6 +786,7 @@ __global__ __launch_bounds__(256) void k_finish_b(FinishArgs a, int de) {
         st[5] = n;
         st[6] = a.logdet[0];
         st[7] = (double)a.info[1];                                         // k_cond_flag: the SVD route is wanted
+        st[8] = a.phi_bound ? *a.phi_bound : 0.0;                          // k_phi_quad_coef: the bound that chose this evaluation's PHI kernel
     }
     if (*a.info != 0) {
         const double nanv = __longlong_as_double(0x7ff8000000000000LL);

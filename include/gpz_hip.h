@@ -162,6 +162,11 @@ int gpz_get_phi(gpz_ctx *ctx, double *PHI);
  * (minimum over outputs), out[2] = largest singular value, out[3] = Jacobi sweeps. */
 int gpz_ctx_set_pinv_mode(gpz_ctx *ctx, int mode);
 int gpz_ctx_last_pinv(const gpz_ctx *ctx, double out[4]);
+/* Covariance kinds with many basis functions (GC / VC, m + k > 256, d <= 10 padded to 8 or 10, one output, no input noise or missing
+ * values) build PHI as a product of centred row features on the f64 MFMA whenever a bound on that product's rounding error over the
+ * context's rows, max_j B_j, is at most 2^-33, and with the vector kernel otherwise; the choice is made on the device per evaluation.
+ * gpz_ctx_last_phi: out[0] = 1 if the last gpz_eval fell back to the vector kernel, out[1] = max_j B_j (0 on every other route). */
+int gpz_ctx_last_phi(const gpz_ctx *ctx, double out[2]);
 
 /* Per-stage GPU time (HIP events on the context's stream).  enable = 1: events around every stage (the evaluation then runs as
  * eager launches); enable = 2: around the dominant stages only (phi_build, syrk, tgemm, moments), the evaluation still replayed as
