@@ -100,6 +100,13 @@ SYMBOLS = {
                                                 C.c_int64, C.c_int64, c_double_p, c_double_p, c_double_p, c_double_p, C.c_int32,
                                                 C.c_uint64, c_double_p, C.c_void_p, C.c_void_p]),
     "gpz_predictor_draws_noisy": (C.c_int, [C.c_void_p, c_double_p, C.c_int64, c_double_p, C.c_int32, C.c_uint64, c_double_p, c_double_p]),
+    # one group of rows sharing a NaN pattern: priors (host, m or NULL) and the bit mask of the observed dimensions
+    "gpz_predictor_run_missing_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int64, c_double_p, c_double_p,
+                                                c_double_p, c_double_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                C.c_void_p, C.c_void_p]),
+    "gpz_predictor_draws_missing_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int64, c_double_p,
+                                                  c_double_p, c_double_p, c_double_p, C.c_uint32, C.c_int32, C.c_uint64, c_double_p,
+                                                  C.c_void_p, C.c_void_p]),
     "gpz_prior": (C.c_int, [C.POINTER(gpz_desc), c_double_p, c_double_p, C.c_int64, c_double_p, C.c_int32, c_double_p,
                             c_int32_p]),
     "gpz_inv_logdet": (C.c_int, [c_double_p, C.c_int32, C.c_int32, c_double_p, c_double_p, c_int32_p]),

@@ -978,6 +978,41 @@ class Predictor:
         if draws and self._flags & GPZ_PREDICT_FORCE_TILES:
             raise ValueError(f"{what} with Psi needs the fused draws route: the predictor was made with force_tiles=True")
 
+    def _check_missing_model(self, what, Psi):
+        """predict_missing_fits (k_predict_missing.hip) for this model and call, before the GPU is touched."""
+        if Psi is not None:
+            raise ValueError(f"{what} with missing=True does not take Psi: rows with both input noise and missing values "
+                             "(predictNoisyMissing) are not on the handle; Predictor.predict takes them")
+        bad = []
+        if self._method[1] == "C":
+            bad.append(f"a diagonal kind (GL, VL, GD, VD), not {self._method}")
+        if self._d > 20:
+            bad.append(f"d <= 20, not d = {self._d}")
+        if self._k > 8:
+            bad.append(f"k <= 8, not k = {self._k}")
+        if self._m > 256:
+            bad.append(f"m <= 256, not m = {self._m}")
+        if bad:
+            raise ValueError(f"{what} with missing=True needs a model inside predict_missing_fits: " + "; ".join(bad) +
+                             " (Predictor.predict takes rows with missing values for every shape)")
+        if self._priors.shape != (self._m,):
+            raise ValueError(f"the priors of the set must be {self._m} values, got {self._priors.size}")
+
+    def _nan_groups_dev(self, X):
+        """The rows of X (n x d, on the device) grouped by NaN pattern (predict.m:45-57) with torch on X's device: a list of
+        (code, index tensor) with bit c of code set where dimension c is missing, in ascending code order; the index tensor lists
+        the group's rows in their order in X, and is None when all rows share one pattern.  Only the distinct codes and the group
+        sizes come to the host."""
+        import torch
+        bits = 2 ** torch.arange(self._d, device=X.device, dtype=torch.int64)
+        code = (torch.isnan(X).to(torch.int64) * bits).sum(dim=1)
+        codes, inv = torch.unique(code, return_inverse=True)
+        if codes.numel() == 1:
+            return [(int(codes[0]), None)]
+        order = torch.argsort(inv, stable=True)
+        bounds = [0] + torch.cumsum(torch.bincount(inv, minlength=codes.numel()), 0).tolist()
+        return [(c, order[bounds[g]:bounds[g + 1]]) for g, c in enumerate(codes.tolist())]
+
     def _check_dev_psi(self, Psi, n, what):
         """Psi of a *_dev call by type, dtype and shape ((n, d), (n, 1) or (n,)); nothing here touches a GPU.  Returns it as n x 1 or n x d."""
         import torch
@@ -1066,7 +1101,7 @@ class Predictor:
         P = Psi.expand(n, self._d)                                       # a view: never a copy
         return P.data_ptr(), 1 if P.dtype == torch.float32 else 0, P.stride(0), P.stride(1)
 
-    def predict_dev(self, X, selection=None, return_phi=False, Psi=None):
+    def predict_dev(self, X, selection=None, return_phi=False, Psi=None, missing=False):
         """``predict`` for a catalogue that is on the GPU already (gpz_predictor_run_dev): X is a float64 or float32 torch tensor of
         shape (n, d) on cuda:<device> with any strides (row-major as torch makes it, a transposed or sliced view: it is read as it lies,
         never copied), ``selection`` a bool tensor there.  Returns mu, sigma, nu, beta_i, gamma [, PHI] as float64 tensors of shape
@@ -1079,11 +1114,20 @@ class Predictor:
         tensors are then ``predict(X, Psi=Psi)``'s, gamma no longer zero, computed on the handle's tiles by k_predict_noisy_small; a
         row's results do not depend on the tile size or the row order.  It needs a model inside predict_noisy_fits (a diagonal kind,
         d <= 20, k <= 8, m <= 256) and does not return PHI; an element of Psi that is NaN, infinite or negative is refused (GpzError).
+        ``missing=True`` (gpz_predictor_run_missing_dev): rows with NaN are taken instead of refused.  The rows are grouped by NaN
+        pattern with torch on the device; complete rows get exactly what they get without the keyword, every other group
+        predictMissing (predictDiag.m:127-209) on the handle's tiles with the priors of the set (1 / m without any), gamma > 0 there.
+        It needs a model inside predict_missing_fits (a diagonal kind, d <= 20, k <= 8, m <= 256), takes neither Psi nor return_phi,
+        and a row's results do not depend on the tile size, the row order or the other rows of the call.
         Type, dtype and shape are checked first, the device last, all before the GPU is touched."""
         import torch
         self._check_open()
         k, m = self._k, self._m
         X = self._check_dev_rows(X, selection, "predict")
+        if missing:
+            self._check_missing_model("predict_dev", Psi)
+            if return_phi:
+                raise ValueError("return_phi=True is not available with missing=True: Predictor.predict returns PHI for such rows")
         if Psi is not None:
             Psi = self._check_dev_psi(Psi, X.shape[0], "predict")
             if return_phi:
@@ -1101,7 +1145,22 @@ class Predictor:
         if n:
             muX, sdX, muY = self._norm_vectors()
             h = self._handle()
-            if Psi is None:
+            if missing:
+                full, stream = (1 << self._d) - 1, torch.cuda.current_stream(X.device).cuda_stream
+                for code, idx in self._nan_groups_dev(X):
+                    Xg = X if idx is None else X[idx]
+                    og = out if idx is None else [torch.empty((k, Xg.shape[0]), dtype=torch.float64, device=X.device).T for _ in range(5)]
+                    if code == 0:
+                        _lib.check(self._lib.gpz_predictor_run_dev(h, *self._x_args(Xg), _lib.dptr(muX), _lib.dptr(sdX), _lib.dptr(muY),
+                                                                   *(t.data_ptr() for t in og), None, stream))
+                    else:
+                        _lib.check(self._lib.gpz_predictor_run_missing_dev(h, *self._x_args(Xg), _lib.dptr(muX), _lib.dptr(sdX),
+                                                                           _lib.dptr(muY), _lib.dptr(self._priors), full & ~code,
+                                                                           *(t.data_ptr() for t in og), stream))
+                    if idx is not None:
+                        for t, g in zip(out, og):
+                            t[idx] = g
+            elif Psi is None:
                 _lib.check(self._lib.gpz_predictor_run_dev(h, *self._x_args(X), _lib.dptr(muX), _lib.dptr(sdX), _lib.dptr(muY),
                                                            *(t.data_ptr() for t in out), None if PHI is None else PHI.data_ptr(),
                                                            torch.cuda.current_stream(X.device).cuda_stream))
@@ -1113,17 +1172,21 @@ class Predictor:
                                                                  torch.cuda.current_stream(X.device).cuda_stream))
         return tuple(out) + (PHI,) if return_phi else tuple(out)
 
-    def draws_dev(self, X, n_draws, seed=0, Z=None, selection=None, Psi=None):
+    def draws_dev(self, X, n_draws, seed=0, Z=None, selection=None, Psi=None, missing=False):
         """``draws`` for a catalogue on the GPU (gpz_predictor_draws_dev): X and ``selection`` as for ``predict_dev``, ``n_draws``,
         ``seed`` and ``Z`` (a host array: it is m x n_draws x k) as for ``draws``.  Returns a float64 tensor of shape (n_draws, n, k) on
         the device, a view of the column-major n x k x n_draws buffer, with the bits of ``draws`` for the same rows.  Any statistic of
         the draws is then a torch reduction over it; nothing comes to the host unless asked.  ``Psi`` as for ``predict_dev``
-        (gpz_predictor_draws_noisy_dev): the draws of ``predict(X, Psi=Psi)``'s mu, with the bits of ``draws(X, ..., Psi=Psi)``."""
+        (gpz_predictor_draws_noisy_dev): the draws of ``predict(X, Psi=Psi)``'s mu, with the bits of ``draws(X, ..., Psi=Psi)``.
+        ``missing=True`` as for ``predict_dev`` (gpz_predictor_draws_missing_dev): for a row with missing values draws[s] is
+        PHI_missing w_s + muY, the mu of predictMissing under weight draw s; one weight draw serves all rows of all groups."""
         import torch
         self._check_open()
         k = self._k
         X = self._check_dev_rows(X, selection, "draws")
         n_draws, z = self._check_draw_args(n_draws, seed, Z, 1)
+        if missing:
+            self._check_missing_model("draws_dev", Psi)
         if Psi is not None:
             Psi = self._check_dev_psi(Psi, X.shape[0], "draws")
             self._check_noisy_model("draws_dev", draws=True)
@@ -1138,7 +1201,21 @@ class Predictor:
         if n:
             muX, sdX, muY = self._norm_vectors()
             h = self._handle()
-            if Psi is None:
+            if missing:
+                full, stream = (1 << self._d) - 1, torch.cuda.current_stream(X.device).cuda_stream
+                for code, idx in self._nan_groups_dev(X):
+                    Xg = X if idx is None else X[idx]
+                    Fg = F if idx is None else torch.empty((n_draws, k, Xg.shape[0]), dtype=torch.float64, device=X.device)
+                    if code == 0:
+                        _lib.check(self._lib.gpz_predictor_draws_dev(h, *self._x_args(Xg), _lib.dptr(muX), _lib.dptr(sdX), _lib.dptr(muY),
+                                                                     n_draws, int(seed), _lib.dptr(z), Fg.data_ptr(), stream))
+                    else:
+                        _lib.check(self._lib.gpz_predictor_draws_missing_dev(h, *self._x_args(Xg), _lib.dptr(muX), _lib.dptr(sdX),
+                                                                             _lib.dptr(muY), _lib.dptr(self._priors), full & ~code,
+                                                                             n_draws, int(seed), _lib.dptr(z), Fg.data_ptr(), stream))
+                    if idx is not None:
+                        F[:, :, idx] = Fg
+            elif Psi is None:
                 _lib.check(self._lib.gpz_predictor_draws_dev(h, *self._x_args(X), _lib.dptr(muX), _lib.dptr(sdX), _lib.dptr(muY), n_draws,
                                                              int(seed), _lib.dptr(z), F.data_ptr(),
                                                              torch.cuda.current_stream(X.device).cuda_stream))

@@ -227,6 +227,29 @@ int launch_pred_stage_psi(hipStream_t st, const void *Psi, int f32, long rs, lon
                           double *Psic, long ldx);
 int launch_pred_finish_noisy_dev(hipStream_t st, const double *out, int nt, int k, const double *muY, long ns, long r0, double *mu,
                                  double *sigma, double *nu, double *beta, double *gamma);
+// ---- rows with missing inputs through the streaming predictor (k_predict_missing.hip; gpz_predictor_*_missing_dev) ----------------
+// One group of rows sharing a NaN pattern; obs: bit c set = dimension c observed.  fits: a diagonal kind, an instantiated de <= 20,
+// k <= 8 and ceil16(m) <= 256.  launch_pmd_tables (per pattern and priors): bt [2][mp], NijS [mp][mp] and, with pairs, the records
+// (predict_missing_groups(m) * 64 of predict_missing_rec(d, k) = 1 + 2 d + 3 k doubles) and U (predict_missing_groups(m) * 64 * ceil16(m)
+// doubles in fragment order).  Per tile: launch_pmd_no (No, Pio: nrow rows of mp, rows >= n zero), launch_tgemm, launch_pmd_phi (PHI over
+// No; hd [2k][ldh] = PHI w | PHI v), launch_predict_missing_pairs (part [predict_missing_chunks(m)][3k][ldp] -> out [4k][n] = mu | nu |
+// beta | gamma).  The chunk count is a function of m alone.  The launchers return -1 when a launch failed.
+bool predict_missing_fits(int kind, int de, int m, int k);
+int predict_missing_rec(int d, int k);
+long predict_missing_groups(int m);
+int predict_missing_chunks(int m);
+size_t predict_missing_lds(int m, int d, int k);   // dynamic LDS of k_predict_missing_pairs, bytes
+int launch_pmd_check(hipStream_t st, const void *X, int f32, long ns, int d, long rs, long cs, unsigned obs, unsigned *rec);
+int launch_pmd_tables(hipStream_t st, int m, int mp, int d, int de, int k, unsigned obs, const double *P, const double *G2,
+                      const double *priors, const double *w, const double *v, const double *iS, double *bt, double *NijS, double *U,
+                      double *rec, bool pairs);
+int launch_pmd_no(hipStream_t st, const double *Xc, long ldx, int n, int nrow, int m, int mp, int d, int de, unsigned obs, const double *P,
+                  const double *G2, const double *bt, double *No, double *Pio);
+int launch_pmd_phi(hipStream_t st, double *No, const double *T, int n, int m, int mp, int k, const double *w, const double *v, double *hd,
+                   long ldh);
+int launch_predict_missing_pairs(hipStream_t st, const double *Xc, long ldx, int n, const double *Pio, int ldpio, int m, int d, int k,
+                                 unsigned obs, const double *U, const double *rec, int nchunk, double *part, long ldp, const double *hd,
+                                 long ldh, const double *bvec, double *out);
 // B (rows x ld row-major) <- [iS (m x m column-major) | nw columns of W from column wcol | nv columns of V (nullptr: 0) from vcol | 0]
 void launch_pred_fill_b(hipStream_t st, const double *iS, const double *W, int nw, int wcol, const double *V, int nv, int vcol, int m,
                         int rows, int ld, double *B);

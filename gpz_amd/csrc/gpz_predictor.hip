@@ -31,11 +31,16 @@
 // gpz_predictor_draws_noisy / _draws_noisy_dev the draws kernel behind a PHI block built from X and Psi.  The pair table (which depends on
 // the model only), the Psi slots, the 4k-row outputs and the chunk slab are allocated on the first such call (predictor_noisy_prepare).
 // gpz_predictor_run with Psi keeps the one-shot route above.
+// Rows with missing inputs, one group of a NaN pattern per call, stay on the handle too where predict_missing_fits holds (the same
+// shapes): gpz_predictor_run_missing_dev / _draws_missing_dev run predictMissing on tiles of at most GPZ_PREDICTOR_TILE_MISSING rows
+// (k_predict_missing.hip): No and Pio, PHI through k_tgemm, then the fused pair kernel, or for the draws k_tgemm against W.  The tables
+// of a pattern (NijS, the pair records, U) are kept until the pattern or the priors change; all of it is allocated on the first such call.
 #include <string>
 
 #include "gpz_ctx.h"
 
 #define GPZ_PREDICTOR_TILE_FUSED (1L << 17)   // default rows per tile, fused route: 4096 blocks of 32 rows = 8 rounds of 512 workgroups
+#define GPZ_PREDICTOR_TILE_MISSING (1L << 14) // most rows per tile of a group with missing inputs: No, Pio and T are [tile][mp] each
 
 struct gpz_predictor {
     gpz_desc desc;
@@ -86,6 +91,16 @@ struct gpz_predictor {
     double *Psic[2] = {}, *nout[2] = {}, *npart = nullptr;   // Psi in the layout of Xc; [4k][tile_pad]; [nchunks][5k][tile_pad]
     double *sd2_d = nullptr;       // sdX ** 2 of the device entries
     double *hpsi[2] = {};          // pinned, gpz_predictor_draws_noisy only
+    // ---- rows with missing inputs on the handle (gpz_predictor_*_missing_dev): nothing of this exists before the first of their calls
+    bool miss_used = false;
+    int64_t mtile = 0;             // rows per tile of a group: min(tile_rows, GPZ_PREDICTOR_TILE_MISSING)
+    int mchunks = 0;               // predict_missing_chunks of the model
+    double *mNo = nullptr, *mPio = nullptr, *mT = nullptr;   // [rup(mtile, 1024)][mp]: No (then PHI), Pio, T = Pio NijS
+    double *mbt = nullptr, *mNij = nullptr, *mpri = nullptr, *mhd = nullptr;   // [2][mp]; [mp][mp]; the priors; [2k][rup(mtile, 1024)]
+    double *mU = nullptr, *mrec = nullptr, *mpart = nullptr, *mout = nullptr;  // the pair tables, chunk slab and [4k] outputs (not for draws)
+    bool mtab_valid = false, mtab_pairs = false, mtab_uniform = false;         // the tables hold (mtab_obs, mtab_pri); U and records too
+    unsigned mtab_obs = 0;
+    std::vector<double> mtab_pri;
 };
 
 namespace gpzi {
@@ -756,7 +771,8 @@ static int predictor_dev_psi_args(const char *who, const DevRows &psi, const dou
 // everything queued on the caller's stream, and k_pred_check_dev over all rows with its verdict.  nan_text: the host entry's refusal.
 static int predictor_dev_begin(gpz_predictor *p, const char *who, const DevRows &x, const double *muX, const double *sdX, const double *muY,
                                const int *lab, int G, const double *wt, void *stream, const char *nan_text, const double **muX_d,
-                               const double **sdX_d, const double **muY_d, const DevRows *psi = nullptr, const double *sd2 = nullptr) {
+                               const double **sdX_d, const double **muY_d, const DevRows *psi = nullptr, const double *sd2 = nullptr,
+                               const unsigned *pattern = nullptr) {
     const size_t d = p->d, k = p->k;
     hipStream_t st = p->s_cmp;
     if (!p->par_d)
@@ -775,7 +791,9 @@ static int predictor_dev_begin(gpz_predictor *p, const char *who, const DevRows 
          (muY && hipMemcpyAsync(p->par_d + 2 * d, muY, k * sizeof(double), hipMemcpyHostToDevice, st) != hipSuccess) ||
          hipMemsetAsync(rec, 0, 4 * sizeof(unsigned), st) != hipSuccess))
         rc = gpz_fail(GPZ_ERR_HIP, "%s: copy failed", who);
-    if (!rc && launch_pred_check_dev(st, x.X, x.f32(), x.ns, p->d, x.rs, x.cs, lab, G, wt, rec))
+    // pattern (the entries for one group of rows with missing inputs): word 0 says that a row does not have exactly that NaN pattern
+    if (!rc && (pattern ? launch_pmd_check(st, x.X, x.f32(), x.ns, p->d, x.rs, x.cs, *pattern, rec)
+                        : launch_pred_check_dev(st, x.X, x.f32(), x.ns, p->d, x.rs, x.cs, lab, G, wt, rec)))
         rc = gpz_fail(GPZ_ERR_HIP, "%s: k_pred_check_dev launch failed", who);
     if (!rc && psi &&   // (predictor_psi_slots has run: sd2_d exists)
         ((sd2 && hipMemcpyAsync(p->sd2_d, sd2, d * sizeof(double), hipMemcpyHostToDevice, st) != hipSuccess) ||
@@ -787,6 +805,7 @@ static int predictor_dev_begin(gpz_predictor *p, const char *who, const DevRows 
     if (rc) return rc;
     if (verdict[1]) return gpz_fail(GPZ_ERR_ARG, "%s: a label is outside [-1, %d)", who, G);
     if (verdict[2]) return gpz_fail(GPZ_ERR_ARG, "%s: a weight is negative or not finite", who);
+    if (verdict[0] && pattern) return gpz_fail(GPZ_ERR_ARG, "%s: %s", who, nan_text);
     if (verdict[0]) return gpz_fail(GPZ_ERR_UNSUPPORTED, "%s: %s", who, nan_text);
     if (verdict[3]) return gpz_fail(GPZ_ERR_ARG, "%s: Psi has an element that is NaN, infinite or negative", who);
     *muX_d = muX ? p->par_d : nullptr;
@@ -875,6 +894,83 @@ static int predictor_run_stack_dev(gpz_predictor *p, const DevRows &x, const dou
         });
     if (!rc) rc = predictor_stack_result(p, who, c, res);
     return predictor_dev_sync(p, who, rc);
+}
+
+// ---- rows with missing inputs on the handle -----------------------------------------------------------------------------------------
+static int predictor_missing_check(const char *who, const gpz_predictor *p, uint32_t obs) {
+    if (!predict_missing_fits(p->kind, p->de, p->m, p->k))
+        return gpz_fail(GPZ_ERR_UNSUPPORTED,
+                        "%s: missing inputs on the handle need predict_missing_fits: a diagonal kind (GL, VL, GD, VD), d <= 20, k <= 8 and "
+                        "ceil16(m) <= 256 (method %.2s, d %d, m %d, k %d); gpz_predict_missing takes every shape",
+                        who, p->desc.method, p->d, p->m, p->k);
+    const uint32_t full = p->d >= 32 ? 0xffffffffu : ((1u << p->d) - 1u);
+    if (obs & ~full) return gpz_fail(GPZ_ERR_ARG, "%s: the mask %#x has a bit at or above d = %d", who, (unsigned)obs, p->d);
+    if (obs == full)
+        return gpz_fail(GPZ_ERR_ARG, "%s: no dimension is missing in the mask (complete rows go to gpz_predictor_run_dev / _draws_dev)", who);
+    return 0;
+}
+
+// What a call for a group needs before its first tile: the tile buffers (on the first call; with pairs the pair tables, the chunk slab
+// and the output slot too) and the tables of (obs, priors), rebuilt where the handle holds another pattern's.  priors: m values or
+// nullptr for 1 / m.
+static int predictor_missing_prepare(gpz_predictor *p, const char *who, uint32_t obs, const double *priors, bool pairs) {
+    const size_t m = p->m, k = p->k, mp = p->mp, nk = rup(p->m, 16);
+    auto &ar = p->ar;
+    hipStream_t st = p->s_cmp;
+    int rc = 0;
+    if (!p->mtile) p->mtile = std::min<int64_t>(p->tile_rows, GPZ_PREDICTOR_TILE_MISSING);
+    const size_t mtp = (size_t)rup(p->mtile, 1024), npad = (size_t)predict_missing_groups(p->m) * 64;
+    p->mchunks = predict_missing_chunks(p->m);
+    if (!p->mNo && (rc = ar.alloc(&p->mNo, mtp * mp))) return rc;
+    if (!p->mPio && (rc = ar.alloc(&p->mPio, mtp * mp))) return rc;
+    if (!p->mT && (rc = ar.alloc(&p->mT, mtp * mp))) return rc;
+    if (!p->mbt && (rc = ar.alloc(&p->mbt, 2 * mp))) return rc;
+    if (!p->mNij && (rc = ar.alloc(&p->mNij, mp * mp))) return rc;
+    if (!p->mpri && (rc = ar.alloc(&p->mpri, m))) return rc;
+    if (!p->mhd && (rc = ar.alloc(&p->mhd, 2 * k * mtp))) return rc;
+    if (pairs) {
+        if (!p->mU && (rc = ar.alloc(&p->mU, npad * nk))) return rc;
+        if (!p->mrec && (rc = ar.alloc(&p->mrec, npad * (size_t)predict_missing_rec(p->d, p->k)))) return rc;
+        if (!p->mpart && (rc = ar.alloc(&p->mpart, (size_t)p->mchunks * 3 * k * mtp))) return rc;
+        if (!p->mout && (rc = ar.alloc(&p->mout, 4 * k * mtp))) return rc;
+    }
+    p->miss_used = true;
+    const bool same_pri = priors ? (!p->mtab_uniform && p->mtab_pri.size() == m && std::equal(priors, priors + m, p->mtab_pri.begin()))
+                                 : p->mtab_uniform;
+    if (p->mtab_valid && p->mtab_obs == obs && same_pri && (p->mtab_pairs || !pairs)) return 0;
+    p->mtab_valid = false;
+    p->mtab_uniform = priors == nullptr;
+    if (priors) {   // the handle's own copy: the upload may still be in flight when the caller has its memory back
+        p->mtab_pri.assign(priors, priors + m);
+        if (hipMemcpyAsync(p->mpri, p->mtab_pri.data(), m * sizeof(double), hipMemcpyHostToDevice, st) != hipSuccess)
+            return gpz_fail(GPZ_ERR_HIP, "%s: copy failed", who);
+    }
+    if (launch_pmd_tables(st, p->m, p->mp, p->d, p->de, p->k, obs, p->pr.P, p->pr.G2, priors ? p->mpri : nullptr, p->w_d,
+                          p->hetero ? p->pr.v : nullptr, p->iS_d, p->mbt, p->mNij, p->mU, p->mrec, pairs))
+        return gpz_fail(GPZ_ERR_HIP, "%s: table kernel launch failed", who);
+    p->mtab_obs = obs;
+    p->mtab_pairs = pairs;
+    p->mtab_valid = true;
+    return 0;
+}
+
+// predictMissing of one tile of nt rows of the group: Xc[s] -> PHI in mNo, mu | ElnS - b in mhd and, with pairs, mout ([4k][nt] = mu | nu |
+// beta | gamma)
+static int predictor_missing_tile(gpz_predictor *p, const char *who, int s, int nt, uint32_t obs, bool pairs) {
+    hipStream_t st = p->s_cmp;
+    const int np = rup(nt, 128);   // the rows of the product: k_tgemm's row tile
+    const long mtp = rup(p->mtile, 1024);
+    const double *v = p->hetero ? p->pr.v : nullptr;
+    if (launch_pmd_no(st, p->Xc[s], p->tile_pad, nt, np, p->m, p->mp, p->d, p->de, obs, p->pr.P, p->pr.G2, p->mbt, p->mNo, p->mPio))
+        return gpz_fail(GPZ_ERR_HIP, "%s: k_pmd_no launch failed", who);
+    launch_tgemm(st, p->mPio, p->mp, p->mNij, p->mp, p->mT, np, p->mp, nullptr, nullptr, p->m, -1);
+    if (hipGetLastError() != hipSuccess) return gpz_fail(GPZ_ERR_HIP, "%s: k_tgemm launch failed", who);
+    if (launch_pmd_phi(st, p->mNo, p->mT, nt, p->m, p->mp, p->k, p->w_d, v, p->mhd, mtp))
+        return gpz_fail(GPZ_ERR_HIP, "%s: k_pmd_phi launch failed", who);
+    if (pairs && launch_predict_missing_pairs(st, p->Xc[s], p->tile_pad, nt, p->mPio, p->mp, p->m, p->d, p->k, obs, p->mU, p->mrec, p->mchunks,
+                                              p->mpart, mtp, p->mhd, mtp, p->pr.b, p->mout))
+        return gpz_fail(GPZ_ERR_HIP, "%s: k_predict_missing_pairs launch failed", who);
+    return 0;
 }
 
 // ---- what the entries share ---------------------------------------------------------------------------------------------------------
@@ -1027,6 +1123,75 @@ static int draws_dev_entry(const char *who, gpz_predictor *p, const DevRows &x, 
         return rc;
     });
 }
+
+static const char *const kMissingPatternText = "the rows of a group must share one NaN pattern, the one of the mask";
+
+// gpz_predictor_run_missing_dev
+static int run_missing_dev_entry(const char *who, gpz_predictor *p, const DevRows &x, const double *muX, const double *sdX, const double *muY,
+                                 const double *priors, uint32_t obs, double *mu_d, double *sigma_d, double *nu_d, double *beta_d,
+                                 double *gamma_d, void *stream) {
+    if (int rc = predictor_check_call(who, p, x.ns)) return rc;
+    if (int rc = predictor_missing_check(who, p, obs)) return rc;
+    if (int rc = predictor_dev_args(who, p, x, muX, sdX)) return rc;
+    if (x.ns == 0) return 0;
+    if (!mu_d || !nu_d || !beta_d) return gpz_fail(GPZ_ERR_ARG, "%s: null argument", who);
+    return predictor_call(p, who, [&] {
+        const double *mx = nullptr, *sx = nullptr, *my = nullptr;
+        const unsigned pat = obs;
+        int rc = predictor_dev_begin(p, who, x, muX, sdX, muY, nullptr, 0, nullptr, stream, kMissingPatternText, &mx, &sx, &my, nullptr,
+                                     nullptr, &pat);
+        if (rc) return rc;   // the outputs are untouched
+        rc = predictor_missing_prepare(p, who, obs, priors, true);
+        if (!rc)
+            rc = predictor_dev_tiles(p, who, x, mx, sx, nullptr, nullptr, p->mtile, [&](int s, int64_t r0, int nt) {
+                if (int rc = predictor_missing_tile(p, who, s, nt, obs, true)) return rc;
+                if (launch_pred_finish_noisy_dev(p->s_cmp, p->mout, nt, p->k, my, x.ns, r0, mu_d, sigma_d, nu_d, beta_d, gamma_d))
+                    return gpz_fail(GPZ_ERR_HIP, "%s: finish kernel launch failed", who);
+                return 0;
+            });
+        rc = predictor_dev_sync(p, who, rc);
+        if (!rc) ++p->runs;
+        return rc;
+    });
+}
+
+// gpz_predictor_draws_missing_dev: F = PHI_missing W + muY (mu is linear in w), PHI of the tile against the handle's W on k_tgemm
+static int draws_missing_dev_entry(const char *who, gpz_predictor *p, const DevRows &x, const double *muX, const double *sdX,
+                                   const double *muY, const double *priors, uint32_t obs, int32_t ndraws, uint64_t seed, const double *Z,
+                                   double *F_d, void *stream) {
+    if (int rc = predictor_check_call(who, p, x.ns)) return rc;
+    if (int rc = predictor_check_ndraws(who, p, ndraws, 1)) return rc;
+    if (int rc = predictor_missing_check(who, p, obs)) return rc;
+    if (int rc = predictor_dev_args(who, p, x, muX, sdX)) return rc;
+    if (x.ns == 0) return 0;
+    if (!F_d) return gpz_fail(GPZ_ERR_ARG, "%s: null argument", who);
+    return predictor_call(p, who, [&] {
+        const double *mx = nullptr, *sx = nullptr, *my = nullptr;
+        const unsigned pat = obs;
+        const int nd = (int)ndraws, ncol = nd * p->k, ldw = rup(ncol, 16);
+        int rc = predictor_dev_begin(p, who, x, muX, sdX, muY, nullptr, 0, nullptr, stream, kMissingPatternText, &mx, &sx, &my, nullptr,
+                                     nullptr, &pat);
+        if (rc) return rc;   // the output is untouched
+        int64_t T = 0;
+        rc = predictor_missing_prepare(p, who, obs, priors, false);
+        if (!rc) rc = predictor_draws_prepare(p, nd, (unsigned long long)seed, Z, false, &T);
+        T = std::min<int64_t>(T, p->mtile);
+        // the product's output tile: the tile route of the draws has one already, the fused route does not
+        if (!rc) rc = predictor_grow(p, &p->Td, &p->t_cap, (size_t)rup(T, 1024) * ldw);
+        const int wrows = p->droute == 0 ? rup(p->m, 16) : p->mp;   // the rows of W (predictor_draws_prepare): K of the product
+        if (!rc)
+            rc = predictor_dev_tiles(p, who, x, mx, sx, nullptr, nullptr, T, [&](int s, int64_t r0, int nt) {
+                if (int rc = predictor_missing_tile(p, who, s, nt, obs, false)) return rc;
+                launch_tgemm(p->s_cmp, p->mNo, p->mp, p->Wd, ldw, p->Td, rup(nt, 128), ldw, nullptr, nullptr, p->m, 0, false, wrows, ldw);
+                launch_transpose_out(p->s_cmp, p->Td, ldw, nt, ncol, p->dout[s]);
+                if (hipGetLastError() != hipSuccess) return gpz_fail(GPZ_ERR_HIP, "%s: kernel launch failed", who);
+                if (launch_draws_finish_dev(p->s_cmp, p->dout[s], nt, p->k, nd, my, x.ns, r0, F_d))
+                    return gpz_fail(GPZ_ERR_HIP, "%s: k_draws_finish_dev launch failed", who);
+                return 0;
+            });
+        return predictor_dev_sync(p, who, rc);
+    });
+}
 }   // namespace gpzi
 
 extern "C" int gpz_predictor_create(const gpz_desc *desc, const double *theta, const double *w, const double *iSigma_w,
@@ -1164,6 +1329,22 @@ extern "C" int gpz_predictor_draws_noisy_dev(gpz_predictor *p, const void *X_d, 
                            ndraws, seed, Z, F_d, stream);
 }
 
+extern "C" int gpz_predictor_run_missing_dev(gpz_predictor *p, const void *X_d, int32_t x_type, int64_t ns, int64_t row_stride,
+                                             int64_t col_stride, const double *muX, const double *sdX, const double *muY,
+                                             const double *priors, uint32_t obs_mask, double *mu_d, double *sigma_d, double *nu_d,
+                                             double *beta_d, double *gamma_d, void *stream) {
+    return run_missing_dev_entry("gpz_predictor_run_missing_dev", p, DevRows{X_d, x_type, ns, row_stride, col_stride}, muX, sdX, muY, priors,
+                                 obs_mask, mu_d, sigma_d, nu_d, beta_d, gamma_d, stream);
+}
+
+extern "C" int gpz_predictor_draws_missing_dev(gpz_predictor *p, const void *X_d, int32_t x_type, int64_t ns, int64_t row_stride,
+                                               int64_t col_stride, const double *muX, const double *sdX, const double *muY,
+                                               const double *priors, uint32_t obs_mask, int32_t ndraws, uint64_t seed, const double *Z,
+                                               double *F_d, void *stream) {
+    return draws_missing_dev_entry("gpz_predictor_draws_missing_dev", p, DevRows{X_d, x_type, ns, row_stride, col_stride}, muX, sdX, muY,
+                                   priors, obs_mask, ndraws, seed, Z, F_d, stream);
+}
+
 extern "C" int gpz_predictor_stack_dev(gpz_predictor *p, const void *X_d, int32_t x_type, int64_t ns, int64_t row_stride,
                                        int64_t col_stride, const double *muX, const double *sdX, int32_t ndraws, uint64_t seed,
                                        const double *Z, const double *edges, int32_t nbins, const int32_t *group_d, int32_t ngroups,
@@ -1216,6 +1397,10 @@ extern "C" int gpz_predictor_route(const gpz_predictor *p, char *buf, int cap) {
     if (p->dev_used) r += "; device entries: k_pred_stage";
     if (p->noisy_ready) {   // after the first call with input noise on the handle
         snprintf(tmp, sizeof tmp, "; noise: k_predict_noisy_small (%d pair chunks)", p->nchunks);
+        r += tmp;
+    }
+    if (p->miss_used) {   // after the first call for a group of rows with missing inputs
+        snprintf(tmp, sizeof tmp, "; missing: k_predict_missing_pairs (%d pair chunks), %lld-row tiles", p->mchunks, (long long)p->mtile);
         r += tmp;
     }
     snprintf(buf, (size_t)cap, "%s", r.c_str());

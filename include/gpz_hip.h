@@ -337,6 +337,33 @@ int gpz_predictor_draws_noisy(gpz_predictor *p, const double *Xs, int64_t ns, co
                               int32_t ndraws, uint64_t seed, const double *Z /* NULL or m x ndraws x k */,
                               double *F /* ns x k x ndraws, column-major */);
 
+/* ---- rows with missing inputs on the predictor handle ------------------------------------------------------------------------------
+ * predictMissing (predictDiag.m:127-209) and the draws for ONE group of rows that share a NaN pattern, on the handle's own tiles,
+ * where predict_missing_fits holds: a diagonal kind (GL, VL, GD, VD), d <= 20, k <= 8 and ceil16(m) <= 256, no Psi.  Any other shape
+ * returns GPZ_ERR_UNSUPPORTED and names the condition; gpz_predict_missing takes every shape.  The entries take what
+ * gpz_predictor_run_dev / _draws_dev take, plus priors (host, m values; NULL: 1 / m each) and obs_mask, the pattern: bit c is set
+ * when dimension c is observed.  A mask with no missing dimension or with a bit at or above d -> GPZ_ERR_ARG; a mask with no observed
+ * dimension is valid.  Before the first tile a scan verifies that every row is NaN exactly where the mask says missing; otherwise
+ * GPZ_ERR_ARG ("the rows of a group must share one NaN pattern"), outputs untouched.  The caller groups the rows (predict.m:45-57).
+ * gpz_predictor_run_missing_dev: mu_d, nu_d, beta_d (required), gamma_d, sigma_d = (nu + beta) + gamma (optional).
+ * gpz_predictor_draws_missing_dev: F(i, o, s) = PHI_missing(i, :) (w(:, o) + R_o z(:, s, o)) + muY[o]; ndraws, seed, Z and the weights
+ * W as gpz_predictor_draws_dev, so draw s is the same weight draw for the rows of every group and for complete rows.
+ * Cost per row: O(m^2) for PHI and 2 ceil16(m) m (m + 1) / 2 flop on the f64 MFMA plus m (m + 1) / 2 exp for the pair sums; the n x pairs
+ * product never reaches memory.  Per pattern (kept until the pattern or the priors change): m (m + 1) / 2 x ceil16(m) doubles of U
+ * (4.5 MB at m = 100, 67 MB at m = 256), the pair records and an mp x mp factor; per handle three [tile][mp] buffers with tile =
+ * min(tile_rows, 16384).  All of it is allocated on the first such call and does not grow with ns or the number of patterns; a
+ * handle that never sees such a call holds what it held.  A row's results have the same bits for any tile size, row order or split
+ * of the rows into calls.  gpz_predictor_route then ends in "; missing: k_predict_missing_pairs (C pair chunks), T-row tiles". */
+int gpz_predictor_run_missing_dev(gpz_predictor *p, const void *X_d, int32_t x_type, int64_t ns, int64_t row_stride, int64_t col_stride,
+                                  const double *muX, const double *sdX, const double *muY /* k or NULL */,
+                                  const double *priors /* m or NULL */, uint32_t obs_mask,
+                                  double *mu_d, double *sigma_d, double *nu_d, double *beta_d, double *gamma_d, void *stream);
+int gpz_predictor_draws_missing_dev(gpz_predictor *p, const void *X_d, int32_t x_type, int64_t ns, int64_t row_stride, int64_t col_stride,
+                                    const double *muX, const double *sdX, const double *muY /* k or NULL */,
+                                    const double *priors /* m or NULL */, uint32_t obs_mask,
+                                    int32_t ndraws, uint64_t seed, const double *Z /* host: NULL or m x ndraws x k */,
+                                    double *F_d /* ns x k x ndraws, column-major */, void *stream);
+
 /* ---- device-resident L-BFGS memory: minFunc's lbfgsAdd.m / lbfgsProd.m (mex/lbfgsAddC.c, mex/lbfgsProdC.c) ----
  * S and Y (p x corrections) live on the device; all vector arguments are device pointers.
  * gpz_lbfgs_add:        y = g - g_old, s = t*d; skipped (added = 0) when y's <= 1e-10        (lbfgsAdd.m:2-4)
