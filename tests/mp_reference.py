@@ -127,7 +127,8 @@ def gradient(theta, *args, h="1e-18", **kw):
 def torch_nlogml(theta, method, m, d, k, hetero, X, Y, Psi=None, omega=None):
     """The objective above on torch.float64 tensors (vectorised over rows of one NaN pattern and over basis functions);
     torch.autograd of it is a second, independent derivation of the gradient of GPz.m:89-234 at sizes mpmath cannot
-    reach.  theta: 1-D float64 tensor with requires_grad; X, Y, Psi, omega: NumPy."""
+    reach.  theta: 1-D float64 tensor with requires_grad; X, Y, Psi, omega: NumPy; omega is n x 1 (one weight per row) or
+    n x k (one per row and output, GPz.m:48)."""
     import math
     import torch
     n = X.shape[0]
@@ -170,9 +171,11 @@ def torch_nlogml(theta, method, m, d, k, hetero, X, Y, Psi=None, omega=None):
         lnphi = -0.5 * quad + 0.5 * torch.logdet(Soo).unsqueeze(0) - 0.5 * torch.logdet(M) - 0.5 * (d - obs.size) * math.log(2.0)
         PHI[rows] = torch.exp(lnphi)
     Yt = torch.as_tensor(Y)
-    om = torch.ones(n, dtype=torch.float64) if omega is None else torch.as_tensor(np.asarray(omega, dtype=np.float64)[:, 0])
+    om_all = torch.ones(n, 1, dtype=torch.float64) if omega is None else torch.as_tensor(np.asarray(omega, dtype=np.float64).reshape(n, -1))
+    assert om_all.shape[1] in (1, k)
     L = torch.zeros((), dtype=torch.float64)
     for q in range(k):
+        om = om_all[:, min(q, om_all.shape[1] - 1)]
         lnb = b[q] + (PHI @ v[:, q] if hetero else 0.0)
         wb = torch.exp(-lnb) * om
         S = PHI.T @ (PHI * wb[:, None]) + torch.diag(torch.exp(lnA[:, q]))
@@ -182,5 +185,5 @@ def torch_nlogml(theta, method, m, d, k, hetero, X, Y, Psi=None, omega=None):
             - 0.5 * torch.logdet(S) - 0.5 * (lnb * om).sum()
         if hetero:
             L = L - 0.5 * (v[:, q] ** 2 * torch.exp(lnT[:, q])).sum() + 0.5 * lnT[:, q].sum() - 0.5 * m * k * math.log(2 * math.pi)
-    L = L - 0.5 * math.log(2 * math.pi) * om.sum()
+    L = L - 0.5 * math.log(2 * math.pi) * om_all.sum()                           # GPz.m:110: every entry of omega, as given
     return -L / (n * k)

@@ -1,8 +1,11 @@
 """Parity of the HIP path (through the C ABI) with the CPU oracle, on a real MI355X.
 
 Gates: |f - f_ref|/|f_ref| <= 1e-8; max|g - g_ref|/max|g_ref| <= max(1e-8, 50*cond(SIGMA)*2.2e-16)
-with cond reported by the oracle; w, inv(SIGMA), mu, sigma under the same rule; the four statistics to 1e-10;
-NaN-pattern group ids bit-exact.  Full-size cases use size-independent properties (directional finite
+with cond reported by the oracle, over the whole of theta AND (in _check_eval and against the 50-digit reference) over every
+group B of helpers.grad_groups on its own - each parameter block, cut into groups of 32 basis functions - relative to
+max|g_ref[B]| and with max(that tolerance, 10 e_B), e_B being the disagreement of the oracle and torch autograd on B (at most
+1e-8, or the inputs cannot be judged; helpers.assert_grad_groups, tests/test_grad_groups.py); w, inv(SIGMA), mu, sigma under
+the whole-vector rule; the four statistics to 1e-10; NaN-pattern group ids bit-exact.  Full-size cases use size-independent properties (directional finite
 differences with the reference's derivative-check step, method-nesting identities).
 """
 import ctypes as C
@@ -15,7 +18,7 @@ import pytest
 import gpz_amd
 from gpz_amd import _lib
 from oracle import gpz_oracle as O
-from helpers import golden_names, grad_tol, load_golden, load_predict_golden, make_problem, rel
+from helpers import assert_grad_groups, golden_names, grad_tol, load_golden, load_predict_golden, make_problem, recondition_gamma, rel
 
 pytestmark = pytest.mark.gpu
 METHODS = ["GL", "VL", "GD", "VD", "GC", "VC"]
@@ -33,7 +36,9 @@ def phi_tol(model, theta):
     return max(1e-12, 200.0 * c * 2.2e-16)
 
 
-def _check_eval(model, theta, X, Y, omega=None, training=None, validation=None):
+def _check_eval(model, theta, X, Y, omega=None, training=None, validation=None, groups=True):
+    """groups=False: a theta whose two CPU references disagree on some group by more than 1e-8 (an ill-conditioned Gamma): the
+    caller runs the gate per group on a judgeable theta of the same shape instead."""
     ref = O.GPz(theta, model, X, Y, None, omega, training, validation)
     ctx = gpz_amd.GPzContext(model, X, Y, None, omega, training, validation)
     try:
@@ -42,6 +47,8 @@ def _check_eval(model, theta, X, Y, omega=None, training=None, validation=None):
         assert ctx.info == 0
         assert abs(f - ref.nlogML) <= FTOL * abs(ref.nlogML)
         assert rel(g, ref.grad) <= tol, (rel(g, ref.grad), tol)
+        if groups:
+            assert_grad_groups(g, model, theta, X, Y, None, omega, training, ref.cond, ref.grad)
         for key, val in ref.stats.items():
             assert abs(ctx.stats[key] - val) <= 1e-10 * max(1.0, abs(val)), key
         r4 = O.GPz(theta, model, X, Y, None, omega, training, validation, nargout=4)
@@ -171,7 +178,13 @@ def test_edge_shapes(shape):
     n, d, m, k = shape
     for method in ("VD", "VC"):
         model, theta, X, Y, _, rng = make_problem(n, d, m, k, method, True, seed=17 * n + d)
-        _check_eval(model, theta, X, Y)
+        # VC at d = 12 and d = 20: Gamma_j as drawn has cond(Gamma_j'Gamma_j) ~ 1e8, and the oracle and torch autograd disagree on dG
+        # by 8e-8 and 2e-3 of its size - no gate per group can be applied to that theta, so it gets the whole-vector gate as
+        # before and the groups are gated on the same problem with Gamma redrawn (the references then agree to 1e-11)
+        unfit = method == "VC" and d in (12, 20)
+        _check_eval(model, theta, X, Y, groups=not unfit)
+        if unfit:
+            _check_eval(model, recondition_gamma(model, theta.copy(), rng), X, Y)
 
 
 def test_defaults_and_masks_equivalence():
@@ -1069,6 +1082,7 @@ def test_hip_path_against_the_50_digit_reference(method, psi, nanfrac):
     cond = O.GPz(theta, model, X, Y, Psi, om).cond
     assert abs(f - f_mp) <= 1e-12 * abs(f_mp)
     assert np.max(np.abs(g - g_mp)) <= max(1e-11, 50 * cond * 2.2e-16) * np.max(np.abs(g_mp))
+    assert_grad_groups(g, model, theta, X, Y, Psi, om, None, cond, g_mp, floor=1e-11)      # ... and group by group
 
 
 # ---- all GPUs behind one synchronous C call (gpz_mgpu_*, gpz_mgpu.hip) and RCCL inside the library ---------------

@@ -1,9 +1,12 @@
 """Developer check on a GPU box: component-by-component comparison with the oracle (verbose)."""
 import sys, os, time
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np
 import gpz_amd
 from oracle import gpz_oracle as O
+from helpers import grad_groups      # the partition of theta the test-suite gates by (tests/helpers.py)
 
 rng = np.random.default_rng(1)
 
@@ -63,13 +66,8 @@ for method in ("GL", "VL", "GD", "VD", "GC", "VC"):
                   f"g {rel(g, ref.grad):.2e} stats {es:.1e} w {rel(w, rs.w):.2e} iS {rel(iS, rs.iSigma_w):.2e} "
                   f"part {rel(part, rs.nlogML):.2e} info={ctx.info} cond={ref.cond:.1e}")
             if rel(g, ref.grad) > 1e-6:
-                # per-block gradient error
-                md = m * model.d; gd = model.g_dim
-                blocks = {"dP": (0, md), "dG": (md, md + gd), "dlnA": (md + gd, md + gd + m * k), "db": (md + gd + m * k, md + gd + m * k + k)}
-                if het:
-                    o = md + gd + m * k + k
-                    blocks["dv"] = (o, o + m * k); blocks["dlnT"] = (o + m * k, o + 2 * m * k)
-                print("     ", {b: f"{rel(g[a:c], ref.grad[a:c]):.1e}" for b, (a, c) in blocks.items()})
+                # error per group of the gradient, relative to the group's own largest entry
+                print("     ", {b: f"{rel(g[idx], ref.grad[idx]):.1e}" for b, idx in grad_groups(model).items()})
             ctx.close()
 
 print("== predict")
