@@ -892,13 +892,36 @@ class Predictor:
         to the rows, labels and weights alike) as in ``predict``.  Complete, noise-free rows only.  Every field but ``edges`` is a plain
         sum over rows, so the results of several calls add: a catalogue read in chunks is a loop over ``stack`` and a ``+=`` per field.
         The same call on the same handle returns the same bits every time; another ``tile_rows`` may change the last ones."""
+        return self._stack_host(X, None, edges, n_draws, seed, Z, groups, n_groups, weights, selection)
+
+    def stack_noisy(self, X, Psi, edges, n_draws=0, seed=0, Z=None, groups=None, n_groups=None, weights=None, selection=None):
+        """``stack`` for rows with input noise (gpz_predictor_stack_noisy): ``Psi`` is the rows' input-noise variances as a host array of
+        shape (n, d), (n, 1) or (n,) (through ``fixPsi``; a d x d x n cube is refused), everything else as for ``stack``.  Column 0 uses
+        ``predict_dev(X, Psi=Psi)``'s mu and sigma = (nu + beta_i) + gamma.  Column 1 + s uses ``draws(X, ..., Psi=Psi)``'s draw s and
+        the width beta_i + max(gamma_s, 0), where gamma_s is predictNoisy's gamma under the weights of draw s, the variance of
+        PHI(x) w_s over the input noise (``draws_dev(..., Psi=Psi, return_gamma=True)`` returns it).  Needs a model inside
+        predict_noisy_fits (a diagonal kind, d <= 20, k <= 8, m <= 256) on the fused route, else ValueError.  ``selection`` applies to
+        rows, Psi, labels and weights alike.  Returns a StackResult with the bits of ``stack_noisy_dev`` on the same handle and rows."""
+        if Psi is None:
+            raise ValueError("stack_noisy needs Psi: noise-free rows go to Predictor.stack")
+        return self._stack_host(X, Psi, edges, n_draws, seed, Z, groups, n_groups, weights, selection)
+
+    def _stack_host(self, X, Psi, edges, n_draws, seed, Z, groups, n_groups, weights, selection):
+        """``stack`` (Psi None) and ``stack_noisy``: the checks, all before the library is loaded, then the entry."""
         self._check_open()
         n_all = np.asarray(X).shape[0] if np.ndim(X) else 0             # rows before the selection: labels and weights go with them
-        X, _ = self._check_inputs(X, None, selection)
+        if Psi is not None and np.ndim(Psi) == 3:
+            raise ValueError("stack_noisy takes Psi as n x d, n x 1 or n variances: a d x d x n cube is for the covariance kinds, "
+                             "which are outside predict_noisy_fits")
+        X, psi = self._check_inputs(X, Psi, selection)
         sel = None if selection is None else np.asarray(selection).astype(bool)
         nbad = int(np.isnan(X).any(axis=1).sum()) if X.size else 0
         if nbad:
             raise ValueError(f"X has {nbad} rows with missing values (NaN): stacks are for complete rows")
+        if psi is not None:
+            self._check_noisy_model("stack_noisy", draws=True)
+            if not np.all(np.isfinite(psi)) or np.any(psi < 0):
+                raise ValueError("Psi must be finite and >= 0")
         e, B = self._check_edges(edges)
         n_draws, z = self._check_draw_args(n_draws, seed, Z, 0)
         ns = X.shape[0]
@@ -940,11 +963,17 @@ class Predictor:
             Xn = self._normalised(X)
             muY = self._norm_vectors()[2]
             es = self._stack_edges(e, muY)
-            h = self._handle()
-            _lib.check(self._lib.gpz_predictor_stack(h, _lib.dptr(Xn), ns, n_draws, int(seed), _lib.dptr(z), _lib.dptr(es), B,
-                                                     None if lab is None else lab.ctypes.data_as(_lib.c_int32_p), G, _lib.dptr(wt),
-                                                     _lib.dptr(hist), _lib.dptr(sum_w), _lib.dptr(sum_mu), _lib.dptr(sum_mu2),
-                                                     _lib.dptr(muY)))          # predict.m:73 inside the sums
+            tail = (n_draws, int(seed), _lib.dptr(z), _lib.dptr(es), B, None if lab is None else lab.ctypes.data_as(_lib.c_int32_p), G,
+                    _lib.dptr(wt), _lib.dptr(hist), _lib.dptr(sum_w), _lib.dptr(sum_mu), _lib.dptr(sum_mu2),
+                    _lib.dptr(muY))                                      # predict.m:73 inside the sums
+            if psi is None:
+                h = self._handle()
+                _lib.check(self._lib.gpz_predictor_stack(h, _lib.dptr(Xn), ns, *tail))
+            else:
+                from .host import fixPsi
+                psin = np.asfortranarray(fixPsi(psi, ns, self.model.sdX, self.model.method))   # predict.m:43: n x d for a diagonal kind
+                h = self._handle()
+                _lib.check(self._lib.gpz_predictor_stack_noisy(h, _lib.dptr(Xn), ns, _lib.dptr(psin), *tail))
         return StackResult(hist, sum_w, sum_mu, sum_mu2, e.copy())
 
     # ---- device-resident entries: the catalogue is a torch tensor on the handle's GPU, per-row results stay there -------------------
@@ -1172,19 +1201,24 @@ class Predictor:
                                                                  torch.cuda.current_stream(X.device).cuda_stream))
         return tuple(out) + (PHI,) if return_phi else tuple(out)
 
-    def draws_dev(self, X, n_draws, seed=0, Z=None, selection=None, Psi=None, missing=False):
+    def draws_dev(self, X, n_draws, seed=0, Z=None, selection=None, Psi=None, missing=False, return_gamma=False):
         """``draws`` for a catalogue on the GPU (gpz_predictor_draws_dev): X and ``selection`` as for ``predict_dev``, ``n_draws``,
         ``seed`` and ``Z`` (a host array: it is m x n_draws x k) as for ``draws``.  Returns a float64 tensor of shape (n_draws, n, k) on
         the device, a view of the column-major n x k x n_draws buffer, with the bits of ``draws`` for the same rows.  Any statistic of
         the draws is then a torch reduction over it; nothing comes to the host unless asked.  ``Psi`` as for ``predict_dev``
         (gpz_predictor_draws_noisy_dev): the draws of ``predict(X, Psi=Psi)``'s mu, with the bits of ``draws(X, ..., Psi=Psi)``.
         ``missing=True`` as for ``predict_dev`` (gpz_predictor_draws_missing_dev): for a row with missing values draws[s] is
-        PHI_missing w_s + muY, the mu of predictMissing under weight draw s; one weight draw serves all rows of all groups."""
+        PHI_missing w_s + muY, the mu of predictMissing under weight draw s; one weight draw serves all rows of all groups.
+        ``return_gamma=True`` (with ``Psi``; gpz_predictor_draws_gamma_noisy_dev) returns ``(F, Gam)``: Gam is a float64 tensor of shape
+        (n_draws, n, k), predictNoisy's gamma under the weights of draw s - the variance of PHI(x) w_s over the input noise, not
+        clamped at 0.  A y-draw of row i under draw s has variance beta_i + Gam[s, i].  Without ``Psi`` it is a ValueError."""
         import torch
         self._check_open()
         k = self._k
         X = self._check_dev_rows(X, selection, "draws")
         n_draws, z = self._check_draw_args(n_draws, seed, Z, 1)
+        if return_gamma and (Psi is None or missing):
+            raise ValueError("return_gamma=True needs Psi (and not missing=True): gamma under a draw is the variance over the input noise")
         if missing:
             self._check_missing_model("draws_dev", Psi)
         if Psi is not None:
@@ -1198,6 +1232,7 @@ class Predictor:
         n = X.shape[0]
         # referenced by this frame for the whole (host-synchronous) call: no record_stream needed
         F = torch.empty((n_draws, k, n), dtype=torch.float64, device=X.device)   # column-major n x k x n_draws, as the C entry writes it
+        Gam = torch.empty((n_draws, k, n), dtype=torch.float64, device=X.device) if return_gamma else None
         if n:
             muX, sdX, muY = self._norm_vectors()
             h = self._handle()
@@ -1219,12 +1254,20 @@ class Predictor:
                 _lib.check(self._lib.gpz_predictor_draws_dev(h, *self._x_args(X), _lib.dptr(muX), _lib.dptr(sdX), _lib.dptr(muY), n_draws,
                                                              int(seed), _lib.dptr(z), F.data_ptr(),
                                                              torch.cuda.current_stream(X.device).cuda_stream))
-            else:
+            elif not return_gamma:
                 sd2 = np.ascontiguousarray(sdX ** 2)                     # fixPsi.m: Psi ./ sdX.^2
                 _lib.check(self._lib.gpz_predictor_draws_noisy_dev(h, *self._x_args(X), *self._psi_args(Psi, n), _lib.dptr(muX),
                                                                    _lib.dptr(sdX), _lib.dptr(sd2), _lib.dptr(muY), n_draws, int(seed),
                                                                    _lib.dptr(z), F.data_ptr(),
                                                                    torch.cuda.current_stream(X.device).cuda_stream))
+            else:
+                sd2 = np.ascontiguousarray(sdX ** 2)
+                _lib.check(self._lib.gpz_predictor_draws_gamma_noisy_dev(h, *self._x_args(X), *self._psi_args(Psi, n), _lib.dptr(muX),
+                                                                         _lib.dptr(sdX), _lib.dptr(sd2), _lib.dptr(muY), n_draws,
+                                                                         int(seed), _lib.dptr(z), F.data_ptr(), Gam.data_ptr(),
+                                                                         torch.cuda.current_stream(X.device).cuda_stream))
+        if return_gamma:
+            return F.permute(0, 2, 1), Gam.permute(0, 2, 1)
         return F.permute(0, 2, 1)                                        # (n_draws, n, k) view
 
     def stack_dev(self, X, edges, n_draws=0, seed=0, Z=None, groups=None, n_groups=None, weights=None, selection=None):
@@ -1233,10 +1276,26 @@ class Predictor:
         before the selection; everything else as for ``stack``.  Returns the same NumPy StackResult, with the bits of ``stack`` on the
         same handle and rows.  ``n_groups`` defaults to ``groups.max() + 1`` (one scalar read back).  Labels outside [-1, n_groups)
         and negative or non-finite weights are found on the device and refused with a GpzError, as rows with NaN are."""
+        return self._stack_dev(X, None, edges, n_draws, seed, Z, groups, n_groups, weights, selection)
+
+    def stack_noisy_dev(self, X, Psi, edges, n_draws=0, seed=0, Z=None, groups=None, n_groups=None, weights=None, selection=None):
+        """``stack_noisy`` for a catalogue on the GPU (gpz_predictor_stack_noisy_dev): X, ``groups``, ``weights`` and ``selection`` as
+        for ``stack_dev``, ``Psi`` as for ``predict_dev`` (float64 or float32, (n, d), (n, 1) or (n,), any strides).  Returns the same
+        NumPy StackResult, with the bits of ``stack_noisy`` on the same handle and rows.  An element of Psi that is NaN, infinite or
+        negative is found on the device and refused with a GpzError, as bad labels, weights and rows with NaN are."""
+        if Psi is None:
+            raise ValueError("stack_noisy_dev needs Psi: noise-free rows go to Predictor.stack_dev")
+        return self._stack_dev(X, Psi, edges, n_draws, seed, Z, groups, n_groups, weights, selection)
+
+    def _stack_dev(self, X, Psi, edges, n_draws, seed, Z, groups, n_groups, weights, selection):
+        """``stack_dev`` (Psi None) and ``stack_noisy_dev``: the checks, the device last, all before the GPU is touched; then the entry."""
         import torch
         self._check_open()
-        X = self._check_dev_rows(X, selection, "stack")
+        X = self._check_dev_rows(X, selection, "stack" if Psi is None else "stack_noisy")
         n_all = X.shape[0]
+        if Psi is not None:
+            Psi = self._check_dev_psi(Psi, n_all, "stack_noisy")
+            self._check_noisy_model("stack_noisy_dev", draws=True)
         e, B = self._check_edges(edges)
         n_draws, z = self._check_draw_args(n_draws, seed, Z, 0)
         if groups is not None:
@@ -1251,10 +1310,12 @@ class Predictor:
             raise ValueError(f"n_groups must be a positive integer, got {n_groups!r}")
         if n_groups is not None and int(n_groups) * B > GPZ_STACK_MAX_GROUP_BINS:
             raise ValueError(f"n_groups * bins = {int(n_groups) * B} is over the limit of {GPZ_STACK_MAX_GROUP_BINS} per call")
-        self._check_dev_device(X=X, selection=selection, groups=groups, weights=weights)
+        self._check_dev_device(X=X, selection=selection, groups=groups, weights=weights, Psi=Psi)
         lab = wt = None
         if selection is not None:
             X = X[selection]
+            if Psi is not None:
+                Psi = Psi[selection]
         if groups is not None:
             lab = (groups if selection is None else groups[selection]).to(torch.int32).contiguous()
         if weights is not None:
@@ -1271,11 +1332,15 @@ class Predictor:
             es = self._stack_edges(e, muY)
             h = self._handle()
             # X, lab and wt are referenced by this frame for the whole (host-synchronous) call: no record_stream needed
-            _lib.check(self._lib.gpz_predictor_stack_dev(h, *self._x_args(X), _lib.dptr(muX), _lib.dptr(sdX), n_draws, int(seed),
-                                                         _lib.dptr(z), _lib.dptr(es), B, None if lab is None else lab.data_ptr(), G,
-                                                         None if wt is None else wt.data_ptr(), _lib.dptr(hist), _lib.dptr(sum_w),
-                                                         _lib.dptr(sum_mu), _lib.dptr(sum_mu2), _lib.dptr(muY),
-                                                         torch.cuda.current_stream(X.device).cuda_stream))
+            tail = (n_draws, int(seed), _lib.dptr(z), _lib.dptr(es), B, None if lab is None else lab.data_ptr(), G,
+                    None if wt is None else wt.data_ptr(), _lib.dptr(hist), _lib.dptr(sum_w), _lib.dptr(sum_mu), _lib.dptr(sum_mu2),
+                    _lib.dptr(muY), torch.cuda.current_stream(X.device).cuda_stream)
+            if Psi is None:
+                _lib.check(self._lib.gpz_predictor_stack_dev(h, *self._x_args(X), _lib.dptr(muX), _lib.dptr(sdX), *tail))
+            else:
+                sd2 = np.ascontiguousarray(sdX ** 2)                     # fixPsi.m: Psi ./ sdX.^2
+                _lib.check(self._lib.gpz_predictor_stack_noisy_dev(h, *self._x_args(X), *self._psi_args(Psi, n), _lib.dptr(muX),
+                                                                   _lib.dptr(sdX), _lib.dptr(sd2), *tail))
         return StackResult(hist, sum_w, sum_mu, sum_mu2, e.copy())
 
 

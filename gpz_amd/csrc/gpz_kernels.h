@@ -227,6 +227,23 @@ int launch_pred_stage_psi(hipStream_t st, const void *Psi, int f32, long rs, lon
                           double *Psic, long ldx);
 int launch_pred_finish_noisy_dev(hipStream_t st, const double *out, int nt, int k, const double *muY, long ns, long r0, double *mu,
                                  double *sigma, double *nu, double *beta, double *gamma);
+// ---- gamma under every weight draw for rows with input noise (k_predict_noisy_gamma.hip; gpz_predictor_stack_noisy*, _draws_gamma_noisy_dev)
+// part [nchunk][ncol][ldp] <- per pair chunk sum_{a >= b} f_ab E[phi_a phi_b](x_i, psi_i) W[a, col] W[b, col] for the n rows of Xc / Psic
+// ([d][ldx]); tab: the handle's pair records (rec doubles apart, [lnZ | c_ab | C_ab] read), W: ceil16(m) x ldw row-major as the draws
+// take it (column o nd + s), nchunk = predict_gamma_chunks(m), the model's shape alone.  finish_dev: gamma_s = sum - mu_s^2 with mu_s =
+// dout [ncol][nt] -> Gam (ns x k x nd column-major, rows r0 ..).  finish_s2: the stack's widths s2 [(1 + nd) k][nt]: row o = (nu + beta) +
+// gamma of nout ([4k][nt]), row (1 + s) k + o = beta + max(gamma_s, 0); nd = 0 reads neither part nor dout.
+// launch_stack_tile_w (k_predict_stack_w.hip): launch_stack_tile with the width^2 of column-output q and row i read from s2[q nt + i] and
+// column 0's mu from row o of out.  All return -1 when a launch failed.
+int predict_gamma_chunks(int m);
+int launch_predict_noisy_gamma(hipStream_t st, int d, const double *Xc, const double *Psic, long ldx, int n, int m, const double *tab,
+                               int rec, const double *W, int ldw, int ncol, int nchunk, double *part, long ldp);
+int launch_gamma_finish_dev(hipStream_t st, const double *part, int nchunk, long ldp, const double *dout, int nt, int k, int nd, long ns,
+                            long r0, double *Gam);
+int launch_gamma_finish_s2(hipStream_t st, const double *part, int nchunk, long ldp, const double *nout, const double *dout, int nt, int k,
+                           int nd, double *s2);
+int launch_stack_tile_w(hipStream_t st, const double *out, const double *s2, const double *dout, const int *lab, const double *wt,
+                        const double *edges, const double *shift, long nt, int k, int nd, int B, int G, int R, double *slab);
 // ---- rows with missing inputs through the streaming predictor (k_predict_missing.hip; gpz_predictor_*_missing_dev) ----------------
 // One group of rows sharing a NaN pattern; obs: bit c set = dimension c observed.  fits: a diagonal kind, an instantiated de <= 20,
 // k <= 8 and ceil16(m) <= 256.  launch_pmd_tables (per pattern and priors): bt [2][mp], NijS [mp][mp] and, with pairs, the records

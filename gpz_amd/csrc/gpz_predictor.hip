@@ -31,6 +31,9 @@
 // gpz_predictor_draws_noisy / _draws_noisy_dev the draws kernel behind a PHI block built from X and Psi.  The pair table (which depends on
 // the model only), the Psi slots, the 4k-row outputs and the chunk slab are allocated on the first such call (predictor_noisy_prepare).
 // gpz_predictor_run with Psi keeps the one-shot route above.
+// gpz_predictor_stack_noisy / _stack_noisy_dev stack such rows: per tile predictNoisy, the draws with Psi, gamma under every draw
+// (k_predict_noisy_gamma.hip, an f64 MFMA product of pair densities and weight products), and k_stack_tile_w with a width per (column,
+// row); gpz_predictor_draws_gamma_noisy_dev returns that gamma beside the draws.  Their buffers are allocated on their first call.
 // Rows with missing inputs, one group of a NaN pattern per call, stay on the handle too where predict_missing_fits holds (the same
 // shapes): gpz_predictor_run_missing_dev / _draws_missing_dev run predictMissing on tiles of at most GPZ_PREDICTOR_TILE_MISSING rows
 // (k_predict_missing.hip): No and Pio, PHI through k_tgemm, then the fused pair kernel, or for the draws k_tgemm against W.  The tables
@@ -91,6 +94,11 @@ struct gpz_predictor {
     double *Psic[2] = {}, *nout[2] = {}, *npart = nullptr;   // Psi in the layout of Xc; [4k][tile_pad]; [nchunks][5k][tile_pad]
     double *sd2_d = nullptr;       // sdX ** 2 of the device entries
     double *hpsi[2] = {};          // pinned, gpz_predictor_draws_noisy only
+    // ---- gamma per draw and stacks of rows with input noise (gpz_predictor_stack_noisy*, _draws_gamma_noisy_dev): nothing before their first call
+    bool gam_used = false;
+    int gchunks = 0;               // predict_gamma_chunks of the model
+    double *gpart = nullptr, *s2_d = nullptr;   // [gchunks][nd k][tile] pair sums per chunk; [(1 + nd) k][tile] widths^2 of the stack
+    size_t gpart_cap = 0, s2_cap = 0;           // doubles
     // ---- rows with missing inputs on the handle (gpz_predictor_*_missing_dev): nothing of this exists before the first of their calls
     bool miss_used = false;
     int64_t mtile = 0;             // rows per tile of a group: min(tile_rows, GPZ_PREDICTOR_TILE_MISSING)
@@ -587,6 +595,25 @@ static int predictor_draws_tile(gpz_predictor *p, int s, int64_t nt, int ncol, i
     return 0;
 }
 
+// What a call that needs gamma under nd draws on tiles of T rows adds to the handle (after predictor_noisy_prepare: the pair table): the
+// chunk slab of the pair sums and, for a stack of Q column-outputs, the widths.  nd = 0 takes no slab.
+static int predictor_gamma_prepare(gpz_predictor *p, int ncol, int Q, int64_t T) {
+    int rc = 0;
+    p->gchunks = predict_gamma_chunks(p->m);
+    if (ncol > 0 && (rc = predictor_grow(p, &p->gpart, &p->gpart_cap, (size_t)p->gchunks * ncol * T))) return rc;
+    if (Q > 0 && (rc = predictor_grow(p, &p->s2_d, &p->s2_cap, (size_t)Q * T))) return rc;
+    p->gam_used = true;
+    return 0;
+}
+
+// the pair sums under every draw of one tile of nt rows: Xc[s], Psic[s], W -> gpart ([gchunks][ncol][nt])
+static int predictor_gamma_tile(gpz_predictor *p, const char *who, int s, int nt, int ncol, int ldw) {
+    if (launch_predict_noisy_gamma(p->s_cmp, p->d, p->Xc[s], p->Psic[s], p->tile_pad, nt, p->m, p->ptab, p->nrec, p->Wd, ldw, ncol,
+                                   p->gchunks, p->gpart, nt))
+        return gpz_fail(GPZ_ERR_HIP, "%s: k_predict_noisy_gamma launch failed", who);
+    return 0;
+}
+
 // gpz_predictor_draws: the draws of every tile come home.  Psi (gpz_predictor_draws_noisy; nullptr: noise-free rows): normalised ns x d
 // column-major, staged into a second pair of pinned slots and uploaded with X's tile
 struct DrawsJob {
@@ -735,6 +762,76 @@ static int predictor_run_stack(gpz_predictor *p, const double *Xs, int64_t ns, i
     return predictor_drain(p, who, rc);
 }
 
+// ---- stack of rows with input noise --------------------------------------------------------------------------------------------
+// predictor_stack_tile for rows with Psi in Psic[s]: predictNoisy (nout[s]), with draws their kernel behind PHI of (X, Psi) (dout[s]) and
+// the pair sums under every draw, the widths (column 0: (nu + beta) + gamma, draw s: beta + max(gamma_s, 0)), then the stack kernel that
+// reads them and k_stack_accum
+static int predictor_stack_noisy_tile(gpz_predictor *p, const char *who, const StackCall &c, int s, int64_t nt, const int *lab,
+                                      const double *wt) {
+    int rc = 0;
+    if ((rc = predictor_noisy_tile(p, s, (int)nt))) return rc;
+    if (c.nd > 0) {
+        if ((rc = predictor_draws_tile(p, s, nt, c.ncol, c.ldw, false, p->Psic[s]))) return rc;
+        if ((rc = predictor_gamma_tile(p, who, s, (int)nt, c.ncol, c.ldw))) return rc;
+    }
+    if (launch_gamma_finish_s2(p->s_cmp, p->gpart, p->gchunks, nt, p->nout[s], c.nd > 0 ? p->dout[s] : nullptr, (int)nt, p->k, c.nd, p->s2_d))
+        return gpz_fail(GPZ_ERR_HIP, "%s: k_gamma_finish_s2 launch failed", who);
+    if (launch_stack_tile_w(p->s_cmp, p->nout[s], p->s2_d, c.nd > 0 ? p->dout[s] : nullptr, lab, wt, p->edges_d, p->edges_d + c.ne, nt, p->k,
+                            c.nd, c.B, c.G, c.R, p->slab_d) ||
+        launch_stack_accum(p->s_cmp, p->slab_d, c.R, c.count, p->acc_d))
+        return gpz_fail(GPZ_ERR_HIP, "%s: k_stack_tile_w launch failed", who);
+    return 0;
+}
+
+// gpz_predictor_stack_noisy: StackJob with Psi's tile staged into the hpsi slots and uploaded with X's, as DrawsJob does
+struct StackNoisyJob {
+    gpz_predictor *p;
+    const StackCall &c;
+    int64_t ns;
+    const double *Psi;
+    const int32_t *group;
+    const double *weight;
+    const char *who = "gpz_predictor_stack_noisy";
+    const char *nan_text = "the rows have missing values (NaN): stacks are for complete rows";
+    static constexpr bool downloads = false;
+    int stage(int s, int64_t r0, int64_t nt) {
+        if (predictor_stage(Psi, ns, p->d, r0, nt, p->hpsi[s], (size_t)p->tile_pad,
+                            [](double v) { return !(v >= 0.0) || !(v <= 1.7976931348623157e308); }))
+            return gpz_fail(GPZ_ERR_ARG, "%s: Psi has an element that is NaN, infinite or negative", who);
+        if (group) memcpy(p->hlab[s], group + r0, (size_t)nt * sizeof(int));
+        if (weight) memcpy(p->hwt[s], weight + r0, (size_t)nt * sizeof(double));
+        return 0;
+    }
+    bool upload(int s, int64_t nt) {
+        const size_t tp = (size_t)p->tile_pad;
+        return hipMemcpy2DAsync(p->Psic[s], tp * sizeof(double), p->hpsi[s], tp * sizeof(double), (size_t)nt * sizeof(double), p->d,
+                                hipMemcpyHostToDevice, p->s_in) != hipSuccess ||
+               (group && hipMemcpyAsync(p->lab_d[s], p->hlab[s], (size_t)nt * sizeof(int), hipMemcpyHostToDevice, p->s_in) != hipSuccess) ||
+               (weight && hipMemcpyAsync(p->wt_d[s], p->hwt[s], (size_t)nt * sizeof(double), hipMemcpyHostToDevice, p->s_in) != hipSuccess);
+    }
+    int kernels(int s, int64_t nt) {
+        return predictor_stack_noisy_tile(p, who, c, s, nt, group ? p->lab_d[s] : nullptr, weight ? p->wt_d[s] : nullptr);
+    }
+};
+
+static int predictor_run_stack_noisy(gpz_predictor *p, const double *Xs, int64_t ns, const double *Psi, int nd, unsigned long long seed,
+                                     const double *Z, const double *edges, const double *shift, int B, const int32_t *group, int G,
+                                     const double *weight, double *res) {
+    const char *who = "gpz_predictor_stack_noisy";
+    StackCall c{};
+    int rc = predictor_noisy_prepare(p);
+    for (int s = 0; s < 2 && !rc; ++s)
+        if (!p->hpsi[s]) HIPCHK(hipHostMalloc((void **)&p->hpsi[s], (size_t)p->d * p->tile_pad * sizeof(double), hipHostMallocDefault));
+    if (!rc) rc = predictor_stack_prepare(p, who, nd, seed, Z, edges, shift, B, G, true, &c);
+    if (!rc) rc = predictor_gamma_prepare(p, c.ncol, (1 + nd) * p->k, c.T);
+    if (!rc) {
+        StackNoisyJob job{p, c, ns, Psi, group, weight};
+        rc = predictor_pipeline(p, Xs, ns, c.T, job);
+    }
+    if (!rc) rc = predictor_stack_result(p, who, c, res);
+    return predictor_drain(p, who, rc);
+}
+
 // ---- device-resident entries -------------------------------------------------------------------------------------------------------
 // the caller's rows: element (i, c) at X[i rs + c cs], type GPZ_X_F64 or GPZ_X_F32
 struct DevRows {
@@ -866,14 +963,21 @@ static int predictor_run_dev(gpz_predictor *p, const char *who, const DevRows &x
 
 // psi (gpz_predictor_draws_noisy_dev; nullptr: noise-free rows) with sd2_d
 static int predictor_run_draws_dev(gpz_predictor *p, const DevRows &x, const double *muX_d, const double *sdX_d, const double *muY_d, int nd,
-                                   unsigned long long seed, const double *Z, double *F, const DevRows *psi, const double *sd2_d) {
-    const char *who = "gpz_predictor_draws_dev";
+                                   unsigned long long seed, const double *Z, double *F, const DevRows *psi, const double *sd2_d,
+                                   double *Gam = nullptr) {
+    const char *who = Gam ? "gpz_predictor_draws_gamma_noisy_dev" : "gpz_predictor_draws_dev";
     const int ncol = nd * p->k, ldw = rup(ncol, 16);
     int64_t T = 0;
     int rc = predictor_draws_prepare(p, nd, seed, Z, false, &T);
+    if (!rc && Gam) rc = predictor_gamma_prepare(p, ncol, 0, T);
     if (!rc)
         rc = predictor_dev_tiles(p, who, x, muX_d, sdX_d, psi, sd2_d, T, [&](int s, int64_t r0, int nt) {
             if (int rc = predictor_draws_tile(p, s, nt, ncol, ldw, false, psi ? p->Psic[s] : nullptr)) return rc;
+            if (Gam) {   // gamma_s = the pair sum under draw s - mu_s^2, mu_s as dout[s] holds it (without muY)
+                if (int rc = predictor_gamma_tile(p, who, s, nt, ncol, ldw)) return rc;
+                if (launch_gamma_finish_dev(p->s_cmp, p->gpart, p->gchunks, nt, p->dout[s], nt, p->k, nd, x.ns, r0, Gam))
+                    return gpz_fail(GPZ_ERR_HIP, "%s: k_gamma_finish_dev launch failed", who);
+            }
             if (launch_draws_finish_dev(p->s_cmp, p->dout[s], nt, p->k, nd, muY_d, x.ns, r0, F))
                 return gpz_fail(GPZ_ERR_HIP, "%s: k_draws_finish_dev launch failed", who);
             return 0;
@@ -891,6 +995,22 @@ static int predictor_run_stack_dev(gpz_predictor *p, const DevRows &x, const dou
     if (!rc)
         rc = predictor_dev_tiles(p, who, x, muX_d, sdX_d, nullptr, nullptr, c.T, [&](int s, int64_t r0, int nt) {
             return predictor_stack_tile(p, who, c, s, nt, group ? group + r0 : nullptr, weight ? weight + r0 : nullptr);
+        });
+    if (!rc) rc = predictor_stack_result(p, who, c, res);
+    return predictor_dev_sync(p, who, rc);
+}
+
+// predictor_run_stack_noisy with the rows, Psi, labels and weights where the caller has them
+static int predictor_run_stack_noisy_dev(gpz_predictor *p, const DevRows &x, const DevRows &psi, const double *muX_d, const double *sdX_d,
+                                         const double *sd2_d, int nd, unsigned long long seed, const double *Z, const double *edges,
+                                         const double *shift, int B, const int32_t *group, int G, const double *weight, double *res) {
+    const char *who = "gpz_predictor_stack_noisy_dev";
+    StackCall c{};
+    int rc = predictor_stack_prepare(p, who, nd, seed, Z, edges, shift, B, G, false, &c);
+    if (!rc) rc = predictor_gamma_prepare(p, c.ncol, (1 + nd) * p->k, c.T);
+    if (!rc)
+        rc = predictor_dev_tiles(p, who, x, muX_d, sdX_d, &psi, sd2_d, c.T, [&](int s, int64_t r0, int nt) {
+            return predictor_stack_noisy_tile(p, who, c, s, nt, group ? group + r0 : nullptr, weight ? weight + r0 : nullptr);
         });
     if (!rc) rc = predictor_stack_result(p, who, c, res);
     return predictor_dev_sync(p, who, rc);
@@ -1102,7 +1222,7 @@ static int run_dev_entry(const char *who, gpz_predictor *p, const DevRows &x, co
 // gpz_predictor_draws_dev and, with psi, gpz_predictor_draws_noisy_dev
 static int draws_dev_entry(const char *who, gpz_predictor *p, const DevRows &x, const DevRows *psi, const double *muX, const double *sdX,
                            const double *sd2, const double *muY, int32_t ndraws, uint64_t seed, const double *Z, double *F_d,
-                           void *stream) {
+                           void *stream, double *Gam_d = nullptr, bool want_gamma = false) {
     if (int rc = predictor_check_call(who, p, x.ns)) return rc;
     if (int rc = predictor_check_ndraws(who, p, ndraws, 1)) return rc;
     if (psi)
@@ -1111,15 +1231,16 @@ static int draws_dev_entry(const char *who, gpz_predictor *p, const DevRows &x, 
     if (psi)
         if (int rc = predictor_dev_psi_args(who, *psi, sdX, sd2)) return rc;
     if (x.ns == 0) return 0;
-    if (!F_d) return gpz_fail(GPZ_ERR_ARG, "%s: null argument", who);
+    if (!F_d || (want_gamma && !Gam_d)) return gpz_fail(GPZ_ERR_ARG, "%s: null argument", who);
     return predictor_call(p, who, [&] {
         const double *mx = nullptr, *sx = nullptr, *my = nullptr;
-        int rc = psi ? predictor_psi_slots(p) : 0;
+        int rc = want_gamma ? predictor_noisy_prepare(p) : psi ? predictor_psi_slots(p) : 0;   // gamma reads the pair table
         if (!rc)
             rc = predictor_dev_begin(p, who, x, muX, sdX, muY, nullptr, 0, nullptr, stream,
                                      "the rows have missing values (NaN): draws are for complete rows", &mx, &sx, &my, psi, sd2);
         if (!rc)
-            rc = predictor_run_draws_dev(p, x, mx, sx, my, (int)ndraws, (unsigned long long)seed, Z, F_d, psi, sd2 ? p->sd2_d : nullptr);
+            rc = predictor_run_draws_dev(p, x, mx, sx, my, (int)ndraws, (unsigned long long)seed, Z, F_d, psi, sd2 ? p->sd2_d : nullptr,
+                                         want_gamma ? Gam_d : nullptr);
         return rc;
     });
 }
@@ -1376,6 +1497,83 @@ extern "C" int gpz_predictor_stack_dev(gpz_predictor *p, const void *X_d, int32_
     return 0;
 }
 
+extern "C" int gpz_predictor_draws_gamma_noisy_dev(gpz_predictor *p, const void *X_d, int32_t x_type, int64_t ns, int64_t row_stride,
+                                                   int64_t col_stride, const void *Psi_d, int32_t psi_type, int64_t psi_row_stride,
+                                                   int64_t psi_col_stride, const double *muX, const double *sdX, const double *sd2,
+                                                   const double *muY, int32_t ndraws, uint64_t seed, const double *Z, double *F_d,
+                                                   double *Gam_d, void *stream) {
+    const DevRows psi{Psi_d, psi_type, ns, psi_row_stride, psi_col_stride};
+    return draws_dev_entry("gpz_predictor_draws_gamma_noisy_dev", p, DevRows{X_d, x_type, ns, row_stride, col_stride}, &psi, muX, sdX, sd2,
+                           muY, ndraws, seed, Z, F_d, stream, Gam_d, true);
+}
+
+extern "C" int gpz_predictor_stack_noisy(gpz_predictor *p, const double *Xs, int64_t ns, const double *Psi, int32_t ndraws, uint64_t seed,
+                                         const double *Z, const double *edges, int32_t nbins, const int32_t *group, int32_t ngroups,
+                                         const double *weight, double *hist, double *sum_w, double *sum_mu, double *sum_mu2,
+                                         const double *mu_shift) {
+    const char *who = "gpz_predictor_stack_noisy";
+    if (int rc = stack_check_shape(who, p, ns, ndraws, nbins, ngroups, edges, hist, sum_w, sum_mu, sum_mu2, Xs)) return rc;
+    if (int rc = predictor_check_noisy_draws(who, p)) return rc;
+    if (ns > 0 && !Psi) return gpz_fail(GPZ_ERR_ARG, "%s: null Psi", who);
+    const int k = p->k, B = nbins, G = ngroups, C = 1 + ndraws;
+    if (group)
+        for (int64_t i = 0; i < ns; ++i)
+            if (group[i] < -1 || group[i] >= G)
+                return gpz_fail(GPZ_ERR_ARG, "%s: label %d of row %lld is outside [-1, %d)", who, (int)group[i], (long long)i, G);
+    if (int rc = stack_check_shift(who, p, mu_shift)) return rc;
+    if (weight)
+        for (int64_t i = 0; i < ns; ++i)
+            if (!(weight[i] >= 0.0) || !std::isfinite(weight[i]))
+                return gpz_fail(GPZ_ERR_ARG, "%s: the weight of row %lld is negative or not finite", who, (long long)i);
+    if (ns == 0) {
+        stack_zero(C, k, G, B, hist, sum_w, sum_mu, sum_mu2);
+        return 0;
+    }
+    std::vector<double> res((size_t)C * k * ((size_t)G * B + 3 * (size_t)G));
+    if (int rc = predictor_call(p, who, [&] {
+            return predictor_run_stack_noisy(p, Xs, ns, Psi, (int)ndraws, (unsigned long long)seed, Z, edges, mu_shift, B, group, G, weight,
+                                             res.data());
+        }))
+        return rc;   // the outputs are untouched
+    stack_unpack(res.data(), C, k, G, B, hist, sum_w, sum_mu, sum_mu2);
+    return 0;
+}
+
+extern "C" int gpz_predictor_stack_noisy_dev(gpz_predictor *p, const void *X_d, int32_t x_type, int64_t ns, int64_t row_stride,
+                                             int64_t col_stride, const void *Psi_d, int32_t psi_type, int64_t psi_row_stride,
+                                             int64_t psi_col_stride, const double *muX, const double *sdX, const double *sd2,
+                                             int32_t ndraws, uint64_t seed, const double *Z, const double *edges, int32_t nbins,
+                                             const int32_t *group_d, int32_t ngroups, const double *weight_d, double *hist, double *sum_w,
+                                             double *sum_mu, double *sum_mu2, const double *mu_shift, void *stream) {
+    const char *who = "gpz_predictor_stack_noisy_dev";
+    const DevRows x{X_d, x_type, ns, row_stride, col_stride}, psi{Psi_d, psi_type, ns, psi_row_stride, psi_col_stride};
+    if (int rc = stack_check_shape(who, p, ns, ndraws, nbins, ngroups, edges, hist, sum_w, sum_mu, sum_mu2, X_d)) return rc;
+    if (int rc = predictor_check_noisy_draws(who, p)) return rc;
+    if (int rc = predictor_dev_args(who, p, x, muX, sdX)) return rc;
+    if (int rc = predictor_dev_psi_args(who, psi, sdX, sd2)) return rc;
+    if (int rc = stack_check_shift(who, p, mu_shift)) return rc;
+    const int k = p->k, B = nbins, G = ngroups, C = 1 + ndraws;
+    if (ns == 0) {
+        stack_zero(C, k, G, B, hist, sum_w, sum_mu, sum_mu2);
+        return 0;
+    }
+    std::vector<double> res((size_t)C * k * ((size_t)G * B + 3 * (size_t)G));
+    if (int rc = predictor_call(p, who, [&] {
+            const double *mx = nullptr, *sx = nullptr, *my = nullptr;
+            int rc = predictor_noisy_prepare(p);
+            if (!rc)   // the refusals of rows, Psi, labels and weights before any tile
+                rc = predictor_dev_begin(p, who, x, muX, sdX, nullptr, group_d, G, weight_d, stream,
+                                         "the rows have missing values (NaN): stacks are for complete rows", &mx, &sx, &my, &psi, sd2);
+            if (!rc)
+                rc = predictor_run_stack_noisy_dev(p, x, psi, mx, sx, sd2 ? p->sd2_d : nullptr, (int)ndraws, (unsigned long long)seed, Z,
+                                                   edges, mu_shift, B, group_d, G, weight_d, res.data());
+            return rc;
+        }))
+        return rc;   // the outputs are untouched
+    stack_unpack(res.data(), C, k, G, B, hist, sum_w, sum_mu, sum_mu2);
+    return 0;
+}
+
 extern "C" int gpz_predictor_route(const gpz_predictor *p, char *buf, int cap) {
     if (!p || !buf || cap < 1) return gpz_fail(GPZ_ERR_ARG, "gpz_predictor_route: null argument");
     char tmp[160];
@@ -1398,6 +1596,11 @@ extern "C" int gpz_predictor_route(const gpz_predictor *p, char *buf, int cap) {
     if (p->noisy_ready) {   // after the first call with input noise on the handle
         snprintf(tmp, sizeof tmp, "; noise: k_predict_noisy_small (%d pair chunks)", p->nchunks);
         r += tmp;
+    }
+    if (p->gam_used) {   // after the first stack or gamma-per-draw call for rows with input noise
+        snprintf(tmp, sizeof tmp, "; noise per draw: k_predict_noisy_gamma (%d pair chunks)", p->gchunks);
+        r += tmp;
+        if (p->s2_d) r += " + k_stack_tile_w";   // the widths exist: a stack call was among them
     }
     if (p->miss_used) {   // after the first call for a group of rows with missing inputs
         snprintf(tmp, sizeof tmp, "; missing: k_predict_missing_pairs (%d pair chunks), %lld-row tiles", p->mchunks, (long long)p->mtile);

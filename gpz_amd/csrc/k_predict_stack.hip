@@ -15,14 +15,28 @@
 //
 // Layout of a workgroup's record, of a slab entry and of the running accumulators, per q: [G][B] bins, then [G][3] = sum of omega,
 // omega (mu + shift_o), omega (mu + shift_o)^2.  Bins wholly beyond the window are left out: at most Phi(-GPZ_STACK_TCUT) = 1.1e-19 omega per row and side.
+//
+// k_predict_stack_w.hip includes this text with GPZ_STACK_WIDTHS defined and gets k_stack_tile_w / launch_stack_tile_w instead: the same
+// kernel with the row's width^2 read from an array s2 [(1 + nd) k][nt] (rows with input noise: the width of a draw column depends on the
+// draw) and column 0's mu from that call's out.  The parameter is a macro, as PREDICT_DRAWS_PSI is, so that this unit keeps its code
+// instruction for instruction; k_stack_accum and the two size functions exist in this unit only.
 #include <hip/hip_runtime.h>
 
 #include "gpz_kernels.h"
 
 #define GPZ_STACK_TCUT 9.0
 
+#ifdef GPZ_STACK_WIDTHS
+#define K_STACK_TILE k_stack_tile_w
+#else
+#define K_STACK_TILE k_stack_tile
+#endif
+
 struct StackArgs {
-    const double *out;     // [3k][nt]: mu, nu, beta of the tile (predictor_tile)
+    const double *out;     // [3k][nt]: mu, nu, beta of the tile (predictor_tile); with GPZ_STACK_WIDTHS only row o = mu is read
+#ifdef GPZ_STACK_WIDTHS
+    const double *s2;      // [(1 + nd) k][nt]: the width^2 of column-output q = c k + o
+#endif
     const double *dout;    // [nd k][nt]: draw s of output o in row o nd + s (nullptr when nd = 0)
     const int *lab;        // nt labels or nullptr (all rows in group 0)
     const double *wt;      // nt weights or nullptr (all 1)
@@ -86,14 +100,18 @@ __device__ __forceinline__ void stack_pass(const double *__restrict__ e, double 
     }
 }
 
-__global__ __launch_bounds__(64) void k_stack_tile(StackArgs a) {
+__global__ __launch_bounds__(64) void K_STACK_TILE(StackArgs a) {
     extern __shared__ double h[];
     const int lane = threadIdx.x, q = blockIdx.x, r = blockIdx.y, Q = gridDim.x;
     const int c = q / a.k, o = q - c * a.k, B = a.B, ne = B + 1, GB = a.G * B, rec = GB + 3 * a.G;
     for (int i = lane; i < rec; i += 64) h[i] = 0.0;
     __syncthreads();
     const double *mu = c == 0 ? a.out + (size_t)o * a.nt : a.dout + ((size_t)o * a.nd + (c - 1)) * a.nt;
+#ifdef GPZ_STACK_WIDTHS
+    const double *w2 = a.s2 + (size_t)q * a.nt;
+#else
     const double *nu = a.out + (size_t)(a.k + o) * a.nt, *beta = a.out + (size_t)(2 * a.k + o) * a.nt;
+#endif
     const double *e = a.edges + (size_t)o * ne;
     const double shift = a.shift[o];
     const long r0 = (long)r * a.rps, r1 = r0 + a.rps < a.nt ? r0 + a.rps : a.nt;
@@ -109,7 +127,11 @@ __global__ __launch_bounds__(64) void k_stack_tile(StackArgs a) {
         }
         if (g >= 0) {
             m = mu[i];
+#ifdef GPZ_STACK_WIDTHS
+            const double s2 = w2[i], s = sqrt(s2);
+#else
             const double s2 = c == 0 ? nu[i] + beta[i] : beta[i], s = sqrt(s2);
+#endif
             inv = 1.0 / s;
             const double lo = m - GPZ_STACK_TCUT * s, hi = m + GPZ_STACK_TCUT * s;
             int l0 = 0, l1 = ne;   // edges below lo
@@ -150,6 +172,7 @@ __global__ __launch_bounds__(64) void k_stack_tile(StackArgs a) {
     for (int i = lane; i < rec; i += 64) dst[i] = h[i];
 }
 
+#ifndef GPZ_STACK_WIDTHS
 size_t predict_stack_lds(int G, int B) { return ((size_t)G * B + 3 * (size_t)G) * sizeof(double); }
 
 // row slabs per tile for Q columns of records of rec doubles on tiles of T rows: enough workgroups to fill the device when the
@@ -162,23 +185,33 @@ int predict_stack_slabs(long Q, long rec, long T) {
     while (R > 1 && Q * R * rec > (1L << 24)) R >>= 1;
     return R < 1 ? 1 : (int)R;
 }
+#endif
 
+#ifdef GPZ_STACK_WIDTHS
+int launch_stack_tile_w(hipStream_t st, const double *out, const double *s2, const double *dout, const int *lab, const double *wt,
+                        const double *edges, const double *shift, long nt, int k, int nd, int B, int G, int R, double *slab) {
+    if (nt <= 0) return 0;
+    StackArgs a{};
+    a.s2 = s2;
+#else
 int launch_stack_tile(hipStream_t st, const double *out, const double *dout, const int *lab, const double *wt, const double *edges,
                       const double *shift, long nt, int k, int nd, int B, int G, int R, double *slab) {
     if (nt <= 0) return 0;
     StackArgs a{};
+#endif
     a.out = out; a.dout = dout; a.lab = lab; a.wt = wt; a.edges = edges; a.shift = shift; a.slab = slab;
     a.nt = nt; a.k = k; a.nd = nd; a.B = B; a.G = G;
     a.rps = (int)(((nt + R - 1) / R + 63) / 64 * 64);
     const size_t lds = predict_stack_lds(G, B);
     // per launch, not once per process: the attribute belongs to the current device's copy of the kernel
     if (lds > 64 * 1024 &&
-        hipFuncSetAttribute((const void *)k_stack_tile, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+        hipFuncSetAttribute((const void *)K_STACK_TILE, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
         return -1;
-    hipLaunchKernelGGL(k_stack_tile, dim3((unsigned)((1 + nd) * k), (unsigned)R), dim3(64), lds, st, a);
+    hipLaunchKernelGGL(K_STACK_TILE, dim3((unsigned)((1 + nd) * k), (unsigned)R), dim3(64), lds, st, a);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
+#ifndef GPZ_STACK_WIDTHS
 __global__ __launch_bounds__(256) void k_stack_accum(const double *__restrict__ slab, int R, size_t count, double *__restrict__ acc) {
     for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < count; e += (size_t)gridDim.x * 256) {
         double s = slab[e];
@@ -194,3 +227,4 @@ int launch_stack_accum(hipStream_t st, const double *slab, int R, size_t count, 
     hipLaunchKernelGGL(k_stack_accum, dim3((unsigned)nb), dim3(256), 0, st, slab, R, count, acc);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
+#endif

@@ -337,6 +337,43 @@ int gpz_predictor_draws_noisy(gpz_predictor *p, const double *Xs, int64_t ns, co
                               int32_t ndraws, uint64_t seed, const double *Z /* NULL or m x ndraws x k */,
                               double *F /* ns x k x ndraws, column-major */);
 
+/* ---- stacked densities of rows with input noise, and gamma under every weight draw ----------------------------------------------------
+ * gpz_predictor_stack / _stack_dev for rows with a variance per input dimension, where predict_noisy_fits holds and the handle is on the
+ * fused route (GPZ_PREDICT_FORCE_TILES not set); anything else returns GPZ_ERR_UNSUPPORTED and names the condition.  Column 0 (the
+ * posterior-mean weights): mu of gpz_predictor_run_noisy_dev, width^2 = (nu + beta) + gamma, the bits of that call's sigma.  Column
+ * 1 + s (weight draw s): mu_s of gpz_predictor_draws_noisy_dev, width^2 = beta_i + max(gamma_s,i, 0) with
+ *   gamma_s,i = sum_{a >= b} f_ab E[phi_a phi_b](x_i, psi_i) w_s,a w_s,b - mu_s,i^2   (f_ab = 2 off the diagonal, 1 on it),
+ * predictNoisy's gamma (predictDiag.m:111-124) under the draw's weights: the variance of PHI(x) w_s over the input noise.  Everything
+ * else - edges, groups, weights, mu_shift, layouts, additivity over calls, the 9-width window - is gpz_predictor_stack's.  The host
+ * entry takes Psi as gpz_predictor_draws_noisy does (ns x d column-major, normalised), the device entry as gpz_predictor_draws_noisy_dev
+ * does (Psi_d, its type and strides, sd2).  An element of Psi that is NaN, negative or infinite -> GPZ_ERR_ARG; rows with NaN ->
+ * GPZ_ERR_UNSUPPORTED; in every refusal the outputs are untouched.  Both entries return the same bits for the same rows on the same
+ * handle.  ndraws = 0 forms no factors and allocates no draws or gamma buffer.
+ * gpz_predictor_draws_gamma_noisy_dev: gpz_predictor_draws_noisy_dev plus Gam_d (ns x k x ndraws column-major, device) <- gamma_s,
+ * unclamped.  A row's gamma_s has the same bits for any tile size, row order, split into calls and any ndraws > s.
+ * The first of these calls adds to the handle what gpz_predictor_run_noisy_dev adds, plus the chunk slab of the pair sums
+ * (predict_gamma_chunks(m) x ndraws k x tile rows doubles) and, for the stacks, the widths ((1 + ndraws) k x tile rows); nothing grows
+ * with ns, and gpz_predictor_route then holds "; noise per draw: k_predict_noisy_gamma (C pair chunks)", followed by
+ * " + k_stack_tile_w" once one of the stack entries has been called. */
+int gpz_predictor_stack_noisy(gpz_predictor *p, const double *Xs, int64_t ns, const double *Psi /* ns x d, normalised */,
+                              int32_t ndraws, uint64_t seed, const double *Z /* NULL or m x ndraws x k */,
+                              const double *edges /* k x (nbins + 1), muY already subtracted */, int32_t nbins,
+                              const int32_t *group /* ns or NULL */, int32_t ngroups, const double *weight /* ns or NULL */,
+                              double *hist, double *sum_w, double *sum_mu, double *sum_mu2, const double *mu_shift /* k or NULL */);
+int gpz_predictor_stack_noisy_dev(gpz_predictor *p, const void *X_d, int32_t x_type, int64_t ns, int64_t row_stride, int64_t col_stride,
+                                  const void *Psi_d, int32_t psi_type, int64_t psi_row_stride, int64_t psi_col_stride,
+                                  const double *muX, const double *sdX, const double *sd2,
+                                  int32_t ndraws, uint64_t seed, const double *Z, const double *edges, int32_t nbins,
+                                  const int32_t *group_d /* ns or NULL */, int32_t ngroups, const double *weight_d /* ns or NULL */,
+                                  double *hist, double *sum_w, double *sum_mu, double *sum_mu2, const double *mu_shift /* k or NULL */,
+                                  void *stream);
+int gpz_predictor_draws_gamma_noisy_dev(gpz_predictor *p, const void *X_d, int32_t x_type, int64_t ns, int64_t row_stride,
+                                        int64_t col_stride, const void *Psi_d, int32_t psi_type, int64_t psi_row_stride,
+                                        int64_t psi_col_stride, const double *muX, const double *sdX, const double *sd2,
+                                        const double *muY /* k or NULL */, int32_t ndraws, uint64_t seed,
+                                        const double *Z /* host: NULL or m x ndraws x k */, double *F_d /* ns x k x ndraws, column-major */,
+                                        double *Gam_d /* ns x k x ndraws, column-major */, void *stream);
+
 /* ---- rows with missing inputs on the predictor handle ------------------------------------------------------------------------------
  * predictMissing (predictDiag.m:127-209) and the draws for ONE group of rows that share a NaN pattern, on the handle's own tiles,
  * where predict_missing_fits holds: a diagonal kind (GL, VL, GD, VD), d <= 20, k <= 8 and ceil16(m) <= 256, no Psi.  Any other shape
