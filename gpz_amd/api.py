@@ -1211,14 +1211,20 @@ class Predictor:
         PHI_missing w_s + muY, the mu of predictMissing under weight draw s; one weight draw serves all rows of all groups.
         ``return_gamma=True`` (with ``Psi``; gpz_predictor_draws_gamma_noisy_dev) returns ``(F, Gam)``: Gam is a float64 tensor of shape
         (n_draws, n, k), predictNoisy's gamma under the weights of draw s - the variance of PHI(x) w_s over the input noise, not
-        clamped at 0.  A y-draw of row i under draw s has variance beta_i + Gam[s, i].  Without ``Psi`` it is a ValueError."""
+        clamped at 0.  A y-draw of row i under draw s has variance beta_i + Gam[s, i].
+        ``return_gamma=True`` with ``missing=True`` (gpz_predictor_draws_gamma_missing_dev) returns the same pair with predictMissing's
+        gamma under the weights of draw s: the variance of PHI(x) w_s over the missing dimensions of the row, exactly 0.0 on complete
+        rows.  A row's Gam has the same bits for any tile size, row order, other rows of the call and any n_draws > s.  The scope is
+        that of ``missing=True`` (diagonal kinds, d <= 20, k <= 8, m <= 256); ``Psi`` together with missing values, the covariance
+        kinds and host arrays are not on the handle.  With neither ``Psi`` nor ``missing``, or with both, it is a ValueError."""
         import torch
         self._check_open()
         k = self._k
         X = self._check_dev_rows(X, selection, "draws")
         n_draws, z = self._check_draw_args(n_draws, seed, Z, 1)
-        if return_gamma and (Psi is None or missing):
-            raise ValueError("return_gamma=True needs Psi (and not missing=True): gamma under a draw is the variance over the input noise")
+        if return_gamma and (Psi is None) != bool(missing):
+            raise ValueError("return_gamma=True needs Psi or missing=True, and not both: gamma under a draw is the variance over the "
+                             "input noise or over the missing dimensions")
         if missing:
             self._check_missing_model("draws_dev", Psi)
         if Psi is not None:
@@ -1241,15 +1247,27 @@ class Predictor:
                 for code, idx in self._nan_groups_dev(X):
                     Xg = X if idx is None else X[idx]
                     Fg = F if idx is None else torch.empty((n_draws, k, Xg.shape[0]), dtype=torch.float64, device=X.device)
+                    Gg = None
+                    if return_gamma:                                     # complete rows: exactly 0.0
+                        Gg = Gam if idx is None else torch.zeros((n_draws, k, Xg.shape[0]), dtype=torch.float64, device=X.device)
                     if code == 0:
                         _lib.check(self._lib.gpz_predictor_draws_dev(h, *self._x_args(Xg), _lib.dptr(muX), _lib.dptr(sdX), _lib.dptr(muY),
                                                                      n_draws, int(seed), _lib.dptr(z), Fg.data_ptr(), stream))
+                        if return_gamma and idx is None:
+                            Gam.zero_()
+                    elif return_gamma:
+                        _lib.check(self._lib.gpz_predictor_draws_gamma_missing_dev(h, *self._x_args(Xg), _lib.dptr(muX), _lib.dptr(sdX),
+                                                                                   _lib.dptr(muY), _lib.dptr(self._priors), full & ~code,
+                                                                                   n_draws, int(seed), _lib.dptr(z), Fg.data_ptr(),
+                                                                                   Gg.data_ptr(), stream))
                     else:
                         _lib.check(self._lib.gpz_predictor_draws_missing_dev(h, *self._x_args(Xg), _lib.dptr(muX), _lib.dptr(sdX),
                                                                              _lib.dptr(muY), _lib.dptr(self._priors), full & ~code,
                                                                              n_draws, int(seed), _lib.dptr(z), Fg.data_ptr(), stream))
                     if idx is not None:
                         F[:, :, idx] = Fg
+                        if return_gamma:
+                            Gam[:, :, idx] = Gg
             elif Psi is None:
                 _lib.check(self._lib.gpz_predictor_draws_dev(h, *self._x_args(X), _lib.dptr(muX), _lib.dptr(sdX), _lib.dptr(muY), n_draws,
                                                              int(seed), _lib.dptr(z), F.data_ptr(),
@@ -1287,12 +1305,29 @@ class Predictor:
             raise ValueError("stack_noisy_dev needs Psi: noise-free rows go to Predictor.stack_dev")
         return self._stack_dev(X, Psi, edges, n_draws, seed, Z, groups, n_groups, weights, selection)
 
-    def _stack_dev(self, X, Psi, edges, n_draws, seed, Z, groups, n_groups, weights, selection):
-        """``stack_dev`` (Psi None) and ``stack_noisy_dev``: the checks, the device last, all before the GPU is touched; then the entry."""
+    def stack_missing_dev(self, X, edges, n_draws=0, seed=0, Z=None, groups=None, n_groups=None, weights=None, selection=None):
+        """``stack_dev`` for a catalogue with missing inputs (non-detections, NaN) on the GPU: arguments and result as for ``stack_dev``.
+        The rows are grouped by NaN pattern with torch on the device, as ``predict_dev(X, missing=True)`` groups them.  The complete
+        rows go to gpz_predictor_stack_dev (a catalogue without NaN gives ``stack_dev``'s bits), every other group with its labels and
+        weights to gpz_predictor_stack_missing_dev, and the groups' results are added field by field in ascending order of the
+        pattern code: the fields are plain sums, so the call is deterministic and equals the ``+=`` of the single-pattern calls bit
+        for bit.  For a row with missing values column 0 uses ``predict_dev(X, missing=True)``'s mu and sigma = (nu + beta_i) + gamma,
+        column 1 + s ``draws_dev(X, ..., missing=True)``'s draw s and the width beta_i + max(gamma_s, 0), where gamma_s is
+        predictMissing's gamma under the weights of draw s (``draws_dev(..., missing=True, return_gamma=True)`` returns it).
+        ``n_groups`` and the range of the labels are decided over all rows.  It needs a model inside predict_missing_fits (a diagonal
+        kind, d <= 20, k <= 8, m <= 256), else ValueError; host arrays, ``Psi`` together with missing values and the covariance
+        kinds are not on the handle (``Predictor.predict`` takes such rows)."""
+        return self._stack_dev(X, None, edges, n_draws, seed, Z, groups, n_groups, weights, selection, missing=True)
+
+    def _stack_dev(self, X, Psi, edges, n_draws, seed, Z, groups, n_groups, weights, selection, missing=False):
+        """``stack_dev`` (Psi None), ``stack_noisy_dev`` and ``stack_missing_dev``: the checks, the device last, all before the GPU is
+        touched; then the entry, or with ``missing`` one entry per NaN-pattern group."""
         import torch
         self._check_open()
         X = self._check_dev_rows(X, selection, "stack" if Psi is None else "stack_noisy")
         n_all = X.shape[0]
+        if missing:
+            self._check_missing_model("stack_missing_dev", None)
         if Psi is not None:
             Psi = self._check_dev_psi(Psi, n_all, "stack_noisy")
             self._check_noisy_model("stack_noisy_dev", draws=True)
@@ -1335,7 +1370,25 @@ class Predictor:
             tail = (n_draws, int(seed), _lib.dptr(z), _lib.dptr(es), B, None if lab is None else lab.data_ptr(), G,
                     None if wt is None else wt.data_ptr(), _lib.dptr(hist), _lib.dptr(sum_w), _lib.dptr(sum_mu), _lib.dptr(sum_mu2),
                     _lib.dptr(muY), torch.cuda.current_stream(X.device).cuda_stream)
-            if Psi is None:
+            if missing:
+                full = (1 << self._d) - 1
+                for code, idx in self._nan_groups_dev(X):                # ascending code: one fixed order of the sums
+                    Xg, lg, wg = (X, lab, wt) if idx is None else (X[idx], None if lab is None else lab[idx],
+                                                                   None if wt is None else wt[idx])
+                    part = self._stack_arrays(n_draws, G, B)
+                    gtail = (n_draws, int(seed), _lib.dptr(z), _lib.dptr(es), B, None if lg is None else lg.data_ptr(), G,
+                             None if wg is None else wg.data_ptr(), *(_lib.dptr(a) for a in part), _lib.dptr(muY), tail[-1])
+                    if code == 0:
+                        _lib.check(self._lib.gpz_predictor_stack_dev(h, *self._x_args(Xg), _lib.dptr(muX), _lib.dptr(sdX), *gtail))
+                    else:
+                        _lib.check(self._lib.gpz_predictor_stack_missing_dev(h, *self._x_args(Xg), _lib.dptr(muX), _lib.dptr(sdX),
+                                                                             _lib.dptr(self._priors), full & ~code, *gtail))
+                    if idx is None:
+                        hist, sum_w, sum_mu, sum_mu2 = part
+                    else:
+                        for total, a in zip((hist, sum_w, sum_mu, sum_mu2), part):
+                            total += a
+            elif Psi is None:
                 _lib.check(self._lib.gpz_predictor_stack_dev(h, *self._x_args(X), _lib.dptr(muX), _lib.dptr(sdX), *tail))
             else:
                 sd2 = np.ascontiguousarray(sdX ** 2)                     # fixPsi.m: Psi ./ sdX.^2

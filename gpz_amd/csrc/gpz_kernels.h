@@ -267,6 +267,15 @@ int launch_pmd_phi(hipStream_t st, double *No, const double *T, int n, int m, in
 int launch_predict_missing_pairs(hipStream_t st, const double *Xc, long ldx, int n, const double *Pio, int ldpio, int m, int d, int k,
                                  unsigned obs, const double *U, const double *rec, int nchunk, double *part, long ldp, const double *hd,
                                  long ldh, const double *bvec, double *out);
+// ---- gamma under every weight draw for rows with missing inputs (k_predict_missing_gamma.hip; gpz_predictor_stack_missing_dev,
+// _draws_gamma_missing_dev).  part [nchunk][ncol][ldp] <- per pair chunk sum_{a >= b} f_ab EcC_ab(x_i) W[a, col] W[b, col] for the n rows
+// of the tile: Xc, Pio, U and rec as launch_predict_missing_pairs takes them (of a record only [lnZ | c | 1 / C] is read), W >= m rows x
+// ldw row-major as the draws take it (column o nd + s, ldw a multiple of 16, columns >= ncol zero), nchunk = predict_missing_chunks(m).
+// launch_gamma_finish_dev / _s2 (above) take part from there, with nout = the missing tile's out.  Returns -1 when a launch failed.
+size_t predict_missing_gamma_lds(int m, int d);   // dynamic LDS of k_predict_missing_gamma, bytes
+int launch_predict_missing_gamma(hipStream_t st, const double *Xc, long ldx, int n, const double *Pio, int ldpio, int m, int d, int k,
+                                 unsigned obs, const double *U, const double *rec, const double *W, int ldw, int ncol, int nchunk,
+                                 double *part, long ldp);
 // B (rows x ld row-major) <- [iS (m x m column-major) | nw columns of W from column wcol | nv columns of V (nullptr: 0) from vcol | 0]
 void launch_pred_fill_b(hipStream_t st, const double *iS, const double *W, int nw, int wcol, const double *V, int nv, int vcol, int m,
                         int rows, int ld, double *B);

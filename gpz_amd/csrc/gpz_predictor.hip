@@ -34,6 +34,9 @@
 // gpz_predictor_stack_noisy / _stack_noisy_dev stack such rows: per tile predictNoisy, the draws with Psi, gamma under every draw
 // (k_predict_noisy_gamma.hip, an f64 MFMA product of pair densities and weight products), and k_stack_tile_w with a width per (column,
 // row); gpz_predictor_draws_gamma_noisy_dev returns that gamma beside the draws.  Their buffers are allocated on their first call.
+// gpz_predictor_stack_missing_dev stacks one group of rows with missing inputs in the same way, with gamma under every draw from
+// k_predict_missing_gamma.hip (the pair kernel's product chained into a second f64 MFMA against the weight products);
+// gpz_predictor_draws_gamma_missing_dev returns that gamma beside the draws.  Their buffers are allocated on their first call.
 // Rows with missing inputs, one group of a NaN pattern per call, stay on the handle too where predict_missing_fits holds (the same
 // shapes): gpz_predictor_run_missing_dev / _draws_missing_dev run predictMissing on tiles of at most GPZ_PREDICTOR_TILE_MISSING rows
 // (k_predict_missing.hip): No and Pio, PHI through k_tgemm, then the fused pair kernel, or for the draws k_tgemm against W.  The tables
@@ -99,6 +102,11 @@ struct gpz_predictor {
     int gchunks = 0;               // predict_gamma_chunks of the model
     double *gpart = nullptr, *s2_d = nullptr;   // [gchunks][nd k][tile] pair sums per chunk; [(1 + nd) k][tile] widths^2 of the stack
     size_t gpart_cap = 0, s2_cap = 0;           // doubles
+    // ---- gamma per draw and stacks of rows with missing inputs (gpz_predictor_stack_missing_dev, _draws_gamma_missing_dev): nothing before
+    // their first call.  The chunk slab of the pair sums is gpart above ([mchunks][nd k][tile] here).
+    bool mgam_used = false;
+    double *ms2_d = nullptr;       // [(1 + nd) k][tile] widths^2 of the stack
+    size_t ms2_cap = 0;            // doubles
     // ---- rows with missing inputs on the handle (gpz_predictor_*_missing_dev): nothing of this exists before the first of their calls
     bool miss_used = false;
     int64_t mtile = 0;             // rows per tile of a group: min(tile_rows, GPZ_PREDICTOR_TILE_MISSING)
@@ -892,6 +900,9 @@ static int predictor_dev_begin(gpz_predictor *p, const char *who, const DevRows 
     if (!rc && (pattern ? launch_pmd_check(st, x.X, x.f32(), x.ns, p->d, x.rs, x.cs, *pattern, rec)
                         : launch_pred_check_dev(st, x.X, x.f32(), x.ns, p->d, x.rs, x.cs, lab, G, wt, rec)))
         rc = gpz_fail(GPZ_ERR_HIP, "%s: k_pred_check_dev launch failed", who);
+    // the labels and weights of a stack of such a group: k_pred_check_dev over no columns (words 1 and 2 only, X is not read)
+    if (!rc && pattern && (lab || wt) && launch_pred_check_dev(st, nullptr, 0, x.ns, 0, 0, 0, lab, G, wt, rec))
+        rc = gpz_fail(GPZ_ERR_HIP, "%s: k_pred_check_dev launch failed", who);
     if (!rc && psi &&   // (predictor_psi_slots has run: sd2_d exists)
         ((sd2 && hipMemcpyAsync(p->sd2_d, sd2, d * sizeof(double), hipMemcpyHostToDevice, st) != hipSuccess) ||
          launch_pred_check_psi(st, psi->X, psi->f32(), psi->ns, p->d, psi->rs, psi->cs, sd2 ? *std::min_element(sd2, sd2 + d) : 1.0, rec)))
@@ -1093,6 +1104,33 @@ static int predictor_missing_tile(gpz_predictor *p, const char *who, int s, int 
     return 0;
 }
 
+// the draws of one tile of the group behind predictor_missing_tile: PHI_missing (mNo) against the handle's W on k_tgemm -> dout[s]
+// ([ncol][nt], without muY).  wrows: the rows of W (predictor_draws_prepare), K of the product
+static int predictor_missing_draws_tile(gpz_predictor *p, const char *who, int s, int nt, int ncol, int ldw, int wrows) {
+    launch_tgemm(p->s_cmp, p->mNo, p->mp, p->Wd, ldw, p->Td, rup(nt, 128), ldw, nullptr, nullptr, p->m, 0, false, wrows, ldw);
+    launch_transpose_out(p->s_cmp, p->Td, ldw, nt, ncol, p->dout[s]);
+    if (hipGetLastError() != hipSuccess) return gpz_fail(GPZ_ERR_HIP, "%s: kernel launch failed", who);
+    return 0;
+}
+
+// What a call that needs gamma under nd draws for a group on tiles of T rows adds to the handle (after predictor_missing_prepare with
+// pairs: U and the records): the chunk slab of the pair sums and, for a stack of Q column-outputs, the widths.  nd = 0 takes no slab.
+static int predictor_missing_gamma_prepare(gpz_predictor *p, int ncol, int Q, int64_t T) {
+    int rc = 0;
+    if (ncol > 0 && (rc = predictor_grow(p, &p->gpart, &p->gpart_cap, (size_t)p->mchunks * ncol * T))) return rc;
+    if (Q > 0 && (rc = predictor_grow(p, &p->ms2_d, &p->ms2_cap, (size_t)Q * T))) return rc;
+    p->mgam_used = true;
+    return 0;
+}
+
+// the pair sums under every draw of one tile of nt rows of the group, after predictor_missing_tile (mPio): -> gpart ([mchunks][ncol][nt])
+static int predictor_missing_gamma_tile(gpz_predictor *p, const char *who, int s, int nt, uint32_t obs, int ncol, int ldw) {
+    if (launch_predict_missing_gamma(p->s_cmp, p->Xc[s], p->tile_pad, nt, p->mPio, p->mp, p->m, p->d, p->k, obs, p->mU, p->mrec, p->Wd, ldw,
+                                     ncol, p->mchunks, p->gpart, nt))
+        return gpz_fail(GPZ_ERR_HIP, "%s: k_predict_missing_gamma launch failed", who);
+    return 0;
+}
+
 // ---- what the entries share ---------------------------------------------------------------------------------------------------------
 static int predictor_check_call(const char *who, const gpz_predictor *p, int64_t ns) {
     if (!p) return gpz_fail(GPZ_ERR_ARG, "%s: null handle", who);
@@ -1276,16 +1314,17 @@ static int run_missing_dev_entry(const char *who, gpz_predictor *p, const DevRow
     });
 }
 
-// gpz_predictor_draws_missing_dev: F = PHI_missing W + muY (mu is linear in w), PHI of the tile against the handle's W on k_tgemm
+// gpz_predictor_draws_missing_dev: F = PHI_missing W + muY (mu is linear in w), PHI of the tile against the handle's W on k_tgemm; with
+// want_gamma (gpz_predictor_draws_gamma_missing_dev) gamma under every draw into Gam_d too
 static int draws_missing_dev_entry(const char *who, gpz_predictor *p, const DevRows &x, const double *muX, const double *sdX,
                                    const double *muY, const double *priors, uint32_t obs, int32_t ndraws, uint64_t seed, const double *Z,
-                                   double *F_d, void *stream) {
+                                   double *F_d, void *stream, double *Gam_d = nullptr, bool want_gamma = false) {
     if (int rc = predictor_check_call(who, p, x.ns)) return rc;
     if (int rc = predictor_check_ndraws(who, p, ndraws, 1)) return rc;
     if (int rc = predictor_missing_check(who, p, obs)) return rc;
     if (int rc = predictor_dev_args(who, p, x, muX, sdX)) return rc;
     if (x.ns == 0) return 0;
-    if (!F_d) return gpz_fail(GPZ_ERR_ARG, "%s: null argument", who);
+    if (!F_d || (want_gamma && !Gam_d)) return gpz_fail(GPZ_ERR_ARG, "%s: null argument", who);
     return predictor_call(p, who, [&] {
         const double *mx = nullptr, *sx = nullptr, *my = nullptr;
         const unsigned pat = obs;
@@ -1294,24 +1333,68 @@ static int draws_missing_dev_entry(const char *who, gpz_predictor *p, const DevR
                                      nullptr, &pat);
         if (rc) return rc;   // the output is untouched
         int64_t T = 0;
-        rc = predictor_missing_prepare(p, who, obs, priors, false);
+        rc = predictor_missing_prepare(p, who, obs, priors, want_gamma);   // gamma reads U and the records
         if (!rc) rc = predictor_draws_prepare(p, nd, (unsigned long long)seed, Z, false, &T);
         T = std::min<int64_t>(T, p->mtile);
+        if (!rc && want_gamma) rc = predictor_missing_gamma_prepare(p, ncol, 0, T);
         // the product's output tile: the tile route of the draws has one already, the fused route does not
         if (!rc) rc = predictor_grow(p, &p->Td, &p->t_cap, (size_t)rup(T, 1024) * ldw);
         const int wrows = p->droute == 0 ? rup(p->m, 16) : p->mp;   // the rows of W (predictor_draws_prepare): K of the product
         if (!rc)
             rc = predictor_dev_tiles(p, who, x, mx, sx, nullptr, nullptr, T, [&](int s, int64_t r0, int nt) {
                 if (int rc = predictor_missing_tile(p, who, s, nt, obs, false)) return rc;
-                launch_tgemm(p->s_cmp, p->mNo, p->mp, p->Wd, ldw, p->Td, rup(nt, 128), ldw, nullptr, nullptr, p->m, 0, false, wrows, ldw);
-                launch_transpose_out(p->s_cmp, p->Td, ldw, nt, ncol, p->dout[s]);
-                if (hipGetLastError() != hipSuccess) return gpz_fail(GPZ_ERR_HIP, "%s: kernel launch failed", who);
+                if (int rc = predictor_missing_draws_tile(p, who, s, nt, ncol, ldw, wrows)) return rc;
+                if (want_gamma) {   // gamma_s = the pair sum under draw s - mu_s^2, mu_s as dout[s] holds it (without muY)
+                    if (int rc = predictor_missing_gamma_tile(p, who, s, nt, obs, ncol, ldw)) return rc;
+                    if (launch_gamma_finish_dev(p->s_cmp, p->gpart, p->mchunks, nt, p->dout[s], nt, p->k, nd, x.ns, r0, Gam_d))
+                        return gpz_fail(GPZ_ERR_HIP, "%s: k_gamma_finish_dev launch failed", who);
+                }
                 if (launch_draws_finish_dev(p->s_cmp, p->dout[s], nt, p->k, nd, my, x.ns, r0, F_d))
                     return gpz_fail(GPZ_ERR_HIP, "%s: k_draws_finish_dev launch failed", who);
                 return 0;
             });
         return predictor_dev_sync(p, who, rc);
     });
+}
+
+// gpz_predictor_stack_missing_dev after its checks: predictor_run_stack_noisy_dev for one group of rows with missing inputs.  Per tile
+// of min(stack tile, mtile) rows: predictMissing (mout), with draws PHI_missing W (dout[s]) and the pair sums under every draw, the
+// widths (column 0: (nu + beta) + gamma, draw s: beta + max(gamma_s, 0)), k_stack_tile_w and k_stack_accum
+static int predictor_run_stack_missing_dev(gpz_predictor *p, const char *who, const DevRows &x, const double *muX_d, const double *sdX_d,
+                                           const double *priors, uint32_t obs, int nd, unsigned long long seed, const double *Z,
+                                           const double *edges, const double *shift, int B, const int32_t *group, int G,
+                                           const double *weight, double *res) {
+    const int k = p->k, Q = (1 + nd) * k;
+    StackCall c{};
+    int rc = predictor_missing_prepare(p, who, obs, priors, true);
+    if (!rc) rc = predictor_stack_prepare(p, who, nd, seed, Z, edges, shift, B, G, false, &c);
+    if (!rc) {   // the group's tile: No, Pio and T hold mtile rows
+        c.T = std::min<int64_t>(c.T, p->mtile);
+        c.R = predict_stack_slabs(Q, (long)((size_t)G * B + 3 * (size_t)G), c.T);   // <= the slabs that were allocated
+        p->stile = c.T;
+        p->sslabs = c.R;
+    }
+    // the product's output tile: the tile route of the draws has one already, the fused route does not
+    if (!rc && nd > 0) rc = predictor_grow(p, &p->Td, &p->t_cap, (size_t)rup(c.T, 1024) * c.ldw);
+    if (!rc) rc = predictor_missing_gamma_prepare(p, c.ncol, Q, c.T);
+    const int wrows = p->droute == 0 ? rup(p->m, 16) : p->mp;
+    if (!rc)
+        rc = predictor_dev_tiles(p, who, x, muX_d, sdX_d, nullptr, nullptr, c.T, [&](int s, int64_t r0, int nt) {
+            if (int rc = predictor_missing_tile(p, who, s, nt, obs, true)) return rc;
+            if (nd > 0) {
+                if (int rc = predictor_missing_draws_tile(p, who, s, nt, c.ncol, c.ldw, wrows)) return rc;
+                if (int rc = predictor_missing_gamma_tile(p, who, s, nt, obs, c.ncol, c.ldw)) return rc;
+            }
+            if (launch_gamma_finish_s2(p->s_cmp, p->gpart, p->mchunks, nt, p->mout, nd > 0 ? p->dout[s] : nullptr, nt, k, nd, p->ms2_d))
+                return gpz_fail(GPZ_ERR_HIP, "%s: k_gamma_finish_s2 launch failed", who);
+            if (launch_stack_tile_w(p->s_cmp, p->mout, p->ms2_d, nd > 0 ? p->dout[s] : nullptr, group ? group + r0 : nullptr,
+                                    weight ? weight + r0 : nullptr, p->edges_d, p->edges_d + c.ne, nt, k, nd, c.B, c.G, c.R, p->slab_d) ||
+                launch_stack_accum(p->s_cmp, p->slab_d, c.R, c.count, p->acc_d))
+                return gpz_fail(GPZ_ERR_HIP, "%s: k_stack_tile_w launch failed", who);
+            return 0;
+        });
+    if (!rc) rc = predictor_stack_result(p, who, c, res);
+    return predictor_dev_sync(p, who, rc);
 }
 }   // namespace gpzi
 
@@ -1574,6 +1657,47 @@ extern "C" int gpz_predictor_stack_noisy_dev(gpz_predictor *p, const void *X_d, 
     return 0;
 }
 
+extern "C" int gpz_predictor_draws_gamma_missing_dev(gpz_predictor *p, const void *X_d, int32_t x_type, int64_t ns, int64_t row_stride,
+                                                     int64_t col_stride, const double *muX, const double *sdX, const double *muY,
+                                                     const double *priors, uint32_t obs_mask, int32_t ndraws, uint64_t seed,
+                                                     const double *Z, double *F_d, double *Gam_d, void *stream) {
+    return draws_missing_dev_entry("gpz_predictor_draws_gamma_missing_dev", p, DevRows{X_d, x_type, ns, row_stride, col_stride}, muX, sdX,
+                                   muY, priors, obs_mask, ndraws, seed, Z, F_d, stream, Gam_d, true);
+}
+
+extern "C" int gpz_predictor_stack_missing_dev(gpz_predictor *p, const void *X_d, int32_t x_type, int64_t ns, int64_t row_stride,
+                                               int64_t col_stride, const double *muX, const double *sdX, const double *priors,
+                                               uint32_t obs_mask, int32_t ndraws, uint64_t seed, const double *Z, const double *edges,
+                                               int32_t nbins, const int32_t *group_d, int32_t ngroups, const double *weight_d,
+                                               double *hist, double *sum_w, double *sum_mu, double *sum_mu2, const double *mu_shift,
+                                               void *stream) {
+    const char *who = "gpz_predictor_stack_missing_dev";
+    const DevRows x{X_d, x_type, ns, row_stride, col_stride};
+    if (int rc = stack_check_shape(who, p, ns, ndraws, nbins, ngroups, edges, hist, sum_w, sum_mu, sum_mu2, X_d)) return rc;
+    if (int rc = predictor_missing_check(who, p, obs_mask)) return rc;
+    if (int rc = predictor_dev_args(who, p, x, muX, sdX)) return rc;
+    if (int rc = stack_check_shift(who, p, mu_shift)) return rc;
+    const int k = p->k, B = nbins, G = ngroups, C = 1 + ndraws;
+    if (ns == 0) {
+        stack_zero(C, k, G, B, hist, sum_w, sum_mu, sum_mu2);
+        return 0;
+    }
+    std::vector<double> res((size_t)C * k * ((size_t)G * B + 3 * (size_t)G));
+    if (int rc = predictor_call(p, who, [&] {
+            const double *mx = nullptr, *sx = nullptr, *my = nullptr;
+            const unsigned pat = obs_mask;
+            // the refusals of rows, labels and weights before any tile
+            int rc = predictor_dev_begin(p, who, x, muX, sdX, nullptr, group_d, G, weight_d, stream, kMissingPatternText, &mx, &sx, &my,
+                                         nullptr, nullptr, &pat);
+            if (rc) return rc;
+            return predictor_run_stack_missing_dev(p, who, x, mx, sx, priors, obs_mask, (int)ndraws, (unsigned long long)seed, Z, edges,
+                                                   mu_shift, B, group_d, G, weight_d, res.data());
+        }))
+        return rc;   // the outputs are untouched
+    stack_unpack(res.data(), C, k, G, B, hist, sum_w, sum_mu, sum_mu2);
+    return 0;
+}
+
 extern "C" int gpz_predictor_route(const gpz_predictor *p, char *buf, int cap) {
     if (!p || !buf || cap < 1) return gpz_fail(GPZ_ERR_ARG, "gpz_predictor_route: null argument");
     char tmp[160];
@@ -1605,6 +1729,11 @@ extern "C" int gpz_predictor_route(const gpz_predictor *p, char *buf, int cap) {
     if (p->miss_used) {   // after the first call for a group of rows with missing inputs
         snprintf(tmp, sizeof tmp, "; missing: k_predict_missing_pairs (%d pair chunks), %lld-row tiles", p->mchunks, (long long)p->mtile);
         r += tmp;
+    }
+    if (p->mgam_used) {   // after the first stack or gamma-per-draw call for such a group
+        snprintf(tmp, sizeof tmp, "; missing per draw: k_predict_missing_gamma (%d pair chunks)", p->mchunks);
+        r += tmp;
+        if (p->ms2_d) r += " + k_stack_tile_w";   // the widths exist: a stack call was among them
     }
     snprintf(buf, (size_t)cap, "%s", r.c_str());
     return (int)r.size();

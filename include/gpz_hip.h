@@ -401,6 +401,41 @@ int gpz_predictor_draws_missing_dev(gpz_predictor *p, const void *X_d, int32_t x
                                     int32_t ndraws, uint64_t seed, const double *Z /* host: NULL or m x ndraws x k */,
                                     double *F_d /* ns x k x ndraws, column-major */, void *stream);
 
+/* ---- stacked densities of rows with missing inputs, and gamma under every weight draw --------------------------------------------------
+ * gpz_predictor_stack_dev for ONE group of rows that share a NaN pattern (non-detections), and gpz_predictor_draws_missing_dev with
+ * gamma: the scope (predict_missing_fits), priors, obs_mask, the scan of the pattern and its refusals are those of the two entries
+ * above; no Psi, no host-array entry.  Column 0 (the posterior-mean weights): mu of gpz_predictor_run_missing_dev, width^2 = (nu + beta)
+ * + gamma, the bits of that call's sigma.  Column 1 + s (weight draw s): mu_s of gpz_predictor_draws_missing_dev, width^2 = beta_i +
+ * max(gamma_s,i, 0) with
+ *   gamma_s,i = sum_{a >= b} f_ab EcC_ab(x_i) w_s,a w_s,b - mu_s,i^2   (f_ab = 2 off the diagonal, 1 on it),
+ * predictMissing's gamma (predictDiag.m:172-198, :209) under the draw's weights: the variance of PHI(x) w_s over the missing
+ * dimensions; beta_i does not depend on w.  Everything else - edges, groups, weights, mu_shift, layouts, additivity over calls, the
+ * 9-width window - is gpz_predictor_stack's, so the results of the groups of a catalogue (and of gpz_predictor_stack_dev on its
+ * complete rows) add field by field.  A bad label or weight -> GPZ_ERR_ARG; in every refusal the outputs are untouched.  ndraws = 0
+ * forms no factors and allocates no draws or gamma buffer.
+ * gpz_predictor_draws_gamma_missing_dev: gpz_predictor_draws_missing_dev plus Gam_d (ns x k x ndraws column-major, device) <- gamma_s,
+ * unclamped.  A row's gamma_s has the same bits for any tile size, row order, position among other rows, split into calls and any
+ * ndraws > s.  k_predict_missing_gamma forms the pair expectations as gpz_predictor_run_missing_dev's pair kernel does and multiplies
+ * them into all draws at once on the f64 MFMA: 2 (ceil16(m) + ceil16(ndraws k)) m (m + 1) / 2 flop per row.
+ * The first of these calls adds to the handle what the two entries above add, plus the chunk slab of the pair sums
+ * (predict_missing_chunks(m) x ndraws k x tile rows doubles, tile = min(draws tile, 16384)) and, for the stack, the widths ((1 + ndraws)
+ * k x tile rows) and gpz_predictor_stack_dev's accumulators and slabs; nothing grows with ns or the number of patterns, and
+ * gpz_predictor_route then holds "; missing per draw: k_predict_missing_gamma (C pair chunks)", followed by " + k_stack_tile_w" once
+ * the stack entry has been called. */
+int gpz_predictor_draws_gamma_missing_dev(gpz_predictor *p, const void *X_d, int32_t x_type, int64_t ns, int64_t row_stride,
+                                          int64_t col_stride, const double *muX, const double *sdX, const double *muY /* k or NULL */,
+                                          const double *priors /* m or NULL */, uint32_t obs_mask,
+                                          int32_t ndraws, uint64_t seed, const double *Z /* host: NULL or m x ndraws x k */,
+                                          double *F_d /* ns x k x ndraws, column-major */,
+                                          double *Gam_d /* ns x k x ndraws, column-major */, void *stream);
+int gpz_predictor_stack_missing_dev(gpz_predictor *p, const void *X_d, int32_t x_type, int64_t ns, int64_t row_stride, int64_t col_stride,
+                                    const double *muX, const double *sdX,
+                                    const double *priors /* m or NULL */, uint32_t obs_mask,
+                                    int32_t ndraws, uint64_t seed, const double *Z, const double *edges, int32_t nbins,
+                                    const int32_t *group_d /* ns or NULL */, int32_t ngroups, const double *weight_d /* ns or NULL */,
+                                    double *hist, double *sum_w, double *sum_mu, double *sum_mu2, const double *mu_shift /* k or NULL */,
+                                    void *stream);
+
 /* ---- device-resident L-BFGS memory: minFunc's lbfgsAdd.m / lbfgsProd.m (mex/lbfgsAddC.c, mex/lbfgsProdC.c) ----
  * S and Y (p x corrections) live on the device; all vector arguments are device pointers.
  * gpz_lbfgs_add:        y = g - g_old, s = t*d; skipped (added = 0) when y's <= 1e-10        (lbfgsAdd.m:2-4)
