@@ -5,7 +5,8 @@
 //   gpz_eval.hip     the evaluation pipeline: stage A (PHI, PHI'W PHI), the m x m stage, the tail; gpz_solve, gpz_get_phi
 //   gpz_graph.hip    one evaluation as recorded hipGraph segments: recording, cuts, replay; gpz_eval / gpz_eval_dev
 //   gpz_predict.hip  the stand-alone entry points (gpz_phi, gpz_predict_*, gpz_prior, gpz_inv_logdet, gpz_dxy, gpz_nan_groups)
-//   gpz_predictor.hip  the streaming predictor handle (gpz_predictor_*)
+//   gpz_predictor.hip  the streaming predictor handle (gpz_predictor_*): its life, the tile functions of every kind of rows, route, info
+//   gpz_predictor_host.hip / gpz_predictor_dev.hip  its entries for host arrays and for device-resident rows (gpz_predictor.h)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>

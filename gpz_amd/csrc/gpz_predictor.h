@@ -1,0 +1,175 @@
+// Internal header of the streaming predictor (gpz_predictor_*): the handle and what its three translation units share.
+//   gpz_predictor.hip       handle life and setup, the prepare and tile functions of every kind of rows, draws preparation and
+//                           factorisation, what a stack call prepares and its tile, the checks the entries share, route and info
+//   gpz_predictor_host.hip  the host pipeline (predictor_stage, predictor_pipeline), its jobs and the entries that take host arrays
+//   gpz_predictor_dev.hip   the device-resident entries: DevRows, predictor_dev_begin, predictor_dev_tiles, predictor_dev_sync
+#pragma once
+#include "gpz_ctx.h"
+
+#define GPZ_PREDICTOR_TILE_FUSED (1L << 17)   // default rows per tile, fused route: 4096 blocks of 32 rows = 8 rounds of 512 workgroups
+#define GPZ_PREDICTOR_TILE_MISSING (1L << 14) // most rows per tile of a group with missing inputs: No, Pio and T are [tile][mp] each
+
+struct gpz_predictor {
+    gpz_desc desc;
+    gpz_options opt = gpz_options_load();
+    int mid = 0, kind = 0, d = 0, de = 0, m = 0, k = 1, hetero = 0, mp = 0;
+    long p = 0;
+    int device = 0;
+    int route = 0;                 // 0 fused, 1 tiles
+    bool force_tiles = false;      // GPZ_PREDICT_FORCE_TILES
+    int64_t tile_rows = 0, tile_pad = 0, runs = 0;
+    int nk = 0, ldb = 0;           // fused: B_o is nk x ldb
+    int nslots = 0;                // tiles: nu partial slots per output
+    Arena ar;
+    hipStream_t s_in = nullptr, s_cmp = nullptr, s_out = nullptr;
+    hipEvent_t ev_in[2] = {}, ev_cmp[2] = {}, ev_out[2] = {};
+    double *theta_d = nullptr, *iS_d = nullptr, *w_d = nullptr, *prep_ws = nullptr;
+    GpzParams pr{};
+    double *B = nullptr;           // fused: k x [nk][ldb];  tiles: k x [mp][mp]
+    double *Xc[2] = {}, *out[2] = {}, *phi_d[2] = {};
+    double *Phi = nullptr, *T = nullptr, *nupart = nullptr, *phiw = nullptr, *lnbeta = nullptr;   // tiles
+    double *hin[2] = {}, *hout[2] = {}, *hphi[2] = {};   // pinned
+    std::vector<double> theta_h, w_h, iS_h;              // the model, for the input-noise branch (gpz_predict_noisy per tile)
+    // ---- draws (gpz_predictor_draws): nothing of this exists before the first draws call
+    int droute = -1;               // -1 no draws call yet, 0 fused (k_predict_draws), 1 tiles (k_phi + k_tgemm)
+    std::vector<int> fkind;        // per output: 0 Cholesky, 1 eigendecomposition
+    double *R = nullptr;           // m x m x k column-major: R_o R_o' = S_o
+    double *Wd = nullptr, *Zd = nullptr, *Td = nullptr, *dout[2] = {}, *hdout[2] = {};
+    size_t w_cap = 0, z_cap = 0, t_cap = 0, dout_cap = 0, hdout_cap = 0;   // doubles
+    int64_t dtile = 0;             // rows per draws tile (last call)
+    bool w_seeded = false;         // Wd holds the draws of (w_seed, w_nd)
+    unsigned long long w_seed = 0;
+    int w_nd = 0;
+    // ---- stack (gpz_predictor_stack): nothing of this exists before the first stack call
+    int *lab_d[2] = {}, *hlab[2] = {};      // the tile's labels: device, pinned
+    double *wt_d[2] = {}, *hwt[2] = {};     // the tile's weights
+    double *edges_d = nullptr, *acc_d = nullptr, *slab_d = nullptr;
+    size_t edges_cap = 0, acc_cap = 0, slab_cap = 0;   // doubles
+    int64_t stile = 0;             // rows per stack tile (last call; 0: no stack call yet)
+    int sslabs = 0;                // row slabs per tile (last call)
+    // ---- device-resident entries: nothing of this exists before the first of their calls
+    double *par_d = nullptr;       // [muX d | sdX d | muY k | the record of k_pred_check_dev, 4 words]
+    hipEvent_t ev_dev = nullptr;   // recorded on the caller's stream, waited for by s_cmp
+    bool dev_used = false;
+    // ---- input noise on the handle (gpz_predictor_*_noisy*): nothing of this exists before the first of their calls
+    bool noisy_ready = false;
+    int nchunks = 0, nrec = 0;     // predict_noisy_chunks, predict_noisy_rec of the model
+    double *ptab = nullptr;        // m (m + 1) / 2 pair records
+    double *Psic[2] = {}, *nout[2] = {}, *npart = nullptr;   // Psi in the layout of Xc; [4k][tile_pad]; [nchunks][5k][tile_pad]
+    double *sd2_d = nullptr;       // sdX ** 2 of the device entries
+    double *hpsi[2] = {};          // pinned, gpz_predictor_draws_noisy only
+    // ---- gamma per draw and stacks of rows with input noise (gpz_predictor_stack_noisy*, _draws_gamma_noisy_dev) and of rows with missing
+    // inputs (gpz_predictor_stack_missing_dev, _draws_gamma_missing_dev): nothing of a kind before its first such call
+    int gchunks = 0;               // predict_gamma_chunks of the model (input noise; a group with missing inputs has mchunks)
+    double *gpart = nullptr;       // [chunks][nd k][tile] pair sums per chunk, of either kind
+    size_t gpart_cap = 0;          // doubles
+    struct PerDraw {
+        bool used = false;
+        double *s2_d = nullptr;    // [(1 + nd) k][tile] widths^2 of the stack
+        size_t s2_cap = 0;         // doubles
+    } gam[2];                      // [ROWS_NOISY - 1], [ROWS_MISSING - 1]
+    // ---- rows with missing inputs on the handle (gpz_predictor_*_missing_dev): nothing of this exists before the first of their calls
+    bool miss_used = false;
+    int64_t mtile = 0;             // rows per tile of a group: min(tile_rows, GPZ_PREDICTOR_TILE_MISSING)
+    int mchunks = 0;               // predict_missing_chunks of the model
+    double *mNo = nullptr, *mPio = nullptr, *mT = nullptr;   // [rup(mtile, 1024)][mp]: No (then PHI), Pio, T = Pio NijS
+    double *mbt = nullptr, *mNij = nullptr, *mpri = nullptr, *mhd = nullptr;   // [2][mp]; [mp][mp]; the priors; [2k][rup(mtile, 1024)]
+    double *mU = nullptr, *mrec = nullptr, *mpart = nullptr, *mout = nullptr;  // the pair tables, chunk slab and [4k] outputs (not for draws)
+    bool mtab_valid = false, mtab_pairs = false, mtab_uniform = false;         // the tables hold (mtab_obs, mtab_pri); U and records too
+    unsigned mtab_obs = 0;
+    std::vector<double> mtab_pri;
+};
+
+namespace gpzi {
+// The kind of rows of a call.  Clean: complete rows.  Noisy: rows with Psi in Psic[s] beside Xc[s].  Missing: one group of rows that
+// share the NaN pattern obs (the bit mask of the observed dimensions), with the priors of the set (m values, or nullptr for 1 / m).
+// What a tile is made of for a kind is answered by the rows_* functions below; the runners of every entry go through them.
+enum RowKind { ROWS_CLEAN = 0, ROWS_NOISY = 1, ROWS_MISSING = 2 };
+struct Rows {
+    RowKind kind = ROWS_CLEAN;
+    uint32_t obs = 0;
+    const double *priors = nullptr;
+};
+
+// ---- what a kind of rows is made of (gpz_predictor.hip) ------------------------------------------------------------------------------
+int rows_check(const char *who, const gpz_predictor *p, const Rows &r, bool draws);
+int rows_prepare(gpz_predictor *p, const char *who, const Rows &r, bool pairs);
+int64_t rows_tile(const gpz_predictor *p, const Rows &r, int64_t T);
+int rows_moments_tile(gpz_predictor *p, const char *who, const Rows &r, int s, int nt, bool want_phi);
+const double *rows_moments(const gpz_predictor *p, const Rows &r, int s);
+int rows_draws_prepare(gpz_predictor *p, const Rows &r, int nd, unsigned long long seed, const double *Z, bool pinned, int64_t *Tout);
+int rows_draws_tile(gpz_predictor *p, const char *who, const Rows &r, int s, int nt, int ncol, int ldw, bool after_moments);
+int rows_gamma_prepare(gpz_predictor *p, const Rows &r, int ncol, int Q, int64_t T);
+int rows_gamma_tile(gpz_predictor *p, const char *who, const Rows &r, int s, int nt, int ncol, int ldw);
+int rows_chunks(const gpz_predictor *p, const Rows &r);
+
+int predictor_want_phi(gpz_predictor *p, bool pinned = true);
+int predictor_psi_slots(gpz_predictor *p);
+
+// ---- stack ---------------------------------------------------------------------------------------------------------------------------
+struct StackCall {
+    int nd, B, G, ncol, ldw;
+    int R;           // row slabs per tile
+    size_t ne;       // the edges; behind them in edges_d, the k shifts of the sums
+    size_t count;    // doubles in the accumulators
+    int64_t T;       // rows per tile
+};
+// the arguments of every stack entry behind its rows
+struct StackArgs {
+    int32_t ndraws;
+    uint64_t seed;
+    const double *Z, *edges;
+    int32_t nbins;
+    const int32_t *group;
+    int32_t ngroups;
+    const double *weight;
+    double *hist, *sum_w, *sum_mu, *sum_mu2;
+    const double *mu_shift;
+};
+int predictor_stack_prepare(gpz_predictor *p, const char *who, const Rows &r, const StackArgs &a, bool pinned, StackCall *c);
+int predictor_stack_tile(gpz_predictor *p, const char *who, const Rows &r, const StackCall &c, int s, int64_t nt, const int *lab,
+                         const double *wt);
+int predictor_stack_result(gpz_predictor *p, const char *who, const StackCall &c, double *res);
+
+// ---- what the entries share ----------------------------------------------------------------------------------------------------------
+int predictor_check_call(const char *who, const gpz_predictor *p, int64_t ns);
+int predictor_check_ndraws(const char *who, const gpz_predictor *p, int32_t ndraws, int least);
+int stack_check_shape(const char *who, const gpz_predictor *p, int64_t ns, const StackArgs &a, const void *Xs);
+int stack_check_shift(const char *who, const gpz_predictor *p, const double *mu_shift);
+void stack_zero(const gpz_predictor *p, const StackArgs &a);
+void stack_unpack(const gpz_predictor *p, const StackArgs &a, const double *res);
+
+// Every entry after create runs its body through here: the handle's options and device for the length of the call, the caller's device
+// again on every way out.
+template <class Body>
+int predictor_call(gpz_predictor *p, const char *who, Body body) {
+    int prev = 0;
+    (void)hipGetDevice(&prev);
+    gpz_opts_scope opts_scope(&p->opt);
+    int rc = 0;
+    if (hipSetDevice(p->device) != hipSuccess) rc = gpz_fail(GPZ_ERR_HIP, "%s: hipSetDevice failed", who);
+    if (!rc) rc = body();
+    (void)hipSetDevice(prev);
+    return rc;
+}
+
+// Every stack entry: the shape checks in the order gpz_predictor_stack has always made them, the entry's own (check: the kind's, then
+// the host loop over the labels or the layout of the device rows), the shift, what the entry checks behind it (late: the host loop over
+// the weights), the empty call, and run(res) inside predictor_call with the records that stack_unpack takes apart.
+// zero_first: gpz_predictor_stack alone clears its outputs once its arguments have passed, so a refusal of its rows leaves zeros; the
+// entries added after it leave their outputs untouched on every refusal.  Callers rely on either, so both stay.
+template <class Check, class Late, class Run>
+int stack_entry(const char *who, gpz_predictor *p, int64_t ns, const void *Xs, const StackArgs &a, bool zero_first, Check check, Late late,
+                Run run) {
+    if (int rc = stack_check_shape(who, p, ns, a, Xs)) return rc;
+    if (int rc = check()) return rc;
+    if (int rc = stack_check_shift(who, p, a.mu_shift)) return rc;
+    if (int rc = late()) return rc;
+    if (zero_first || ns == 0) stack_zero(p, a);
+    if (ns == 0) return 0;
+    std::vector<double> res((size_t)(1 + a.ndraws) * p->k * ((size_t)a.ngroups * a.nbins + 3 * (size_t)a.ngroups));
+    if (int rc = predictor_call(p, who, [&] { return run(res.data()); })) return rc;
+    stack_unpack(p, a, res.data());
+    return 0;
+}
+}   // namespace gpzi

@@ -260,6 +260,297 @@ def test_stack_dev_refusals_in_order(handles):
     assert rc == 0 and all(np.all(a[:n] == 0.0) for a, n in zip(o, (2 * K * 2, 2, 2 * K, 2 * K)))
 
 
+# ---- the entries for rows with input noise and with missing inputs ------------------------------------------------------------------------
+MISS_FITS = ("missing inputs on the handle need predict_missing_fits: a diagonal kind (GL, VL, GD, VD), d <= 20, k <= 8 and "
+             "ceil16(m) <= 256 (method VC, d 5, m 50, k 2); gpz_predict_missing takes every shape")
+FULL_MASK = "no dimension is missing in the mask (complete rows go to gpz_predictor_run_dev / _draws_dev)"
+PATTERN = "the rows of a group must share one NaN pattern, the one of the mask"
+BAD_PSI = "Psi has an element that is NaN, infinite or negative"
+BAD_LAB = np.array([0, 1, -1, 7, 0, 1, 9, 0], dtype=np.int32)
+BAD_WT = np.array([1, 1, 1, 1, 1, -2.0, 1, 1], dtype=np.float64)
+OBS = 0x0f                                                                # dimension 4 is missing
+
+
+def sevens(*shape):
+    return torch.full(shape, 7.0, dtype=torch.float64, device=DEV)
+
+
+def refused_whole(got, code, text):
+    """refused, and the outputs of the call hold the 7.0 they were filled with."""
+    rc, o = got
+    refused(rc, code, text)
+    assert all(bool((a == 7.0).all()) for a in o)
+
+
+def stack_sevens(ndraws, nbins, ngroups):
+    C_, B, G = 1 + max(ndraws, 0), max(nbins, 1), max(ngroups, 1)
+    return [np.full(C_ * G * K * B, 7.0), np.full(G, 7.0), np.full(C_ * G * K, 7.0), np.full(C_ * G * K, 7.0)]
+
+
+def stack_tail(edges, nbins, group, ngroups, weight, o, shift, hist, ptr):
+    """edges .. mu_shift of a stack entry; ptr: what turns group and weight into the argument."""
+    e = np.ascontiguousarray(np.tile(np.asarray(edges, dtype=np.float64), (K, 1)))
+    return (_lib.dptr(e), nbins, ptr(group), ngroups, ptr(weight), _lib.dptr(o[0]) if hist else None, _lib.dptr(o[1]), _lib.dptr(o[2]),
+            _lib.dptr(o[3]), _lib.dptr(shift))
+
+
+def bad_rows():
+    """Rows with one NaN, and a Psi with one negative element (both normalised, column-major)."""
+    Xn, Pn = host_rows(), np.asfortranarray(np.full((8, D), 0.01))
+    Xn[6, 2] = np.nan
+    Pn[1, 4] = -0.5
+    return Xn, Pn
+
+
+def missing_rows():
+    """Eight rows of the pattern OBS; the same with a second NaN in row 3."""
+    Xm = np.ascontiguousarray(host_rows())
+    Xm[:, 4] = np.nan
+    Xw = Xm.copy()
+    Xw[3, 1] = np.nan
+    return torch.from_numpy(Xm).to(DEV), torch.from_numpy(Xw).to(DEV)
+
+
+def test_stack_zeroes_its_outputs_before_it_runs(handles):
+    """gpz_predictor_stack alone clears its outputs once its arguments have passed: a refusal of the rows leaves zeros, an earlier one 7.0."""
+    lib = _lib.load()
+    _, h = handles["VD"]
+    Xn, _ = bad_rows()
+    e = np.ascontiguousarray(np.tile(np.array([0.0, 1.0, 2.0]), (K, 1)))
+
+    def call(weight=None):
+        o = stack_sevens(0, 2, 2)
+        ptr = [_lib.dptr(a) for a in o]
+        rc = lib.gpz_predictor_stack(h, _lib.dptr(Xn), 8, 0, 0, None, _lib.dptr(e), 2, None, 2, _lib.dptr(weight), *ptr, None)
+        return rc, o
+
+    refused_whole(call(weight=BAD_WT), ARG, "gpz_predictor_stack: the weight of row 5 is negative or not finite")
+    rc, o = call()
+    refused(rc, UNSUPPORTED, "gpz_predictor_stack: the rows have missing values (NaN): stacks are for complete rows")
+    assert all(np.all(a == 0.0) for a in o)
+
+
+def test_stack_noisy_refusals_in_order(handles):
+    lib = _lib.load()
+    X, P = host_rows(), np.asfortranarray(np.full((8, D), 0.01))
+    Xn, Pn = bad_rows()
+    inf_shift = np.array([0.0, np.inf])
+    who = "gpz_predictor_stack_noisy: "
+    vd, vdt, vc = (handles[n][1] for n in ("VD", "VDt", "VC"))
+
+    def call(h, x=X, psi=P, ns=8, ndraws=0, edges=(0.0, 1.0, 2.0), nbins=2, group=None, ngroups=2, weight=None, shift=None, hist=True):
+        o = stack_sevens(ndraws, nbins, ngroups)
+        lab = lambda a: None if a is None else (a.ctypes.data_as(_lib.c_int32_p) if a.dtype == np.int32 else _lib.dptr(a))
+        return lib.gpz_predictor_stack_noisy(h, _lib.dptr(x), ns, _lib.dptr(psi), ndraws, 0, None,
+                                             *stack_tail(edges, nbins, group, ngroups, weight, o, shift, hist, lab)), o
+
+    refused_whole(call(None, ns=-1, ndraws=-1), ARG, who + "null handle")
+    refused_whole(call(vc, ns=-1, ndraws=-1), ARG, who + "ns < 0")
+    refused_whole(call(vc, ndraws=-1, nbins=0), ARG, who + "need 0 <= ndraws and (1 + ndraws) * k <= 16384 (ndraws -1, k 2)")
+    refused_whole(call(vc, nbins=0, edges=(0.0, 1.0, 1.0)), ARG, who + "need nbins >= 1 and ngroups >= 1")
+    refused_whole(call(vc, nbins=41, ngroups=100, edges=np.arange(42.0), hist=False), ARG,
+                  who + "ngroups * nbins = 4100 is over GPZ_STACK_MAX_GROUP_BINS = 4096")
+    refused_whole(call(vc, edges=(0.0, 1.0, 1.0), hist=False), ARG, who + "null argument")
+    refused_whole(call(vc, x=None, edges=(0.0, 1.0, 1.0)), ARG, who + "the edges must be finite and strictly increasing (output 0, edge 2)")
+    refused_whole(call(vc, x=None), ARG, who + "null argument")
+    refused_whole(call(vc, psi=None), UNSUPPORTED, who + NOT_FITS)
+    refused_whole(call(vdt, psi=None), UNSUPPORTED, who + FORCED)
+    refused_whole(call(vdt, x=None, psi=None, ns=0), UNSUPPORTED, who + FORCED)
+    refused_whole(call(vd, psi=None, group=BAD_LAB), ARG, who + "null Psi")
+    refused_whole(call(vd, group=BAD_LAB, weight=BAD_WT, shift=inf_shift), ARG, who + "label 7 of row 3 is outside [-1, 2)")
+    refused_whole(call(vd, weight=BAD_WT, shift=inf_shift), ARG, who + "mu_shift must be finite")
+    refused_whole(call(vd, x=Xn, weight=BAD_WT), ARG, who + "the weight of row 5 is negative or not finite")
+    rc, o = call(vd, x=None, psi=None, ns=0)
+    assert rc == 0 and all(np.all(a == 0.0) for a in o)                   # no rows: zeros
+    refused_whole(call(vd, x=Xn, psi=Pn), UNSUPPORTED, who + "the rows have missing values (NaN): stacks are for complete rows")
+    refused_whole(call(vd, psi=Pn), ARG, who + BAD_PSI)
+
+
+def test_stack_noisy_dev_refusals_in_order(handles):
+    lib = _lib.load()
+    X, P = dev_rows(), torch.full((8, D), 0.01, dtype=torch.float64, device=DEV)
+    Xn, Pn = (torch.from_numpy(np.ascontiguousarray(a)).to(DEV) for a in bad_rows())
+    lab, wt = torch.from_numpy(BAD_LAB).to(DEV), torch.from_numpy(BAD_WT).to(DEV)
+    v, nan_shift = np.ones(D), np.array([np.nan, 0.0])
+    who = "gpz_predictor_stack_noisy_dev: "
+    vd, vdt, vc = (handles[n][1] for n in ("VD", "VDt", "VC"))
+
+    def call(h, x=X.data_ptr(), x_type=0, ns=8, rs=D, psi=P.data_ptr(), psi_type=0, psi_rs=D, mu=None, sd=None, sd2=None, ndraws=0,
+             edges=(0.0, 1.0, 2.0), nbins=2, group=None, ngroups=2, weight=None, shift=None, hist=True):
+        o = stack_sevens(ndraws, nbins, ngroups)
+        ptr = lambda t: None if t is None else t.data_ptr()
+        return lib.gpz_predictor_stack_noisy_dev(h, x, x_type, ns, rs, 1, psi, psi_type, psi_rs, 1, _lib.dptr(mu), _lib.dptr(sd),
+                                                 _lib.dptr(sd2), ndraws, 0, None,
+                                                 *stack_tail(edges, nbins, group, ngroups, weight, o, shift, hist, ptr), None), o
+
+    refused_whole(call(None, ns=-1, ndraws=-1), ARG, who + "null handle")
+    refused_whole(call(vc, ns=-1, ndraws=-1), ARG, who + "ns < 0")
+    refused_whole(call(vc, ndraws=-1, nbins=0), ARG, who + "need 0 <= ndraws and (1 + ndraws) * k <= 16384 (ndraws -1, k 2)")
+    refused_whole(call(vc, nbins=0, hist=False), ARG, who + "need nbins >= 1 and ngroups >= 1")
+    refused_whole(call(vc, hist=False, edges=(0.0, np.inf, 2.0)), ARG, who + "null argument")
+    refused_whole(call(vc, x=None, edges=(0.0, np.inf, 2.0)), ARG,
+                  who + "the edges must be finite and strictly increasing (output 0, edge 1)")
+    refused_whole(call(vc, x=None), ARG, who + "null argument")
+    refused_whole(call(vc, x_type=7), UNSUPPORTED, who + NOT_FITS)
+    refused_whole(call(vdt, x_type=7), UNSUPPORTED, who + FORCED)
+    refused_whole(call(vd, x_type=7, psi_type=9), ARG, who + "x_type 7 is neither GPZ_X_F64 nor GPZ_X_F32")
+    refused_whole(call(vd, mu=v, psi_type=9), ARG, who + "muX and sdX go together (both or neither)")
+    refused_whole(call(vd, rs=0, psi_type=9), ARG, who + "strides (0, 1) of 8 rows: a stride must be positive")
+    refused_whole(call(vd, psi_type=9, mu=v, sd=v), ARG, who + "psi_type 9 is neither GPZ_X_F64 nor GPZ_X_F32")
+    refused_whole(call(vd, psi=None, mu=v, sd=v), ARG, who + "sdX and sd2 go together (both or neither)")
+    refused_whole(call(vd, psi=None, psi_rs=0), ARG, who + "null Psi")
+    refused_whole(call(vd, psi_rs=0, shift=nan_shift), ARG, who + "Psi strides (0, 1) of 8 rows: the row stride must be positive")
+    refused_whole(call(vd, shift=nan_shift, group=lab), ARG, who + "mu_shift must be finite")
+    refused_whole(call(vd, ns=0, shift=nan_shift), ARG, who + "mu_shift must be finite")
+    rc, o = call(vd, x=None, psi=None, ns=0)
+    assert rc == 0 and all(np.all(a == 0.0) for a in o)                   # no rows: zeros
+    # the scan of the rows, Psi, labels and weights
+    refused_whole(call(vd, group=lab, weight=wt), ARG, who + "a label is outside [-1, 2)")
+    refused_whole(call(vd, x=Xn.data_ptr(), weight=wt), ARG, who + "a weight is negative or not finite")
+    refused_whole(call(vd, x=Xn.data_ptr(), psi=Pn.data_ptr()), UNSUPPORTED,
+                  who + "the rows have missing values (NaN): stacks are for complete rows")
+    refused_whole(call(vd, psi=Pn.data_ptr()), ARG, who + BAD_PSI)
+
+
+def test_draws_gamma_noisy_dev_refusals_in_order(handles):
+    lib = _lib.load()
+    X, P = dev_rows(), torch.full((8, D), 0.01, dtype=torch.float64, device=DEV)
+    Xn, Pn = (torch.from_numpy(np.ascontiguousarray(a)).to(DEV) for a in bad_rows())
+    v = np.ones(D)
+    who = "gpz_predictor_draws_gamma_noisy_dev: "
+    vd, vdt, vc = (handles[n][1] for n in ("VD", "VDt", "VC"))
+
+    def call(h, ndraws=3, x=X.data_ptr(), x_type=0, psi=P.data_ptr(), psi_type=0, psi_rs=D, sdX=None, ns=8, F=True, Gam=True):
+        o = [sevens(3, 8, K), sevens(3, 8, K)]
+        return lib.gpz_predictor_draws_gamma_noisy_dev(h, x, x_type, ns, D, 1, psi, psi_type, psi_rs, 1, _lib.dptr(sdX), _lib.dptr(sdX), None,
+                                                       None, ndraws, 0, None, o[0].data_ptr() if F else None,
+                                                       o[1].data_ptr() if Gam else None, None), o
+
+    refused_whole(call(None, ndraws=0, ns=-1), ARG, who + "null handle")
+    refused_whole(call(vc, ndraws=0, ns=-1), ARG, who + "ns < 0")
+    refused_whole(call(vc, ndraws=0), ARG, who + "need 1 <= ndraws and ndraws * k <= 16384 (ndraws 0, k 2)")
+    refused_whole(call(vc, x_type=7), UNSUPPORTED, who + NOT_FITS)
+    refused_whole(call(vdt, x_type=7), UNSUPPORTED, who + FORCED)
+    refused_whole(call(vd, x_type=7, psi=None), ARG, who + "x_type 7 is neither GPZ_X_F64 nor GPZ_X_F32")
+    refused_whole(call(vd, psi=None, psi_type=9), ARG, who + "psi_type 9 is neither GPZ_X_F64 nor GPZ_X_F32")
+    refused_whole(call(vd, psi=None, sdX=v), ARG, who + "sdX and sd2 go together (both or neither)")
+    refused_whole(call(vd, psi=None, psi_rs=0), ARG, who + "null Psi")
+    refused_whole(call(vd, psi_rs=0, Gam=False), ARG, who + "Psi strides (0, 1) of 8 rows: the row stride must be positive")
+    assert call(vd, ns=0, F=False, Gam=False)[0] == 0
+    refused_whole(call(vd, x=Xn.data_ptr(), Gam=False), ARG, who + "null argument")
+    refused_whole(call(vd, x=Xn.data_ptr(), F=False), ARG, who + "null argument")
+    refused_whole(call(vd, x=Xn.data_ptr(), psi=Pn.data_ptr()), UNSUPPORTED,
+                  who + "the rows have missing values (NaN): draws are for complete rows")
+    refused_whole(call(vd, psi=Pn.data_ptr()), ARG, who + BAD_PSI)
+
+
+def missing_ladder(handles, who, call, outputs_needed):
+    """The refusals that gpz_predictor_run_missing_dev, _draws_missing_dev and _draws_gamma_missing_dev share behind their own first
+    ones: the model, the mask, the rows' layout, the outputs, then the scan.  call(h, **what is wrong) -> (rc, outputs)."""
+    vd, vc = handles["VD"][1], handles["VC"][1]
+    Xm, Xw = missing_rows()
+    v = np.ones(D)
+    refused_whole(call(vc, obs=0x2f), UNSUPPORTED, who + MISS_FITS)
+    refused_whole(call(vd, obs=0x2f, x_type=7), ARG, who + "the mask 0x2f has a bit at or above d = 5")
+    refused_whole(call(vd, obs=0x1f, x_type=7), ARG, who + FULL_MASK)
+    refused_whole(call(vd, x_type=7, mu=v), ARG, who + "x_type 7 is neither GPZ_X_F64 nor GPZ_X_F32")
+    refused_whole(call(vd, mu=v, x=None), ARG, who + "muX and sdX go together (both or neither)")
+    refused_whole(call(vd, x=None, rs=0), ARG, who + "null argument")
+    refused_whole(call(vd, x=Xw.data_ptr(), rs=0), ARG, who + "strides (0, 1) of 8 rows: a stride must be positive")
+    assert call(vd, x=None, ns=0, out=False)[0] == 0
+    for drop in outputs_needed:
+        refused_whole(call(vd, x=Xw.data_ptr(), out=drop), ARG, who + "null argument")
+    refused_whole(call(vd, x=Xw.data_ptr()), ARG, who + PATTERN)            # a row with a second NaN
+    refused_whole(call(vd, x=dev_rows().data_ptr()), ARG, who + PATTERN)    # complete rows under a mask with a missing dimension
+    rc, o = call(vd, x=Xm.data_ptr())
+    assert rc == 0 and not bool((o[0] == 7.0).any())                      # the group itself is taken
+
+
+def test_run_missing_dev_refusals_in_order(handles):
+    lib = _lib.load()
+    who = "gpz_predictor_run_missing_dev: "
+
+    def call(h, x=None, x_type=0, ns=8, rs=D, mu=None, obs=OBS, out=True):
+        o = [sevens(K, 8) for _ in range(5)]
+        ptr = [None] * 5 if out is False else [None if i == out and out is not True else t.data_ptr() for i, t in enumerate(o)]
+        return lib.gpz_predictor_run_missing_dev(h, x, x_type, ns, rs, 1, _lib.dptr(mu), None, None, None, obs, *ptr, None), o
+
+    refused_whole(call(None, ns=-1, obs=0x2f), ARG, who + "null handle")
+    refused_whole(call(handles["VC"][1], ns=-1, obs=0x2f), ARG, who + "ns < 0")
+    missing_ladder(handles, who, call, outputs_needed=(0, 2, 3))          # mu, nu, beta; sigma and gamma may be left out
+
+
+def test_draws_missing_dev_refusals_in_order(handles):
+    lib = _lib.load()
+    who = "gpz_predictor_draws_missing_dev: "
+
+    def call(h, x=None, x_type=0, ns=8, rs=D, mu=None, obs=OBS, ndraws=3, out=True):
+        o = [sevens(3, 8, K)]
+        return lib.gpz_predictor_draws_missing_dev(h, x, x_type, ns, rs, 1, _lib.dptr(mu), None, None, None, obs, ndraws, 0, None,
+                                                   o[0].data_ptr() if out is True else None, None), o
+
+    refused_whole(call(None, ns=-1, ndraws=0), ARG, who + "null handle")
+    refused_whole(call(handles["VC"][1], ns=-1, ndraws=0), ARG, who + "ns < 0")
+    refused_whole(call(handles["VC"][1], ndraws=0, obs=0x2f), ARG, who + "need 1 <= ndraws and ndraws * k <= 16384 (ndraws 0, k 2)")
+    missing_ladder(handles, who, call, outputs_needed=(0,))
+
+
+def test_draws_gamma_missing_dev_refusals_in_order(handles):
+    lib = _lib.load()
+    who = "gpz_predictor_draws_gamma_missing_dev: "
+
+    def call(h, x=None, x_type=0, ns=8, rs=D, mu=None, obs=OBS, ndraws=3, out=True):
+        o = [sevens(3, 8, K), sevens(3, 8, K)]
+        ptr = [None, None] if out is False else [None if i == out and out is not True else t.data_ptr() for i, t in enumerate(o)]
+        return lib.gpz_predictor_draws_gamma_missing_dev(h, x, x_type, ns, rs, 1, _lib.dptr(mu), None, None, None, obs, ndraws, 0, None,
+                                                         *ptr, None), o
+
+    refused_whole(call(None, ns=-1, ndraws=0), ARG, who + "null handle")
+    refused_whole(call(handles["VC"][1], ns=-1, ndraws=0), ARG, who + "ns < 0")
+    refused_whole(call(handles["VC"][1], ndraws=0, obs=0x2f), ARG, who + "need 1 <= ndraws and ndraws * k <= 16384 (ndraws 0, k 2)")
+    missing_ladder(handles, who, call, outputs_needed=(0, 1))
+
+
+def test_stack_missing_dev_refusals_in_order(handles):
+    lib = _lib.load()
+    Xm, Xw = missing_rows()
+    lab, wt = torch.from_numpy(BAD_LAB).to(DEV), torch.from_numpy(BAD_WT).to(DEV)
+    v, nan_shift = np.ones(D), np.array([np.nan, 0.0])
+    who = "gpz_predictor_stack_missing_dev: "
+    vd, vc = handles["VD"][1], handles["VC"][1]
+
+    def call(h, x=Xm.data_ptr(), x_type=0, ns=8, rs=D, mu=None, obs=OBS, ndraws=0, edges=(0.0, 1.0, 2.0), nbins=2, group=None, ngroups=2,
+             weight=None, shift=None, hist=True):
+        o = stack_sevens(ndraws, nbins, ngroups)
+        ptr = lambda t: None if t is None else t.data_ptr()
+        return lib.gpz_predictor_stack_missing_dev(h, x, x_type, ns, rs, 1, _lib.dptr(mu), None, None, obs, ndraws, 0, None,
+                                                   *stack_tail(edges, nbins, group, ngroups, weight, o, shift, hist, ptr), None), o
+
+    refused_whole(call(None, ns=-1, ndraws=-1), ARG, who + "null handle")
+    refused_whole(call(vc, ns=-1, ndraws=-1), ARG, who + "ns < 0")
+    refused_whole(call(vc, ndraws=-1, nbins=0), ARG, who + "need 0 <= ndraws and (1 + ndraws) * k <= 16384 (ndraws -1, k 2)")
+    refused_whole(call(vc, nbins=0, hist=False), ARG, who + "need nbins >= 1 and ngroups >= 1")
+    refused_whole(call(vc, hist=False, edges=(0.0, np.inf, 2.0)), ARG, who + "null argument")
+    refused_whole(call(vc, x=None, edges=(0.0, np.inf, 2.0)), ARG,
+                  who + "the edges must be finite and strictly increasing (output 0, edge 1)")
+    refused_whole(call(vc, x=None, obs=0x2f), ARG, who + "null argument")
+    refused_whole(call(vc, obs=0x2f), UNSUPPORTED, who + MISS_FITS)
+    refused_whole(call(vd, obs=0x2f, x_type=7), ARG, who + "the mask 0x2f has a bit at or above d = 5")
+    refused_whole(call(vd, obs=0x1f, x_type=7), ARG, who + FULL_MASK)
+    refused_whole(call(vd, x_type=7, mu=v), ARG, who + "x_type 7 is neither GPZ_X_F64 nor GPZ_X_F32")
+    refused_whole(call(vd, mu=v, rs=0), ARG, who + "muX and sdX go together (both or neither)")
+    refused_whole(call(vd, rs=0, shift=nan_shift), ARG, who + "strides (0, 1) of 8 rows: a stride must be positive")
+    refused_whole(call(vd, shift=nan_shift, group=lab), ARG, who + "mu_shift must be finite")
+    refused_whole(call(vd, ns=0, shift=nan_shift), ARG, who + "mu_shift must be finite")
+    rc, o = call(vd, x=None, ns=0)
+    assert rc == 0 and all(np.all(a == 0.0) for a in o)                   # no rows: zeros
+    # the scan of the rows, labels and weights
+    refused_whole(call(vd, group=lab, weight=wt), ARG, who + "a label is outside [-1, 2)")
+    refused_whole(call(vd, x=Xw.data_ptr(), weight=wt), ARG, who + "a weight is negative or not finite")
+    refused_whole(call(vd, x=Xw.data_ptr()), ARG, who + PATTERN)          # a row with a second NaN
+    refused_whole(call(vd, x=dev_rows().data_ptr()), ARG, who + PATTERN)  # complete rows under a mask with a missing dimension
+
+
 # ---- the Python methods -------------------------------------------------------------------------------------------------------------------
 def raises(kind, text):
     return pytest.raises(kind, match="^" + re.escape(text))

@@ -1,12 +1,17 @@
 """SHA-256 of everything the streaming predictor returns, for comparing two builds of the library bit for bit
-(profiles/r11_predictor_refactor.txt: the host code of gpz_predictor.hip before and after it was folded onto one pipeline).
+(profiles/r11_predictor_refactor.txt: the host code of gpz_predictor.hip before and after it was folded onto one pipeline;
+profiles/r14_predictor_row_kinds.txt: before and after clean, noisy and missing rows were folded onto one set of runners and the unit
+was cut into gpz_predictor.hip, gpz_predictor_host.hip and gpz_predictor_dev.hip behind gpz_predictor.h).
 
     python tools/predictor_digest.py > digest.txt        # in each tree, on the same machine; then diff the two files
 
 Seeded models of both kinds (VD, VC) on both routes (fused, force_tiles) with k = 1 and 3, d = 5, m = 50; 2500 rows in 1024-row tiles
 (the last one partial).  Every entry of the handle is called: predict with and without PHI and with Psi, draws by seed and by an
 explicit Z and with Psi, stack with and without draws, groups and weights, and the device entries on float64, float32 and strided
-rows.  After each call one line: the call, the digest of each array it returned, and the handle's route and info."""
+rows; on the VD models the stacks of rows with input noise (host and device) and gamma per draw beside the draws, and, on the same
+rows with four NaN patterns knocked out, predict_dev, draws_dev (with and without gamma) and the stack of rows with missing inputs; a
+third handle meets the missing stack first, then the noisy one, then predict.  After each call one line: the call, the digest of
+each array it returned, and the handle's route and info."""
 import hashlib
 import os
 import sys
@@ -31,6 +36,17 @@ def digest(a):
 def report(tag, p, out):
     out = out if isinstance(out, tuple) else (out,)
     print(f"{tag}: {' '.join(digest(a) for a in out)} | {p.route} | {p.info}", flush=True)
+
+
+def four_patterns(X):
+    """tests/test_predictor_stack_missing.py's: of every ten rows five without the last dimension, one with dimension 0 only, one with
+    nothing observed, three complete."""
+    X = X.copy()
+    r = np.arange(X.shape[0]) % 10
+    X[r < 5, X.shape[1] - 1] = np.nan
+    X[r == 5, 1:] = np.nan
+    X[r == 6, :] = np.nan
+    return X
 
 
 def run(method, k, force):
@@ -74,11 +90,35 @@ def run(method, k, force):
         report(f"{tag} predict_dev sel", p, p.predict_dev(Xd, selection=sd))
         report(f"{tag} draws_dev Z sel", p, p.draws_dev(Xd, DRAWS, Z=Z, selection=sd))
         report(f"{tag} stack_dev plain", p, tuple(p.stack_dev(Xd, edges, selection=sd)))
+        by_group = dict(groups=groups, n_groups=3, weights=weights)
+        by_group_d = dict(groups=gd, n_groups=3, weights=wd)
+        if noisy and not force:                                          # the stacks with Psi and gamma per draw need the fused draws route
+            report(f"{tag} stack_noisy", p, tuple(p.stack_noisy(X, Psi, edges)))
+            report(f"{tag} stack_noisy draws", p, tuple(p.stack_noisy(X, Psi, edges, n_draws=DRAWS, seed=11, **by_group)))
+            report(f"{tag} stack_noisy Z sel", p, tuple(p.stack_noisy(X, Psi, edges, n_draws=DRAWS, Z=Z, selection=sel, **by_group)))
+            report(f"{tag} stack_noisy_dev", p, tuple(p.stack_noisy_dev(Xd, Pd, edges)))
+            report(f"{tag} stack_noisy_dev draws", p, tuple(p.stack_noisy_dev(Xd, Pd, edges, n_draws=DRAWS, seed=11, **by_group_d)))
+            report(f"{tag} stack_noisy_dev Z sel", p, tuple(p.stack_noisy_dev(Xd, Pd, edges, n_draws=DRAWS, Z=Z, selection=sd, **by_group_d)))
+            report(f"{tag} draws_dev psi gamma", p, p.draws_dev(Xd, DRAWS, seed=11, Psi=Pd, return_gamma=True))
+        if noisy:                                                        # predict_missing_fits: rows with missing inputs on the handle
+            Xm = torch.from_numpy(four_patterns(X)).to(DEV)
+            report(f"{tag} predict_dev missing", p, p.predict_dev(Xm, missing=True))
+            report(f"{tag} draws_dev missing", p, p.draws_dev(Xm, DRAWS, seed=11, missing=True))
+            report(f"{tag} draws_dev missing gamma", p, p.draws_dev(Xm, DRAWS, Z=Z, missing=True, return_gamma=True))
+            report(f"{tag} stack_missing_dev", p, tuple(p.stack_missing_dev(Xm, edges)))
+            report(f"{tag} stack_missing_dev draws", p, tuple(p.stack_missing_dev(Xm, edges, n_draws=DRAWS, seed=11, **by_group_d)))
+            report(f"{tag} stack_missing_dev Z sel", p, tuple(p.stack_missing_dev(Xm, edges, n_draws=DRAWS, Z=Z, selection=sd, **by_group_d)))
     with gpz_amd.Predictor(model, tile_rows=TILE, force_tiles=force) as p:   # a handle that meets the stack first, then PHI
         report(f"{tag} second handle stack_dev", p, tuple(p.stack_dev(Xd, edges, n_draws=2, seed=3)))
         report(f"{tag} second handle stack", p, tuple(p.stack(X, edges, n_draws=DRAWS, seed=3)))
         report(f"{tag} second handle predict_dev phi", p, p.predict_dev(Xd, return_phi=True))
         report(f"{tag} second handle predict phi", p, p.predict(X, return_phi=True))
+    if noisy and not force:   # a handle that meets the missing stack first, then the noisy one, then predict: the per-kind state the other way
+        with gpz_amd.Predictor(model, tile_rows=TILE) as p:
+            report(f"{tag} third handle stack_missing_dev", p, tuple(p.stack_missing_dev(Xm, edges, n_draws=2, seed=3)))
+            report(f"{tag} third handle stack_noisy_dev", p, tuple(p.stack_noisy_dev(Xd, Pd, edges, n_draws=DRAWS, seed=3)))
+            report(f"{tag} third handle stack_noisy", p, tuple(p.stack_noisy(X, Psi, edges, n_draws=2, seed=3)))
+            report(f"{tag} third handle predict", p, p.predict(X))
 
 
 def main():
