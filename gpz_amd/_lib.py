@@ -126,6 +126,15 @@ SYMBOLS = {
                                                   c_double_p, c_double_p, C.c_uint32, C.c_int32, C.c_uint64, c_double_p, c_double_p,
                                                   C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, c_double_p, c_double_p, c_double_p,
                                                   c_double_p, c_double_p, C.c_void_p]),
+    # such a group whose rows have Psi too: the noisy entries with the priors and the mask behind muY
+    "gpz_predictor_run_noisy_missing_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_void_p,
+                                                      C.c_int32, C.c_int64, C.c_int64, c_double_p, c_double_p, c_double_p, c_double_p,
+                                                      c_double_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                      C.c_void_p]),
+    "gpz_predictor_draws_noisy_missing_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_void_p,
+                                                        C.c_int32, C.c_int64, C.c_int64, c_double_p, c_double_p, c_double_p, c_double_p,
+                                                        c_double_p, C.c_uint32, C.c_int32, C.c_uint64, c_double_p, C.c_void_p,
+                                                        C.c_void_p]),
     "gpz_prior": (C.c_int, [C.POINTER(gpz_desc), c_double_p, c_double_p, C.c_int64, c_double_p, C.c_int32, c_double_p,
                             c_int32_p]),
     "gpz_inv_logdet": (C.c_int, [c_double_p, C.c_int32, C.c_int32, c_double_p, c_double_p, c_int32_p]),

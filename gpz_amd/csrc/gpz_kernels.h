@@ -267,6 +267,26 @@ int launch_pmd_phi(hipStream_t st, double *No, const double *T, int n, int m, in
 int launch_predict_missing_pairs(hipStream_t st, const double *Xc, long ldx, int n, const double *Pio, int ldpio, int m, int d, int k,
                                  unsigned obs, const double *U, const double *rec, int nchunk, double *part, long ldp, const double *hd,
                                  long ldh, const double *bvec, double *out);
+// the finish kernel behind the pair kernel, on its own: hd [2k][ldh] = mu | ElnS - b and part [nchunk][3k][ldp] -> out [4k][n]
+int launch_pmd_finish(hipStream_t st, const double *part, int nchunk, long ldp, const double *hd, long ldh, int n, int k,
+                      const double *bvec, double *out);
+// ---- rows with input noise AND missing inputs through the streaming predictor (k_predict_noisy_missing.hip;
+// gpz_predictor_*_noisy_missing_dev).  One group as above, with Psic in the layout of Xc; the scope is predict_missing_fits.  NijS, bt
+// and U are launch_pmd_tables'; launch_pnm_records writes the second record table (predict_missing_groups(m) * 64 records of
+// predict_missing_rec(d, k) doubles: [lnZ without the ln det of the observed block | c | C | coefficients], the model's alone).  Per tile:
+// launch_pnm_no for launch_pmd_no, then launch_tgemm and launch_pmd_phi as above, launch_predict_noisy_missing_pairs (part and out as
+// launch_predict_missing_pairs; launch_pmd_finish inside).  launch_pnm_check_psi: word 3 of rec is set when Psi is NaN, negative or
+// infinite in an observed dimension; the missing ones are not read.  Every loop over dimensions runs over the set bits of obs.
+size_t predict_noisy_missing_lds(int m, int d, int k);   // dynamic LDS of k_predict_noisy_missing_pairs, bytes
+int launch_pnm_check_psi(hipStream_t st, const void *Psi, int f32, long ns, int d, long rs, long cs, unsigned obs, double smin,
+                         unsigned *rec);
+int launch_pnm_records(hipStream_t st, int m, int d, int de, int k, const double *P, const double *G2, const double *w, const double *v,
+                       const double *iS, double *rec);
+int launch_pnm_no(hipStream_t st, const double *Xc, const double *Psic, long ldx, int n, int nrow, int m, int mp, int de, unsigned obs,
+                  const double *P, const double *G2, const double *bt, double *No, double *Pio);
+int launch_predict_noisy_missing_pairs(hipStream_t st, const double *Xc, const double *Psic, long ldx, int n, const double *Pio, int ldpio,
+                                       int m, int d, int k, unsigned obs, const double *U, const double *rec, int nchunk, double *part,
+                                       long ldp, const double *hd, long ldh, const double *bvec, double *out);
 // ---- gamma under every weight draw for rows with missing inputs (k_predict_missing_gamma.hip; gpz_predictor_stack_missing_dev,
 // _draws_gamma_missing_dev).  part [nchunk][ncol][ldp] <- per pair chunk sum_{a >= b} f_ab EcC_ab(x_i) W[a, col] W[b, col] for the n rows
 // of the tile: Xc, Pio, U and rec as launch_predict_missing_pairs takes them (of a record only [lnZ | c | 1 / C] is read), W >= m rows x

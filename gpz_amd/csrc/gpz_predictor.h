@@ -78,17 +78,24 @@ struct gpz_predictor {
     bool mtab_valid = false, mtab_pairs = false, mtab_uniform = false;         // the tables hold (mtab_obs, mtab_pri); U and records too
     unsigned mtab_obs = 0;
     std::vector<double> mtab_pri;
+    // ---- rows with input noise and missing inputs (gpz_predictor_*_noisy_missing_dev): beyond the buffers above and the Psi slots, which
+    // such a call takes where the handle does not hold them yet, only this exists, and not before the first of their calls
+    bool nm_used = false;
+    double *nmrec = nullptr;       // the second pair-record table (k_pnm_records): the model's alone, written once
 };
 
 namespace gpzi {
 // The kind of rows of a call.  Clean: complete rows.  Noisy: rows with Psi in Psic[s] beside Xc[s].  Missing: one group of rows that
 // share the NaN pattern obs (the bit mask of the observed dimensions), with the priors of the set (m values, or nullptr for 1 / m).
-// What a tile is made of for a kind is answered by the rows_* functions below; the runners of every entry go through them.
-enum RowKind { ROWS_CLEAN = 0, ROWS_NOISY = 1, ROWS_MISSING = 2 };
+// Noisy missing: such a group with Psi in Psic[s] too (read in the observed dimensions only); moments and draws, no gamma per draw and
+// no stack.  What a tile is made of for a kind is answered by the rows_* functions below; the runners of every entry go through them.
+enum RowKind { ROWS_CLEAN = 0, ROWS_NOISY = 1, ROWS_MISSING = 2, ROWS_NOISY_MISSING = 3 };
 struct Rows {
     RowKind kind = ROWS_CLEAN;
     uint32_t obs = 0;
     const double *priors = nullptr;
+    bool psi() const { return kind == ROWS_NOISY || kind == ROWS_NOISY_MISSING; }        // Psic[s] is staged beside Xc[s]
+    bool group() const { return kind == ROWS_MISSING || kind == ROWS_NOISY_MISSING; }    // one NaN pattern, tiles of at most mtile rows
 };
 
 // ---- what a kind of rows is made of (gpz_predictor.hip) ------------------------------------------------------------------------------

@@ -41,6 +41,9 @@
 // shapes): gpz_predictor_run_missing_dev / _draws_missing_dev run predictMissing on tiles of at most GPZ_PREDICTOR_TILE_MISSING rows
 // (k_predict_missing.hip): No and Pio, PHI through k_tgemm, then the fused pair kernel, or for the draws k_tgemm against W.  The tables
 // of a pattern (NijS, the pair records, U) are kept until the pattern or the priors change; all of it is allocated on the first such call.
+// A group whose rows have Psi as well goes through gpz_predictor_run_noisy_missing_dev / _draws_noisy_missing_dev (predictNoisyMissing,
+// k_predict_noisy_missing.hip): the same tiles and tables with No widened by psi and a pair kernel whose epilogue is predictNoisy's, on a
+// second record table that is the model's alone.  Moments and draws only.
 // Layout: gpz_predictor.h holds the handle and what the three units share.  This unit holds the handle's life and setup, what a tile is
 // made of for each kind of rows (clean, with Psi, one NaN-pattern group: the rows_* functions), draws preparation and factorisation, the
 // stack's preparation and tile, the checks the entries share, route and info.  gpz_predictor_host.hip holds the host pipeline, its jobs
@@ -421,11 +424,24 @@ static int predictor_missing_check(const char *who, const gpz_predictor *p, uint
 // What a call for a group needs before its first tile: the tile buffers (on the first call; with pairs the pair tables, the chunk slab
 // and the output slot too) and the tables of (obs, priors), rebuilt where the handle holds another pattern's.  priors: m values or
 // nullptr for 1 / m.
-static int predictor_missing_prepare(gpz_predictor *p, const char *who, uint32_t obs, const double *priors, bool pairs) {
+// noisy: the rows have Psi too (ROWS_NOISY_MISSING) - the Psi slots and, with pairs, the second record table, which is the model's
+// alone and written once; the tables of the pattern are the same ones.
+static int predictor_missing_prepare(gpz_predictor *p, const char *who, uint32_t obs, const double *priors, bool pairs, bool noisy) {
     const size_t m = p->m, k = p->k, mp = p->mp, nk = rup(p->m, 16);
     auto &ar = p->ar;
     hipStream_t st = p->s_cmp;
     int rc = 0;
+    if (noisy) {
+        if ((rc = predictor_psi_slots(p))) return rc;
+        if (pairs && !p->nmrec) {
+            double *rec = nullptr;
+            if ((rc = ar.alloc(&rec, (size_t)predict_missing_groups(p->m) * 64 * (size_t)predict_missing_rec(p->d, p->k)))) return rc;
+            if (launch_pnm_records(st, p->m, p->d, p->de, p->k, p->pr.P, p->pr.G2, p->w_d, p->hetero ? p->pr.v : nullptr, p->iS_d, rec))
+                return gpz_fail(GPZ_ERR_HIP, "%s: record kernel launch failed", who);
+            p->nmrec = rec;
+        }
+        p->nm_used = true;
+    }
     if (!p->mtile) p->mtile = std::min<int64_t>(p->tile_rows, GPZ_PREDICTOR_TILE_MISSING);
     const size_t mtp = (size_t)rup(p->mtile, 1024), npad = (size_t)predict_missing_groups(p->m) * 64;
     p->mchunks = predict_missing_chunks(p->m);
@@ -442,7 +458,7 @@ static int predictor_missing_prepare(gpz_predictor *p, const char *who, uint32_t
         if (!p->mpart && (rc = ar.alloc(&p->mpart, (size_t)p->mchunks * 3 * k * mtp))) return rc;
         if (!p->mout && (rc = ar.alloc(&p->mout, 4 * k * mtp))) return rc;
     }
-    p->miss_used = true;
+    if (!noisy) p->miss_used = true;
     const bool same_pri = priors ? (!p->mtab_uniform && p->mtab_pri.size() == m && std::equal(priors, priors + m, p->mtab_pri.begin()))
                                  : p->mtab_uniform;
     if (p->mtab_valid && p->mtab_obs == obs && same_pri && (p->mtab_pairs || !pairs)) return 0;
@@ -463,18 +479,26 @@ static int predictor_missing_prepare(gpz_predictor *p, const char *who, uint32_t
 }
 
 // predictMissing of one tile of nt rows of the group: Xc[s] -> PHI in mNo, mu | ElnS - b in mhd and, with pairs, mout ([4k][nt] = mu | nu |
-// beta | gamma)
-static int predictor_missing_tile(gpz_predictor *p, const char *who, int s, int nt, uint32_t obs, bool pairs) {
+// beta | gamma).  Psic: the tile's Psi slot for a group with input noise too (predictNoisyMissing: No widened by psi, and the pair kernel
+// of k_predict_noisy_missing.hip on the second record table), else nullptr
+static int predictor_missing_tile(gpz_predictor *p, const char *who, int s, int nt, uint32_t obs, bool pairs, const double *Psic = nullptr) {
     hipStream_t st = p->s_cmp;
     const int np = rup(nt, 128);   // the rows of the product: k_tgemm's row tile
     const long mtp = rup(p->mtile, 1024);
     const double *v = p->hetero ? p->pr.v : nullptr;
-    if (launch_pmd_no(st, p->Xc[s], p->tile_pad, nt, np, p->m, p->mp, p->d, p->de, obs, p->pr.P, p->pr.G2, p->mbt, p->mNo, p->mPio))
-        return gpz_fail(GPZ_ERR_HIP, "%s: k_pmd_no launch failed", who);
+    if (Psic ? launch_pnm_no(st, p->Xc[s], Psic, p->tile_pad, nt, np, p->m, p->mp, p->de, obs, p->pr.P, p->pr.G2, p->mbt, p->mNo, p->mPio)
+             : launch_pmd_no(st, p->Xc[s], p->tile_pad, nt, np, p->m, p->mp, p->d, p->de, obs, p->pr.P, p->pr.G2, p->mbt, p->mNo, p->mPio))
+        return gpz_fail(GPZ_ERR_HIP, "%s: k_%s_no launch failed", who, Psic ? "pnm" : "pmd");
     launch_tgemm(st, p->mPio, p->mp, p->mNij, p->mp, p->mT, np, p->mp, nullptr, nullptr, p->m, -1);
     if (hipGetLastError() != hipSuccess) return gpz_fail(GPZ_ERR_HIP, "%s: k_tgemm launch failed", who);
     if (launch_pmd_phi(st, p->mNo, p->mT, nt, p->m, p->mp, p->k, p->w_d, v, p->mhd, mtp))
         return gpz_fail(GPZ_ERR_HIP, "%s: k_pmd_phi launch failed", who);
+    if (pairs && Psic) {
+        if (launch_predict_noisy_missing_pairs(st, p->Xc[s], Psic, p->tile_pad, nt, p->mPio, p->mp, p->m, p->d, p->k, obs, p->mU, p->nmrec,
+                                               p->mchunks, p->mpart, mtp, p->mhd, mtp, p->pr.b, p->mout))
+            return gpz_fail(GPZ_ERR_HIP, "%s: k_predict_noisy_missing_pairs launch failed", who);
+        return 0;
+    }
     if (pairs && launch_predict_missing_pairs(st, p->Xc[s], p->tile_pad, nt, p->mPio, p->mp, p->m, p->d, p->k, obs, p->mU, p->mrec, p->mchunks,
                                               p->mpart, mtp, p->mhd, mtp, p->pr.b, p->mout))
         return gpz_fail(GPZ_ERR_HIP, "%s: k_predict_missing_pairs launch failed", who);
@@ -494,7 +518,7 @@ static int predictor_missing_draws_tile(gpz_predictor *p, const char *who, int s
 // ---- what a kind of rows is made of ---------------------------------------------------------------------------------------------------
 // the kind's refusal of the model and, for a group, of its mask.  draws: the call has draws, which with Psi need the fused draws route
 int rows_check(const char *who, const gpz_predictor *p, const Rows &r, bool draws) {
-    if (r.kind == ROWS_MISSING) return predictor_missing_check(who, p, r.obs);
+    if (r.group()) return predictor_missing_check(who, p, r.obs);   // (with Psi too: its product against W needs no fused draws route)
     if (r.kind == ROWS_CLEAN) return 0;
     if (int rc = predictor_noisy_check(who, p)) return rc;
     if (draws && p->force_tiles)
@@ -505,31 +529,31 @@ int rows_check(const char *who, const gpz_predictor *p, const Rows &r, bool draw
 // What the call needs on the handle before its first tile.  pairs: it reads the kind's pair tables (the moments, gamma per draw, the
 // stack); the draws alone do not, and take the Psi slots or the group's tables without them.
 int rows_prepare(gpz_predictor *p, const char *who, const Rows &r, bool pairs) {
-    if (r.kind == ROWS_MISSING) return predictor_missing_prepare(p, who, r.obs, r.priors, pairs);
+    if (r.group()) return predictor_missing_prepare(p, who, r.obs, r.priors, pairs, r.kind == ROWS_NOISY_MISSING);
     if (r.kind == ROWS_NOISY) return pairs ? predictor_noisy_prepare(p) : predictor_psi_slots(p);
     return 0;
 }
 
 // the rows per tile of a call that would take T: No, Pio and T of a group hold mtile rows
-int64_t rows_tile(const gpz_predictor *p, const Rows &r, int64_t T) { return r.kind == ROWS_MISSING ? std::min<int64_t>(T, p->mtile) : T; }
+int64_t rows_tile(const gpz_predictor *p, const Rows &r, int64_t T) { return r.group() ? std::min<int64_t>(T, p->mtile) : T; }
 
 // the moments of one tile of nt rows in slot s -> rows_moments: [3k][nt] = mu | nu | beta for clean rows (and PHI when asked), else
 // [4k][nt] = mu | nu | beta | gamma
 int rows_moments_tile(gpz_predictor *p, const char *who, const Rows &r, int s, int nt, bool want_phi) {
-    if (r.kind == ROWS_MISSING) return predictor_missing_tile(p, who, s, nt, r.obs, true);
+    if (r.group()) return predictor_missing_tile(p, who, s, nt, r.obs, true, r.psi() ? p->Psic[s] : nullptr);
     if (r.kind == ROWS_NOISY) return predictor_noisy_tile(p, who, s, nt);
     return predictor_tile(p, s, nt, want_phi);
 }
 
 const double *rows_moments(const gpz_predictor *p, const Rows &r, int s) {
-    return r.kind == ROWS_MISSING ? p->mout : r.kind == ROWS_NOISY ? p->nout[s] : p->out[s];
+    return r.group() ? p->mout : r.kind == ROWS_NOISY ? p->nout[s] : p->out[s];
 }
 
 // the kind's tile for a call whose draws (or stack) would take *T rows, and for a group the output tile of its product PHI_missing W:
 // the tile route of the draws has one already, the fused route does not
 static int rows_fit_tile(gpz_predictor *p, const Rows &r, int ncol, int ldw, int64_t *T) {
     *T = rows_tile(p, r, *T);
-    if (r.kind != ROWS_MISSING || ncol == 0) return 0;
+    if (!r.group() || ncol == 0) return 0;
     return predictor_grow(p, &p->Td, &p->t_cap, (size_t)rup(*T, 1024) * ldw);
 }
 
@@ -545,7 +569,7 @@ int rows_draws_tile(gpz_predictor *p, const char *who, const Rows &r, int s, int
     if (r.kind == ROWS_CLEAN) return predictor_draws_tile(p, s, nt, ncol, ldw, after_moments && p->route == 1);
     if (r.kind == ROWS_NOISY) return predictor_draws_tile(p, s, nt, ncol, ldw, false, p->Psic[s]);
     if (!after_moments)
-        if (int rc = predictor_missing_tile(p, who, s, nt, r.obs, false)) return rc;
+        if (int rc = predictor_missing_tile(p, who, s, nt, r.obs, false, r.psi() ? p->Psic[s] : nullptr)) return rc;
     return predictor_missing_draws_tile(p, who, s, nt, ncol, ldw);
 }
 
@@ -554,6 +578,8 @@ int rows_chunks(const gpz_predictor *p, const Rows &r) { return r.kind == ROWS_M
 // What a call that needs gamma under nd draws on tiles of T rows adds to the handle (after rows_prepare with pairs: the pair table, or U
 // and the records): the chunk slab of the pair sums and, for a stack of Q column-outputs, the kind's widths.  nd = 0 takes no slab.
 int rows_gamma_prepare(gpz_predictor *p, const Rows &r, int ncol, int Q, int64_t T) {
+    if (r.kind == ROWS_NOISY_MISSING)   // (no entry comes here: gam[] has no slot for the kind)
+        return gpz_fail(GPZ_ERR_UNSUPPORTED, "gpz_predictor: gamma per draw and stacks are not there for rows with input noise and missing inputs");
     gpz_predictor::PerDraw &g = p->gam[r.kind - 1];
     int rc = 0;
     if (r.kind == ROWS_NOISY) p->gchunks = predict_gamma_chunks(p->m);
@@ -565,6 +591,8 @@ int rows_gamma_prepare(gpz_predictor *p, const Rows &r, int ncol, int Q, int64_t
 
 // the pair sums under every draw of one tile of nt rows (a group: after predictor_missing_tile, mPio): -> gpart ([chunks][ncol][nt])
 int rows_gamma_tile(gpz_predictor *p, const char *who, const Rows &r, int s, int nt, int ncol, int ldw) {
+    if (r.kind == ROWS_NOISY_MISSING)
+        return gpz_fail(GPZ_ERR_UNSUPPORTED, "%s: gamma per draw is not there for rows with input noise and missing inputs", who);
     if (r.kind == ROWS_NOISY
             ? launch_predict_noisy_gamma(p->s_cmp, p->d, p->Xc[s], p->Psic[s], p->tile_pad, nt, p->m, p->ptab, p->nrec, p->Wd, ldw, ncol,
                                          p->gchunks, p->gpart, nt)
@@ -593,6 +621,8 @@ int predictor_stack_prepare(gpz_predictor *p, const char *who, const Rows &r, co
     hipStream_t st = p->s_cmp;
     int rc = 0;
     int64_t T = p->tile_rows;
+    if (r.kind == ROWS_NOISY_MISSING)
+        return gpz_fail(GPZ_ERR_UNSUPPORTED, "%s: stacks are not there for rows with input noise and missing inputs", who);
     if (nd > 0 && (rc = predictor_draws_prepare(p, nd, (unsigned long long)a.seed, a.Z, false, &T))) return rc;
     for (int s = 0; s < 2 && pinned; ++s) {   // each one where it is missing: a call that failed half-way here leaves the next one its rest
         if (!p->lab_d[s] && (rc = p->ar.alloc(&p->lab_d[s], tp))) return rc;
@@ -792,6 +822,10 @@ extern "C" int gpz_predictor_route(const gpz_predictor *p, char *buf, int cap) {
         snprintf(tmp, sizeof tmp, "; missing per draw: k_predict_missing_gamma (%d pair chunks)", p->mchunks);
         r += tmp;
         if (p->gam[1].s2_d) r += " + k_stack_tile_w";   // the widths exist: a stack call was among them
+    }
+    if (p->nm_used) {   // after the first call for a group of rows with input noise and missing inputs
+        snprintf(tmp, sizeof tmp, "; noisy missing: k_predict_noisy_missing_pairs (%d pair chunks)", p->mchunks);
+        r += tmp;
     }
     snprintf(buf, (size_t)cap, "%s", r.c_str());
     return (int)r.size();

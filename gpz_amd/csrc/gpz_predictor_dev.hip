@@ -44,6 +44,12 @@ static DevCall with_pattern(DevCall c, const double *priors, uint32_t obs_mask) 
     return c;
 }
 
+// a group whose rows have Psi too: with_psi first, then the pattern
+static DevCall with_noisy_pattern(DevCall c, const double *priors, uint32_t obs_mask) {
+    c.rows = Rows{ROWS_NOISY_MISSING, obs_mask, priors};
+    return c;
+}
+
 static int predictor_dev_args(const char *who, const gpz_predictor *p, const DevRows &x, const double *muX, const double *sdX) {
     if (x.type != GPZ_X_F64 && x.type != GPZ_X_F32)
         return gpz_fail(GPZ_ERR_ARG, "%s: x_type %d is neither GPZ_X_F64 nor GPZ_X_F32", who, (int)x.type);
@@ -69,7 +75,7 @@ static int predictor_dev_psi_args(const char *who, const DevRows &psi, const dou
 
 static int predictor_dev_check(const char *who, const gpz_predictor *p, const DevCall &c) {
     if (int rc = predictor_dev_args(who, p, c.x, c.muX, c.sdX)) return rc;
-    return c.rows.kind == ROWS_NOISY ? predictor_dev_psi_args(who, c.psi, c.sdX, c.sd2) : 0;
+    return c.rows.psi() ? predictor_dev_psi_args(who, c.psi, c.sdX, c.sd2) : 0;
 }
 
 // the end of every device entry once it has prepared anything after predictor_dev_begin, failed or not: copies from the caller's memory
@@ -82,14 +88,15 @@ static int predictor_dev_sync(gpz_predictor *p, const char *who, int rc) {
 // What a device call does before its first tile: the parameter buffer (once per handle), muX, sdX and muY up, the compute stream after
 // everything queued on the caller's stream, and k_pred_check_dev over all rows with its verdict.  nan_text: the host entry's refusal of
 // rows with NaN.  What the kind needs on the handle (rows_prepare with pairs) comes before the scan for rows with Psi - a call that the
-// scan refuses leaves it there - and after it for a group with missing inputs: a refused group adds no byte to the handle.  A refusal
-// leaves the caller's outputs untouched.
+// scan refuses leaves it there - and after it for a group with missing inputs: a refused group adds no byte to the handle.  A group with
+// Psi too has its Psi scanned in the observed dimensions only (k_pnm_check_psi needs no device copy of sd2, which goes up behind
+// rows_prepare).  A refusal leaves the caller's outputs untouched.
 static int predictor_dev_begin(gpz_predictor *p, const char *who, DevCall &c, const int *lab, int G, const double *wt, const char *nan_text,
                                bool pairs) {
     const size_t d = p->d, k = p->k;
-    const DevRows &x = c.x, *psi = c.rows.kind == ROWS_NOISY ? &c.psi : nullptr;
+    const DevRows &x = c.x, *psi = c.rows.psi() ? &c.psi : nullptr;
     const double *muX = c.muX, *sdX = c.sdX, *muY = c.muY, *sd2 = c.sd2;
-    const unsigned obs = c.rows.obs, *pattern = c.rows.kind == ROWS_MISSING ? &obs : nullptr;
+    const unsigned obs = c.rows.obs, *pattern = c.rows.group() ? &obs : nullptr;
     if (!pattern)   // (the scan below needs sd2_d and the Psi slots)
         if (int rc = rows_prepare(p, who, c.rows, pairs)) return rc;
     hipStream_t st = p->s_cmp;
@@ -116,7 +123,10 @@ static int predictor_dev_begin(gpz_predictor *p, const char *who, DevCall &c, co
     // the labels and weights of a stack of such a group: k_pred_check_dev over no columns (words 1 and 2 only, X is not read)
     if (!rc && pattern && (lab || wt) && launch_pred_check_dev(st, nullptr, 0, x.ns, 0, 0, 0, lab, G, wt, rec))
         rc = gpz_fail(GPZ_ERR_HIP, "%s: k_pred_check_dev launch failed", who);
-    if (!rc && psi &&
+    if (!rc && psi && pattern &&
+        launch_pnm_check_psi(st, psi->X, psi->f32(), psi->ns, p->d, psi->rs, psi->cs, obs, sd2 ? *std::min_element(sd2, sd2 + d) : 1.0, rec))
+        rc = gpz_fail(GPZ_ERR_HIP, "%s: k_pnm_check_psi launch failed", who);
+    if (!rc && psi && !pattern &&
         ((sd2 && hipMemcpyAsync(p->sd2_d, sd2, d * sizeof(double), hipMemcpyHostToDevice, st) != hipSuccess) ||
          launch_pred_check_psi(st, psi->X, psi->f32(), psi->ns, p->d, psi->rs, psi->cs, sd2 ? *std::min_element(sd2, sd2 + d) : 1.0, rec)))
         rc = gpz_fail(GPZ_ERR_HIP, "%s: k_pred_check_psi launch failed", who);
@@ -133,9 +143,12 @@ static int predictor_dev_begin(gpz_predictor *p, const char *who, DevCall &c, co
     c.muX_d = muX ? p->par_d : nullptr;
     c.sdX_d = muX ? p->par_d + d : nullptr;
     c.muY_d = muY ? p->par_d + 2 * d : nullptr;
-    c.sd2_d = sd2 ? p->sd2_d : nullptr;
-    if (pattern)
+    if (pattern) {
         if (int rc = rows_prepare(p, who, c.rows, pairs)) return predictor_dev_sync(p, who, rc);
+        if (psi && sd2 && hipMemcpyAsync(p->sd2_d, sd2, d * sizeof(double), hipMemcpyHostToDevice, st) != hipSuccess)
+            return predictor_dev_sync(p, who, gpz_fail(GPZ_ERR_HIP, "%s: copy failed", who));
+    }
+    c.sd2_d = sd2 ? p->sd2_d : nullptr;   // (a group's first call with Psi has it from rows_prepare only)
     return 0;
 }
 
@@ -149,7 +162,7 @@ static int predictor_dev_tiles(gpz_predictor *p, const char *who, const DevCall 
         const int s = (int)(t & 1), nt = (int)std::min<int64_t>(T, x.ns - r0);
         if (launch_pred_stage(st, x.X, x.f32(), x.rs, x.cs, r0, nt, p->d, c.muX_d, c.sdX_d, p->Xc[s], p->tile_pad))
             return gpz_fail(GPZ_ERR_HIP, "%s: k_pred_stage launch failed", who);
-        if (c.rows.kind == ROWS_NOISY &&
+        if (c.rows.psi() &&
             launch_pred_stage_psi(st, psi.X, psi.f32(), psi.rs, psi.cs, r0, nt, p->d, c.sd2_d, p->Psic[s], p->tile_pad))
             return gpz_fail(GPZ_ERR_HIP, "%s: k_pred_stage_psi launch failed", who);
         if (int rc = body(s, r0, nt)) return rc;
@@ -167,7 +180,7 @@ static int predictor_run_dev(gpz_predictor *p, const char *who, DevCall &c, doub
     int rc = PHI ? predictor_want_phi(p, false) : 0;
     if (!rc)
         rc = predictor_dev_begin(p, who, c, nullptr, 0, nullptr,
-                                 r.kind == ROWS_NOISY
+                                 r.psi()
                                      ? "the rows have missing values (NaN): input noise on the handle is for complete rows"
                                      : "the rows have missing values (NaN): group them by pattern and call gpz_predict_missing (predict.m:45-69)",
                                  true);
@@ -186,7 +199,7 @@ static int predictor_run_dev(gpz_predictor *p, const char *who, DevCall &c, doub
     return rc;
 }
 
-// gpz_predictor_run_dev, _run_noisy_dev and _run_missing_dev
+// gpz_predictor_run_dev, _run_noisy_dev, _run_missing_dev and _run_noisy_missing_dev
 static int run_dev_entry(const char *who, gpz_predictor *p, DevCall c, double *mu_d, double *sigma_d, double *nu_d, double *beta_d,
                          double *gamma_d, double *PHI_d) {
     if (int rc = predictor_check_call(who, p, c.x.ns)) return rc;
@@ -225,7 +238,7 @@ static int predictor_run_draws_dev(gpz_predictor *p, const char *who, DevCall &c
     return predictor_dev_sync(p, who, rc);
 }
 
-// gpz_predictor_draws_dev, _draws_noisy_dev, _draws_missing_dev and, with want_gamma, _draws_gamma_noisy_dev and _draws_gamma_missing_dev
+// gpz_predictor_draws_dev, _draws_noisy_dev, _draws_missing_dev, _draws_noisy_missing_dev and, with want_gamma, _draws_gamma_noisy_dev and _draws_gamma_missing_dev
 static int draws_dev_entry(const char *who, gpz_predictor *p, DevCall c, int32_t ndraws, uint64_t seed, const double *Z, double *F_d,
                            double *Gam_d = nullptr, bool want_gamma = false) {
     if (int rc = predictor_check_call(who, p, c.x.ns)) return rc;
@@ -316,6 +329,28 @@ extern "C" int gpz_predictor_draws_missing_dev(gpz_predictor *p, const void *X_d
                                                double *F_d, void *stream) {
     const DevCall x = dev_call(X_d, x_type, ns, row_stride, col_stride, muX, sdX, muY, stream);
     return draws_dev_entry("gpz_predictor_draws_missing_dev", p, with_pattern(x, priors, obs_mask), ndraws, seed, Z, F_d);
+}
+
+extern "C" int gpz_predictor_run_noisy_missing_dev(gpz_predictor *p, const void *X_d, int32_t x_type, int64_t ns, int64_t row_stride,
+                                                   int64_t col_stride, const void *Psi_d, int32_t psi_type, int64_t psi_row_stride,
+                                                   int64_t psi_col_stride, const double *muX, const double *sdX, const double *sd2,
+                                                   const double *muY, const double *priors, uint32_t obs_mask, double *mu_d,
+                                                   double *sigma_d, double *nu_d, double *beta_d, double *gamma_d, void *stream) {
+    const DevCall x = dev_call(X_d, x_type, ns, row_stride, col_stride, muX, sdX, muY, stream);
+    return run_dev_entry("gpz_predictor_run_noisy_missing_dev", p,
+                         with_noisy_pattern(with_psi(x, Psi_d, psi_type, psi_row_stride, psi_col_stride, sd2), priors, obs_mask), mu_d,
+                         sigma_d, nu_d, beta_d, gamma_d, nullptr);
+}
+
+extern "C" int gpz_predictor_draws_noisy_missing_dev(gpz_predictor *p, const void *X_d, int32_t x_type, int64_t ns, int64_t row_stride,
+                                                     int64_t col_stride, const void *Psi_d, int32_t psi_type, int64_t psi_row_stride,
+                                                     int64_t psi_col_stride, const double *muX, const double *sdX, const double *sd2,
+                                                     const double *muY, const double *priors, uint32_t obs_mask, int32_t ndraws,
+                                                     uint64_t seed, const double *Z, double *F_d, void *stream) {
+    const DevCall x = dev_call(X_d, x_type, ns, row_stride, col_stride, muX, sdX, muY, stream);
+    return draws_dev_entry("gpz_predictor_draws_noisy_missing_dev", p,
+                           with_noisy_pattern(with_psi(x, Psi_d, psi_type, psi_row_stride, psi_col_stride, sd2), priors, obs_mask), ndraws,
+                           seed, Z, F_d);
 }
 
 extern "C" int gpz_predictor_stack_dev(gpz_predictor *p, const void *X_d, int32_t x_type, int64_t ns, int64_t row_stride,

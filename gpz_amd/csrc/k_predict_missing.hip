@@ -436,6 +436,12 @@ int launch_predict_missing_pairs(hipStream_t st, const double *Xc, long ldx, int
         hipLaunchKernelGGL(k_predict_missing_pairs<8>, grid, dim3(256), lds, st, a);
     }
     if (hipGetLastError() != hipSuccess) return -1;
+    return launch_pmd_finish(st, part, nchunk, ldp, hd, ldh, n, k, bvec, out);
+}
+
+int launch_pmd_finish(hipStream_t st, const double *part, int nchunk, long ldp, const double *hd, long ldh, int n, int k,
+                      const double *bvec, double *out) {
+    if (n <= 0) return 0;
     hipLaunchKernelGGL(k_pmd_finish, dim3((unsigned)((n + 255) / 256), (unsigned)k), dim3(256), 0, st, part, nchunk, ldp, hd, ldh, n, k, bvec,
                        out);
     return hipGetLastError() == hipSuccess ? 0 : -1;

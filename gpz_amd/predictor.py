@@ -1,10 +1,10 @@
 """The streaming predictor: a trained model held on one GPU (gpz_predictor_* of the C ABI) behind ``Predictor``.
 
-The methods ask one of four questions (run: the moments of ``predict``; draws; draws with gamma per draw; stack) of rows of one of three
-kinds (clean, noisy: with Psi, missing: one NaN-pattern group).  ``_DEV_ENTRIES`` names the device-resident entry of each pair,
-``Predictor._dev_entry`` builds the arguments the entries of a pair share, and ``Predictor._dev_groups`` is the one loop over the groups
-of a call; the host methods choose between two entries each by whether Psi is there (``_HOST_ENTRIES``).  Everything numeric happens in
-the library; ``torch`` is only imported by the device methods.
+The methods ask one of four questions (run: the moments of ``predict``; draws; draws with gamma per draw; stack) of rows of one of four
+kinds (clean, noisy: with Psi, missing: one NaN-pattern group, noisy_missing: such a group with Psi, moments and draws only).
+``_DEV_ENTRIES`` names the device-resident entry of each pair, ``Predictor._dev_entry`` builds the arguments the entries of a pair
+share, and ``Predictor._dev_groups`` is the one loop over the groups of a call; the host methods choose between two entries each by
+whether Psi is there (``_HOST_ENTRIES``).  Everything numeric happens in the library; ``torch`` is only imported by the device methods.
 """
 from __future__ import annotations
 
@@ -25,9 +25,9 @@ StackResult = namedtuple("StackResult", ["hist", "sum_w", "sum_mu", "sum_mu2", "
 # (question, row kind) -> the device-resident entry.  Complete rows have no gamma entry: their gamma is exactly 0.
 _DEV_ENTRIES = {
     ("run", "clean"): "gpz_predictor_run_dev", ("run", "noisy"): "gpz_predictor_run_noisy_dev",
-    ("run", "missing"): "gpz_predictor_run_missing_dev",
+    ("run", "missing"): "gpz_predictor_run_missing_dev", ("run", "noisy_missing"): "gpz_predictor_run_noisy_missing_dev",
     ("draws", "clean"): "gpz_predictor_draws_dev", ("draws", "noisy"): "gpz_predictor_draws_noisy_dev",
-    ("draws", "missing"): "gpz_predictor_draws_missing_dev",
+    ("draws", "missing"): "gpz_predictor_draws_missing_dev", ("draws", "noisy_missing"): "gpz_predictor_draws_noisy_missing_dev",
     ("draws_gamma", "noisy"): "gpz_predictor_draws_gamma_noisy_dev", ("draws_gamma", "missing"): "gpz_predictor_draws_gamma_missing_dev",
     ("stack", "clean"): "gpz_predictor_stack_dev", ("stack", "noisy"): "gpz_predictor_stack_noisy_dev",
     ("stack", "missing"): "gpz_predictor_stack_missing_dev",
@@ -400,16 +400,16 @@ class Predictor:
         if draws and self._flags & GPZ_PREDICT_FORCE_TILES:
             raise ValueError(f"{what} with Psi needs the fused draws route: the predictor was made with force_tiles=True")
 
-    def _check_missing_model(self, what, Psi):
+    def _check_missing_model(self, what, Psi, how=" with missing=True"):
         """predict_missing_fits (k_predict_missing.hip) for this model and call, before the GPU is touched."""
         if Psi is not None:
             raise ValueError(f"{what} with missing=True does not take Psi: rows with both input noise and missing values "
-                             "(predictNoisyMissing) are not on the handle; Predictor.predict takes them")
+                             "(predictNoisyMissing) go to predict_noisy_missing_dev / draws_noisy_missing_dev")
         bad = [text for outside, text in ((self._method[1] == "C", f"a diagonal kind (GL, VL, GD, VD), not {self._method}"),
                                           (self._d > 20, f"d <= 20, not d = {self._d}"), (self._k > 8, f"k <= 8, not k = {self._k}"),
                                           (self._m > 256, f"m <= 256, not m = {self._m}")) if outside]
         if bad:
-            raise ValueError(f"{what} with missing=True needs a model inside predict_missing_fits: " + "; ".join(bad) +
+            raise ValueError(f"{what}{how} needs a model inside predict_missing_fits: " + "; ".join(bad) +
                              " (Predictor.predict takes rows with missing values for every shape)")
         if self._priors.shape != (self._m,):
             raise ValueError(f"the priors of the set must be {self._m} values, got {self._priors.size}")
@@ -555,20 +555,21 @@ class Predictor:
 
     def _dev_entry(self, question, call, code, Xg, Pg):
         """The bound entry of ``_DEV_ENTRIES`` for one group and the arguments up to where the questions differ, in the order of
-        include/gpz_hip.h: the handle, the rows, Psi for noisy rows, muX, sdX, sd2 for noisy rows; then muY and, for a group with
+        include/gpz_hip.h: the handle, the rows, Psi for rows with one, muX, sdX, sd2 for rows with Psi; then muY and, for a group with
         missing values, the priors and the mask of the observed dimensions.  ``run`` and ``draws`` take muY there, in front of the
         priors; ``stack`` takes the priors straight after sdX and muY at the end of its own arguments.  Returns (entry, arguments, row
         kind)."""
-        kind = "missing" if code else "clean" if Pg is None else "noisy"
+        noisy = Pg is not None
+        kind = ("noisy_missing" if noisy else "missing") if code else ("noisy" if noisy else "clean")
         lead = [call.h, *self._x_args(Xg)]
-        if kind == "noisy":
+        if noisy:
             lead += self._psi_args(Pg, Xg.shape[0])
         lead += [_lib.dptr(call.muX), _lib.dptr(call.sdX)]
-        if kind == "noisy":
+        if noisy:
             lead.append(_lib.dptr(call.sd2))
         if question != "stack":
             lead.append(_lib.dptr(call.muY))
-        if kind == "missing":
+        if code:
             lead += [_lib.dptr(self._priors), ((1 << self._d) - 1) & ~code]
         return getattr(self._lib, _DEV_ENTRIES[question, kind]), lead, kind
 
@@ -588,12 +589,11 @@ class Predictor:
         ``missing=True`` (gpz_predictor_run_missing_dev): rows with NaN are taken instead of refused.  The rows are grouped by NaN
         pattern with torch on the device; complete rows get exactly what they get without the keyword, every other group
         predictMissing (predictDiag.m:127-209) on the handle's tiles with the priors of the set (1 / m without any), gamma > 0 there.
-        It needs a model inside predict_missing_fits (a diagonal kind, d <= 20, k <= 8, m <= 256), takes neither Psi nor return_phi,
-        and a row's results do not depend on the tile size, the row order or the other rows of the call.
+        It needs a model inside predict_missing_fits (a diagonal kind, d <= 20, k <= 8, m <= 256), takes neither Psi
+        (``predict_noisy_missing_dev`` does) nor return_phi, and a row's results do not depend on the tile size, the row order or the
+        other rows of the call.
         Type, dtype and shape are checked first, the device last, all before the GPU is touched."""
-        import torch
         self._check_open()
-        k, m = self._k, self._m
         X = self._check_dev_rows(X, selection, "predict")
         if missing:
             self._check_missing_model("predict_dev", Psi)
@@ -605,6 +605,13 @@ class Predictor:
                 raise ValueError("return_phi=True is not available with Psi on the device: Predictor.predict returns PHI for noisy rows")
             self._check_noisy_model("predict_dev")
         self._check_dev_device(X=X, selection=selection, Psi=Psi)
+        return self._moments_dev(X, Psi, selection, missing, return_phi)
+
+    def _moments_dev(self, X, Psi, selection, missing, return_phi=False):
+        """The checked call of ``predict_dev`` and ``predict_noisy_missing_dev``: the selection, the result tensors and one entry per
+        group of ``_dev_groups``."""
+        import torch
+        k, m = self._k, self._m
         X, Psi = self._selected(selection, X, Psi)
         n = X.shape[0]
         # the tensors are referenced by this frame for the whole call, which returns when the device is done: no record_stream needed
@@ -634,11 +641,10 @@ class Predictor:
         ``return_gamma=True`` with ``missing=True`` (gpz_predictor_draws_gamma_missing_dev) returns the same pair with predictMissing's
         gamma under the weights of draw s: the variance of PHI(x) w_s over the missing dimensions of the row, exactly 0.0 on complete
         rows.  A row's Gam has the same bits for any tile size, row order, other rows of the call and any n_draws > s.  The scope is
-        that of ``missing=True`` (diagonal kinds, d <= 20, k <= 8, m <= 256); ``Psi`` together with missing values, the covariance
-        kinds and host arrays are not on the handle.  With neither ``Psi`` nor ``missing``, or with both, it is a ValueError."""
-        import torch
+        that of ``missing=True`` (diagonal kinds, d <= 20, k <= 8, m <= 256); gamma per draw for ``Psi`` together with missing
+        values, the covariance kinds and host arrays are not on the handle (``draws_noisy_missing_dev`` returns the draws of such
+        rows).  With neither ``Psi`` nor ``missing``, or with both, it is a ValueError."""
         self._check_open()
-        k = self._k
         X = self._check_dev_rows(X, selection, "draws")
         n_draws, z = self._check_draw_args(n_draws, seed, Z, 1)
         if return_gamma and (Psi is None) != bool(missing):
@@ -650,6 +656,13 @@ class Predictor:
             Psi = self._check_dev_psi(Psi, X.shape[0], "draws")
             self._check_noisy_model("draws_dev", draws=True)
         self._check_dev_device(X=X, selection=selection, Psi=Psi)
+        return self._draws_dev(X, Psi, selection, missing, n_draws, seed, z, return_gamma)
+
+    def _draws_dev(self, X, Psi, selection, missing, n_draws, seed, z, return_gamma=False):
+        """The checked call of ``draws_dev`` and ``draws_noisy_missing_dev``: the selection, the result tensors and one entry per group
+        of ``_dev_groups``, all under the one weight draw of (seed, z)."""
+        import torch
+        k = self._k
         X, Psi = self._selected(selection, X, Psi)
         n = X.shape[0]
         # referenced by this frame for the whole (host-synchronous) call: no record_stream needed
@@ -670,6 +683,51 @@ class Predictor:
                 self._merge(idx, (F, Gam), (Fg, Gg), 2)
         F = F.permute(0, 2, 1)                                           # (n_draws, n, k) view
         return (F, Gam.permute(0, 2, 1)) if return_gamma else F
+
+    def _check_noisy_missing(self, what, X, Psi, selection, draws=False):
+        """The checks the two methods for rows with Psi and missing values share, none of which touches a GPU: types, dtypes and shapes
+        of X and Psi, the model's shape (predict_missing_fits), the priors; for the draws the route of the complete rows.  Returns X
+        as n x d and Psi as n x 1 or n x d."""
+        X = self._check_dev_rows(X, selection, what)
+        if Psi is None:
+            raise ValueError(f"{what}_noisy_missing_dev needs Psi: rows without input noise go to {what}_dev(X, missing=True)")
+        Psi = self._check_dev_psi(Psi, X.shape[0], what)
+        self._check_missing_model(f"{what}_noisy_missing_dev", None, how="")
+        if draws and self._flags & GPZ_PREDICT_FORCE_TILES:
+            raise ValueError(f"{what}_noisy_missing_dev needs the fused draws route for its complete rows: the predictor was made with "
+                             "force_tiles=True")
+        return X, Psi
+
+    def predict_noisy_missing_dev(self, X, Psi, selection=None):
+        """``predict_dev`` for a catalogue whose rows have input noise and, some of them, missing values (a flux error in every band,
+        NaN for the non-detections): X, ``selection`` and ``Psi`` (variances, (n, d), (n, 1) or (n,), float64 or float32, any strides)
+        as for ``predict_dev``.  Returns mu, sigma, nu, beta_i, gamma as ``predict(X, Psi=Psi)`` does, as float64 tensors of shape
+        (n, k) on the device.  The rows are grouped by NaN pattern with torch on the device: the complete rows go to
+        gpz_predictor_run_noisy_dev and get the bits of ``predict_dev(X[full], Psi=Psi[full])``; every other group is gathered with its
+        Psi and goes to gpz_predictor_run_noisy_missing_dev, predictNoisyMissing (predictDiag.m:211-297) on the handle's tiles with
+        the priors of the set (1 / m without any).  Psi must be finite and >= 0 in a row's observed dimensions (else GpzError); in its
+        missing dimensions it is not read, whatever it holds.  It needs a model inside predict_missing_fits (a diagonal kind,
+        d <= 20, k <= 8, m <= 256), else ValueError; PHI, stacks, gamma per draw, host arrays and the covariance kinds are not on
+        this route (``Predictor.predict`` takes such rows for every shape).  A row's results do not depend on the tile size, the row
+        order or the other rows of the call.  Type, dtype and shape are checked first, the device last, all before the GPU is
+        touched."""
+        self._check_open()
+        X, Psi = self._check_noisy_missing("predict", X, Psi, selection)
+        self._check_dev_device(X=X, selection=selection, Psi=Psi)
+        return self._moments_dev(X, Psi, selection, True)
+
+    def draws_noisy_missing_dev(self, X, Psi, n_draws, seed=0, Z=None, selection=None):
+        """``draws_dev`` for such a catalogue (gpz_predictor_draws_noisy_missing_dev): X, ``Psi`` and ``selection`` as for
+        ``predict_noisy_missing_dev``, ``n_draws``, ``seed`` and ``Z`` as for ``draws_dev``.  Returns a float64 tensor of shape
+        (n_draws, n, k) on the device: draws[s] is ``predict_noisy_missing_dev``'s mu under weight draw s, PHI w_s + muY with the PHI
+        of predictNoisy or predictNoisyMissing - the mean is linear in the weights, so this is exact.  One weight draw serves all
+        rows of all groups; complete rows get the bits of ``draws_dev(X[full], ..., Psi=Psi[full])``.  The predictor must not have
+        been made with force_tiles=True."""
+        self._check_open()
+        X, Psi = self._check_noisy_missing("draws", X, Psi, selection, draws=True)
+        n_draws, z = self._check_draw_args(n_draws, seed, Z, 1)
+        self._check_dev_device(X=X, selection=selection, Psi=Psi)
+        return self._draws_dev(X, Psi, selection, True, n_draws, seed, z)
 
     def stack_dev(self, X, edges, n_draws=0, seed=0, Z=None, groups=None, n_groups=None, weights=None, selection=None):
         """``stack`` for a catalogue on the GPU (gpz_predictor_stack_dev): X and ``selection`` as for ``predict_dev``; ``groups`` an

@@ -436,6 +436,35 @@ int gpz_predictor_stack_missing_dev(gpz_predictor *p, const void *X_d, int32_t x
                                     double *hist, double *sum_w, double *sum_mu, double *sum_mu2, const double *mu_shift /* k or NULL */,
                                     void *stream);
 
+/* ---- rows with input noise AND missing inputs on the predictor handle -------------------------------------------------------------------
+ * predictNoisyMissing (predictDiag.m:211-297) and the draws for ONE group of rows that share a NaN pattern and carry a variance per
+ * input dimension, on the handle's own tiles, where predict_missing_fits holds (a diagonal kind, d <= 20, k <= 8, ceil16(m) <= 256);
+ * any other shape returns GPZ_ERR_UNSUPPORTED and names the condition, and gpz_predict_missing takes every shape.  The entries take
+ * what gpz_predictor_run_noisy_dev / _draws_noisy_dev take (Psi_d with its type and strides, sd2), with priors and obs_mask behind muY
+ * as the missing entries have them, and the mask rules are theirs.  The scan before the first tile refuses a row whose NaN pattern
+ * differs from the mask (GPZ_ERR_ARG, "the rows of a group must share one NaN pattern") and an element of Psi that is NaN, negative or
+ * infinite IN AN OBSERVED DIMENSION (GPZ_ERR_ARG, the text of the noisy entries); outputs untouched in both cases.  Psi in a missing
+ * dimension is never read, whatever it holds.  Complete rows go to gpz_predictor_run_noisy_dev / _draws_noisy_dev.
+ * The tables of the pattern are those of the missing entries (Psi touches the observed dimensions only); a second pair-record table,
+ * a function of the model alone, is written on the first call.  Per tile: No and Pio with psi in the widths, PHI through the T-GEMM,
+ * and k_predict_noisy_missing_pairs: the f64-MFMA product of the missing pair kernel with the epilogue of k_predict_noisy_small, one
+ * (C_q + psi)^-1/2 per (row, pair, observed dimension).  The draws are PHI W + muY with the handle's weight draws, the same draw s for
+ * the rows of every group.  The first call allocates what the missing and noisy entries would (where the handle does not hold it yet)
+ * plus the second record table; nothing grows with ns or the number of patterns, a handle that never makes such a call holds what it
+ * held, and a row's results have the same bits for any tile size, row order or split of the rows into calls.  gpz_predictor_route then
+ * holds "; noisy missing: k_predict_noisy_missing_pairs (C pair chunks)".  No stack, no gamma per draw and no host-array entry. */
+int gpz_predictor_run_noisy_missing_dev(gpz_predictor *p, const void *X_d, int32_t x_type, int64_t ns, int64_t row_stride,
+                                        int64_t col_stride, const void *Psi_d, int32_t psi_type, int64_t psi_row_stride,
+                                        int64_t psi_col_stride, const double *muX, const double *sdX, const double *sd2,
+                                        const double *muY /* k or NULL */, const double *priors /* m or NULL */, uint32_t obs_mask,
+                                        double *mu_d, double *sigma_d, double *nu_d, double *beta_d, double *gamma_d, void *stream);
+int gpz_predictor_draws_noisy_missing_dev(gpz_predictor *p, const void *X_d, int32_t x_type, int64_t ns, int64_t row_stride,
+                                          int64_t col_stride, const void *Psi_d, int32_t psi_type, int64_t psi_row_stride,
+                                          int64_t psi_col_stride, const double *muX, const double *sdX, const double *sd2,
+                                          const double *muY /* k or NULL */, const double *priors /* m or NULL */, uint32_t obs_mask,
+                                          int32_t ndraws, uint64_t seed, const double *Z /* host: NULL or m x ndraws x k */,
+                                          double *F_d /* ns x k x ndraws, column-major */, void *stream);
+
 /* ---- device-resident L-BFGS memory: minFunc's lbfgsAdd.m / lbfgsProd.m (mex/lbfgsAddC.c, mex/lbfgsProdC.c) ----
  * S and Y (p x corrections) live on the device; all vector arguments are device pointers.
  * gpz_lbfgs_add:        y = g - g_old, s = t*d; skipped (added = 0) when y's <= 1e-10        (lbfgsAdd.m:2-4)
