@@ -296,6 +296,13 @@ size_t predict_missing_gamma_lds(int m, int d);   // dynamic LDS of k_predict_mi
 int launch_predict_missing_gamma(hipStream_t st, const double *Xc, long ldx, int n, const double *Pio, int ldpio, int m, int d, int k,
                                  unsigned obs, const double *U, const double *rec, const double *W, int ldw, int ncol, int nchunk,
                                  double *part, long ldp);
+// ---- gamma under every weight draw for rows with input noise and missing inputs (k_predict_noisy_missing_gamma.hip;
+// gpz_predictor_stack_noisy_missing_dev, _draws_gamma_noisy_missing_dev).  launch_predict_missing_gamma with Psic in the layout of Xc and
+// rec the SECOND record table (launch_pnm_records; of a record only [lnZ | c | C] is read): EcC_ab(x_i, psi_i) in place of EcC_ab(x_i).
+size_t predict_noisy_missing_gamma_lds(int m, int d);   // dynamic LDS of k_predict_noisy_missing_gamma, bytes
+int launch_predict_noisy_missing_gamma(hipStream_t st, const double *Xc, const double *Psic, long ldx, int n, const double *Pio, int ldpio,
+                                       int m, int d, int k, unsigned obs, const double *U, const double *rec, const double *W, int ldw,
+                                       int ncol, int nchunk, double *part, long ldp);
 // B (rows x ld row-major) <- [iS (m x m column-major) | nw columns of W from column wcol | nv columns of V (nullptr: 0) from vcol | 0]
 void launch_pred_fill_b(hipStream_t st, const double *iS, const double *W, int nw, int wcol, const double *V, int nv, int vcol, int m,
                         int rows, int ld, double *B);

@@ -59,7 +59,8 @@ struct gpz_predictor {
     double *sd2_d = nullptr;       // sdX ** 2 of the device entries
     double *hpsi[2] = {};          // pinned, gpz_predictor_draws_noisy only
     // ---- gamma per draw and stacks of rows with input noise (gpz_predictor_stack_noisy*, _draws_gamma_noisy_dev) and of rows with missing
-    // inputs (gpz_predictor_stack_missing_dev, _draws_gamma_missing_dev): nothing of a kind before its first such call
+    // inputs (gpz_predictor_stack_missing_dev, _draws_gamma_missing_dev), and of rows with both (gpz_predictor_stack_noisy_missing_dev,
+    // _draws_gamma_noisy_missing_dev): nothing of a kind before its first such call
     int gchunks = 0;               // predict_gamma_chunks of the model (input noise; a group with missing inputs has mchunks)
     double *gpart = nullptr;       // [chunks][nd k][tile] pair sums per chunk, of either kind
     size_t gpart_cap = 0;          // doubles
@@ -67,7 +68,7 @@ struct gpz_predictor {
         bool used = false;
         double *s2_d = nullptr;    // [(1 + nd) k][tile] widths^2 of the stack
         size_t s2_cap = 0;         // doubles
-    } gam[2];                      // [ROWS_NOISY - 1], [ROWS_MISSING - 1]
+    } gam[3];                      // [ROWS_NOISY - 1], [ROWS_MISSING - 1], [ROWS_NOISY_MISSING - 1]
     // ---- rows with missing inputs on the handle (gpz_predictor_*_missing_dev): nothing of this exists before the first of their calls
     bool miss_used = false;
     int64_t mtile = 0;             // rows per tile of a group: min(tile_rows, GPZ_PREDICTOR_TILE_MISSING)
@@ -87,8 +88,7 @@ struct gpz_predictor {
 namespace gpzi {
 // The kind of rows of a call.  Clean: complete rows.  Noisy: rows with Psi in Psic[s] beside Xc[s].  Missing: one group of rows that
 // share the NaN pattern obs (the bit mask of the observed dimensions), with the priors of the set (m values, or nullptr for 1 / m).
-// Noisy missing: such a group with Psi in Psic[s] too (read in the observed dimensions only); moments and draws, no gamma per draw and
-// no stack.  What a tile is made of for a kind is answered by the rows_* functions below; the runners of every entry go through them.
+// Noisy missing: such a group with Psi in Psic[s] too (read in the observed dimensions only).  What a tile is made of for a kind is answered by the rows_* functions below; the runners of every entry go through them.
 enum RowKind { ROWS_CLEAN = 0, ROWS_NOISY = 1, ROWS_MISSING = 2, ROWS_NOISY_MISSING = 3 };
 struct Rows {
     RowKind kind = ROWS_CLEAN;

@@ -43,7 +43,9 @@
 // of a pattern (NijS, the pair records, U) are kept until the pattern or the priors change; all of it is allocated on the first such call.
 // A group whose rows have Psi as well goes through gpz_predictor_run_noisy_missing_dev / _draws_noisy_missing_dev (predictNoisyMissing,
 // k_predict_noisy_missing.hip): the same tiles and tables with No widened by psi and a pair kernel whose epilogue is predictNoisy's, on a
-// second record table that is the model's alone.  Moments and draws only.
+// second record table that is the model's alone.  gpz_predictor_stack_noisy_missing_dev stacks such a group as the two stacks above,
+// with gamma under every draw from k_predict_noisy_missing_gamma.hip (k_predict_missing_gamma's two chained products with that
+// epilogue between them); gpz_predictor_draws_gamma_noisy_missing_dev returns that gamma beside the draws.
 // Layout: gpz_predictor.h holds the handle and what the three units share.  This unit holds the handle's life and setup, what a tile is
 // made of for each kind of rows (clean, with Psi, one NaN-pattern group: the rows_* functions), draws preparation and factorisation, the
 // stack's preparation and tile, the checks the entries share, route and info.  gpz_predictor_host.hip holds the host pipeline, its jobs
@@ -573,13 +575,11 @@ int rows_draws_tile(gpz_predictor *p, const char *who, const Rows &r, int s, int
     return predictor_missing_draws_tile(p, who, s, nt, ncol, ldw);
 }
 
-int rows_chunks(const gpz_predictor *p, const Rows &r) { return r.kind == ROWS_MISSING ? p->mchunks : p->gchunks; }
+int rows_chunks(const gpz_predictor *p, const Rows &r) { return r.group() ? p->mchunks : p->gchunks; }
 
 // What a call that needs gamma under nd draws on tiles of T rows adds to the handle (after rows_prepare with pairs: the pair table, or U
 // and the records): the chunk slab of the pair sums and, for a stack of Q column-outputs, the kind's widths.  nd = 0 takes no slab.
 int rows_gamma_prepare(gpz_predictor *p, const Rows &r, int ncol, int Q, int64_t T) {
-    if (r.kind == ROWS_NOISY_MISSING)   // (no entry comes here: gam[] has no slot for the kind)
-        return gpz_fail(GPZ_ERR_UNSUPPORTED, "gpz_predictor: gamma per draw and stacks are not there for rows with input noise and missing inputs");
     gpz_predictor::PerDraw &g = p->gam[r.kind - 1];
     int rc = 0;
     if (r.kind == ROWS_NOISY) p->gchunks = predict_gamma_chunks(p->m);
@@ -591,14 +591,17 @@ int rows_gamma_prepare(gpz_predictor *p, const Rows &r, int ncol, int Q, int64_t
 
 // the pair sums under every draw of one tile of nt rows (a group: after predictor_missing_tile, mPio): -> gpart ([chunks][ncol][nt])
 int rows_gamma_tile(gpz_predictor *p, const char *who, const Rows &r, int s, int nt, int ncol, int ldw) {
-    if (r.kind == ROWS_NOISY_MISSING)
-        return gpz_fail(GPZ_ERR_UNSUPPORTED, "%s: gamma per draw is not there for rows with input noise and missing inputs", who);
+    // a group with Psi: the second record table (C, not 1 / C, and lnZ without the determinant, which depends on the row's Psi)
     if (r.kind == ROWS_NOISY
             ? launch_predict_noisy_gamma(p->s_cmp, p->d, p->Xc[s], p->Psic[s], p->tile_pad, nt, p->m, p->ptab, p->nrec, p->Wd, ldw, ncol,
                                          p->gchunks, p->gpart, nt)
-            : launch_predict_missing_gamma(p->s_cmp, p->Xc[s], p->tile_pad, nt, p->mPio, p->mp, p->m, p->d, p->k, r.obs, p->mU, p->mrec, p->Wd,
-                                           ldw, ncol, p->mchunks, p->gpart, nt))
-        return gpz_fail(GPZ_ERR_HIP, "%s: k_predict_%s_gamma launch failed", who, r.kind == ROWS_NOISY ? "noisy" : "missing");
+        : r.kind == ROWS_MISSING
+            ? launch_predict_missing_gamma(p->s_cmp, p->Xc[s], p->tile_pad, nt, p->mPio, p->mp, p->m, p->d, p->k, r.obs, p->mU, p->mrec, p->Wd,
+                                           ldw, ncol, p->mchunks, p->gpart, nt)
+            : launch_predict_noisy_missing_gamma(p->s_cmp, p->Xc[s], p->Psic[s], p->tile_pad, nt, p->mPio, p->mp, p->m, p->d, p->k, r.obs,
+                                                 p->mU, p->nmrec, p->Wd, ldw, ncol, p->mchunks, p->gpart, nt))
+        return gpz_fail(GPZ_ERR_HIP, "%s: k_predict_%s_gamma launch failed", who,
+                        r.kind == ROWS_NOISY ? "noisy" : r.kind == ROWS_MISSING ? "missing" : "noisy_missing");
     return 0;
 }
 
@@ -621,8 +624,6 @@ int predictor_stack_prepare(gpz_predictor *p, const char *who, const Rows &r, co
     hipStream_t st = p->s_cmp;
     int rc = 0;
     int64_t T = p->tile_rows;
-    if (r.kind == ROWS_NOISY_MISSING)
-        return gpz_fail(GPZ_ERR_UNSUPPORTED, "%s: stacks are not there for rows with input noise and missing inputs", who);
     if (nd > 0 && (rc = predictor_draws_prepare(p, nd, (unsigned long long)a.seed, a.Z, false, &T))) return rc;
     for (int s = 0; s < 2 && pinned; ++s) {   // each one where it is missing: a call that failed half-way here leaves the next one its rest
         if (!p->lab_d[s] && (rc = p->ar.alloc(&p->lab_d[s], tp))) return rc;
@@ -826,6 +827,11 @@ extern "C" int gpz_predictor_route(const gpz_predictor *p, char *buf, int cap) {
     if (p->nm_used) {   // after the first call for a group of rows with input noise and missing inputs
         snprintf(tmp, sizeof tmp, "; noisy missing: k_predict_noisy_missing_pairs (%d pair chunks)", p->mchunks);
         r += tmp;
+    }
+    if (p->gam[2].used) {   // after the first stack or gamma-per-draw call for such a group
+        snprintf(tmp, sizeof tmp, "; noisy missing per draw: k_predict_noisy_missing_gamma (%d pair chunks)", p->mchunks);
+        r += tmp;
+        if (p->gam[2].s2_d) r += " + k_stack_tile_w";   // the widths exist: a stack call was among them
     }
     snprintf(buf, (size_t)cap, "%s", r.c_str());
     return (int)r.size();

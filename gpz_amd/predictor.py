@@ -1,7 +1,7 @@
 """The streaming predictor: a trained model held on one GPU (gpz_predictor_* of the C ABI) behind ``Predictor``.
 
 The methods ask one of four questions (run: the moments of ``predict``; draws; draws with gamma per draw; stack) of rows of one of four
-kinds (clean, noisy: with Psi, missing: one NaN-pattern group, noisy_missing: such a group with Psi, moments and draws only).
+kinds (clean, noisy: with Psi, missing: one NaN-pattern group, noisy_missing: such a group with Psi).
 ``_DEV_ENTRIES`` names the device-resident entry of each pair, ``Predictor._dev_entry`` builds the arguments the entries of a pair
 share, and ``Predictor._dev_groups`` is the one loop over the groups of a call; the host methods choose between two entries each by
 whether Psi is there (``_HOST_ENTRIES``).  Everything numeric happens in the library; ``torch`` is only imported by the device methods.
@@ -29,8 +29,9 @@ _DEV_ENTRIES = {
     ("draws", "clean"): "gpz_predictor_draws_dev", ("draws", "noisy"): "gpz_predictor_draws_noisy_dev",
     ("draws", "missing"): "gpz_predictor_draws_missing_dev", ("draws", "noisy_missing"): "gpz_predictor_draws_noisy_missing_dev",
     ("draws_gamma", "noisy"): "gpz_predictor_draws_gamma_noisy_dev", ("draws_gamma", "missing"): "gpz_predictor_draws_gamma_missing_dev",
+    ("draws_gamma", "noisy_missing"): "gpz_predictor_draws_gamma_noisy_missing_dev",
     ("stack", "clean"): "gpz_predictor_stack_dev", ("stack", "noisy"): "gpz_predictor_stack_noisy_dev",
-    ("stack", "missing"): "gpz_predictor_stack_missing_dev",
+    ("stack", "missing"): "gpz_predictor_stack_missing_dev", ("stack", "noisy_missing"): "gpz_predictor_stack_noisy_missing_dev",
 }
 # (question, Psi there) -> the host entry
 _HOST_ENTRIES = {("draws", False): "gpz_predictor_draws", ("draws", True): "gpz_predictor_draws_noisy",
@@ -641,9 +642,8 @@ class Predictor:
         ``return_gamma=True`` with ``missing=True`` (gpz_predictor_draws_gamma_missing_dev) returns the same pair with predictMissing's
         gamma under the weights of draw s: the variance of PHI(x) w_s over the missing dimensions of the row, exactly 0.0 on complete
         rows.  A row's Gam has the same bits for any tile size, row order, other rows of the call and any n_draws > s.  The scope is
-        that of ``missing=True`` (diagonal kinds, d <= 20, k <= 8, m <= 256); gamma per draw for ``Psi`` together with missing
-        values, the covariance kinds and host arrays are not on the handle (``draws_noisy_missing_dev`` returns the draws of such
-        rows).  With neither ``Psi`` nor ``missing``, or with both, it is a ValueError."""
+        that of ``missing=True`` (diagonal kinds, d <= 20, k <= 8, m <= 256); the covariance kinds and host arrays are not on the handle;
+        gamma per draw for ``Psi`` together with missing values is ``draws_noisy_missing_dev(..., return_gamma=True)``'s.  With neither ``Psi`` nor ``missing``, or with both, it is a ValueError."""
         self._check_open()
         X = self._check_dev_rows(X, selection, "draws")
         n_draws, z = self._check_draw_args(n_draws, seed, Z, 1)
@@ -690,7 +690,8 @@ class Predictor:
         as n x d and Psi as n x 1 or n x d."""
         X = self._check_dev_rows(X, selection, what)
         if Psi is None:
-            raise ValueError(f"{what}_noisy_missing_dev needs Psi: rows without input noise go to {what}_dev(X, missing=True)")
+            raise ValueError(f"{what}_noisy_missing_dev needs Psi: rows without input noise go to " +
+                             ("stack_missing_dev(X, ...)" if what == "stack" else f"{what}_dev(X, missing=True)"))
         Psi = self._check_dev_psi(Psi, X.shape[0], what)
         self._check_missing_model(f"{what}_noisy_missing_dev", None, how="")
         if draws and self._flags & GPZ_PREDICT_FORCE_TILES:
@@ -707,7 +708,7 @@ class Predictor:
         Psi and goes to gpz_predictor_run_noisy_missing_dev, predictNoisyMissing (predictDiag.m:211-297) on the handle's tiles with
         the priors of the set (1 / m without any).  Psi must be finite and >= 0 in a row's observed dimensions (else GpzError); in its
         missing dimensions it is not read, whatever it holds.  It needs a model inside predict_missing_fits (a diagonal kind,
-        d <= 20, k <= 8, m <= 256), else ValueError; PHI, stacks, gamma per draw, host arrays and the covariance kinds are not on
+        d <= 20, k <= 8, m <= 256), else ValueError; PHI, host arrays and the covariance kinds are not on
         this route (``Predictor.predict`` takes such rows for every shape).  A row's results do not depend on the tile size, the row
         order or the other rows of the call.  Type, dtype and shape are checked first, the device last, all before the GPU is
         touched."""
@@ -716,18 +717,23 @@ class Predictor:
         self._check_dev_device(X=X, selection=selection, Psi=Psi)
         return self._moments_dev(X, Psi, selection, True)
 
-    def draws_noisy_missing_dev(self, X, Psi, n_draws, seed=0, Z=None, selection=None):
+    def draws_noisy_missing_dev(self, X, Psi, n_draws, seed=0, Z=None, selection=None, return_gamma=False):
         """``draws_dev`` for such a catalogue (gpz_predictor_draws_noisy_missing_dev): X, ``Psi`` and ``selection`` as for
         ``predict_noisy_missing_dev``, ``n_draws``, ``seed`` and ``Z`` as for ``draws_dev``.  Returns a float64 tensor of shape
         (n_draws, n, k) on the device: draws[s] is ``predict_noisy_missing_dev``'s mu under weight draw s, PHI w_s + muY with the PHI
         of predictNoisy or predictNoisyMissing - the mean is linear in the weights, so this is exact.  One weight draw serves all
         rows of all groups; complete rows get the bits of ``draws_dev(X[full], ..., Psi=Psi[full])``.  The predictor must not have
-        been made with force_tiles=True."""
+        been made with force_tiles=True.
+        ``return_gamma=True`` returns ``(F, Gam)``: Gam (n_draws, n, k) is predictNoisyMissing's gamma under the weights of draw s,
+        the variance of PHI(x) w_s over the input noise and the missing dimensions together, not clamped at 0
+        (gpz_predictor_draws_gamma_noisy_missing_dev); complete rows get ``draws_dev(..., Psi=, return_gamma=True)``'s, the variance
+        over their input noise, which is not zero.  A row's Gam has the same bits for any tile size, row order, other rows of the
+        call and any n_draws > s."""
         self._check_open()
         X, Psi = self._check_noisy_missing("draws", X, Psi, selection, draws=True)
         n_draws, z = self._check_draw_args(n_draws, seed, Z, 1)
         self._check_dev_device(X=X, selection=selection, Psi=Psi)
-        return self._draws_dev(X, Psi, selection, True, n_draws, seed, z)
+        return self._draws_dev(X, Psi, selection, True, n_draws, seed, z, bool(return_gamma))
 
     def stack_dev(self, X, edges, n_draws=0, seed=0, Z=None, groups=None, n_groups=None, weights=None, selection=None):
         """``stack`` for a catalogue on the GPU (gpz_predictor_stack_dev): X and ``selection`` as for ``predict_dev``; ``groups`` an
@@ -760,16 +766,36 @@ class Predictor:
         kinds are not on the handle (``Predictor.predict`` takes such rows)."""
         return self._stack_dev(X, None, edges, n_draws, seed, Z, groups, n_groups, weights, selection, missing=True)
 
-    def _stack_dev(self, X, Psi, edges, n_draws, seed, Z, groups, n_groups, weights, selection, missing=False):
-        """``stack_dev`` (Psi None), ``stack_noisy_dev`` and ``stack_missing_dev``: the checks, the device last, all before the GPU is
-        touched; then the entry, or with ``missing`` one entry per NaN-pattern group."""
+    def stack_noisy_missing_dev(self, X, Psi, edges, n_draws=0, seed=0, Z=None, groups=None, n_groups=None, weights=None,
+                                selection=None):
+        """``stack_noisy_dev`` for a catalogue whose rows have input noise and, some of them, missing values (a flux error in every
+        band, NaN for the non-detections): arguments and result as for ``stack_noisy_dev``, ``Psi`` as for
+        ``predict_noisy_missing_dev`` (not read in a row's missing dimensions).  The rows are grouped by NaN pattern with torch on the
+        device.  The complete rows go to gpz_predictor_stack_noisy_dev (a catalogue without NaN gives ``stack_noisy_dev``'s bits),
+        every other group with its Psi, labels and weights to gpz_predictor_stack_noisy_missing_dev, and the groups' results are
+        added field by field in ascending order of the pattern code, so the call equals the ``+=`` of the single-pattern calls bit
+        for bit.  For a row with missing values column 0 uses ``predict_noisy_missing_dev``'s mu and sigma = (nu + beta_i) + gamma,
+        column 1 + s ``draws_noisy_missing_dev``'s draw s and the width beta_i + max(gamma_s, 0), where gamma_s is
+        predictNoisyMissing's gamma under the weights of draw s (``draws_noisy_missing_dev(..., return_gamma=True)`` returns it).
+        ``n_groups`` and the range of the labels are decided over all rows.  It needs a model inside predict_missing_fits (a diagonal
+        kind, d <= 20, k <= 8, m <= 256), else ValueError, and a predictor that was not made with force_tiles=True; host arrays and
+        the covariance kinds are not on the handle."""
+        return self._stack_dev(X, Psi, edges, n_draws, seed, Z, groups, n_groups, weights, selection, missing=True, both=True)
+
+    def _stack_dev(self, X, Psi, edges, n_draws, seed, Z, groups, n_groups, weights, selection, missing=False, both=False):
+        """``stack_dev`` (Psi None), ``stack_noisy_dev``, ``stack_missing_dev`` and (``both``: Psi and ``missing`` together)
+        ``stack_noisy_missing_dev``: the checks, the device last, all before the GPU is touched; then the entry, or with ``missing``
+        one entry per NaN-pattern group."""
         import torch
         self._check_open()
-        X = self._check_dev_rows(X, selection, "stack" if Psi is None else "stack_noisy")
+        if both:
+            X, Psi = self._check_noisy_missing("stack", X, Psi, selection, draws=True)
+        else:
+            X = self._check_dev_rows(X, selection, "stack" if Psi is None else "stack_noisy")
         n_all = X.shape[0]
-        if missing:
+        if missing and not both:
             self._check_missing_model("stack_missing_dev", None)
-        if Psi is not None:
+        if Psi is not None and not both:
             Psi = self._check_dev_psi(Psi, n_all, "stack_noisy")
             self._check_noisy_model("stack_noisy_dev", draws=True)
         e, B = self._check_edges(edges)

@@ -452,7 +452,8 @@ int gpz_predictor_stack_missing_dev(gpz_predictor *p, const void *X_d, int32_t x
  * the rows of every group.  The first call allocates what the missing and noisy entries would (where the handle does not hold it yet)
  * plus the second record table; nothing grows with ns or the number of patterns, a handle that never makes such a call holds what it
  * held, and a row's results have the same bits for any tile size, row order or split of the rows into calls.  gpz_predictor_route then
- * holds "; noisy missing: k_predict_noisy_missing_pairs (C pair chunks)".  No stack, no gamma per draw and no host-array entry. */
+ * holds "; noisy missing: k_predict_noisy_missing_pairs (C pair chunks)".  The stack and gamma per draw follow below; no host-array
+ * entry. */
 int gpz_predictor_run_noisy_missing_dev(gpz_predictor *p, const void *X_d, int32_t x_type, int64_t ns, int64_t row_stride,
                                         int64_t col_stride, const void *Psi_d, int32_t psi_type, int64_t psi_row_stride,
                                         int64_t psi_col_stride, const double *muX, const double *sdX, const double *sd2,
@@ -464,6 +465,43 @@ int gpz_predictor_draws_noisy_missing_dev(gpz_predictor *p, const void *X_d, int
                                           const double *muY /* k or NULL */, const double *priors /* m or NULL */, uint32_t obs_mask,
                                           int32_t ndraws, uint64_t seed, const double *Z /* host: NULL or m x ndraws x k */,
                                           double *F_d /* ns x k x ndraws, column-major */, void *stream);
+
+/* ---- stacked densities of rows with input noise AND missing inputs, and gamma under every weight draw ----------------------------------
+ * gpz_predictor_stack_noisy_dev for ONE group of rows that share a NaN pattern and carry a variance per input dimension, and
+ * gpz_predictor_draws_noisy_missing_dev with gamma: the scope (predict_missing_fits), Psi, priors, obs_mask, the scans of the pattern
+ * and of Psi in the observed dimensions and their refusals are those of the two entries above; no host-array entry.  Column 0 (the
+ * posterior-mean weights): mu of gpz_predictor_run_noisy_missing_dev, width^2 = (nu + beta) + gamma, the bits of that call's sigma.
+ * Column 1 + s (weight draw s): mu_s of gpz_predictor_draws_noisy_missing_dev, width^2 = beta_i + max(gamma_s,i, 0) with
+ *   gamma_s,i = sum_{a >= b} f_ab EcC_ab(x_i, psi_i) w_s,a w_s,b - mu_s,i^2   (f_ab = 2 off the diagonal, 1 on it),
+ * predictNoisyMissing's gamma (predictDiag.m:257-295) under the draw's weights: the variance of PHI(x) w_s over the input noise and the
+ * missing dimensions together; beta_i does not depend on w.  On a complete row gamma_s is gpz_predictor_draws_gamma_noisy_dev's.
+ * Everything else - edges, groups, weights, mu_shift, layouts, additivity over calls, the 9-width window - is gpz_predictor_stack's, so
+ * the results of the groups of a catalogue (and of gpz_predictor_stack_noisy_dev on its complete rows) add field by field.  A bad
+ * label or weight -> GPZ_ERR_ARG; in every refusal the outputs are untouched and the handle gains no byte.
+ * gpz_predictor_draws_gamma_noisy_missing_dev: gpz_predictor_draws_noisy_missing_dev plus Gam_d (ns x k x ndraws column-major, device)
+ * <- gamma_s, unclamped.  A row's gamma_s has the same bits for any tile size, row order, position among other rows, split into calls
+ * and any ndraws > s.  k_predict_noisy_missing_gamma forms the pair expectations as k_predict_noisy_missing_pairs does and multiplies
+ * them into all draws at once on the f64 MFMA, up to 128 columns per launch.  The first of these calls adds to the handle what the two
+ * entries above add, plus the chunk slab of the pair sums and, for the stack, the widths and gpz_predictor_stack_dev's accumulators
+ * and slabs; nothing grows with ns or the number of patterns, and gpz_predictor_route then holds
+ * "; noisy missing per draw: k_predict_noisy_missing_gamma (C pair chunks)", followed by " + k_stack_tile_w" once the stack entry has
+ * been called. */
+int gpz_predictor_draws_gamma_noisy_missing_dev(gpz_predictor *p, const void *X_d, int32_t x_type, int64_t ns, int64_t row_stride,
+                                                int64_t col_stride, const void *Psi_d, int32_t psi_type, int64_t psi_row_stride,
+                                                int64_t psi_col_stride, const double *muX, const double *sdX, const double *sd2,
+                                                const double *muY /* k or NULL */, const double *priors /* m or NULL */,
+                                                uint32_t obs_mask, int32_t ndraws, uint64_t seed,
+                                                const double *Z /* host: NULL or m x ndraws x k */,
+                                                double *F_d /* ns x k x ndraws, column-major */,
+                                                double *Gam_d /* ns x k x ndraws, column-major */, void *stream);
+int gpz_predictor_stack_noisy_missing_dev(gpz_predictor *p, const void *X_d, int32_t x_type, int64_t ns, int64_t row_stride,
+                                          int64_t col_stride, const void *Psi_d, int32_t psi_type, int64_t psi_row_stride,
+                                          int64_t psi_col_stride, const double *muX, const double *sdX, const double *sd2,
+                                          const double *priors /* m or NULL */, uint32_t obs_mask,
+                                          int32_t ndraws, uint64_t seed, const double *Z, const double *edges, int32_t nbins,
+                                          const int32_t *group_d /* ns or NULL */, int32_t ngroups, const double *weight_d /* ns or NULL */,
+                                          double *hist, double *sum_w, double *sum_mu, double *sum_mu2,
+                                          const double *mu_shift /* k or NULL */, void *stream);
 
 /* ---- device-resident L-BFGS memory: minFunc's lbfgsAdd.m / lbfgsProd.m (mex/lbfgsAddC.c, mex/lbfgsProdC.c) ----
  * S and Y (p x corrections) live on the device; all vector arguments are device pointers.
