@@ -42,6 +42,39 @@ __device__ __forceinline__ double gpz_rcp1(double u) {
     return fma(y, e, y);
 }
 
+// 1 / sqrt(p) in fp64 without the library's sqrt + divide (~50 instructions): v_rsq_f64 seed and two Newton steps.
+__device__ __forceinline__ double rsqrt_nr2(double p) {
+    double y = __builtin_amdgcn_rsq(p);
+    const double h = 0.5 * p;
+    double e = fma(-h * y, y, 0.5);
+    y = fma(y, e, y);
+    e = fma(-h * y, y, 0.5);
+    y = fma(y, e, y);
+    return y;
+}
+
+// the pair (i, j), j <= i, of the triangular index q = i (i + 1) / 2 + j
+__device__ __forceinline__ void gpz_pair_of(long q, int *pi, int *pj) {
+    long i = (long)((sqrt(8.0 * (double)q + 1.0) - 1.0) * 0.5);
+    while ((i + 1) * (i + 2) / 2 <= q) ++i;
+    while (i * (i + 1) / 2 > q) --i;
+    *pi = (int)i;
+    *pj = (int)(q - i * (i + 1) / 2);
+}
+
+// The per-output tail of the pair record of (i, j), j <= i: cf [3k] = [f w_i w_j, f v_i v_j, f iS(i, j)] per output, f = 2 off the diagonal
+// and 1 on it (predictDiag.m:113-119, :191-198, :277-284).  w, v: m x k column-major (v nullptr: 0); iS: m x m x k column-major, read at
+// i >= j only as the reference does.
+__device__ __forceinline__ void gpz_pair_coef(double *cf, int i, int j, int m, int k, const double *__restrict__ w,
+                                              const double *__restrict__ v, const double *__restrict__ iS) {
+    const double f = i == j ? 1.0 : 2.0;
+    for (int o = 0; o < k; ++o) {
+        cf[3 * o] = f * (w[i + (size_t)m * o] * w[j + (size_t)m * o]);
+        cf[3 * o + 1] = v ? f * (v[i + (size_t)m * o] * v[j + (size_t)m * o]) : 0.0;
+        cf[3 * o + 2] = f * iS[i + (size_t)m * j + (size_t)m * m * o];
+    }
+}
+
 __device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);

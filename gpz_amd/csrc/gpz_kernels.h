@@ -244,65 +244,53 @@ int launch_gamma_finish_s2(hipStream_t st, const double *part, int nchunk, long 
                            int nd, double *s2);
 int launch_stack_tile_w(hipStream_t st, const double *out, const double *s2, const double *dout, const int *lab, const double *wt,
                         const double *edges, const double *shift, long nt, int k, int nd, int B, int G, int R, double *slab);
-// ---- rows with missing inputs through the streaming predictor (k_predict_missing.hip; gpz_predictor_*_missing_dev) ----------------
+// ---- rows with missing inputs through the streaming predictor, with or without input noise (k_predict_missing.hip,
+// k_predict_noisy_missing.hip, the pair kernels' body in k_predict_group_impl.h; gpz_predictor_*_missing_dev, _*_noisy_missing_dev) ----
 // One group of rows sharing a NaN pattern; obs: bit c set = dimension c observed.  fits: a diagonal kind, an instantiated de <= 20,
 // k <= 8 and ceil16(m) <= 256.  launch_pmd_tables (per pattern and priors): bt [2][mp], NijS [mp][mp] and, with pairs, the records
 // (predict_missing_groups(m) * 64 of predict_missing_rec(d, k) = 1 + 2 d + 3 k doubles) and U (predict_missing_groups(m) * 64 * ceil16(m)
-// doubles in fragment order).  Per tile: launch_pmd_no (No, Pio: nrow rows of mp, rows >= n zero), launch_tgemm, launch_pmd_phi (PHI over
-// No; hd [2k][ldh] = PHI w | PHI v), launch_predict_missing_pairs (part [predict_missing_chunks(m)][3k][ldp] -> out [4k][n] = mu | nu |
-// beta | gamma).  The chunk count is a function of m alone.  The launchers return -1 when a launch failed.
+// doubles in fragment order).  launch_pnm_records (per handle) writes the second record table, for rows with Psi: as many records of as
+// many doubles, [lnZ without the ln det of the observed block | c | C | coefficients], the model's alone.
+// Psic: nullptr, or the tile's Psi in the layout of Xc for a group with input noise too; rec is then the second table, and every loop
+// over dimensions runs over the set bits of obs.  Per tile: launch_pmd_no (No, Pio: nrow rows of mp, rows >= n zero; widened by psi:
+// k_pnm_no), launch_tgemm, launch_pmd_phi (PHI over No; hd [2k][ldh] = PHI w | PHI v), launch_predict_missing_pairs
+// (k_predict_missing_pairs or k_predict_noisy_missing_pairs: part [predict_missing_chunks(m)][3k][ldp] -> out [4k][n] = mu | nu | beta |
+// gamma; launch_pmd_finish inside).  The chunk count is a function of m alone.  The launchers return -1 when a launch failed.
 bool predict_missing_fits(int kind, int de, int m, int k);
 int predict_missing_rec(int d, int k);
 long predict_missing_groups(int m);
 int predict_missing_chunks(int m);
-size_t predict_missing_lds(int m, int d, int k);   // dynamic LDS of k_predict_missing_pairs, bytes
+size_t predict_missing_lds(int m, int d, int k, bool psi);   // dynamic LDS of the pair kernels, bytes
 int launch_pmd_check(hipStream_t st, const void *X, int f32, long ns, int d, long rs, long cs, unsigned obs, unsigned *rec);
 int launch_pmd_tables(hipStream_t st, int m, int mp, int d, int de, int k, unsigned obs, const double *P, const double *G2,
                       const double *priors, const double *w, const double *v, const double *iS, double *bt, double *NijS, double *U,
                       double *rec, bool pairs);
-int launch_pmd_no(hipStream_t st, const double *Xc, long ldx, int n, int nrow, int m, int mp, int d, int de, unsigned obs, const double *P,
-                  const double *G2, const double *bt, double *No, double *Pio);
+int launch_pnm_records(hipStream_t st, int m, int d, int de, int k, const double *P, const double *G2, const double *w, const double *v,
+                       const double *iS, double *rec);
+int launch_pmd_no(hipStream_t st, const double *Xc, const double *Psic, long ldx, int n, int nrow, int m, int mp, int d, int de,
+                  unsigned obs, const double *P, const double *G2, const double *bt, double *No, double *Pio);
 int launch_pmd_phi(hipStream_t st, double *No, const double *T, int n, int m, int mp, int k, const double *w, const double *v, double *hd,
                    long ldh);
-int launch_predict_missing_pairs(hipStream_t st, const double *Xc, long ldx, int n, const double *Pio, int ldpio, int m, int d, int k,
-                                 unsigned obs, const double *U, const double *rec, int nchunk, double *part, long ldp, const double *hd,
-                                 long ldh, const double *bvec, double *out);
+int launch_predict_missing_pairs(hipStream_t st, const double *Xc, const double *Psic, long ldx, int n, const double *Pio, int ldpio, int m,
+                                 int d, int k, unsigned obs, const double *U, const double *rec, int nchunk, double *part, long ldp,
+                                 const double *hd, long ldh, const double *bvec, double *out);
 // the finish kernel behind the pair kernel, on its own: hd [2k][ldh] = mu | ElnS - b and part [nchunk][3k][ldp] -> out [4k][n]
 int launch_pmd_finish(hipStream_t st, const double *part, int nchunk, long ldp, const double *hd, long ldh, int n, int k,
                       const double *bvec, double *out);
-// ---- rows with input noise AND missing inputs through the streaming predictor (k_predict_noisy_missing.hip;
-// gpz_predictor_*_noisy_missing_dev).  One group as above, with Psic in the layout of Xc; the scope is predict_missing_fits.  NijS, bt
-// and U are launch_pmd_tables'; launch_pnm_records writes the second record table (predict_missing_groups(m) * 64 records of
-// predict_missing_rec(d, k) doubles: [lnZ without the ln det of the observed block | c | C | coefficients], the model's alone).  Per tile:
-// launch_pnm_no for launch_pmd_no, then launch_tgemm and launch_pmd_phi as above, launch_predict_noisy_missing_pairs (part and out as
-// launch_predict_missing_pairs; launch_pmd_finish inside).  launch_pnm_check_psi: word 3 of rec is set when Psi is NaN, negative or
-// infinite in an observed dimension; the missing ones are not read.  Every loop over dimensions runs over the set bits of obs.
-size_t predict_noisy_missing_lds(int m, int d, int k);   // dynamic LDS of k_predict_noisy_missing_pairs, bytes
+// launch_pred_check_psi (k_predict_noisy.hip) for such a group: word 3 of rec is set when Psi is NaN, negative or infinite in an observed
+// dimension; the missing ones are not read, and with obs == 0 nothing is launched
 int launch_pnm_check_psi(hipStream_t st, const void *Psi, int f32, long ns, int d, long rs, long cs, unsigned obs, double smin,
                          unsigned *rec);
-int launch_pnm_records(hipStream_t st, int m, int d, int de, int k, const double *P, const double *G2, const double *w, const double *v,
-                       const double *iS, double *rec);
-int launch_pnm_no(hipStream_t st, const double *Xc, const double *Psic, long ldx, int n, int nrow, int m, int mp, int de, unsigned obs,
-                  const double *P, const double *G2, const double *bt, double *No, double *Pio);
-int launch_predict_noisy_missing_pairs(hipStream_t st, const double *Xc, const double *Psic, long ldx, int n, const double *Pio, int ldpio,
-                                       int m, int d, int k, unsigned obs, const double *U, const double *rec, int nchunk, double *part,
-                                       long ldp, const double *hd, long ldh, const double *bvec, double *out);
-// ---- gamma under every weight draw for rows with missing inputs (k_predict_missing_gamma.hip; gpz_predictor_stack_missing_dev,
-// _draws_gamma_missing_dev).  part [nchunk][ncol][ldp] <- per pair chunk sum_{a >= b} f_ab EcC_ab(x_i) W[a, col] W[b, col] for the n rows
-// of the tile: Xc, Pio, U and rec as launch_predict_missing_pairs takes them (of a record only [lnZ | c | 1 / C] is read), W >= m rows x
-// ldw row-major as the draws take it (column o nd + s, ldw a multiple of 16, columns >= ncol zero), nchunk = predict_missing_chunks(m).
+// ---- gamma under every weight draw for such a group (k_predict_missing_gamma.hip, k_predict_noisy_missing_gamma.hip;
+// gpz_predictor_stack_missing_dev, _draws_gamma_missing_dev and their _noisy_missing_ forms).  part [nchunk][ncol][ldp] <- per pair chunk
+// sum_{a >= b} f_ab EcC_ab(x_i) W[a, col] W[b, col] for the n rows of the tile (with Psic: EcC_ab(x_i, psi_i)): Xc, Psic, Pio, U and rec as
+// launch_predict_missing_pairs takes them (of a record only [lnZ | c | 1 / C], with Psic [lnZ | c | C], is read), W >= m rows x ldw
+// row-major as the draws take it (column o nd + s, ldw a multiple of 16, columns >= ncol zero), nchunk = predict_missing_chunks(m).
 // launch_gamma_finish_dev / _s2 (above) take part from there, with nout = the missing tile's out.  Returns -1 when a launch failed.
-size_t predict_missing_gamma_lds(int m, int d);   // dynamic LDS of k_predict_missing_gamma, bytes
-int launch_predict_missing_gamma(hipStream_t st, const double *Xc, long ldx, int n, const double *Pio, int ldpio, int m, int d, int k,
-                                 unsigned obs, const double *U, const double *rec, const double *W, int ldw, int ncol, int nchunk,
-                                 double *part, long ldp);
-// ---- gamma under every weight draw for rows with input noise and missing inputs (k_predict_noisy_missing_gamma.hip;
-// gpz_predictor_stack_noisy_missing_dev, _draws_gamma_noisy_missing_dev).  launch_predict_missing_gamma with Psic in the layout of Xc and
-// rec the SECOND record table (launch_pnm_records; of a record only [lnZ | c | C] is read): EcC_ab(x_i, psi_i) in place of EcC_ab(x_i).
-size_t predict_noisy_missing_gamma_lds(int m, int d);   // dynamic LDS of k_predict_noisy_missing_gamma, bytes
-int launch_predict_noisy_missing_gamma(hipStream_t st, const double *Xc, const double *Psic, long ldx, int n, const double *Pio, int ldpio,
-                                       int m, int d, int k, unsigned obs, const double *U, const double *rec, const double *W, int ldw,
-                                       int ncol, int nchunk, double *part, long ldp);
+size_t predict_missing_gamma_lds(int m, int d, bool psi);   // dynamic LDS of the gamma kernels, bytes
+int launch_predict_missing_gamma(hipStream_t st, const double *Xc, const double *Psic, long ldx, int n, const double *Pio, int ldpio, int m,
+                                 int d, int k, unsigned obs, const double *U, const double *rec, const double *W, int ldw, int ncol,
+                                 int nchunk, double *part, long ldp);
 // B (rows x ld row-major) <- [iS (m x m column-major) | nw columns of W from column wcol | nv columns of V (nullptr: 0) from vcol | 0]
 void launch_pred_fill_b(hipStream_t st, const double *iS, const double *W, int nw, int wcol, const double *V, int nv, int vcol, int m,
                         int rows, int ld, double *B);

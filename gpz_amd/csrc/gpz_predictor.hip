@@ -488,22 +488,16 @@ static int predictor_missing_tile(gpz_predictor *p, const char *who, int s, int 
     const int np = rup(nt, 128);   // the rows of the product: k_tgemm's row tile
     const long mtp = rup(p->mtile, 1024);
     const double *v = p->hetero ? p->pr.v : nullptr;
-    if (Psic ? launch_pnm_no(st, p->Xc[s], Psic, p->tile_pad, nt, np, p->m, p->mp, p->de, obs, p->pr.P, p->pr.G2, p->mbt, p->mNo, p->mPio)
-             : launch_pmd_no(st, p->Xc[s], p->tile_pad, nt, np, p->m, p->mp, p->d, p->de, obs, p->pr.P, p->pr.G2, p->mbt, p->mNo, p->mPio))
+    if (launch_pmd_no(st, p->Xc[s], Psic, p->tile_pad, nt, np, p->m, p->mp, p->d, p->de, obs, p->pr.P, p->pr.G2, p->mbt, p->mNo, p->mPio))
         return gpz_fail(GPZ_ERR_HIP, "%s: k_%s_no launch failed", who, Psic ? "pnm" : "pmd");
     launch_tgemm(st, p->mPio, p->mp, p->mNij, p->mp, p->mT, np, p->mp, nullptr, nullptr, p->m, -1);
     if (hipGetLastError() != hipSuccess) return gpz_fail(GPZ_ERR_HIP, "%s: k_tgemm launch failed", who);
     if (launch_pmd_phi(st, p->mNo, p->mT, nt, p->m, p->mp, p->k, p->w_d, v, p->mhd, mtp))
         return gpz_fail(GPZ_ERR_HIP, "%s: k_pmd_phi launch failed", who);
-    if (pairs && Psic) {
-        if (launch_predict_noisy_missing_pairs(st, p->Xc[s], Psic, p->tile_pad, nt, p->mPio, p->mp, p->m, p->d, p->k, obs, p->mU, p->nmrec,
-                                               p->mchunks, p->mpart, mtp, p->mhd, mtp, p->pr.b, p->mout))
-            return gpz_fail(GPZ_ERR_HIP, "%s: k_predict_noisy_missing_pairs launch failed", who);
-        return 0;
-    }
-    if (pairs && launch_predict_missing_pairs(st, p->Xc[s], p->tile_pad, nt, p->mPio, p->mp, p->m, p->d, p->k, obs, p->mU, p->mrec, p->mchunks,
-                                              p->mpart, mtp, p->mhd, mtp, p->pr.b, p->mout))
-        return gpz_fail(GPZ_ERR_HIP, "%s: k_predict_missing_pairs launch failed", who);
+    // with Psi: the second record table (C, not 1 / C, and lnZ without the determinant, which depends on the row's Psi)
+    if (pairs && launch_predict_missing_pairs(st, p->Xc[s], Psic, p->tile_pad, nt, p->mPio, p->mp, p->m, p->d, p->k, obs, p->mU,
+                                              Psic ? p->nmrec : p->mrec, p->mchunks, p->mpart, mtp, p->mhd, mtp, p->pr.b, p->mout))
+        return gpz_fail(GPZ_ERR_HIP, "%s: k_predict_%smissing_pairs launch failed", who, Psic ? "noisy_" : "");
     return 0;
 }
 
@@ -591,15 +585,12 @@ int rows_gamma_prepare(gpz_predictor *p, const Rows &r, int ncol, int Q, int64_t
 
 // the pair sums under every draw of one tile of nt rows (a group: after predictor_missing_tile, mPio): -> gpart ([chunks][ncol][nt])
 int rows_gamma_tile(gpz_predictor *p, const char *who, const Rows &r, int s, int nt, int ncol, int ldw) {
-    // a group with Psi: the second record table (C, not 1 / C, and lnZ without the determinant, which depends on the row's Psi)
+    // a group with Psi: the second record table
     if (r.kind == ROWS_NOISY
             ? launch_predict_noisy_gamma(p->s_cmp, p->d, p->Xc[s], p->Psic[s], p->tile_pad, nt, p->m, p->ptab, p->nrec, p->Wd, ldw, ncol,
                                          p->gchunks, p->gpart, nt)
-        : r.kind == ROWS_MISSING
-            ? launch_predict_missing_gamma(p->s_cmp, p->Xc[s], p->tile_pad, nt, p->mPio, p->mp, p->m, p->d, p->k, r.obs, p->mU, p->mrec, p->Wd,
-                                           ldw, ncol, p->mchunks, p->gpart, nt)
-            : launch_predict_noisy_missing_gamma(p->s_cmp, p->Xc[s], p->Psic[s], p->tile_pad, nt, p->mPio, p->mp, p->m, p->d, p->k, r.obs,
-                                                 p->mU, p->nmrec, p->Wd, ldw, ncol, p->mchunks, p->gpart, nt))
+            : launch_predict_missing_gamma(p->s_cmp, p->Xc[s], r.psi() ? p->Psic[s] : nullptr, p->tile_pad, nt, p->mPio, p->mp, p->m, p->d,
+                                           p->k, r.obs, p->mU, r.psi() ? p->nmrec : p->mrec, p->Wd, ldw, ncol, p->mchunks, p->gpart, nt))
         return gpz_fail(GPZ_ERR_HIP, "%s: k_predict_%s_gamma launch failed", who,
                         r.kind == ROWS_NOISY ? "noisy" : r.kind == ROWS_MISSING ? "missing" : "noisy_missing");
     return 0;

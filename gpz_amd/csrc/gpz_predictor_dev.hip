@@ -125,7 +125,7 @@ static int predictor_dev_begin(gpz_predictor *p, const char *who, DevCall &c, co
         rc = gpz_fail(GPZ_ERR_HIP, "%s: k_pred_check_dev launch failed", who);
     if (!rc && psi && pattern &&
         launch_pnm_check_psi(st, psi->X, psi->f32(), psi->ns, p->d, psi->rs, psi->cs, obs, sd2 ? *std::min_element(sd2, sd2 + d) : 1.0, rec))
-        rc = gpz_fail(GPZ_ERR_HIP, "%s: k_pnm_check_psi launch failed", who);
+        rc = gpz_fail(GPZ_ERR_HIP, "%s: k_pred_check_psi launch failed", who);
     if (!rc && psi && !pattern &&
         ((sd2 && hipMemcpyAsync(p->sd2_d, sd2, d * sizeof(double), hipMemcpyHostToDevice, st) != hipSuccess) ||
          launch_pred_check_psi(st, psi->X, psi->f32(), psi->ns, p->d, psi->rs, psi->cs, sd2 ? *std::min_element(sd2, sd2 + d) : 1.0, rec)))

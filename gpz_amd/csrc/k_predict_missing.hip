@@ -14,33 +14,23 @@
 //                  pair; padded to whole groups of 64 pairs.  One wave load of a fragment is 512 contiguous bytes.
 // Per tile, on Xc [d][ldx] as k_pred_stage left it (NaN in the missing dimensions: every kernel here selects on the mask):
 //   k_pmd_no       No(r, j) = exp(lno_j - 1/2 sum_o (x - p_j)^2 gamma_j^2), Pio = No prior / sum_j (No prior); one wave per row   :142-154
+//   k_pnm_no       the same for rows with Psi: No(r, j) = exp(-1/2 sum_o [(x - p_j)^2 / (psi + sigma_jo) + ln(psi + sigma_jo)]).  With
+//                  u = 1 + psi gamma_j^2: (psi + sigma) = u / gamma^2, so the exponent is lno_j - 1/2 (sum_o (x - p)^2 gamma^2 / u +
+//                  sum_o ln u): at psi = 0 the bits of k_pmd_no.  The loop runs over the set bits of obs.                      :227-238
 //   launch_tgemm   T = Pio NijS on the f64 MFMA (k_gemm.hip)
 //   k_pmd_phi      PHI = No o T (over No), mu = PHI w, ElnS - b = PHI v; one wave per row                                        :162-166
-//   k_predict_missing_pairs<KM>   the hot one: gamma, VlnS and nu's pair sums (:172-200) with the n x pairs product Pio Nu' never in memory.
-//                  A workgroup holds the Pio block of its 32 rows in LDS and walks the 64-pair groups of its chunk; wave w takes the
-//                  16-pair block 4 g + w of group g: one MFMA K loop over nk with the U fragments fetched four steps ahead, the product
-//                  transposed (U is the A operand) so that lane l owns rows l & 15 and 16 + (l & 15) and, in accumulator register r, pair
-//                  (l >> 4) + 4 r of the block.  Epilogue in the accumulators: z = acc exp(lnZ_q - 1/2 sum_c (x_c - c_qc)^2 / C_qc), three
-//                  FMAs per output into the lane's running sums.  The group's 64 records are staged in LDS while the K loop runs and
-//                  read as broadcasts (one address per 16 lanes).  At the end the sums are added over the four lane groups (two
-//                  butterfly steps) and over the waves (in wave order, through LDS): no atomics, one fixed order that depends on
-//                  the model only.  gridDim.y = predict_missing_chunks(m) chunks of the groups, each into its own slab part [C][3k][ldp].
+//   k_predict_missing_pairs<KM>   the hot one: gamma, VlnS and nu's pair sums (:172-200) with the n x pairs product Pio Nu' never in memory:
+//                  the clean z and the pairs sink of k_predict_group_impl.h, where the layout is described once.  KM = 1 or 8 outputs in
+//                  registers.  gridDim.y = predict_missing_chunks(m) chunks of the groups, each into its own slab part [C][3k][ldp].
 //                  LDS: (32 (nk + 2) + 64 (1 + 2 d + 3 k) + 32 d) doubles, at least 4 * 32 * 3 KM for the last reduction.
+//                  k_predict_noisy_missing_pairs<KM> (k_predict_noisy_missing.hip, rows with Psi too) is launched from here as well.
 //   k_pmd_finish   the chunks added in chunk order; VlnS -= ElnS^2, beta = exp(ElnS + b) (1 + VlnS / 2), gamma -= mu^2 -> out [4k][nt] =
 //                  mu | nu | beta | gamma, the layout k_pred_finish_noisy_dev reads.                                         :203-209
 //   k_pmd_check    word 0 of the device entries' record is set when an element's NaN-ness differs from the mask.
 // A row's results depend on its own values and the model only: the same bits for any tile size, position in the block and row order.
 #include "gpz_dev.h"
 #include "gpz_kernels.h"
-
-// q = i (i + 1) / 2 + j, j <= i
-__device__ __forceinline__ void pmd_pair_of(long q, int *pi, int *pj) {
-    long i = (long)((sqrt(8.0 * (double)q + 1.0) - 1.0) * 0.5);
-    while ((i + 1) * (i + 2) / 2 <= q) ++i;
-    while (i * (i + 1) / 2 > q) --i;
-    *pi = (int)i;
-    *pj = (int)(q - i * (i + 1) / 2);
-}
+#include "k_predict_group_impl.h"
 
 __device__ __forceinline__ bool pmd_obs(unsigned obs, int c) { return (obs >> c) & 1u; }
 
@@ -103,7 +93,7 @@ __global__ __launch_bounds__(256) void k_pmd_pairs(long npair, long npad, int m,
         return;
     }
     int i, j;
-    pmd_pair_of(q, &i, &j);
+    gpz_pair_of(q, &i, &j);
     double lz = 0.0, qd = 0.0, ls = 0.0, lo = 0.0;
     for (int c = 0; c < d; ++c) {
         const double isi = G2[(size_t)i * de + c], isj = G2[(size_t)j * de + c];
@@ -119,13 +109,7 @@ __global__ __launch_bounds__(256) void k_pmd_pairs(long npair, long npad, int m,
         r[1 + d + c] = o ? iC : 0.0;
     }
     r[0] = -0.5 * lz - 0.5 * qd - 0.5 * ls - 0.5 * lo;                                           // :189 and the row-free part of :179
-    const double f = i == j ? 1.0 : 2.0;
-    double *cf = r + 1 + 2 * d;
-    for (int o = 0; o < k; ++o) {
-        cf[3 * o] = f * (w[i + (size_t)m * o] * w[j + (size_t)m * o]);
-        cf[3 * o + 1] = v ? f * (v[i + (size_t)m * o] * v[j + (size_t)m * o]) : 0.0;
-        cf[3 * o + 2] = f * iS[i + (size_t)m * j + (size_t)m * m * o];
-    }
+    gpz_pair_coef(r + 1 + 2 * d, i, j, m, k, w, v, iS);
 }
 
 // one thread per element of U in its stored order: e = (b * nks + ks) * 64 + lane
@@ -140,7 +124,7 @@ __global__ __launch_bounds__(256) void k_pmd_u(long npair, long nelem, int m, in
     double val = 0.0;
     if (q < npair && l < m) {
         int i, j;
-        pmd_pair_of(q, &i, &j);
+        gpz_pair_of(q, &i, &j);
         double qd = 0.0, ls = 0.0;
         for (int c = 0; c < d; ++c) {
             if (pmd_obs(obs, c)) continue;
@@ -158,9 +142,11 @@ __global__ __launch_bounds__(256) void k_pmd_u(long npair, long nelem, int m, in
 }
 
 // rows [0, nrow) of No and Pio (ld = mp), rows >= n and columns >= m zero; one wave per row, lanes along the basis functions
-__global__ __launch_bounds__(256) void k_pmd_no(const double *__restrict__ Xc, long ldx, int n, int nrow, int m, int mp, int d, int de,
-                                                unsigned obs, const double *__restrict__ P, const double *__restrict__ G2,
-                                                const double *__restrict__ bt, double *__restrict__ No, double *__restrict__ Pio) {
+template <bool PSI>
+__device__ __forceinline__ void pmd_no_body(const double *__restrict__ Xc, const double *__restrict__ Psic, long ldx, int n, int nrow, int m,
+                                            int mp, int d, int de, unsigned obs, const double *__restrict__ P,
+                                            const double *__restrict__ G2, const double *__restrict__ bt, double *__restrict__ No,
+                                            double *__restrict__ Pio) {
     const int lane = threadIdx.x & 63;
     const long i = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (i >= nrow) return;
@@ -171,21 +157,47 @@ __global__ __launch_bounds__(256) void k_pmd_no(const double *__restrict__ Xc, l
     }
     double s = 0.0;
     for (int j = lane; j < m; j += 64) {
-        double q = 0.0;
-        for (int c = 0; c < d; ++c)
-            if (pmd_obs(obs, c)) {
+        double q = 0.0, v;
+        if constexpr (!PSI) {
+            for (int c = 0; c < d; ++c)
+                if (pmd_obs(obs, c)) {
+                    const double dl = Xc[(size_t)c * ldx + i] - P[(size_t)j * de + c];
+                    q = fma(dl * dl, G2[(size_t)j * de + c], q);
+                }
+            v = exp(bt[j] - 0.5 * q);
+        } else {
+            double lu = 0.0;
+            for (unsigned mk = obs; mk; mk &= mk - 1) {
+                const int c = __builtin_ctz(mk);
+                const double g = G2[(size_t)j * de + c];
                 const double dl = Xc[(size_t)c * ldx + i] - P[(size_t)j * de + c];
-                q = fma(dl * dl, G2[(size_t)j * de + c], q);
+                const double u = fma(Psic[(size_t)c * ldx + i], g, 1.0);   // (psi + sigma) / sigma
+                q = fma(dl * dl, g / u, q);                                // :231
+                lu += log(u);
             }
-        const double v = exp(bt[j] - 0.5 * q);
+            v = exp(bt[j] - 0.5 * (q + lu));
+        }
         no[j] = v;
         s = fma(v, bt[mp + j], s);
     }
     s = wave_sum(s);
     for (int j = lane; j < mp; j += 64) {
-        if (j < m) pio[j] = no[j] * bt[mp + j] / s;                    // :154
+        if (j < m) pio[j] = no[j] * bt[mp + j] / s;                    // :154, :238
         else { no[j] = 0.0; pio[j] = 0.0; }
     }
+}
+
+__global__ __launch_bounds__(256) void k_pmd_no(const double *__restrict__ Xc, long ldx, int n, int nrow, int m, int mp, int d, int de,
+                                                unsigned obs, const double *__restrict__ P, const double *__restrict__ G2,
+                                                const double *__restrict__ bt, double *__restrict__ No, double *__restrict__ Pio) {
+    pmd_no_body<false>(Xc, nullptr, ldx, n, nrow, m, mp, d, de, obs, P, G2, bt, No, Pio);
+}
+
+__global__ __launch_bounds__(256) void k_pnm_no(const double *__restrict__ Xc, const double *__restrict__ Psic, long ldx, int n, int nrow,
+                                                int m, int mp, int de, unsigned obs, const double *__restrict__ P,
+                                                const double *__restrict__ G2, const double *__restrict__ bt, double *__restrict__ No,
+                                                double *__restrict__ Pio) {
+    pmd_no_body<true>(Xc, Psic, ldx, n, nrow, m, mp, 0, de, obs, P, G2, bt, No, Pio);
 }
 
 // PHI = No o T over No; hd [2k][ldh] = PHI w | PHI v; one wave per row
@@ -214,121 +226,9 @@ __global__ __launch_bounds__(256) void k_pmd_phi(double *__restrict__ No, const 
     }
 }
 
-struct PredMissArgs {
-    const double *Xc; long ldx; int n;   // the tile's rows, [d][ldx]
-    const double *Pio; int ldpio;        // [rows][ldpio]
-    int nk;                              // ceil16(m): K of the product
-    const double *U;                     // in fragment order (k_pmd_u)
-    const double *rec; int nrec;         // pair records, whole groups of 64
-    int d, k;
-    unsigned obs;
-    int ngrp, gpc;                       // groups of 64 pairs in all, and per chunk
-    double *part; long ldp;              // [chunks][3 k][ldp]: gamma | VlnS | nu
-};
-
 template <int KM>
-__global__ __launch_bounds__(256, 2) void k_predict_missing_pairs(PredMissArgs a) {
-    extern __shared__ double smem[];
-    const int nk = a.nk, lda = nk + 2, nrec = a.nrec, d = a.d, k = a.k;
-    double *sP = smem;                   // [32][lda]: Pio of the block (2 mod 4: the 16 rows of an operand read start 4 banks apart)
-    double *sR = sP + 32 * lda;          // [64][nrec]: the records of the group
-    double *sX = sR + 64 * nrec;         // [32][d]: the block's rows, zero where missing
-    const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const long i0 = (long)blockIdx.x * 32;
-    const int ch = blockIdx.y;
-    for (int e = tid; e < 32 * nk; e += 256) {
-        const int r = e / nk, c = e - r * nk;
-        sP[r * lda + c] = (i0 + r < a.n) ? a.Pio[(size_t)(i0 + r) * a.ldpio + c] : 0.0;
-    }
-    for (int e = tid; e < 32 * d; e += 256) {
-        const int r = e / d, c = e - r * d;
-        sX[e] = (pmd_obs(a.obs, c) && i0 + r < a.n) ? a.Xc[(size_t)c * a.ldx + i0 + r] : 0.0;
-    }
-    double ga[2][KM], vl[2][KM], nu[2][KM];
-#pragma unroll
-    for (int o = 0; o < KM; ++o) { ga[0][o] = ga[1][o] = 0.0; vl[0][o] = vl[1][o] = 0.0; nu[0][o] = nu[1][o] = 0.0; }
-    const int nks = nk >> 2;             // K steps of 4 (a multiple of 4)
-    const double *pa0 = sP + (lane & 15) * lda + (lane >> 4), *pa1 = pa0 + 16 * lda;
-    const double *x0 = sX + (lane & 15) * d, *x1 = x0 + 16 * d;
-    const double *rb = sR + (16 * wv + (lane >> 4)) * nrec;   // the records of pairs (lane >> 4) + 4 r of this wave's block, r = 0 .. 3
-    const int g0 = ch * a.gpc, g1 = min(a.ngrp, g0 + a.gpc);
-    for (int g = g0; g < g1; ++g) {
-        __syncthreads();   // the group before is read (first trip: sP and sX are written)
-        {
-            const double *src = a.rec + (size_t)g * 64 * nrec;
-            for (int t = tid; t < 64 * nrec; t += 256) sR[t] = src[t];
-        }
-        const double *ub = a.U + ((size_t)(4 * g + wv) * nks) * 64 + lane;
-        d4_t acc0 = (d4_t){0.0, 0.0, 0.0, 0.0}, acc1 = (d4_t){0.0, 0.0, 0.0, 0.0};
-        double ua[4], un[4] = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-        for (int q = 0; q < 4; ++q) ua[q] = ub[q * 64];
-        for (int ks = 0; ks < nks; ks += 4) {
-            if (ks + 4 < nks) {
-#pragma unroll
-                for (int q = 0; q < 4; ++q) un[q] = ub[(size_t)(ks + 4 + q) * 64];
-            }
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                acc0 = MFMA_F64(ua[q], pa0[4 * (ks + q)], acc0);
-                acc1 = MFMA_F64(ua[q], pa1[4 * (ks + q)], acc1);
-            }
-#pragma unroll
-            for (int q = 0; q < 4; ++q) ua[q] = un[q];
-        }
-        __syncthreads();   // the records are in LDS
-        // ---- epilogue: acc0[r], acc1[r] = sum_l Pio(row, l) Nu_q(l) for rows l & 15, 16 + (l & 15) and pair q = (l >> 4) + 4 r     :185-186
-        double qa[4] = {0.0, 0.0, 0.0, 0.0}, qb[4] = {0.0, 0.0, 0.0, 0.0};
-        for (int c = 0; c < d; ++c) {
-            const double xa = x0[c], xb = x1[c];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const double *t = rb + 4 * r * nrec;
-                const double cc = t[1 + c], ic = t[1 + d + c];
-                const double da = xa - cc, db = xb - cc;
-                qa[r] = fma(da * da, ic, qa[r]);                       // :178-179
-                qb[r] = fma(db * db, ic, qb[r]);
-            }
-        }
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const double *t = rb + 4 * r * nrec;
-            const double lz = t[0];
-            const double za = acc0[r] * exp(lz - 0.5 * qa[r]), zb = acc1[r] * exp(lz - 0.5 * qb[r]);   // :189
-            const double *cf = t + 1 + 2 * d;
-#pragma unroll
-            for (int o = 0; o < KM; ++o) {
-                if (o >= k) break;   // (a test per output instead of the break costs four spilled scalar registers at KM = 8)
-                const double c0 = cf[3 * o], c1 = cf[3 * o + 1], c2 = cf[3 * o + 2];
-                ga[0][o] = fma(za, c0, ga[0][o]); ga[1][o] = fma(zb, c0, ga[1][o]);   // :191-198
-                vl[0][o] = fma(za, c1, vl[0][o]); vl[1][o] = fma(zb, c1, vl[1][o]);
-                nu[0][o] = fma(za, c2, nu[0][o]); nu[1][o] = fma(zb, c2, nu[1][o]);
-            }
-        }
-    }
-    // ---- the four lane groups of a wave, then the waves in their order
-    __syncthreads();   // every wave is done with sP, sR and sX
-    double *sRed = smem;   // [4 waves][32 rows][3 KM]
-#pragma unroll
-    for (int s = 0; s < 2; ++s)
-#pragma unroll
-        for (int o = 0; o < KM; ++o) {
-            double v3[3] = {ga[s][o], vl[s][o], nu[s][o]};
-#pragma unroll
-            for (int q = 0; q < 3; ++q) {
-                double v = v3[q];
-                v += __shfl_xor(v, 16, 64);
-                v += __shfl_xor(v, 32, 64);
-                if (lane < 16) sRed[((wv * 32) + 16 * s + lane) * 3 * KM + q * KM + o] = v;
-            }
-        }
-    __syncthreads();
-    for (int t = tid; t < 32 * 3 * k; t += 256) {
-        const int row = t & 31, e = t >> 5, q = e / k, o = e - q * k;
-        const int at = row * 3 * KM + q * KM + o;
-        const double s = ((sRed[at] + sRed[32 * 3 * KM + at]) + sRed[2 * 32 * 3 * KM + at]) + sRed[3 * 32 * 3 * KM + at];
-        if (i0 + row < a.n) a.part[((size_t)ch * 3 * k + e) * a.ldp + i0 + row] = s;
-    }
+__global__ __launch_bounds__(256, 2) void k_predict_missing_pairs(PredGroupArgs a) {
+    predict_group_body<false, PredPairsSink<KM>>(a);
 }
 
 // hd [2k][ldh] = mu | ElnS - b; part [nchunk][3k][ldp] -> out [4k][nt]
@@ -365,9 +265,12 @@ int predict_missing_chunks(int m) {
     return (int)(c < 1 ? 1 : (c > 8 ? 8 : c));
 }
 
-size_t predict_missing_lds(int m, int d, int k) {
+// dynamic LDS of the pair kernels, bytes: the Pio block, the 64 records of a group, the block's rows of X and, with psi, of Psi
+size_t predict_missing_lds(int m, int d, int k, bool psi) {
     const size_t nk = ((size_t)m + 15) / 16 * 16, km = k == 1 ? 1 : 8;
-    const size_t work = 32 * (nk + 2) + 64 * (size_t)predict_missing_rec(d, k) + 32 * (size_t)d, red = 4 * 32 * 3 * km;
+    const size_t work = psi ? 32 * (nk + 2) + 64 * (size_t)predict_missing_rec(d, k) + 64 * (size_t)d
+                            : 32 * (nk + 2) + 64 * (size_t)predict_missing_rec(d, k) + 32 * (size_t)d;
+    const size_t red = 4 * 32 * 3 * km;
     return (work > red ? work : red) * sizeof(double);
 }
 
@@ -396,10 +299,12 @@ int launch_pmd_tables(hipStream_t st, int m, int mp, int d, int de, int k, unsig
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
-int launch_pmd_no(hipStream_t st, const double *Xc, long ldx, int n, int nrow, int m, int mp, int d, int de, unsigned obs, const double *P,
-                  const double *G2, const double *bt, double *No, double *Pio) {
+int launch_pmd_no(hipStream_t st, const double *Xc, const double *Psic, long ldx, int n, int nrow, int m, int mp, int d, int de,
+                  unsigned obs, const double *P, const double *G2, const double *bt, double *No, double *Pio) {
     if (nrow <= 0) return 0;
-    hipLaunchKernelGGL(k_pmd_no, dim3((unsigned)((nrow + 3) / 4)), dim3(256), 0, st, Xc, ldx, n, nrow, m, mp, d, de, obs, P, G2, bt, No, Pio);
+    const dim3 grid((unsigned)((nrow + 3) / 4));
+    if (Psic) hipLaunchKernelGGL(k_pnm_no, grid, dim3(256), 0, st, Xc, Psic, ldx, n, nrow, m, mp, de, obs, P, G2, bt, No, Pio);
+    else hipLaunchKernelGGL(k_pmd_no, grid, dim3(256), 0, st, Xc, ldx, n, nrow, m, mp, d, de, obs, P, G2, bt, No, Pio);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
@@ -410,32 +315,26 @@ int launch_pmd_phi(hipStream_t st, double *No, const double *T, int n, int m, in
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
-int launch_predict_missing_pairs(hipStream_t st, const double *Xc, long ldx, int n, const double *Pio, int ldpio, int m, int d, int k,
-                                 unsigned obs, const double *U, const double *rec, int nchunk, double *part, long ldp, const double *hd,
-                                 long ldh, const double *bvec, double *out) {
+int launch_predict_missing_pairs(hipStream_t st, const double *Xc, const double *Psic, long ldx, int n, const double *Pio, int ldpio, int m,
+                                 int d, int k, unsigned obs, const double *U, const double *rec, int nchunk, double *part, long ldp,
+                                 const double *hd, long ldh, const double *bvec, double *out) {
     if (n <= 0) return 0;
-    if (d < 1 || d > 20 || k < 1 || k > 8 || m < 1 || ((m + 15) / 16) * 16 > 256 || nchunk != predict_missing_chunks(m)) return -1;
-    PredMissArgs a{};
-    a.Xc = Xc; a.ldx = ldx; a.n = n; a.Pio = Pio; a.ldpio = ldpio; a.nk = ((m + 15) / 16) * 16; a.U = U; a.rec = rec;
+    if (d < 1 || d > 20 || k < 1 || k > 8 || m < 1 || ((m + 15) / 16) * 16 > 256 || nchunk != predict_missing_chunks(m) ||
+        (Psic && (obs >> d)))
+        return -1;
+    PredGroupArgs a{};
+    a.Xc = Xc; a.Psic = Psic; a.ldx = ldx; a.n = n; a.Pio = Pio; a.ldpio = ldpio; a.nk = ((m + 15) / 16) * 16; a.U = U; a.rec = rec;
     a.nrec = predict_missing_rec(d, k); a.d = d; a.k = k; a.obs = obs;
     a.ngrp = (int)predict_missing_groups(m);
     a.gpc = (a.ngrp + nchunk - 1) / nchunk;
     a.part = part; a.ldp = ldp;
-    const size_t lds = predict_missing_lds(m, d, k);
+    const size_t lds = predict_missing_lds(m, d, k, Psic != nullptr);
     const dim3 grid((unsigned)((n + 31) / 32), (unsigned)nchunk);
-    // per launch, not once per process: the attribute belongs to the current device's copy of the kernel
-    if (k == 1) {
-        if (lds > 65536 &&
-            hipFuncSetAttribute((const void *)k_predict_missing_pairs<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-            return -1;
-        hipLaunchKernelGGL(k_predict_missing_pairs<1>, grid, dim3(256), lds, st, a);
-    } else {
-        if (lds > 65536 &&
-            hipFuncSetAttribute((const void *)k_predict_missing_pairs<8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-            return -1;
-        hipLaunchKernelGGL(k_predict_missing_pairs<8>, grid, dim3(256), lds, st, a);
-    }
-    if (hipGetLastError() != hipSuccess) return -1;
+    if (Psic ? (k == 1 ? launch_predict_group<k_predict_noisy_missing_pairs<1>>(st, grid, lds, a)
+                       : launch_predict_group<k_predict_noisy_missing_pairs<8>>(st, grid, lds, a))
+             : (k == 1 ? launch_predict_group<k_predict_missing_pairs<1>>(st, grid, lds, a)
+                       : launch_predict_group<k_predict_missing_pairs<8>>(st, grid, lds, a)))
+        return -1;
     return launch_pmd_finish(st, part, nchunk, ldp, hd, ldh, n, k, bvec, out);
 }
 

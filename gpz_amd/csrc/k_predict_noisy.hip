@@ -33,17 +33,6 @@
 #define PREDICT_DRAWS_PSI   // k_predict_draws_psi<D>
 #include "k_predict_draws_impl.h"
 
-// 1 / sqrt(p): v_rsq_f64 seed and two Newton steps (k_psi.hip's rsqrt_nr)
-__device__ __forceinline__ double pn_rsqrt(double p) {
-    double y = __builtin_amdgcn_rsq(p);
-    const double h = 0.5 * p;
-    double e = fma(-h * y, y, 0.5);
-    y = fma(y, e, y);
-    e = fma(-h * y, y, 0.5);
-    y = fma(y, e, y);
-    return y;
-}
-
 struct PredNoisyArgs {
     const double *Xc, *Psic; long ldx;   // [d][ldx] column layout, n rows
     int n, m, k, de;                     // de: row stride of P and G2
@@ -126,8 +115,8 @@ __global__ __launch_bounds__(256) void k_predict_noisy_small(PredNoisyArgs a) {
             double q0 = 0.0, q1 = 0.0, r0p = 1.0, r1p = 1.0;
 #pragma unroll
             for (int c = 0; c < DT; ++c) {
-                const double r0 = pn_rsqrt(t0[1 + DT + c] + ps[c]);    // (Cij + Psi)^-1/2            :105
-                const double r1 = pn_rsqrt(t1[1 + DT + c] + ps[c]);
+                const double r0 = rsqrt_nr2(t0[1 + DT + c] + ps[c]);    // (Cij + Psi)^-1/2            :105
+                const double r1 = rsqrt_nr2(t1[1 + DT + c] + ps[c]);
                 const double d0 = (x[c] - t0[1 + c]) * r0, d1 = (x[c] - t1[1 + c]) * r1;
                 q0 = fma(d0, d0, q0);
                 q1 = fma(d1, d1, q1);
@@ -149,7 +138,7 @@ __global__ __launch_bounds__(256) void k_predict_noisy_small(PredNoisyArgs a) {
             double q0 = 0.0, r0p = 1.0;
 #pragma unroll
             for (int c = 0; c < DT; ++c) {
-                const double r0 = pn_rsqrt(t0[1 + DT + c] + ps[c]);
+                const double r0 = rsqrt_nr2(t0[1 + DT + c] + ps[c]);
                 const double d0 = (x[c] - t0[1 + c]) * r0;
                 q0 = fma(d0, d0, q0);
                 r0p *= r0;
@@ -199,17 +188,9 @@ __global__ __launch_bounds__(256) void k_noisy_pair_coef(int m, int k, int d, co
                                                          const double *__restrict__ iS, double *__restrict__ tab, int rec) {
     const long e = (long)blockIdx.x * 256 + threadIdx.x, npair = (long)m * (m + 1) / 2;
     if (e >= npair) return;
-    long a = (long)((sqrt(8.0 * (double)e + 1.0) - 1.0) * 0.5);
-    while (a * (a + 1) / 2 > e) --a;
-    while ((a + 1) * (a + 2) / 2 <= e) ++a;
-    const long b = e - a * (a + 1) / 2;
-    const double f = a == b ? 1.0 : 2.0;                               // 2x in the loop, 1x on the diagonal  (predictDiag.m:113-119)
-    double *cf = tab + (size_t)e * rec + 1 + 2 * d;
-    for (int o = 0; o < k; ++o) {
-        cf[3 * o] = f * (w[a + (size_t)m * o] * w[b + (size_t)m * o]);
-        cf[3 * o + 1] = v ? f * (v[a + (size_t)m * o] * v[b + (size_t)m * o]) : 0.0;
-        cf[3 * o + 2] = f * iS[a + (size_t)m * b + (size_t)m * m * o];
-    }
+    int a, b;
+    gpz_pair_of(e, &a, &b);                                            // f: 2x in the loop, 1x on the diagonal  (predictDiag.m:113-119)
+    gpz_pair_coef(tab + (size_t)e * rec + 1 + 2 * d, a, b, m, k, w, v, iS);
 }
 
 bool predict_noisy_fits(int kind, int de, int m, int k) {
@@ -302,13 +283,18 @@ int launch_predict_draws_psi(hipStream_t st, int de, const double *Xc, const dou
 }
 
 // ---- byte movers of the device entries ----------------------------------------------------------------------------------------------
-// smin: the smallest sd2 (1 without a normalisation) - psi / smin is the largest value a kernel can see of this element
+// dc: the columns of Psi that differ (1 for a broadcast column).  obs: the dimensions that are read (a group of rows with missing inputs:
+// its observed ones; else all ones).  smin: the smallest sd2 (1 without a normalisation) - psi / smin is the largest value a kernel can
+// see of this element
 __global__ __launch_bounds__(256) void k_pred_check_psi(const void *__restrict__ Psi, int f32, long ns, int dc, long rs, long cs,
-                                                        double smin, unsigned *__restrict__ rec) {
+                                                        unsigned obs, double smin, unsigned *__restrict__ rec) {
     const long ne = ns * dc, step = (long)gridDim.x * 256;
     int bad = 0;
     for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < ne; e += step) {
-        const long r = e / dc, at = r * rs + (e - r * dc) * cs;
+        const long r = e / dc;
+        const int c = (int)(e - r * dc);
+        if (dc > 1 && !((obs >> (c & 31)) & 1u)) continue;             // a missing dimension: not read
+        const long at = r * rs + c * cs;
         const double v = f32 ? (double)((const float *)Psi)[at] : ((const double *)Psi)[at];
         bad |= !(v >= 0.0) || !(v / smin <= 1.7976931348623157e308);   // NaN, negative, infinite (after the division by sd2 too)
     }
@@ -344,13 +330,18 @@ __global__ __launch_bounds__(256) void k_pred_finish_noisy_dev(const double *__r
     if (sigma) sigma[at] = v + b + g;
 }
 
-int launch_pred_check_psi(hipStream_t st, const void *Psi, int f32, long ns, int d, long rs, long cs, double smin, unsigned *rec) {
-    if (ns <= 0) return 0;
-    const int dc = (cs == 0) ? 1 : d;   // a broadcast column: once per row
+int launch_pnm_check_psi(hipStream_t st, const void *Psi, int f32, long ns, int d, long rs, long cs, unsigned obs, double smin,
+                         unsigned *rec) {
+    if (ns <= 0 || obs == 0) return 0;   // nothing observed: Psi is not read at all
+    const int dc = (cs == 0) ? 1 : d;    // a broadcast column: once per row
     long nb = (ns * dc + 255) / 256;
     if (nb > 4096) nb = 4096;
-    hipLaunchKernelGGL(k_pred_check_psi, dim3((unsigned)nb), dim3(256), 0, st, Psi, f32, ns, dc, rs, cs, smin, rec);
+    hipLaunchKernelGGL(k_pred_check_psi, dim3((unsigned)nb), dim3(256), 0, st, Psi, f32, ns, dc, rs, cs, obs, smin, rec);
     return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int launch_pred_check_psi(hipStream_t st, const void *Psi, int f32, long ns, int d, long rs, long cs, double smin, unsigned *rec) {
+    return launch_pnm_check_psi(st, Psi, f32, ns, d, rs, cs, ~0u, smin, rec);
 }
 
 int launch_pred_stage_psi(hipStream_t st, const void *Psi, int f32, long rs, long cs, long r0, int nt, int d, const double *sd2,

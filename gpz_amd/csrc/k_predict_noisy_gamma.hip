@@ -30,17 +30,6 @@
 #define GPZ_GAMMA_NB 8    // 16-column blocks of accumulators per pass
 #define GPZ_GAMMA_PF 4    // of these, the blocks whose W rows are fetched ahead of the density work (64 columns: the usual 64 draws)
 
-// 1 / sqrt(p): v_rsq_f64 seed and two Newton steps (k_predict_noisy.hip's pn_rsqrt)
-__device__ __forceinline__ double pg_rsqrt(double p) {
-    double y = __builtin_amdgcn_rsq(p);
-    const double h = 0.5 * p;
-    double e = fma(-h * y, y, 0.5);
-    y = fma(y, e, y);
-    e = fma(-h * y, y, 0.5);
-    y = fma(y, e, y);
-    return y;
-}
-
 struct PredGammaArgs {
     const double *Xc, *Psic; long ldx;   // [d][ldx] column layout, n rows
     int n, m;
@@ -123,7 +112,7 @@ __global__ __launch_bounds__(256) void k_predict_noisy_gamma(PredGammaArgs a) {
             double q = 0.0, rp = 1.0;
 #pragma unroll
             for (int c = 0; c < DT; ++c) {
-                const double r = pg_rsqrt(t[1 + DT + c] + ps[c]);      // (Cij + Psi)^-1/2            :105
+                const double r = rsqrt_nr2(t[1 + DT + c] + ps[c]);      // (Cij + Psi)^-1/2            :105
                 const double dl = (x[c] - t[1 + c]) * r;
                 q = fma(dl, dl, q);
                 rp *= r;

@@ -13,17 +13,6 @@
 // packed lower triangle, row-major: element (r, c), c <= r, at r(r+1)/2 + c
 #define LT(r, c) ((r) * ((r) + 1) / 2 + (c))
 
-// 1/sqrt(p) in fp64 without the library's sqrt + divide (~50 instructions): v_rsq_f64 seed and two Newton steps.
-__device__ __forceinline__ double rsqrt_nr(double p) {
-    double y = __builtin_amdgcn_rsq(p);
-    const double h = 0.5 * p;
-    double e = fma(-h * y, y, 0.5);
-    y = fma(y, e, y);
-    e = fma(-h * y, y, 0.5);
-    y = fma(y, e, y);
-    return y;
-}
-
 // In-place Cholesky of a packed lower triangle, division-free: rd[c] = 1 / L_cc (the diagonal slots of M hold L_cc for the
 // callers that read them), *prod_rd = prod_c rd[c] = |M|^-1/2.  A non-positive pivot gives NaN as sqrt() would.
 template <int D>
@@ -34,7 +23,7 @@ __device__ __forceinline__ void chol_packed_rd(double (&M)[D * (D + 1) / 2], dou
         double p = M[LT(c, c)];
 #pragma unroll
         for (int q = 0; q < c; ++q) p = fma(-M[LT(c, q)], M[LT(c, q)], p);
-        const double inv = rsqrt_nr(p);
+        const double inv = rsqrt_nr2(p);
         rd[c] = inv;
         M[LT(c, c)] = p * inv;
         prod *= inv;
@@ -483,7 +472,7 @@ __global__ __launch_bounds__(64) void k_predict_noisy_diag(int n, long ldx, int 
 #pragma unroll
         for (int c = 0; c < D; ++c)
             if (c < d) {
-                const double r = rsqrt_nr(t[1 + d + c] + ps[c]);               // (Cij + Psi)^-1/2          predictDiag.m:105
+                const double r = rsqrt_nr2(t[1 + d + c] + ps[c]);               // (Cij + Psi)^-1/2          predictDiag.m:105
                 const double dl = (x[c] - t[1 + c]) * r;
                 q = fma(dl, dl, q);
                 pr *= r;

@@ -17,9 +17,12 @@ from gpz_amd import _lib
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "gpz_amd", "csrc")
 SRC = os.path.join(CSRC, "k_predict_missing.hip")
+IMPL = os.path.join(CSRC, "k_predict_group_impl.h")              # the pair kernels' body and the helper that launches them
 HEADER = os.path.join(ROOT, "include", "gpz_hip.h")
 ENTRIES = {"gpz_predictor_run_missing_dev": 17, "gpz_predictor_draws_missing_dev": 16}
-KERNELS = ("k_pmd_check", "k_pmd_basis", "k_pmd_pairs", "k_pmd_u", "k_pmd_no", "k_pmd_phi", "k_predict_missing_pairs", "k_pmd_finish")
+# k_pnm_no: k_pmd_no for rows with Psi too, one body behind both (it came here from k_predict_noisy_missing.hip)
+KERNELS = ("k_pmd_check", "k_pmd_basis", "k_pmd_pairs", "k_pmd_u", "k_pmd_no", "k_pnm_no", "k_pmd_phi", "k_predict_missing_pairs",
+           "k_pmd_finish")
 
 
 def _model(d=3, m=6, k=1, method="VD"):
@@ -146,10 +149,10 @@ def test_missing_kernels_compiled_form(tmp_path):
         assert q["VGPRs"] + q.get("AGPRs", 0) <= 256, (name, q)           # two workgroups of 256 per compute unit
         assert q["LDS Size [bytes/block]"] == 0, (name, q)
     src = open(SRC).read()
-    body = re.search(r"size_t predict_missing_lds\(int m, int d, int k\) \{(.*?)\n\}", src, flags=re.S).group(1)
-    assert "32 * (nk + 2) + 64 * (size_t)predict_missing_rec(d, k) + 32 * (size_t)d" in body and "red = 4 * 32 * 3 * km" in body
+    body = re.search(r"size_t predict_missing_lds\(int m, int d, int k, bool psi\) \{(.*?)\n\}", src, flags=re.S).group(1)
+    assert ": 32 * (nk + 2) + 64 * (size_t)predict_missing_rec(d, k) + 32 * (size_t)d;" in body and "red = 4 * 32 * 3 * km" in body
     assert "int predict_missing_rec(int d, int k) { return 1 + 2 * d + 3 * k; }" in src
-    assert "hipFuncAttributeMaxDynamicSharedMemorySize" in src
+    assert "hipFuncAttributeMaxDynamicSharedMemorySize" in open(IMPL).read() and "launch_predict_group<k_predict_missing_pairs<" in src
     design = open(os.path.join(ROOT, "DESIGN.md")).read()
     assert "32 (nk + 2) + 64 (1 + 2 d + 3 k) + 32 d" in design
     # what the rule gives at the shapes section 17 names: the benchmark shape fits two workgroups per compute unit, the largest one
@@ -197,3 +200,32 @@ def test_fit_and_chunk_rules_are_functions_of_the_model_shape():
     changes = [m for m in range(2, 257) if chunks_rule(m) != chunks_rule(m - 1)]
     assert changes == [63, 78, 90, 101, 110, 119, 128]
     assert [chunks_rule(m) for m in (1, 11, 62, 63, 100, 127, 128, 256)] == [1, 1, 1, 2, 4, 7, 8, 8]
+
+
+# ---- the four units of the one pair-kernel body ----------------------------------------------------------------------------------------------
+GROUP_UNITS = {"k_predict_missing": ("k_predict_missing_pairs", [1, 8]),
+               "k_predict_noisy_missing": ("k_predict_noisy_missing_pairs", [1, 8]),
+               "k_predict_missing_gamma": ("k_predict_missing_gamma", list(range(1, 9))),
+               "k_predict_noisy_missing_gamma": ("k_predict_noisy_missing_gamma", list(range(1, 9)))}
+
+
+@pytest.mark.skipif(shutil.which("hipcc") is None, reason="needs hipcc")
+def test_each_unit_holds_exactly_its_own_pair_kernels(tmp_path):
+    """The four pair kernels are wrappers around predict_group_body<PSI, Sink> of k_predict_group_impl.h.  Each unit's listing holds the
+    instantiations of its own kernel and of no other of the four, every one on the shared argument struct, and the unit's text names
+    the body once, with the PSI and the sink of its name: a wrapper that named the wrong ones would still compile."""
+    procs = {u: subprocess.Popen(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-I" + os.path.join(ROOT, "include"), "-I" + CSRC,
+                                  "-S", "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage", os.path.join(CSRC, u + ".hip"),
+                                  "-o", str(tmp_path / (u + ".s"))], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
+             for u in GROUP_UNITS}
+    for u, (kname, counts) in GROUP_UNITS.items():
+        _, err = procs[u].communicate(timeout=1800)
+        assert procs[u].returncode == 0, err[-2000:]
+        recs = _resource_records(err)
+        found = sorted((m.group(1), int(m.group(2))) for m in (re.match(r"_Z\d+(k_predict_\w+?)ILi(\d+)EEv", n) for n in recs) if m)
+        assert found == [(kname, c) for c in counts], (u, found)
+        assert not any("k_predict_" in n and not re.match(r"_Z\d+k_predict_\w+?ILi\d+EEv13PredGroupArgs$", n) for n in recs), sorted(recs)
+        src = open(os.path.join(CSRC, u + ".hip")).read()
+        psi, sink = "noisy" in u, "PredGammaSink<NB>" if "gamma" in u else "PredPairsSink<KM>"
+        assert f"predict_group_body<{'true' if psi else 'false'}, {sink}>(a);" in src, u
+        assert src.count("predict_group_body<") == 1, u

@@ -21,10 +21,14 @@ from test_predictor_missing_cpu import _model, _resource_records
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "gpz_amd", "csrc")
 SRC = os.path.join(CSRC, "k_predict_noisy_missing.hip")
+LAUNCH = os.path.join(CSRC, "k_predict_missing.hip")               # the pair launcher and the LDS rule, with and without Psi
+IMPL = os.path.join(CSRC, "k_predict_group_impl.h")
 HEADER = os.path.join(ROOT, "include", "gpz_hip.h")
 ENTRIES = {"gpz_predictor_run_noisy_missing_dev": ("gpz_predictor_run_noisy_dev", 22),
            "gpz_predictor_draws_noisy_missing_dev": ("gpz_predictor_draws_noisy_dev", 21)}
-KERNELS = ("k_pnm_check_psi", "k_pnm_records", "k_pnm_no", "k_predict_noisy_missing_pairs")
+# k_pnm_no sits beside k_pmd_no in k_predict_missing.hip (one body), k_pnm_check_psi became k_pred_check_psi with a mask (k_predict_noisy.hip):
+# test_predictor_missing_cpu.py and test_predictor_noisy_cpu.py hold them
+KERNELS = ("k_pnm_records", "k_predict_noisy_missing_pairs")
 
 # where include/gpz_hip.h puts the arguments of the two entries (the stand-in checks the vectors behind the pointers there)
 calls.POS.setdefault("gpz_predictor_run_noisy_missing_dev",
@@ -128,12 +132,13 @@ def test_header_binding_and_library_agree_on_the_entries():
     build = open(os.path.join(ROOT, "build.sh")).read()
     assert re.search(r'UNITS="[^"]*\bk_predict_noisy_missing\b', build)
     kh = open(os.path.join(CSRC, "gpz_kernels.h")).read()
-    assert re.search(r"\bint launch_predict_noisy_missing_pairs\(", kh) and re.search(r"\bsize_t predict_noisy_missing_lds\(", kh)
+    assert re.search(r"\bint launch_predict_missing_pairs\(hipStream_t st, const double \*Xc, const double \*Psic,", kh)
+    assert re.search(r"\bsize_t predict_missing_lds\(int m, int d, int k, bool psi\);", kh)
 
 
 # ---- the compiled form ---------------------------------------------------------------------------------------------------------------------
 def lds_rule(m, d, k):
-    """predict_noisy_missing_lds of k_predict_noisy_missing.hip and DESIGN.md section 22, stated a second time on purpose: the Pio block
+    """predict_missing_lds with psi (k_predict_missing.hip) and DESIGN.md section 22, stated a second time on purpose: the Pio block
     of 32 rows (row stride ceil16(m) + 2), the 64 records of a pair group, the block's rows of X and of Psi; at least the 4 x 32 x 3 KM
     doubles of the last reduction (KM = 1 for one output, else 8)."""
     nk = (m + 15) // 16 * 16
@@ -143,7 +148,7 @@ def lds_rule(m, d, k):
 @pytest.mark.skipif(shutil.which("hipcc") is None, reason="needs hipcc")
 def test_kernels_compiled_form(tmp_path):
     """Every kernel of the unit: no scratch, no spilled register.  The pair kernel: two instantiations (1 or 8 outputs in registers), at
-    most 256 vector registers, no static LDS (all of it is the dynamic block of predict_noisy_missing_lds), the f64 MFMA, no
+    most 256 vector registers, no static LDS (all of it is the dynamic block of predict_missing_lds), the f64 MFMA, no
     floating-point atomic."""
     asm = tmp_path / "k_predict_noisy_missing.s"
     r = subprocess.run(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-I" + os.path.join(ROOT, "include"), "-I" + CSRC, "-S",
@@ -160,10 +165,11 @@ def test_kernels_compiled_form(tmp_path):
     for name, q in pairs.items():
         assert q["VGPRs"] + q.get("AGPRs", 0) <= 256, (name, q)           # two workgroups of 256 per compute unit
         assert q["LDS Size [bytes/block]"] == 0, (name, q)
-    src = open(SRC).read()
-    body = re.search(r"size_t predict_noisy_missing_lds\(int m, int d, int k\) \{(.*?)\n\}", src, flags=re.S).group(1)
-    assert "32 * (nk + 2) + 64 * (size_t)predict_missing_rec(d, k) + 64 * (size_t)d" in body and "red = 4 * 32 * 3 * km" in body
-    assert "hipFuncAttributeMaxDynamicSharedMemorySize" in src
+    src = open(LAUNCH).read()
+    body = re.search(r"size_t predict_missing_lds\(int m, int d, int k, bool psi\) \{(.*?)\n\}", src, flags=re.S).group(1)
+    assert "psi ? 32 * (nk + 2) + 64 * (size_t)predict_missing_rec(d, k) + 64 * (size_t)d\n" in body and "red = 4 * 32 * 3 * km" in body
+    assert "hipFuncAttributeMaxDynamicSharedMemorySize" in open(IMPL).read()
+    assert "launch_predict_group<k_predict_noisy_missing_pairs<" in src
     design = open(os.path.join(ROOT, "DESIGN.md")).read()
     assert "32 (nk + 2) + 64 (1 + 2 d + 3 k) + 64 d" in design
     # the benchmark shape fits two workgroups per compute unit, the largest shape one (opted in above 64 KB)

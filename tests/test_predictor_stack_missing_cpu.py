@@ -148,7 +148,7 @@ def test_header_binding_library_and_build_agree_on_the_new_entries():
     build = open(os.path.join(ROOT, "build.sh")).read()
     assert re.search(r'UNITS="[^"]*\bk_predict_missing_gamma\b', build)
     kh = open(os.path.join(CSRC, "gpz_kernels.h")).read()
-    assert "int launch_predict_missing_gamma(" in kh and "size_t predict_missing_gamma_lds(int m, int d);" in kh
+    assert "int launch_predict_missing_gamma(" in kh and "size_t predict_missing_gamma_lds(int m, int d, bool psi);" in kh
     host = open(os.path.join(CSRC, "gpz_predictor.hip")).read()
     assert "p->mchunks, p->gpart, nt))" in host                          # the pair kernel's own chunk count: predict_missing_chunks(m)
     assert "; missing per draw: k_predict_missing_gamma (%d pair chunks)" in host
@@ -200,9 +200,11 @@ def test_missing_gamma_kernel_compiled_form(tmp_path):
     for word in ("global_atomic", "flat_atomic", "ds_add_f", "ds_add_rtn_f", "cmpswap", "scratch_"):
         assert word not in text, word
     src = open(src_path).read()
-    body = re.search(r"size_t predict_missing_gamma_lds\(int m, int d\) \{(.*?)\n\}", src, flags=re.S).group(1)
-    assert "32 * (nk + 2) + 64 * (1 + 2 * (size_t)d) + 32 * (size_t)d + 64" in body and "red = 4 * 32 * 16" in body
-    assert "hipFuncAttributeMaxDynamicSharedMemorySize" in src and "nchunk != predict_missing_chunks(m)" in src
+    body = re.search(r"size_t predict_missing_gamma_lds\(int m, int d, bool psi\) \{(.*?)\n\}", src, flags=re.S).group(1)
+    assert ": 32 * (nk + 2) + 64 * (1 + 2 * (size_t)d) + 32 * (size_t)d + 64;" in body and "red = 4 * 32 * 16" in body
+    impl = open(os.path.join(CSRC, "k_predict_group_impl.h")).read()      # the helper that launches the four kernels
+    assert "hipFuncAttributeMaxDynamicSharedMemorySize" in impl and "launch_predict_group<k_predict_missing_gamma<NBT>>" in src
+    assert "nchunk != predict_missing_chunks(m)" in src
     design = open(os.path.join(ROOT, "DESIGN.md")).read()
     assert "32 (nk + 2) + 64 (1 + 2 d) + 32 d + 64" in design
     # what the rule gives at the shapes section 19 names: the timing shape fits two workgroups per compute unit, the largest one

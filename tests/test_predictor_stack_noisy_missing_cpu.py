@@ -25,6 +25,7 @@ from test_predictor_stack_noisy import noise, with_weights
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "gpz_amd", "csrc")
 SRC = os.path.join(CSRC, "k_predict_noisy_missing_gamma.hip")
+LAUNCH = os.path.join(CSRC, "k_predict_missing_gamma.hip")         # the gamma launcher and the LDS rule, with and without Psi
 HEADER = os.path.join(ROOT, "include", "gpz_hip.h")
 NB_MAX = 8                                                                # column blocks per launch
 GAMMA, STACK = "gpz_predictor_draws_gamma_noisy_missing_dev", "gpz_predictor_stack_noisy_missing_dev"
@@ -110,7 +111,8 @@ def test_header_binding_library_and_build_agree_on_the_new_entries():
     build = open(os.path.join(ROOT, "build.sh")).read()
     assert re.search(r'UNITS="[^"]*\bk_predict_noisy_missing_gamma\b', build)
     kh = open(os.path.join(CSRC, "gpz_kernels.h")).read()
-    assert "int launch_predict_noisy_missing_gamma(" in kh and "size_t predict_noisy_missing_gamma_lds(int m, int d);" in kh
+    assert "int launch_predict_missing_gamma(hipStream_t st, const double *Xc, const double *Psic," in kh
+    assert "size_t predict_missing_gamma_lds(int m, int d, bool psi);" in kh
     host = open(os.path.join(CSRC, "gpz_predictor.hip")).read()
     assert "; noisy missing per draw: k_predict_noisy_missing_gamma (%d pair chunks)" in host
     assert "are not there for rows with input noise and missing inputs" not in host
@@ -253,7 +255,7 @@ def test_methods_refuse_in_order_before_the_gpu(monkeypatch):
 
 # ---- the compiled form ---------------------------------------------------------------------------------------------------------------------
 def gamma_lds_rule(m, d):
-    """predict_noisy_missing_gamma_lds of k_predict_noisy_missing_gamma.hip and DESIGN.md section 23, stated a second time on purpose: the
+    """predict_missing_gamma_lds with psi (k_predict_missing_gamma.hip) and DESIGN.md section 23, stated a second time on purpose: the
     Pio block of 32 rows (row stride ceil16(m) + 2), [lnZ | c | C] of the 64 pairs of a group, the block's rows of X and of Psi, (a, b) of
     the 64 pairs as 128 ints; at least the 4 x 32 x 16 doubles of the last reduction, one column block at a time."""
     nk = (m + 15) // 16 * 16
@@ -264,11 +266,13 @@ def test_lds_rule_at_the_three_shapes():
     assert gamma_lds_rule(100, 5) == 37_888 and 2 * gamma_lds_rule(100, 5) <= 160 * 1024   # two workgroups per compute unit
     assert gamma_lds_rule(256, 20) == 97_792 and gamma_lds_rule(256, 20) <= 160 * 1024     # one, opted in per launch
     assert gamma_lds_rule(1, 1) == 16_384
-    src = open(SRC).read()
-    body = re.search(r"size_t predict_noisy_missing_gamma_lds\(int m, int d\) \{(.*?)\n\}", src, flags=re.S).group(1)
-    assert "32 * (nk + 2) + 64 * (1 + 2 * (size_t)d) + 64 * (size_t)d + 64" in body and "red = 4 * 32 * 16" in body
-    assert "hipFuncAttributeMaxDynamicSharedMemorySize" in src and "nchunk != predict_missing_chunks(m)" in src
-    assert f"#define GPZ_NMGAMMA_NB {NB_MAX}" in src
+    src = open(LAUNCH).read()
+    body = re.search(r"size_t predict_missing_gamma_lds\(int m, int d, bool psi\) \{(.*?)\n\}", src, flags=re.S).group(1)
+    assert "psi ? 32 * (nk + 2) + 64 * (1 + 2 * (size_t)d) + 64 * (size_t)d + 64\n" in body and "red = 4 * 32 * 16" in body
+    impl = open(os.path.join(CSRC, "k_predict_group_impl.h")).read()      # the helper that launches the four kernels
+    assert "hipFuncAttributeMaxDynamicSharedMemorySize" in impl and "launch_predict_group<k_predict_noisy_missing_gamma<NBT>>" in src
+    assert "nchunk != predict_missing_chunks(m)" in src
+    assert f"#define GPZ_MGAMMA_NB {NB_MAX}" in src                         # one count for the kernels with and without Psi
     design = open(os.path.join(ROOT, "DESIGN.md")).read()
     assert "32 (nk + 2) + 64 (1 + 2 d) + 64 d + 64" in design
 
@@ -276,7 +280,7 @@ def test_lds_rule_at_the_three_shapes():
 @pytest.mark.skipif(shutil.which("hipcc") is None, reason="needs hipcc")
 def test_noisy_missing_gamma_kernel_compiled_form(tmp_path):
     """k_predict_noisy_missing_gamma<NB>, NB = 1 .. NB_MAX column blocks: no scratch, no spilled register, VGPRs + AGPRs <= 256 (two
-    workgroups of 256 per compute unit), no static LDS (all of it is the dynamic block of predict_noisy_missing_gamma_lds), the f64
+    workgroups of 256 per compute unit), no static LDS (all of it is the dynamic block of predict_missing_gamma_lds), the f64
     MFMA, no atomic of any kind and no other kernel in the unit."""
     asm = tmp_path / "k_predict_noisy_missing_gamma.s"
     r = subprocess.run(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-I" + os.path.join(ROOT, "include"), "-I" + CSRC, "-S",

@@ -1,7 +1,9 @@
 """SHA-256 of everything the streaming predictor returns, for comparing two builds of the library bit for bit
 (profiles/r11_predictor_refactor.txt: the host code of gpz_predictor.hip before and after it was folded onto one pipeline;
 profiles/r14_predictor_row_kinds.txt: before and after clean, noisy and missing rows were folded onto one set of runners and the unit
-was cut into gpz_predictor.hip, gpz_predictor_host.hip and gpz_predictor_dev.hip behind gpz_predictor.h).
+was cut into gpz_predictor.hip, gpz_predictor_host.hip and gpz_predictor_dev.hip behind gpz_predictor.h;
+profiles/r18_predict_group_kernels.txt: before and after the four pair kernels of a group of rows with missing inputs were folded onto
+the one body of k_predict_group_impl.h).
 
     python tools/predictor_digest.py > digest.txt        # in each tree, on the same machine; then diff the two files
 
@@ -9,9 +11,11 @@ Seeded models of both kinds (VD, VC) on both routes (fused, force_tiles) with k 
 (the last one partial).  Every entry of the handle is called: predict with and without PHI and with Psi, draws by seed and by an
 explicit Z and with Psi, stack with and without draws, groups and weights, and the device entries on float64, float32 and strided
 rows; on the VD models the stacks of rows with input noise (host and device) and gamma per draw beside the draws, and, on the same
-rows with four NaN patterns knocked out, predict_dev, draws_dev (with and without gamma) and the stack of rows with missing inputs; a
-third handle meets the missing stack first, then the noisy one, then predict.  After each call one line: the call, the digest of
-each array it returned, and the handle's route and info."""
+rows with four NaN patterns knocked out, predict_dev, draws_dev (with and without gamma) and the stack of rows with missing inputs,
+and the same with Psi (predict_noisy_missing_dev, draws_noisy_missing_dev with and without gamma, stack_noisy_missing_dev plain, with
+draws and groups, and with Z and a selection); a third handle meets the missing stack first, then the noisy one, then predict.  One
+more VD model has m = 128 and k = 3: predict_missing_chunks is 8 there and the KM = 8 pair kernels walk more than one group per chunk.
+After each call one line: the call, the digest of each array it returned, and the handle's route and info."""
 import hashlib
 import os
 import sys
@@ -49,8 +53,8 @@ def four_patterns(X):
     return X
 
 
-def run(method, k, force):
-    tag = f"{method} k={k} {'tiles' if force else 'fused'}"
+def run(method, k, force, M=M):
+    tag = f"{method} k={k} {'tiles' if force else 'fused'}" + ("" if M == 50 else f" m={M}")
     model = synth_model(method, M, D, k, True, seed=100 * k + (method == "VC"))
     rng = np.random.default_rng(7 * k)
     X = catalogue(model, NS, seed=k)
@@ -108,6 +112,15 @@ def run(method, k, force):
             report(f"{tag} stack_missing_dev", p, tuple(p.stack_missing_dev(Xm, edges)))
             report(f"{tag} stack_missing_dev draws", p, tuple(p.stack_missing_dev(Xm, edges, n_draws=DRAWS, seed=11, **by_group_d)))
             report(f"{tag} stack_missing_dev Z sel", p, tuple(p.stack_missing_dev(Xm, edges, n_draws=DRAWS, Z=Z, selection=sd, **by_group_d)))
+            report(f"{tag} predict_noisy_missing_dev", p, p.predict_noisy_missing_dev(Xm, Pd))
+        if noisy and not force:                                          # with Psi the draws and the stack need the fused draws route
+            report(f"{tag} draws_noisy_missing_dev", p, p.draws_noisy_missing_dev(Xm, Pd, DRAWS, seed=11))
+            report(f"{tag} draws_noisy_missing_dev gamma", p, p.draws_noisy_missing_dev(Xm, Pd, DRAWS, Z=Z, return_gamma=True))
+            report(f"{tag} stack_noisy_missing_dev", p, tuple(p.stack_noisy_missing_dev(Xm, Pd, edges)))
+            report(f"{tag} stack_noisy_missing_dev draws", p,
+                   tuple(p.stack_noisy_missing_dev(Xm, Pd, edges, n_draws=DRAWS, seed=11, **by_group_d)))
+            report(f"{tag} stack_noisy_missing_dev Z sel", p,
+                   tuple(p.stack_noisy_missing_dev(Xm, Pd, edges, n_draws=DRAWS, Z=Z, selection=sd, **by_group_d)))
     with gpz_amd.Predictor(model, tile_rows=TILE, force_tiles=force) as p:   # a handle that meets the stack first, then PHI
         report(f"{tag} second handle stack_dev", p, tuple(p.stack_dev(Xd, edges, n_draws=2, seed=3)))
         report(f"{tag} second handle stack", p, tuple(p.stack(X, edges, n_draws=DRAWS, seed=3)))
@@ -126,6 +139,7 @@ def main():
         for k in (1, 3):
             for force in (False, True):
                 run(method, k, force)
+    run("VD", 3, False, M=128)
 
 
 if __name__ == "__main__":
