@@ -692,7 +692,8 @@ extern "C" int gpz_dxy(const double *X, int64_t nx, const double *Y, int64_t ny,
         if (e == hipSuccess) e = hipMemcpy(dy, Y, (size_t)ny * d * sizeof(double), hipMemcpyHostToDevice);
         if (e == hipSuccess) {
             launch_dxy(nullptr, dx, nx, dy, ny, d, dd);
-            e = hipMemcpy(D, dd, (size_t)nx * ny * sizeof(double), hipMemcpyDeviceToHost);
+            e = hipGetLastError();                       // a rejected launch: the copy below would succeed on memory nobody wrote
+            if (e == hipSuccess) e = hipMemcpy(D, dd, (size_t)nx * ny * sizeof(double), hipMemcpyDeviceToHost);
         }
         if (e != hipSuccess) rc = gpz_fail(GPZ_ERR_HIP, "gpz_dxy: %s", hipGetErrorString(e));
     }

@@ -634,6 +634,25 @@ __global__ __launch_bounds__(256) void k_prior_iter(const double *__restrict__ N
     }
 }
 
+// The same for ANY m (launch_prior_iter takes it past 16 strips of 256 columns, m > 4096, where the register arrays above end): a
+// thread walks its columns j = tid, tid + 256, ... twice per row - the row total first - and adds into its own entries of the
+// workgroup's colslab row, which no other thread touches.
+__global__ __launch_bounds__(256) void k_prior_iter_loop(const double *__restrict__ N, int ld, int n, int m,
+                                                          const double *__restrict__ prior, double *__restrict__ colslab) {
+    __shared__ double sh4[4];
+    const int tid = threadIdx.x;
+    double *acc = colslab + (size_t)blockIdx.x * m;
+    for (int j = tid; j < m; j += 256) acc[j] = 0.0;
+    for (int i = blockIdx.x; i < n; i += gridDim.x) {
+        const double *row = N + (size_t)i * ld;
+        double part = 0.0;
+        for (int j = tid; j < m; j += 256) part += row[j] * prior[j];
+        const double tot = block_sum_256(part, sh4);
+        for (int j = tid; j < m; j += 256) acc[j] += row[j] * prior[j] / tot;
+        __syncthreads();
+    }
+}
+
 // The same iteration for m <= 256 with a WAVE per row (lane l holds columns l, l + 64, l + 128, l + 192): the row sum is a wave
 // reduction - no LDS, no barrier in the row loop (the workgroup-per-row form above pays two barriers per row: 88 us a pass at
 // n = 1e5, m = 200, where the 160 MB of N are 40 us of HBM time; getPrior runs up to 100 passes, twice per train()).
@@ -691,7 +710,8 @@ void launch_prior_iter(hipStream_t st, const double *N, int ld, int n, int m, co
     else if (nj <= 2) hipLaunchKernelGGL(k_prior_iter<2>, g, b, 0, st, N, ld, n, m, prior, colslab);
     else if (nj <= 4) hipLaunchKernelGGL(k_prior_iter<4>, g, b, 0, st, N, ld, n, m, prior, colslab);
     else if (nj <= 8) hipLaunchKernelGGL(k_prior_iter<8>, g, b, 0, st, N, ld, n, m, prior, colslab);
-    else hipLaunchKernelGGL(k_prior_iter<16>, g, b, 0, st, N, ld, n, m, prior, colslab);
+    else if (nj <= 16) hipLaunchKernelGGL(k_prior_iter<16>, g, b, 0, st, N, ld, n, m, prior, colslab);
+    else hipLaunchKernelGGL(k_prior_iter_loop, g, b, 0, st, N, ld, n, m, prior, colslab);
 }
 
 // grid of a general-path kernel: one thread per item in 64-thread workgroups (d <= 20), or the fixed grid-stride pool

@@ -170,8 +170,8 @@ struct gpz_lbfgs {
     double hdiag = 1.0;
     std::vector<double> SS, SY, YY;     // Gram blocks over physical columns: SS[a*nc+b] = s_a.s_b, SY[a*nc+b] = s_a.y_b, YY likewise
     std::vector<double> hbuf;
-    std::vector<double> gdots;          // [S Y]' g of the g gpz_lbfgs_add was called with (the direction call that follows it takes them)
-    const double *g_of_gdots = nullptr;
+    std::vector<double> gdots;          // [S Y]' g of the g gpz_lbfgs_add was called with (a direction call with g_dev = NULL takes them)
+    const double *g_of_gdots = nullptr; // that g, until the next direction call
 };
 #define LBCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { snprintf(lb_err, sizeof lb_err, "%s: %s", #x, hipGetErrorString(e_)); return GPZ_ERR_HIP; } } while (0)
 
@@ -259,12 +259,20 @@ extern "C" int gpz_lbfgs_add(gpz_lbfgs *h, const double *g_dev, const double *g_
 }
 
 // lbfgsProd.m: d = -H*g through the two-loop recursion in coefficient space.
+// g_dev = NULL: "the g of the gpz_lbfgs_add just before" - that call's products [S Y]'g and its pointer are used.  A pointer is never
+// compared with the kept one: the same address may hold another vector by now (updated in place, or handed out again by an allocator).
 extern "C" int gpz_lbfgs_direction(gpz_lbfgs *h, const double *g_dev, double *d_dev) {
-    if (!h || !g_dev || !d_dev) { snprintf(lb_err, sizeof lb_err, "gpz_lbfgs_direction: null argument"); return GPZ_ERR_ARG; }
-    LBCHK(hipSetDevice(h->device));
+    if (!h || !d_dev) { snprintf(lb_err, sizeof lb_err, "gpz_lbfgs_direction: null argument"); return GPZ_ERR_ARG; }
     const int nc = h->nc, k = (int)h->order.size();
     const long p = h->p;
-    if (h->g_of_gdots == g_dev && (int)h->gdots.size() == 2 * nc) {   // the g of the gpz_lbfgs_add just before: its dots are here already
+    const bool kept = !g_dev;
+    if (kept && (!h->g_of_gdots || (int)h->gdots.size() != 2 * nc)) {
+        snprintf(lb_err, sizeof lb_err, "gpz_lbfgs_direction: g_dev = NULL stands for the g of the gpz_lbfgs_add just before, and no such call precedes this one");
+        return GPZ_ERR_ARG;
+    }
+    LBCHK(hipSetDevice(h->device));
+    if (kept) {
+        g_dev = h->g_of_gdots;
         for (int c = 0; c < 2 * nc; ++c) h->hbuf[(size_t)c * 3] = h->gdots[c];
     } else {
         hipLaunchKernelGGL(k_lb_dots, dim3(h->nchunk, (2 * nc + LB_CG - 1) / LB_CG), dim3(256), 0, h->st, (const double *)h->S, (const double *)h->Y, p, nc, g_dev,
@@ -274,7 +282,7 @@ extern "C" int gpz_lbfgs_direction(gpz_lbfgs *h, const double *g_dev, double *d_
         LBCHK(hipMemcpyAsync(h->hbuf.data(), h->red, (size_t)cnt * sizeof(double), hipMemcpyDeviceToHost, h->st));
         LBCHK(hipStreamSynchronize(h->st));
     }
-    h->g_of_gdots = nullptr;   // (one use: the same address may hold another vector at the next call)
+    h->g_of_gdots = nullptr;   // (one use: after any direction call NULL no longer names a vector)
     std::vector<double> ds(nc, 0.0), dy(nc, 0.0), al(nc, 0.0);
     double dg = -1.0;                                                          // q = -g
     auto sg = [&](int c) { return h->hbuf[(size_t)c * 3]; };                   // s_c . g

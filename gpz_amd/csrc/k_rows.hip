@@ -948,20 +948,23 @@ void launch_sums1(hipStream_t st, const double *omega, long om_ld, const double 
 __global__ void k_dxy(const double *__restrict__ X, long nx, const double *__restrict__ Y, long ny, int d,
                       double *__restrict__ D) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    const long j = blockIdx.y;
     if (i >= nx) return;
-    double xx = 0.0, yy = 0.0, xy = 0.0;
-    for (int c = 0; c < d; ++c) {
-        const double xv = X[c * nx + i], yv = Y[c * ny + j];
-        xx = fma(xv, xv, xx);
-        yy = fma(yv, yv, yy);
-        xy = fma(xv, yv, xy);
+    for (long j = blockIdx.y; j < ny; j += gridDim.y) {      // (the launcher caps gridDim.y: ny may exceed what a device takes there)
+        double xx = 0.0, yy = 0.0, xy = 0.0;
+        for (int c = 0; c < d; ++c) {
+            const double xv = X[c * nx + i], yv = Y[c * ny + j];
+            xx = fma(xv, xv, xx);
+            yy = fma(yv, yv, yy);
+            xy = fma(xv, yv, xy);
+        }
+        D[j * nx + i] = fabs(fabs(yy + (xx - 2.0 * xy)));
     }
-    D[j * nx + i] = fabs(fabs(yy + (xx - 2.0 * xy)));
 }
 
+#define DXY_MAX_GY 4096
 void launch_dxy(hipStream_t st, const double *X, long nx, const double *Y, long ny, int d, double *D) {
-    hipLaunchKernelGGL(k_dxy, dim3((unsigned)((nx + 255) / 256), (unsigned)ny), dim3(256), 0, st, X, nx, Y, ny, d, D);
+    const unsigned gy = (unsigned)(ny < DXY_MAX_GY ? ny : DXY_MAX_GY);
+    hipLaunchKernelGGL(k_dxy, dim3((unsigned)((nx + 255) / 256), gy), dim3(256), 0, st, X, nx, Y, ny, d, D);
 }
 
 // dst (n x m column-major) = src (row-major, leading dimension ld), tiled through LDS.

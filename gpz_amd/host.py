@@ -296,19 +296,26 @@ class _LBFGSDevice:
         import ctypes as C
         self._lib = _lib
         self._h = C.c_void_p()
+        self._last_g = None     # the DevVec the last add_step took as g, until the next direction
         _lib.check_plain(_lib.load().gpz_lbfgs_create(int(p), int(corrections), int(device), None, C.byref(self._h)))
 
     def add_step(self, g, g_old, t, d):
         import ctypes as C
         added = C.c_int32()
+        self._last_g = None
         self._lib.check_plain(self._lib.load().gpz_lbfgs_add(self._h, g.t.data_ptr(), g_old.t.data_ptr(), float(t),
                                                             d.t.data_ptr(), C.byref(added)))
+        self._last_g = g
         return bool(added.value)
 
     def direction(self, g):
+        """g NULL for the library exactly when g is the very DevVec add_step was just given (a DevVec is never modified in place, and
+        the reference held here keeps its memory from being handed out again): the library then takes the products [S Y]'g of that
+        pass; any other vector, an equal one at another or the same address included, goes by pointer and is multiplied afresh."""
         import torch
         d = torch.empty_like(g.t)
-        self._lib.check_plain(self._lib.load().gpz_lbfgs_direction(self._h, g.t.data_ptr(), d.data_ptr()))
+        same, self._last_g = g is self._last_g, None
+        self._lib.check_plain(self._lib.load().gpz_lbfgs_direction(self._h, None if same else g.t.data_ptr(), d.data_ptr()))
         return DevVec(d)
 
     def close(self):

@@ -507,7 +507,10 @@ int gpz_predictor_stack_noisy_missing_dev(gpz_predictor *p, const void *X_d, int
  * S and Y (p x corrections) live on the device; all vector arguments are device pointers.
  * gpz_lbfgs_add:        y = g - g_old, s = t*d; skipped (added = 0) when y's <= 1e-10        (lbfgsAdd.m:2-4)
  * gpz_lbfgs_direction:  d = -H*g with Hdiag = y's/y'y of the newest pair                      (lbfgsProd.m, minFunc.m:553-578)
- *                       (called with the g of the gpz_lbfgs_add just before - minFunc's order - it reuses the products [S Y]'g of that pass)
+ *                       g_dev = NULL stands for the g of the gpz_lbfgs_add just before (minFunc's order): the products [S Y]'g of that
+ *                       pass and its pointer are used, one pass over the memory less; GPZ_ERR_ARG when no gpz_lbfgs_add precedes the
+ *                       call or another gpz_lbfgs_direction has come between.  A non-NULL g_dev always forms [S Y]'g itself - the
+ *                       address is never compared with an earlier one, the buffer may hold another vector by now
  * gpz_vec_stats:        out = [g.d, max|g|, sum|g|, max|d|] (NaN-propagating), the scalars of minFunc's tests
  * gpz_vec_axpy:         out = x + t*d */
 typedef struct gpz_lbfgs gpz_lbfgs;

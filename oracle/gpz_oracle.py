@@ -753,20 +753,22 @@ def predict_any(X, model: Model, Psi=None, whichSet="best", selection=None):
     return mu + model.muY, sigma, nu, beta_i, gamma, PHI
 
 
-def getPrior(X, Psi, theta, model: Model, selection=None):
+def getPrior(X, Psi, theta, model: Model, selection=None, return_iterations=False):
     """prior = getPrior(X,Sx,theta,model,set)   (getPrior.m:1-22): EM-style fixed point on the mixture weights of
-    the normalised basis densities N (N is loop-invariant; the reference recomputes it every iteration)."""
+    the normalised basis densities N (N is loop-invariant; the reference recomputes it every iteration).
+    return_iterations: (prior, number of passes of the loop of getPrior.m:7-20) - no counterpart in the reference's outputs."""
     m = model.m
     prior = np.ones(m) / m
     N = getPHI(X, Psi, theta, model, selection, want_N=True)[3]
-    for _ in range(100):
+    it = 0
+    for it in range(1, 101):
         old = prior
         wgt = N * prior
         wgt = wgt / wgt.sum(axis=1, keepdims=True)
         prior = wgt.mean(axis=0)
         if np.linalg.norm(old - prior) / np.linalg.norm(old + prior) < 1e-10:
             break
-    return prior
+    return (prior, it) if return_iterations else prior
 
 
 # --------------------------------------------------------------------------
