@@ -100,6 +100,13 @@ SYMBOLS = {
                                                 C.c_int64, C.c_int64, c_double_p, c_double_p, c_double_p, c_double_p, C.c_int32,
                                                 C.c_uint64, c_double_p, C.c_void_p, C.c_void_p]),
     "gpz_predictor_draws_noisy": (C.c_int, [C.c_void_p, c_double_p, C.c_int64, c_double_p, C.c_int32, C.c_uint64, c_double_p, c_double_p]),
+    # the same two for the covariance kinds (GC, VC; predict_noisy_cov_fits): the arguments of the two entries above
+    "gpz_predictor_run_noisy_cov_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_void_p,
+                                                  C.c_int32, C.c_int64, C.c_int64, c_double_p, c_double_p, c_double_p, c_double_p,
+                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gpz_predictor_draws_noisy_cov_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_void_p,
+                                                    C.c_int32, C.c_int64, C.c_int64, c_double_p, c_double_p, c_double_p, c_double_p,
+                                                    C.c_int32, C.c_uint64, c_double_p, C.c_void_p, C.c_void_p]),
     # stacks of rows with input noise and gamma under every draw: the stack / draws entries with Psi as the noisy draws take it
     "gpz_predictor_stack_noisy": (C.c_int, [C.c_void_p, c_double_p, C.c_int64, c_double_p, C.c_int32, C.c_uint64, c_double_p, c_double_p,
                                             C.c_int32, c_int32_p, C.c_int32, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p,

@@ -227,6 +227,28 @@ int launch_pred_stage_psi(hipStream_t st, const void *Psi, int f32, long rs, lon
                           double *Psic, long ldx);
 int launch_pred_finish_noisy_dev(hipStream_t st, const double *out, int nt, int k, const double *muY, long ns, long r0, double *mu,
                                  double *sigma, double *nu, double *beta, double *gamma);
+// the finish kernel behind launch_predict_noisy_small, on its own: part [nchunk][5k][ldp] -> out [4k][n]
+int launch_predict_noisy_finish(hipStream_t st, const double *part, int nchunk, long ldp, int n, int k, const double *bvec, double *out);
+// ---- rows with input noise, covariance kinds (k_predict_noisy_cov.hip; gpz_predictor_*_noisy_cov_dev) -------------------------------
+// fits: GC or VC, 1 <= d <= 10, 1 <= k <= 8 and ceil16(m) <= 256.  Xc, Psic: [d][ldx] as above.  The tables are the model's alone:
+// basis records brec [m][predict_noisy_cov_brec(d, k)] = [1/2 ln|Sigma_j| | p_j | Sigma_j packed lower | w_j (k) | v_j (k)], pair records
+// prec [m (m + 1) / 2][predict_noisy_cov_prec(d, k)] = [lnZ | c_ab | C_ab packed lower | 3 k coefficients as gpz_pair_coef writes them].
+// launch_noisy_cov_records repacks them from launch_gen_prep's Sig (m x d x d) and lnS (m) and launch_pair_table's records (raw,
+// 1 + d + d d doubles each; prec and raw nullptr: the basis records only).  launch_predict_noisy_cov_small: part [nchunk][5k][ldp] ->
+// out [4k][n] = mu | nu | beta | gamma.  launch_predict_noisy_cov_phi: Phi [nrow][mp] row-major <- E_x[PHI] of the n rows, zeros in rows
+// >= n and columns >= m (what launch_tgemm takes).  shared: GC, one covariance for every basis function.  nchunk =
+// predict_noisy_cov_chunks(m, d, k), the model's shape only.  The launchers return -1 when a launch failed or d is outside 1 .. 10.
+bool predict_noisy_cov_fits(int kind, int d, int m, int k);
+int predict_noisy_cov_chunks(int m, int d, int k);
+int predict_noisy_cov_brec(int d, int k);
+int predict_noisy_cov_prec(int d, int k);
+int launch_noisy_cov_records(hipStream_t st, int m, int d, int de, int k, const double *P, const double *Sig, const double *lnS,
+                             const double *raw, const double *w, const double *v, const double *iS, double *brec, double *prec);
+int launch_predict_noisy_cov_small(hipStream_t st, int d, bool shared, const double *Xc, const double *Psic, long ldx, int n, int m, int k,
+                                   const double *brec, const double *prec, const double *bvec, int nchunk, double *part, long ldp,
+                                   double *out);
+int launch_predict_noisy_cov_phi(hipStream_t st, int d, bool shared, const double *Xc, const double *Psic, long ldx, int n, int nrow,
+                                 int m, int mp, int k, const double *brec, int nchunk, double *Phi);
 // ---- gamma under every weight draw for rows with input noise (k_predict_noisy_gamma.hip; gpz_predictor_stack_noisy*, _draws_gamma_noisy_dev)
 // part [nchunk][ncol][ldp] <- per pair chunk sum_{a >= b} f_ab E[phi_a phi_b](x_i, psi_i) W[a, col] W[b, col] for the n rows of Xc / Psic
 // ([d][ldx]); tab: the handle's pair records (rec doubles apart, [lnZ | c_ab | C_ab] read), W: ceil16(m) x ldw row-major as the draws

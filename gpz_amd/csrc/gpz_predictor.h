@@ -83,18 +83,25 @@ struct gpz_predictor {
     // such a call takes where the handle does not hold them yet, only this exists, and not before the first of their calls
     bool nm_used = false;
     double *nmrec = nullptr;       // the second pair-record table (k_pnm_records): the model's alone, written once
+    // ---- input noise for the covariance kinds (gpz_predictor_*_noisy_cov_dev): beyond the Psi slots and, for the moments, nout and npart
+    // (which a covariance kind has from nowhere else), only this exists, and not before the first of their calls
+    bool ncov_ready = false;       // the pair records, the output slots and the chunk slab exist (the first moments call)
+    int cchunks = 0;               // predict_noisy_cov_chunks of the model
+    double *cbrec = nullptr, *cprec = nullptr;   // the basis and pair records (k_noisy_cov_records): the model's alone, written once
+    double *cphi = nullptr;        // the draws: E_x[PHI] of a tile, [tile_pad][mp] (the tile route's own Phi where there is one)
 };
 
 namespace gpzi {
 // The kind of rows of a call.  Clean: complete rows.  Noisy: rows with Psi in Psic[s] beside Xc[s].  Missing: one group of rows that
 // share the NaN pattern obs (the bit mask of the observed dimensions), with the priors of the set (m values, or nullptr for 1 / m).
-// Noisy missing: such a group with Psi in Psic[s] too (read in the observed dimensions only).  What a tile is made of for a kind is answered by the rows_* functions below; the runners of every entry go through them.
-enum RowKind { ROWS_CLEAN = 0, ROWS_NOISY = 1, ROWS_MISSING = 2, ROWS_NOISY_MISSING = 3 };
+// Noisy missing: such a group with Psi in Psic[s] too (read in the observed dimensions only).  Noisy cov: complete rows with Psi of a
+// covariance kind (moments and draws only: no gamma per draw, no stack).  What a tile is made of for a kind is answered by the rows_* functions below; the runners of every entry go through them.
+enum RowKind { ROWS_CLEAN = 0, ROWS_NOISY = 1, ROWS_MISSING = 2, ROWS_NOISY_MISSING = 3, ROWS_NOISY_COV = 4 };
 struct Rows {
     RowKind kind = ROWS_CLEAN;
     uint32_t obs = 0;
     const double *priors = nullptr;
-    bool psi() const { return kind == ROWS_NOISY || kind == ROWS_NOISY_MISSING; }        // Psic[s] is staged beside Xc[s]
+    bool psi() const { return kind == ROWS_NOISY || kind == ROWS_NOISY_MISSING || kind == ROWS_NOISY_COV; }   // Psic[s] is staged beside Xc[s]
     bool group() const { return kind == ROWS_MISSING || kind == ROWS_NOISY_MISSING; }    // one NaN pattern, tiles of at most mtile rows
 };
 

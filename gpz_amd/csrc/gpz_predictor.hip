@@ -31,6 +31,10 @@
 // gpz_predictor_draws_noisy / _draws_noisy_dev the draws kernel behind a PHI block built from X and Psi.  The pair table (which depends on
 // the model only), the Psi slots, the 4k-row outputs and the chunk slab are allocated on the first such call (predictor_noisy_prepare).
 // gpz_predictor_run with Psi keeps the one-shot route above.
+// The covariance kinds (GC, VC) have the same two questions where predict_noisy_cov_fits holds (1 <= d <= 10, k <= 8, m <= 256), for a
+// variance per input dimension: gpz_predictor_run_noisy_cov_dev runs k_predict_noisy_cov_small per tile (k_predict_noisy_cov.hip: a
+// packed Cholesky per row and record in registers) with the same finish, and gpz_predictor_draws_noisy_cov_dev E_x[PHI] of the tile
+// (k_predict_noisy_cov_phi) against W on k_tgemm.  Their record tables are written on the first such call (predictor_noisy_cov_prepare).
 // gpz_predictor_stack_noisy / _stack_noisy_dev stack such rows: per tile predictNoisy, the draws with Psi, gamma under every draw
 // (k_predict_noisy_gamma.hip, an f64 MFMA product of pair densities and weight products), and k_stack_tile_w with a width per (column,
 // row); gpz_predictor_draws_gamma_noisy_dev returns that gamma beside the draws.  Their buffers are allocated on their first call.
@@ -275,6 +279,78 @@ static int predictor_noisy_tile(gpz_predictor *p, const char *who, int s, int nt
     return 0;
 }
 
+// ---- input noise on the handle, covariance kinds --------------------------------------------------------------------------------------
+static int predictor_noisy_cov_check(const char *who, const gpz_predictor *p) {
+    if (!predict_noisy_cov_fits(p->kind, p->d, p->m, p->k))
+        return gpz_fail(GPZ_ERR_UNSUPPORTED,
+                        "%s: input noise for a covariance kind on the handle needs predict_noisy_cov_fits: GC or VC, 1 <= d <= 10, "
+                        "1 <= k <= 8 and ceil16(m) <= 256 (method %.2s, d %d, m %d, k %d); a diagonal kind goes to "
+                        "gpz_predictor_run_noisy_dev / _draws_noisy_dev, and gpz_predictor_run takes Psi for every shape",
+                        who, p->desc.method, p->d, p->m, p->k);
+    return 0;
+}
+
+// The tables of the covariance kinds, the model's alone: Sigma_j and ln|Sigma_j| from Gamma_j (launch_gen_prep, as the evaluation has
+// them) and, with pairs, launch_pair_table's records, repacked by k_noisy_cov_records.  The d x d forms are temporaries of this call.
+static int predictor_noisy_cov_tables(gpz_predictor *p, bool pairs) {
+    const size_t m = p->m, d = p->d, npair = m * (m + 1) / 2, rawrec = 1 + d + d * d;
+    hipStream_t st = p->s_cmp;
+    double *tmp = nullptr;
+    const size_t nsig = m * d * d, ntmp = 2 * nsig + m + (pairs ? npair * rawrec : 0) + (d + 7) / 8;
+    if (hipMalloc((void **)&tmp, ntmp * sizeof(double)) != hipSuccess) return gpz_fail(GPZ_ERR_ALLOC, "gpz_predictor: out of device memory");
+    double *Sig = tmp, *iSig = Sig + nsig, *lnS = iSig + nsig, *raw = lnS + m;
+    unsigned char *pat = (unsigned char *)(raw + (pairs ? npair * rawrec : 0));   // one pattern: every dimension observed
+    int rc = 0;
+    if (hipMemsetAsync(pat, 1, d, st) != hipSuccess) rc = gpz_fail(GPZ_ERR_HIP, "gpz_predictor: memset failed");
+    if (!rc) {
+        launch_gen_prep(st, p->pr.G, p->m, p->d, p->de, Sig, iSig, pat, 1, lnS, nullptr);
+        if (pairs) launch_pair_table(st, GPZ_KIND_COV, p->m, p->d, p->de, p->pr.P, p->pr.G, Sig, iSig, raw, (int)rawrec, nullptr);
+        if (hipGetLastError() != hipSuccess ||
+            launch_noisy_cov_records(st, p->m, p->d, p->de, p->k, p->pr.P, Sig, lnS, pairs ? raw : nullptr, p->w_d,
+                                     p->hetero ? p->pr.v : nullptr, p->iS_d, p->cbrec, pairs ? p->cprec : nullptr))
+            rc = gpz_fail(GPZ_ERR_HIP, "gpz_predictor: record table launch failed");
+    }
+    if (hipStreamSynchronize(st) != hipSuccess && !rc) rc = gpz_fail(GPZ_ERR_HIP, "gpz_predictor: sync failed");
+    (void)hipFree(tmp);
+    return rc;
+}
+
+// What a call for such rows adds to the handle, each thing where it is missing: the Psi slots and the basis records (every call); with
+// pairs (the moments) the pair records, the 4k-row output slots and the chunk slab of predictor_noisy_prepare, which a covariance kind
+// has from nowhere else; without (the draws) the PHI tile on a handle whose own route has none.
+static int predictor_noisy_cov_prepare(gpz_predictor *p, bool pairs) {
+    const size_t m = p->m, k = p->k, tp = (size_t)p->tile_pad, npair = m * (m + 1) / 2;
+    auto &ar = p->ar;
+    int rc = 0;
+    if ((rc = predictor_psi_slots(p))) return rc;
+    p->cchunks = predict_noisy_cov_chunks(p->m, p->d, p->k);
+    const bool basis = !p->cbrec, table = pairs && !p->ncov_ready;
+    if (basis && (rc = ar.alloc(&p->cbrec, m * predict_noisy_cov_brec(p->d, p->k)))) return rc;
+    if (!pairs) {
+        if (!p->cphi) {
+            if (p->Phi) p->cphi = p->Phi;   // the tile route's PHI, [tile_pad][mp]: a tile's kernels are done with it before the next one's
+            else if ((rc = ar.alloc(&p->cphi, tp * p->mp))) return rc;
+        }
+    } else {
+        if (!p->cprec && (rc = ar.alloc(&p->cprec, npair * predict_noisy_cov_prec(p->d, p->k)))) return rc;
+        for (int s = 0; s < 2; ++s)
+            if (!p->nout[s] && (rc = ar.alloc(&p->nout[s], 4 * k * tp))) return rc;
+        if (!p->npart && (rc = ar.alloc(&p->npart, (size_t)p->cchunks * 5 * k * tp))) return rc;
+    }
+    if (basis || table)
+        if ((rc = predictor_noisy_cov_tables(p, table))) return rc;
+    if (table) p->ncov_ready = true;
+    return 0;
+}
+
+// predictNoisy of one tile of nt rows: Xc[s], Psic[s] -> nout[s] ([4k][nt] = mu | nu | beta | gamma)
+static int predictor_noisy_cov_tile(gpz_predictor *p, const char *who, int s, int nt) {
+    if (launch_predict_noisy_cov_small(p->s_cmp, p->d, p->mid == 4, p->Xc[s], p->Psic[s], p->tile_pad, nt, p->m, p->k, p->cbrec, p->cprec,
+                                       p->pr.b, p->cchunks, p->npart, p->tile_pad, p->nout[s]))
+        return gpz_fail(GPZ_ERR_HIP, "%s: k_predict_noisy_cov_small launch failed", who);
+    return 0;
+}
+
 // ---- draws ------------------------------------------------------------------------------------------------------------------------
 // R_o for every output, once per handle: the blocked Cholesky steps of k_chol.hip on S_o (padded to a multiple of 32 with the identity),
 // the eigen-factor of k_pinv.hip's sweeps where that breaks down.
@@ -511,11 +587,25 @@ static int predictor_missing_draws_tile(gpz_predictor *p, const char *who, int s
     return 0;
 }
 
+// the draws of one tile of nt rows with Psi, covariance kinds: E_x[PHI] (k_predict_noisy_cov_phi, rows of the product padded with
+// zeros) against the handle's W on k_tgemm -> dout[s] ([ncol][nt], without muY)
+static int predictor_noisy_cov_draws_tile(gpz_predictor *p, const char *who, int s, int nt, int ncol, int ldw) {
+    const int np = rup(nt, 128);   // the rows of the product: k_tgemm's row tile
+    if (launch_predict_noisy_cov_phi(p->s_cmp, p->d, p->mid == 4, p->Xc[s], p->Psic[s], p->tile_pad, nt, np, p->m, p->mp, p->k, p->cbrec,
+                                     p->cchunks, p->cphi))
+        return gpz_fail(GPZ_ERR_HIP, "%s: k_predict_noisy_cov_phi launch failed", who);
+    launch_tgemm(p->s_cmp, p->cphi, p->mp, p->Wd, ldw, p->Td, np, ldw, nullptr, nullptr, p->m, 0, false, predictor_wrows(p), ldw);
+    launch_transpose_out(p->s_cmp, p->Td, ldw, nt, ncol, p->dout[s]);
+    if (hipGetLastError() != hipSuccess) return gpz_fail(GPZ_ERR_HIP, "%s: kernel launch failed", who);
+    return 0;
+}
+
 // ---- what a kind of rows is made of ---------------------------------------------------------------------------------------------------
 // the kind's refusal of the model and, for a group, of its mask.  draws: the call has draws, which with Psi need the fused draws route
 int rows_check(const char *who, const gpz_predictor *p, const Rows &r, bool draws) {
     if (r.group()) return predictor_missing_check(who, p, r.obs);   // (with Psi too: its product against W needs no fused draws route)
     if (r.kind == ROWS_CLEAN) return 0;
+    if (r.kind == ROWS_NOISY_COV) return predictor_noisy_cov_check(who, p);   // (its draws are a product on the T-GEMM: any route)
     if (int rc = predictor_noisy_check(who, p)) return rc;
     if (draws && p->force_tiles)
         return gpz_fail(GPZ_ERR_UNSUPPORTED, "%s: input noise needs the fused draws route (GPZ_PREDICT_FORCE_TILES is set)", who);
@@ -527,6 +617,7 @@ int rows_check(const char *who, const gpz_predictor *p, const Rows &r, bool draw
 int rows_prepare(gpz_predictor *p, const char *who, const Rows &r, bool pairs) {
     if (r.group()) return predictor_missing_prepare(p, who, r.obs, r.priors, pairs, r.kind == ROWS_NOISY_MISSING);
     if (r.kind == ROWS_NOISY) return pairs ? predictor_noisy_prepare(p) : predictor_psi_slots(p);
+    if (r.kind == ROWS_NOISY_COV) return predictor_noisy_cov_prepare(p, pairs);
     return 0;
 }
 
@@ -538,18 +629,19 @@ int64_t rows_tile(const gpz_predictor *p, const Rows &r, int64_t T) { return r.g
 int rows_moments_tile(gpz_predictor *p, const char *who, const Rows &r, int s, int nt, bool want_phi) {
     if (r.group()) return predictor_missing_tile(p, who, s, nt, r.obs, true, r.psi() ? p->Psic[s] : nullptr);
     if (r.kind == ROWS_NOISY) return predictor_noisy_tile(p, who, s, nt);
+    if (r.kind == ROWS_NOISY_COV) return predictor_noisy_cov_tile(p, who, s, nt);
     return predictor_tile(p, s, nt, want_phi);
 }
 
 const double *rows_moments(const gpz_predictor *p, const Rows &r, int s) {
-    return r.group() ? p->mout : r.kind == ROWS_NOISY ? p->nout[s] : p->out[s];
+    return r.group() ? p->mout : r.psi() ? p->nout[s] : p->out[s];
 }
 
 // the kind's tile for a call whose draws (or stack) would take *T rows, and for a group the output tile of its product PHI_missing W:
 // the tile route of the draws has one already, the fused route does not
 static int rows_fit_tile(gpz_predictor *p, const Rows &r, int ncol, int ldw, int64_t *T) {
     *T = rows_tile(p, r, *T);
-    if (!r.group() || ncol == 0) return 0;
+    if ((!r.group() && r.kind != ROWS_NOISY_COV) || ncol == 0) return 0;   // (a covariance kind with Psi: the output tile of E_x[PHI] W)
     return predictor_grow(p, &p->Td, &p->t_cap, (size_t)rup(*T, 1024) * ldw);
 }
 
@@ -564,6 +656,7 @@ int rows_draws_prepare(gpz_predictor *p, const Rows &r, int nd, unsigned long lo
 int rows_draws_tile(gpz_predictor *p, const char *who, const Rows &r, int s, int nt, int ncol, int ldw, bool after_moments) {
     if (r.kind == ROWS_CLEAN) return predictor_draws_tile(p, s, nt, ncol, ldw, after_moments && p->route == 1);
     if (r.kind == ROWS_NOISY) return predictor_draws_tile(p, s, nt, ncol, ldw, false, p->Psic[s]);
+    if (r.kind == ROWS_NOISY_COV) return predictor_noisy_cov_draws_tile(p, who, s, nt, ncol, ldw);
     if (!after_moments)
         if (int rc = predictor_missing_tile(p, who, s, nt, r.obs, false, r.psi() ? p->Psic[s] : nullptr)) return rc;
     return predictor_missing_draws_tile(p, who, s, nt, ncol, ldw);
@@ -799,6 +892,10 @@ extern "C" int gpz_predictor_route(const gpz_predictor *p, char *buf, int cap) {
     if (p->dev_used) r += "; device entries: k_pred_stage";
     if (p->noisy_ready) {   // after the first call with input noise on the handle
         snprintf(tmp, sizeof tmp, "; noise: k_predict_noisy_small (%d pair chunks)", p->nchunks);
+        r += tmp;
+    }
+    if (p->ncov_ready) {   // after the first moments call with input noise on a covariance kind
+        snprintf(tmp, sizeof tmp, "; noise: k_predict_noisy_cov_small (%d pair chunks)", p->cchunks);
         r += tmp;
     }
     if (p->gam[0].used) {   // after the first stack or gamma-per-draw call for rows with input noise

@@ -39,6 +39,12 @@ static DevCall with_psi(DevCall c, const void *Psi_d, int32_t psi_type, int64_t 
     return c;
 }
 
+// rows with Psi of a covariance kind: with_psi first
+static DevCall with_cov(DevCall c) {
+    c.rows.kind = ROWS_NOISY_COV;
+    return c;
+}
+
 static DevCall with_pattern(DevCall c, const double *priors, uint32_t obs_mask) {
     c.rows = Rows{ROWS_MISSING, obs_mask, priors};
     return c;
@@ -199,7 +205,7 @@ static int predictor_run_dev(gpz_predictor *p, const char *who, DevCall &c, doub
     return rc;
 }
 
-// gpz_predictor_run_dev, _run_noisy_dev, _run_missing_dev and _run_noisy_missing_dev
+// gpz_predictor_run_dev, _run_noisy_dev, _run_noisy_cov_dev, _run_missing_dev and _run_noisy_missing_dev
 static int run_dev_entry(const char *who, gpz_predictor *p, DevCall c, double *mu_d, double *sigma_d, double *nu_d, double *beta_d,
                          double *gamma_d, double *PHI_d) {
     if (int rc = predictor_check_call(who, p, c.x.ns)) return rc;
@@ -238,7 +244,7 @@ static int predictor_run_draws_dev(gpz_predictor *p, const char *who, DevCall &c
     return predictor_dev_sync(p, who, rc);
 }
 
-// gpz_predictor_draws_dev, _draws_noisy_dev, _draws_missing_dev, _draws_noisy_missing_dev and, with want_gamma, _draws_gamma_noisy_dev, _draws_gamma_missing_dev and _draws_gamma_noisy_missing_dev
+// gpz_predictor_draws_dev, _draws_noisy_dev, _draws_noisy_cov_dev, _draws_missing_dev, _draws_noisy_missing_dev and, with want_gamma, _draws_gamma_noisy_dev, _draws_gamma_missing_dev and _draws_gamma_noisy_missing_dev
 static int draws_dev_entry(const char *who, gpz_predictor *p, DevCall c, int32_t ndraws, uint64_t seed, const double *Z, double *F_d,
                            double *Gam_d = nullptr, bool want_gamma = false) {
     if (int rc = predictor_check_call(who, p, c.x.ns)) return rc;
@@ -312,6 +318,27 @@ extern "C" int gpz_predictor_draws_noisy_dev(gpz_predictor *p, const void *X_d, 
     const DevCall x = dev_call(X_d, x_type, ns, row_stride, col_stride, muX, sdX, muY, stream);
     return draws_dev_entry("gpz_predictor_draws_noisy_dev", p, with_psi(x, Psi_d, psi_type, psi_row_stride, psi_col_stride, sd2), ndraws,
                            seed, Z, F_d);
+}
+
+extern "C" int gpz_predictor_run_noisy_cov_dev(gpz_predictor *p, const void *X_d, int32_t x_type, int64_t ns, int64_t row_stride,
+                                               int64_t col_stride, const void *Psi_d, int32_t psi_type, int64_t psi_row_stride,
+                                               int64_t psi_col_stride, const double *muX, const double *sdX, const double *sd2,
+                                               const double *muY, double *mu_d, double *sigma_d, double *nu_d, double *beta_d,
+                                               double *gamma_d, void *stream) {
+    const DevCall x = dev_call(X_d, x_type, ns, row_stride, col_stride, muX, sdX, muY, stream);
+    return run_dev_entry("gpz_predictor_run_noisy_cov_dev", p,
+                         with_cov(with_psi(x, Psi_d, psi_type, psi_row_stride, psi_col_stride, sd2)), mu_d, sigma_d, nu_d, beta_d, gamma_d,
+                         nullptr);
+}
+
+extern "C" int gpz_predictor_draws_noisy_cov_dev(gpz_predictor *p, const void *X_d, int32_t x_type, int64_t ns, int64_t row_stride,
+                                                 int64_t col_stride, const void *Psi_d, int32_t psi_type, int64_t psi_row_stride,
+                                                 int64_t psi_col_stride, const double *muX, const double *sdX, const double *sd2,
+                                                 const double *muY, int32_t ndraws, uint64_t seed, const double *Z, double *F_d,
+                                                 void *stream) {
+    const DevCall x = dev_call(X_d, x_type, ns, row_stride, col_stride, muX, sdX, muY, stream);
+    return draws_dev_entry("gpz_predictor_draws_noisy_cov_dev", p,
+                           with_cov(with_psi(x, Psi_d, psi_type, psi_row_stride, psi_col_stride, sd2)), ndraws, seed, Z, F_d);
 }
 
 extern "C" int gpz_predictor_run_missing_dev(gpz_predictor *p, const void *X_d, int32_t x_type, int64_t ns, int64_t row_stride,

@@ -239,6 +239,12 @@ int launch_predict_noisy_small(hipStream_t st, int d, int de, const double *Xc, 
         default: return -1;
     }
     if (hipGetLastError() != hipSuccess) return -1;
+    return launch_predict_noisy_finish(st, part, nchunk, ldp, n, k, bvec, out);
+}
+
+// the finish kernel on its own: behind the pair kernel above and that of the covariance kinds (k_predict_noisy_cov.hip)
+int launch_predict_noisy_finish(hipStream_t st, const double *part, int nchunk, long ldp, int n, int k, const double *bvec, double *out) {
+    if (n <= 0) return 0;
     hipLaunchKernelGGL(k_predict_noisy_finish, dim3((unsigned)((n + 255) / 256), (unsigned)k), dim3(256), 0, st, part, nchunk, ldp, n, k,
                        bvec, out);
     return hipGetLastError() == hipSuccess ? 0 : -1;

@@ -1,7 +1,8 @@
 """The streaming predictor: a trained model held on one GPU (gpz_predictor_* of the C ABI) behind ``Predictor``.
 
 The methods ask one of four questions (run: the moments of ``predict``; draws; draws with gamma per draw; stack) of rows of one of four
-kinds (clean, noisy: with Psi, missing: one NaN-pattern group, noisy_missing: such a group with Psi).
+kinds (clean, noisy: with Psi, missing: one NaN-pattern group, noisy_missing: such a group with Psi); noisy_cov is the noisy kind of a
+covariance model (GC, VC), which has the first two questions only.
 ``_DEV_ENTRIES`` names the device-resident entry of each pair, ``Predictor._dev_entry`` builds the arguments the entries of a pair
 share, and ``Predictor._dev_groups`` is the one loop over the groups of a call; the host methods choose between two entries each by
 whether Psi is there (``_HOST_ENTRIES``).  Everything numeric happens in the library; ``torch`` is only imported by the device methods.
@@ -25,6 +26,7 @@ StackResult = namedtuple("StackResult", ["hist", "sum_w", "sum_mu", "sum_mu2", "
 # (question, row kind) -> the device-resident entry.  Complete rows have no gamma entry: their gamma is exactly 0.
 _DEV_ENTRIES = {
     ("run", "clean"): "gpz_predictor_run_dev", ("run", "noisy"): "gpz_predictor_run_noisy_dev",
+    ("run", "noisy_cov"): "gpz_predictor_run_noisy_cov_dev", ("draws", "noisy_cov"): "gpz_predictor_draws_noisy_cov_dev",
     ("run", "missing"): "gpz_predictor_run_missing_dev", ("run", "noisy_missing"): "gpz_predictor_run_noisy_missing_dev",
     ("draws", "clean"): "gpz_predictor_draws_dev", ("draws", "noisy"): "gpz_predictor_draws_noisy_dev",
     ("draws", "missing"): "gpz_predictor_draws_missing_dev", ("draws", "noisy_missing"): "gpz_predictor_draws_noisy_missing_dev",
@@ -554,14 +556,14 @@ class Predictor:
             elif g is not None:
                 t[(slice(None),) * axis + (idx,)] = g
 
-    def _dev_entry(self, question, call, code, Xg, Pg):
+    def _dev_entry(self, question, call, code, Xg, Pg, cov=False):
         """The bound entry of ``_DEV_ENTRIES`` for one group and the arguments up to where the questions differ, in the order of
         include/gpz_hip.h: the handle, the rows, Psi for rows with one, muX, sdX, sd2 for rows with Psi; then muY and, for a group with
         missing values, the priors and the mask of the observed dimensions.  ``run`` and ``draws`` take muY there, in front of the
-        priors; ``stack`` takes the priors straight after sdX and muY at the end of its own arguments.  Returns (entry, arguments, row
-        kind)."""
+        priors; ``stack`` takes the priors straight after sdX and muY at the end of its own arguments.  ``cov``: complete rows with Psi
+        of a covariance kind, whose entries take the noisy kind's arguments.  Returns (entry, arguments, row kind)."""
         noisy = Pg is not None
-        kind = ("noisy_missing" if noisy else "missing") if code else ("noisy" if noisy else "clean")
+        kind = ("noisy_missing" if noisy else "missing") if code else (("noisy_cov" if cov else "noisy") if noisy else "clean")
         lead = [call.h, *self._x_args(Xg)]
         if noisy:
             lead += self._psi_args(Pg, Xg.shape[0])
@@ -608,9 +610,9 @@ class Predictor:
         self._check_dev_device(X=X, selection=selection, Psi=Psi)
         return self._moments_dev(X, Psi, selection, missing, return_phi)
 
-    def _moments_dev(self, X, Psi, selection, missing, return_phi=False):
-        """The checked call of ``predict_dev`` and ``predict_noisy_missing_dev``: the selection, the result tensors and one entry per
-        group of ``_dev_groups``."""
+    def _moments_dev(self, X, Psi, selection, missing, return_phi=False, cov=False):
+        """The checked call of ``predict_dev``, ``predict_noisy_missing_dev`` and ``predict_noisy_cov_dev``: the selection, the
+        result tensors and one entry per group of ``_dev_groups``."""
         import torch
         k, m = self._k, self._m
         X, Psi = self._selected(selection, X, Psi)
@@ -622,7 +624,7 @@ class Predictor:
             call = self._dev_begin(X.device)
             for code, idx, Xg, Pg in self._dev_groups(X, missing, Psi):
                 og = out if idx is None else [torch.empty((k, Xg.shape[0]), dtype=torch.float64, device=X.device).T for _ in range(5)]
-                fn, lead, kind = self._dev_entry("run", call, code, Xg, Pg)
+                fn, lead, kind = self._dev_entry("run", call, code, Xg, Pg, cov)
                 phi = [None if PHI is None else PHI.data_ptr()] if kind == "clean" else []   # the clean entry alone returns PHI
                 _lib.check(fn(*lead, *(t.data_ptr() for t in og), *phi, call.stream))
                 self._merge(idx, out, og, 0)
@@ -658,9 +660,9 @@ class Predictor:
         self._check_dev_device(X=X, selection=selection, Psi=Psi)
         return self._draws_dev(X, Psi, selection, missing, n_draws, seed, z, return_gamma)
 
-    def _draws_dev(self, X, Psi, selection, missing, n_draws, seed, z, return_gamma=False):
-        """The checked call of ``draws_dev`` and ``draws_noisy_missing_dev``: the selection, the result tensors and one entry per group
-        of ``_dev_groups``, all under the one weight draw of (seed, z)."""
+    def _draws_dev(self, X, Psi, selection, missing, n_draws, seed, z, return_gamma=False, cov=False):
+        """The checked call of ``draws_dev``, ``draws_noisy_missing_dev`` and ``draws_noisy_cov_dev``: the selection, the result
+        tensors and one entry per group of ``_dev_groups``, all under the one weight draw of (seed, z)."""
         import torch
         k = self._k
         X, Psi = self._selected(selection, X, Psi)
@@ -676,7 +678,7 @@ class Predictor:
                 if return_gamma and idx is not None:
                     Gg = torch.zeros((n_draws, k, Xg.shape[0]), dtype=torch.float64, device=X.device)
                 gamma = return_gamma and (code != 0 or Pg is not None)   # complete rows have no gamma entry
-                fn, lead, _ = self._dev_entry("draws_gamma" if gamma else "draws", call, code, Xg, Pg)
+                fn, lead, _ = self._dev_entry("draws_gamma" if gamma else "draws", call, code, Xg, Pg, cov)
                 _lib.check(fn(*lead, n_draws, int(seed), _lib.dptr(z), Fg.data_ptr(), *([Gg.data_ptr()] if gamma else []), call.stream))
                 if return_gamma and not gamma and idx is None:
                     Gam.zero_()
@@ -734,6 +736,53 @@ class Predictor:
         n_draws, z = self._check_draw_args(n_draws, seed, Z, 1)
         self._check_dev_device(X=X, selection=selection, Psi=Psi)
         return self._draws_dev(X, Psi, selection, True, n_draws, seed, z, bool(return_gamma))
+
+    def _check_noisy_cov(self, what, X, Psi, selection):
+        """The checks the two methods for rows with Psi of a covariance kind share, none of which touches a GPU: X, then where such
+        rows go when this is not their route (no Psi, a full Psi cube, a diagonal kind, a shape outside predict_noisy_cov_fits of
+        k_predict_noisy_cov.hip), then Psi's type, dtype and shape.  Returns X as n x d and Psi as n x 1 or n x d."""
+        X = self._check_dev_rows(X, selection, what)
+        name = f"{what}_noisy_cov_dev"
+        if Psi is None:
+            raise ValueError(f"{name} needs Psi: rows without input noise go to {what}_dev(X)")
+        if np.ndim(Psi) == 3 or (hasattr(Psi, "dim") and Psi.dim() == 3):
+            raise ValueError(f"{name} takes Psi as n x d, n x 1 or n variances: a full d x d x n Psi stays on "
+                             "Predictor.predict(X, Psi=Psi)")
+        if self._method[1] != "C":
+            raise ValueError(f"{name} is for the covariance kinds (GC, VC): a diagonal kind such as {self._method} goes to "
+                             f"{what}_dev(X, Psi=Psi)")
+        if not (1 <= self._d <= 10 and 1 <= self._k <= 8 and 1 <= self._m <= 256):
+            raise ValueError(f"{name} needs a model inside predict_noisy_cov_fits: GC or VC, d <= 10, k <= 8 and m <= 256; this one is "
+                             f"{self._method} with d = {self._d}, m = {self._m}, k = {self._k} (Predictor.predict takes Psi for every "
+                             "shape)")
+        return X, self._check_dev_psi(Psi, X.shape[0], what)
+
+    def predict_noisy_cov_dev(self, X, Psi, selection=None):
+        """``predict_dev(X, Psi=Psi)`` for a covariance kind (GC, VC; gpz_predictor_run_noisy_cov_dev): X, ``selection`` and ``Psi``
+        (variances per input dimension, (n, d), (n, 1) or (n,), float64 or float32, any strides) as for ``predict_dev``.  Returns mu,
+        sigma, nu, beta_i, gamma as ``predict(X, Psi=Psi)`` does, as float64 tensors of shape (n, k) on the device: predictNoisy of
+        predictCov.m on the handle's tiles by k_predict_noisy_cov_small, with the variances on the diagonal of each row's Psi as fixPsi
+        puts them there.  A row's results do not depend on the tile size, the row order or the other rows of the call.  It needs a
+        model inside predict_noisy_cov_fits (GC or VC, d <= 10, k <= 8, m <= 256), else ValueError; a full d x d x n Psi, PHI, host
+        arrays, stacks, gamma per draw and rows with missing values are not on this route (``Predictor.predict`` takes them).  Rows
+        with NaN and an element of Psi that is NaN, infinite or negative are refused (GpzError).  Type, dtype and shape are checked
+        first, the device last, all before the GPU is touched."""
+        self._check_open()
+        X, Psi = self._check_noisy_cov("predict", X, Psi, selection)
+        self._check_dev_device(X=X, selection=selection, Psi=Psi)
+        return self._moments_dev(X, Psi, selection, False, cov=True)
+
+    def draws_noisy_cov_dev(self, X, Psi, n_draws, seed=0, Z=None, selection=None):
+        """``draws_dev(X, ..., Psi=Psi)`` for a covariance kind (gpz_predictor_draws_noisy_cov_dev): X, ``Psi`` and ``selection`` as for
+        ``predict_noisy_cov_dev``, ``n_draws``, ``seed`` and ``Z`` as for ``draws_dev``.  Returns a float64 tensor of shape
+        (n_draws, n, k) on the device: draws[s] is ``predict_noisy_cov_dev``'s mu under weight draw s, E_x[PHI] w_s + muY - the mean is
+        linear in the weights, so this is exact.  E_x[PHI] of a tile comes from k_predict_noisy_cov_phi and meets the draws' weights on
+        the T-GEMM, whatever route the handle's noise-free draws take."""
+        self._check_open()
+        X, Psi = self._check_noisy_cov("draws", X, Psi, selection)
+        n_draws, z = self._check_draw_args(n_draws, seed, Z, 1)
+        self._check_dev_device(X=X, selection=selection, Psi=Psi)
+        return self._draws_dev(X, Psi, selection, False, n_draws, seed, z, cov=True)
 
     def stack_dev(self, X, edges, n_draws=0, seed=0, Z=None, groups=None, n_groups=None, weights=None, selection=None):
         """``stack`` for a catalogue on the GPU (gpz_predictor_stack_dev): X and ``selection`` as for ``predict_dev``; ``groups`` an

@@ -336,6 +336,28 @@ int gpz_predictor_draws_noisy_dev(gpz_predictor *p, const void *X_d, int32_t x_t
 int gpz_predictor_draws_noisy(gpz_predictor *p, const double *Xs, int64_t ns, const double *Psi /* ns x d, normalised */,
                               int32_t ndraws, uint64_t seed, const double *Z /* NULL or m x ndraws x k */,
                               double *F /* ns x k x ndraws, column-major */);
+/* The same two questions for the covariance kinds (predictCov.m:70-132), where predict_noisy_cov_fits holds: GC or VC, 1 <= d <= 10,
+ * 1 <= k <= 8 and ceil16(m) <= 256.  Any other shape returns GPZ_ERR_UNSUPPORTED and names the condition.  The arguments are exactly
+ * those of gpz_predictor_run_noisy_dev / _draws_noisy_dev: Psi is a variance per input dimension (or one per row), the diagonal that
+ * fixPsi puts into the d x d x n cube of these kinds, entering the kernels as double(psi) / sd2[c]; a full Psi cube stays on
+ * gpz_predictor_run.  Complete rows only; NaN rows and bad elements of Psi are refused as above, before the first tile, outputs
+ * untouched.  Per tile k_predict_noisy_cov_small (a packed Cholesky of Sigma_j + Psi_i and of C_ab + Psi_i per row and record in
+ * registers; k_predict_noisy_cov.hip) and the finish kernel of the diagonal kinds; the draws are E_x[PHI] from k_predict_noisy_cov_phi
+ * against W on the T-GEMM.  Same bits for any tile size, row order or split of the rows into calls.  The first call writes the basis
+ * records (m of 1 + d + d (d + 1) / 2 + 2 k doubles), takes the Psi slots and, for the draws on a fused-route handle, a PHI tile; the
+ * first gpz_predictor_run_noisy_cov_dev the pair records (m (m + 1) / 2 of 1 + d + d (d + 1) / 2 + 3 k doubles), the output slots and
+ * the chunk slab.  None of it depends on the number of rows, a handle that never calls these holds what it held, and
+ * gpz_predictor_route then ends in "; noise: k_predict_noisy_cov_small (C pair chunks)". */
+int gpz_predictor_run_noisy_cov_dev(gpz_predictor *p, const void *X_d, int32_t x_type, int64_t ns, int64_t row_stride, int64_t col_stride,
+                                    const void *Psi_d, int32_t psi_type, int64_t psi_row_stride, int64_t psi_col_stride,
+                                    const double *muX, const double *sdX, const double *sd2, const double *muY /* k or NULL */,
+                                    double *mu_d, double *sigma_d, double *nu_d, double *beta_d, double *gamma_d, void *stream);
+int gpz_predictor_draws_noisy_cov_dev(gpz_predictor *p, const void *X_d, int32_t x_type, int64_t ns, int64_t row_stride,
+                                      int64_t col_stride, const void *Psi_d, int32_t psi_type, int64_t psi_row_stride,
+                                      int64_t psi_col_stride, const double *muX, const double *sdX, const double *sd2,
+                                      const double *muY /* k or NULL */, int32_t ndraws, uint64_t seed,
+                                      const double *Z /* host: NULL or m x ndraws x k */,
+                                      double *F_d /* ns x k x ndraws, column-major */, void *stream);
 
 /* ---- stacked densities of rows with input noise, and gamma under every weight draw ----------------------------------------------------
  * gpz_predictor_stack / _stack_dev for rows with a variance per input dimension, where predict_noisy_fits holds and the handle is on the
