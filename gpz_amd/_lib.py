@@ -118,6 +118,15 @@ SYMBOLS = {
     "gpz_predictor_draws_gamma_noisy_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_void_p,
                                                       C.c_int32, C.c_int64, C.c_int64, c_double_p, c_double_p, c_double_p, c_double_p,
                                                       C.c_int32, C.c_uint64, c_double_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    # the same two for the covariance kinds (GC, VC; predict_noisy_cov_fits): the arguments of the two entries above
+    "gpz_predictor_stack_noisy_cov_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_void_p,
+                                                    C.c_int32, C.c_int64, C.c_int64, c_double_p, c_double_p, c_double_p, C.c_int32,
+                                                    C.c_uint64, c_double_p, c_double_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p,
+                                                    c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, C.c_void_p]),
+    "gpz_predictor_draws_gamma_noisy_cov_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_void_p,
+                                                          C.c_int32, C.c_int64, C.c_int64, c_double_p, c_double_p, c_double_p,
+                                                          c_double_p, C.c_int32, C.c_uint64, c_double_p, C.c_void_p, C.c_void_p,
+                                                          C.c_void_p]),
     # one group of rows sharing a NaN pattern: priors (host, m or NULL) and the bit mask of the observed dimensions
     "gpz_predictor_run_missing_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int64, c_double_p, c_double_p,
                                                 c_double_p, c_double_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,

@@ -266,6 +266,13 @@ int launch_gamma_finish_s2(hipStream_t st, const double *part, int nchunk, long 
                            int nd, double *s2);
 int launch_stack_tile_w(hipStream_t st, const double *out, const double *s2, const double *dout, const int *lab, const double *wt,
                         const double *edges, const double *shift, long nt, int k, int nd, int B, int G, int R, double *slab);
+// ---- the same for a covariance kind (k_predict_noisy_cov_gamma.hip; gpz_predictor_stack_noisy_cov_dev, _draws_gamma_noisy_cov_dev) ----
+// part [nchunk][ncol][ldp] <- per pair chunk sum_{a >= b} f_ab z_ab(x_i, psi_i) W[a, col] W[b, col] with k_predict_noisy_cov_small's pair
+// density; tab: the handle's packed pair records (prec above, rec = predict_noisy_cov_prec(d, k) doubles apart, the head [lnZ | c_ab |
+// C_ab packed lower] read), shared: GC.  nchunk = predict_gamma_chunks(m); the finish kernels and the stack kernel are the ones above.
+// Returns -1 when the launch failed or d is outside 1 .. 10.
+int launch_predict_noisy_cov_gamma(hipStream_t st, int d, bool shared, const double *Xc, const double *Psic, long ldx, int n, int m,
+                                   const double *tab, int rec, const double *W, int ldw, int ncol, int nchunk, double *part, long ldp);
 // ---- rows with missing inputs through the streaming predictor, with or without input noise (k_predict_missing.hip,
 // k_predict_noisy_missing.hip, the pair kernels' body in k_predict_group_impl.h; gpz_predictor_*_missing_dev, _*_noisy_missing_dev) ----
 // One group of rows sharing a NaN pattern; obs: bit c set = dimension c observed.  fits: a diagonal kind, an instantiated de <= 20,

@@ -59,16 +59,17 @@ struct gpz_predictor {
     double *sd2_d = nullptr;       // sdX ** 2 of the device entries
     double *hpsi[2] = {};          // pinned, gpz_predictor_draws_noisy only
     // ---- gamma per draw and stacks of rows with input noise (gpz_predictor_stack_noisy*, _draws_gamma_noisy_dev) and of rows with missing
-    // inputs (gpz_predictor_stack_missing_dev, _draws_gamma_missing_dev), and of rows with both (gpz_predictor_stack_noisy_missing_dev,
-    // _draws_gamma_noisy_missing_dev): nothing of a kind before its first such call
-    int gchunks = 0;               // predict_gamma_chunks of the model (input noise; a group with missing inputs has mchunks)
+    // inputs (gpz_predictor_stack_missing_dev, _draws_gamma_missing_dev), of rows with both (gpz_predictor_stack_noisy_missing_dev,
+    // _draws_gamma_noisy_missing_dev), and of rows with input noise on a covariance kind (gpz_predictor_stack_noisy_cov_dev,
+    // _draws_gamma_noisy_cov_dev): nothing of a kind before its first such call
+    int gchunks = 0;               // predict_gamma_chunks of the model (input noise, either kind; a group with missing inputs has mchunks)
     double *gpart = nullptr;       // [chunks][nd k][tile] pair sums per chunk, of either kind
     size_t gpart_cap = 0;          // doubles
     struct PerDraw {
         bool used = false;
         double *s2_d = nullptr;    // [(1 + nd) k][tile] widths^2 of the stack
         size_t s2_cap = 0;         // doubles
-    } gam[3];                      // [ROWS_NOISY - 1], [ROWS_MISSING - 1], [ROWS_NOISY_MISSING - 1]
+    } gam[4];                      // [ROWS_NOISY - 1], [ROWS_MISSING - 1], [ROWS_NOISY_MISSING - 1], [ROWS_NOISY_COV - 1]
     // ---- rows with missing inputs on the handle (gpz_predictor_*_missing_dev): nothing of this exists before the first of their calls
     bool miss_used = false;
     int64_t mtile = 0;             // rows per tile of a group: min(tile_rows, GPZ_PREDICTOR_TILE_MISSING)
@@ -85,17 +86,17 @@ struct gpz_predictor {
     double *nmrec = nullptr;       // the second pair-record table (k_pnm_records): the model's alone, written once
     // ---- input noise for the covariance kinds (gpz_predictor_*_noisy_cov_dev): beyond the Psi slots and, for the moments, nout and npart
     // (which a covariance kind has from nowhere else), only this exists, and not before the first of their calls
-    bool ncov_ready = false;       // the pair records, the output slots and the chunk slab exist (the first moments call)
+    bool ncov_ready = false;       // the pair records, the output slots and the chunk slab exist (the first call that reads the pairs)
     int cchunks = 0;               // predict_noisy_cov_chunks of the model
     double *cbrec = nullptr, *cprec = nullptr;   // the basis and pair records (k_noisy_cov_records): the model's alone, written once
-    double *cphi = nullptr;        // the draws: E_x[PHI] of a tile, [tile_pad][mp] (the tile route's own Phi where there is one)
+    double *cphi = nullptr;        // the draws (and a stack with draws): E_x[PHI] of a tile, [tile_pad][mp] (the tile route's own Phi where there is one)
 };
 
 namespace gpzi {
 // The kind of rows of a call.  Clean: complete rows.  Noisy: rows with Psi in Psic[s] beside Xc[s].  Missing: one group of rows that
 // share the NaN pattern obs (the bit mask of the observed dimensions), with the priors of the set (m values, or nullptr for 1 / m).
 // Noisy missing: such a group with Psi in Psic[s] too (read in the observed dimensions only).  Noisy cov: complete rows with Psi of a
-// covariance kind (moments and draws only: no gamma per draw, no stack).  What a tile is made of for a kind is answered by the rows_* functions below; the runners of every entry go through them.
+// covariance kind (a handle has either this kind or the diagonal noisy one, never both).  What a tile is made of for a kind is answered by the rows_* functions below; the runners of every entry go through them.
 enum RowKind { ROWS_CLEAN = 0, ROWS_NOISY = 1, ROWS_MISSING = 2, ROWS_NOISY_MISSING = 3, ROWS_NOISY_COV = 4 };
 struct Rows {
     RowKind kind = ROWS_CLEAN;

@@ -35,7 +35,10 @@
 // variance per input dimension: gpz_predictor_run_noisy_cov_dev runs k_predict_noisy_cov_small per tile (k_predict_noisy_cov.hip: a
 // packed Cholesky per row and record in registers) with the same finish, and gpz_predictor_draws_noisy_cov_dev E_x[PHI] of the tile
 // (k_predict_noisy_cov_phi) against W on k_tgemm.  Their record tables are written on the first such call (predictor_noisy_cov_prepare).
-// gpz_predictor_stack_noisy / _stack_noisy_dev stack such rows: per tile predictNoisy, the draws with Psi, gamma under every draw
+// gpz_predictor_stack_noisy_cov_dev / _draws_gamma_noisy_cov_dev answer the other two questions for them as the entries of the next
+// paragraph do for the diagonal kinds, with gamma under every draw from k_predict_noisy_cov_gamma.hip (the same f64 MFMA product with
+// that kernel's pair density) on the handle's packed pair records.
+// gpz_predictor_stack_noisy / _stack_noisy_dev stack rows with Psi of a diagonal kind: per tile predictNoisy, the draws with Psi, gamma under every draw
 // (k_predict_noisy_gamma.hip, an f64 MFMA product of pair densities and weight products), and k_stack_tile_w with a width per (column,
 // row); gpz_predictor_draws_gamma_noisy_dev returns that gamma beside the draws.  Their buffers are allocated on their first call.
 // gpz_predictor_stack_missing_dev stacks one group of rows with missing inputs in the same way, with gamma under every draw from
@@ -315,9 +318,20 @@ static int predictor_noisy_cov_tables(gpz_predictor *p, bool pairs) {
     return rc;
 }
 
+// the PHI tile of the draws of such rows, on a handle whose own route has none
+static int predictor_noisy_cov_phi_tile(gpz_predictor *p) {
+    if (p->cphi) return 0;
+    if (p->Phi) {   // the tile route's PHI, [tile_pad][mp]: a tile's kernels are done with it before the next one's
+        p->cphi = p->Phi;
+        return 0;
+    }
+    return p->ar.alloc(&p->cphi, (size_t)p->tile_pad * p->mp);
+}
+
 // What a call for such rows adds to the handle, each thing where it is missing: the Psi slots and the basis records (every call); with
-// pairs (the moments) the pair records, the 4k-row output slots and the chunk slab of predictor_noisy_prepare, which a covariance kind
-// has from nowhere else; without (the draws) the PHI tile on a handle whose own route has none.
+// pairs (the moments, gamma per draw, the stack) the pair records, the 4k-row output slots and the chunk slab of predictor_noisy_prepare,
+// which a covariance kind has from nowhere else; without (the draws) the PHI tile, which a call with pairs and draws takes in
+// rows_fit_tile.
 static int predictor_noisy_cov_prepare(gpz_predictor *p, bool pairs) {
     const size_t m = p->m, k = p->k, tp = (size_t)p->tile_pad, npair = m * (m + 1) / 2;
     auto &ar = p->ar;
@@ -327,10 +341,7 @@ static int predictor_noisy_cov_prepare(gpz_predictor *p, bool pairs) {
     const bool basis = !p->cbrec, table = pairs && !p->ncov_ready;
     if (basis && (rc = ar.alloc(&p->cbrec, m * predict_noisy_cov_brec(p->d, p->k)))) return rc;
     if (!pairs) {
-        if (!p->cphi) {
-            if (p->Phi) p->cphi = p->Phi;   // the tile route's PHI, [tile_pad][mp]: a tile's kernels are done with it before the next one's
-            else if ((rc = ar.alloc(&p->cphi, tp * p->mp))) return rc;
-        }
+        if ((rc = predictor_noisy_cov_phi_tile(p))) return rc;
     } else {
         if (!p->cprec && (rc = ar.alloc(&p->cprec, npair * predict_noisy_cov_prec(p->d, p->k)))) return rc;
         for (int s = 0; s < 2; ++s)
@@ -642,6 +653,8 @@ const double *rows_moments(const gpz_predictor *p, const Rows &r, int s) {
 static int rows_fit_tile(gpz_predictor *p, const Rows &r, int ncol, int ldw, int64_t *T) {
     *T = rows_tile(p, r, *T);
     if ((!r.group() && r.kind != ROWS_NOISY_COV) || ncol == 0) return 0;   // (a covariance kind with Psi: the output tile of E_x[PHI] W)
+    if (r.kind == ROWS_NOISY_COV)   // (a call that reads the pairs too - gamma per draw, a stack with draws - has no PHI tile from rows_prepare)
+        if (int rc = predictor_noisy_cov_phi_tile(p)) return rc;
     return predictor_grow(p, &p->Td, &p->t_cap, (size_t)rup(*T, 1024) * ldw);
 }
 
@@ -669,7 +682,7 @@ int rows_chunks(const gpz_predictor *p, const Rows &r) { return r.group() ? p->m
 int rows_gamma_prepare(gpz_predictor *p, const Rows &r, int ncol, int Q, int64_t T) {
     gpz_predictor::PerDraw &g = p->gam[r.kind - 1];
     int rc = 0;
-    if (r.kind == ROWS_NOISY) p->gchunks = predict_gamma_chunks(p->m);
+    if (r.kind == ROWS_NOISY || r.kind == ROWS_NOISY_COV) p->gchunks = predict_gamma_chunks(p->m);   // (a handle has one of the two kinds)
     if (ncol > 0 && (rc = predictor_grow(p, &p->gpart, &p->gpart_cap, (size_t)rows_chunks(p, r) * ncol * T))) return rc;
     if (Q > 0 && (rc = predictor_grow(p, &g.s2_d, &g.s2_cap, (size_t)Q * T))) return rc;
     g.used = true;
@@ -678,6 +691,12 @@ int rows_gamma_prepare(gpz_predictor *p, const Rows &r, int ncol, int Q, int64_t
 
 // the pair sums under every draw of one tile of nt rows (a group: after predictor_missing_tile, mPio): -> gpart ([chunks][ncol][nt])
 int rows_gamma_tile(gpz_predictor *p, const char *who, const Rows &r, int s, int nt, int ncol, int ldw) {
+    if (r.kind == ROWS_NOISY_COV) {   // the head of the packed pair records, read with the table's stride
+        if (launch_predict_noisy_cov_gamma(p->s_cmp, p->d, p->mid == 4, p->Xc[s], p->Psic[s], p->tile_pad, nt, p->m, p->cprec,
+                                           predict_noisy_cov_prec(p->d, p->k), p->Wd, ldw, ncol, p->gchunks, p->gpart, nt))
+            return gpz_fail(GPZ_ERR_HIP, "%s: k_predict_noisy_cov_gamma launch failed", who);
+        return 0;
+    }
     // a group with Psi: the second record table
     if (r.kind == ROWS_NOISY
             ? launch_predict_noisy_gamma(p->s_cmp, p->d, p->Xc[s], p->Psic[s], p->tile_pad, nt, p->m, p->ptab, p->nrec, p->Wd, ldw, ncol,
@@ -894,9 +913,14 @@ extern "C" int gpz_predictor_route(const gpz_predictor *p, char *buf, int cap) {
         snprintf(tmp, sizeof tmp, "; noise: k_predict_noisy_small (%d pair chunks)", p->nchunks);
         r += tmp;
     }
-    if (p->ncov_ready) {   // after the first moments call with input noise on a covariance kind
+    if (p->ncov_ready) {   // after the first call with input noise on a covariance kind that reads the pairs
         snprintf(tmp, sizeof tmp, "; noise: k_predict_noisy_cov_small (%d pair chunks)", p->cchunks);
         r += tmp;
+    }
+    if (p->gam[3].used) {   // after the first stack or gamma-per-draw call for such rows
+        snprintf(tmp, sizeof tmp, "; noise per draw: k_predict_noisy_cov_gamma (%d pair chunks)", p->gchunks);
+        r += tmp;
+        if (p->gam[3].s2_d) r += " + k_stack_tile_w";   // the widths exist: a stack call was among them
     }
     if (p->gam[0].used) {   // after the first stack or gamma-per-draw call for rows with input noise
         snprintf(tmp, sizeof tmp, "; noise per draw: k_predict_noisy_gamma (%d pair chunks)", p->gchunks);

@@ -28,7 +28,7 @@
 // no atomics, and a row's results have the same bits for any tile size, position in the tile and row order.
 #include "gpz_dev.h"
 #include "gpz_kernels.h"
-#include "k_chol_packed.h"   // LT, chol_packed_rd
+#include "k_ncov_density.h"   // LT, ncov_factor, ncov_density (shared with k_predict_noisy_cov_gamma.hip)
 
 #define NC_TP 32   // records per LDS stage
 
@@ -41,34 +41,6 @@ struct PredNoisyCovArgs {
     double *part; long ldp;              // [chunks][5 k][ldp]
     double *Phi; int nrow, mp;           // k_predict_noisy_cov_phi: [nrow][mp]
 };
-
-// M <- S + diag(ps), factorised in place by chol_packed_rd (rd[c] = 1 / L_cc, *prd = their product = |M|^-1/2; a non-positive pivot
-// gives NaN as sqrt() would).  S: a packed lower triangle, the same address in every lane.
-template <int D>
-__device__ __forceinline__ void ncov_factor(const double *S, const double (&ps)[D], double (&M)[D * (D + 1) / 2], double (&rd)[D],
-                                            double *prd) {
-#pragma unroll
-    for (int r = 0; r < D; ++r)
-#pragma unroll
-        for (int c = 0; c <= r; ++c) M[LT(r, c)] = (r == c) ? S[LT(r, c)] + ps[r] : S[LT(r, c)];   // Sigma + Psi    getPHI.m:84, predictCov.m:109
-    chol_packed_rd<D>(M, rd, prd);
-}
-
-// exp(lnz - 1/2 |L^-1 (x - cen)|^2) prod(1 / L_cc): N(x; cen, M) up to the constant that lnz carries - no logarithm, no division
-template <int D>
-__device__ __forceinline__ double ncov_density(const double *cen, double lnz, const double (&x)[D], const double (&M)[D * (D + 1) / 2],
-                                               const double (&rd)[D], double prd) {
-    double q = 0.0, y[D];
-#pragma unroll
-    for (int r = 0; r < D; ++r) {
-        double s = x[r] - cen[r];
-#pragma unroll
-        for (int c = 0; c < r; ++c) s = fma(-M[LT(r, c)], y[c], s);
-        y[r] = s * rd[r];
-        q = fma(y[r], y[r], q);
-    }
-    return exp(lnz - 0.5 * q) * prd;
-}
 
 template <int D, bool SHARED, int KM>
 __global__ __launch_bounds__(256) void k_predict_noisy_cov_small(PredNoisyCovArgs a) {

@@ -2,7 +2,7 @@
 
 The methods ask one of four questions (run: the moments of ``predict``; draws; draws with gamma per draw; stack) of rows of one of four
 kinds (clean, noisy: with Psi, missing: one NaN-pattern group, noisy_missing: such a group with Psi); noisy_cov is the noisy kind of a
-covariance model (GC, VC), which has the first two questions only.
+covariance model (GC, VC), which has all four questions through methods of its own (``*_noisy_cov_dev``).
 ``_DEV_ENTRIES`` names the device-resident entry of each pair, ``Predictor._dev_entry`` builds the arguments the entries of a pair
 share, and ``Predictor._dev_groups`` is the one loop over the groups of a call; the host methods choose between two entries each by
 whether Psi is there (``_HOST_ENTRIES``).  Everything numeric happens in the library; ``torch`` is only imported by the device methods.
@@ -32,6 +32,7 @@ _DEV_ENTRIES = {
     ("draws", "missing"): "gpz_predictor_draws_missing_dev", ("draws", "noisy_missing"): "gpz_predictor_draws_noisy_missing_dev",
     ("draws_gamma", "noisy"): "gpz_predictor_draws_gamma_noisy_dev", ("draws_gamma", "missing"): "gpz_predictor_draws_gamma_missing_dev",
     ("draws_gamma", "noisy_missing"): "gpz_predictor_draws_gamma_noisy_missing_dev",
+    ("draws_gamma", "noisy_cov"): "gpz_predictor_draws_gamma_noisy_cov_dev", ("stack", "noisy_cov"): "gpz_predictor_stack_noisy_cov_dev",
     ("stack", "clean"): "gpz_predictor_stack_dev", ("stack", "noisy"): "gpz_predictor_stack_noisy_dev",
     ("stack", "missing"): "gpz_predictor_stack_missing_dev", ("stack", "noisy_missing"): "gpz_predictor_stack_noisy_missing_dev",
 }
@@ -644,7 +645,8 @@ class Predictor:
         ``return_gamma=True`` with ``missing=True`` (gpz_predictor_draws_gamma_missing_dev) returns the same pair with predictMissing's
         gamma under the weights of draw s: the variance of PHI(x) w_s over the missing dimensions of the row, exactly 0.0 on complete
         rows.  A row's Gam has the same bits for any tile size, row order, other rows of the call and any n_draws > s.  The scope is
-        that of ``missing=True`` (diagonal kinds, d <= 20, k <= 8, m <= 256); the covariance kinds and host arrays are not on the handle;
+        that of ``missing=True`` (diagonal kinds, d <= 20, k <= 8, m <= 256); the covariance kinds and host arrays are not on the handle
+        (gamma per draw over the input noise of a covariance kind is ``draws_noisy_cov_dev(..., return_gamma=True)``'s);
         gamma per draw for ``Psi`` together with missing values is ``draws_noisy_missing_dev(..., return_gamma=True)``'s.  With neither ``Psi`` nor ``missing``, or with both, it is a ValueError."""
         self._check_open()
         X = self._check_dev_rows(X, selection, "draws")
@@ -738,23 +740,27 @@ class Predictor:
         return self._draws_dev(X, Psi, selection, True, n_draws, seed, z, bool(return_gamma))
 
     def _check_noisy_cov(self, what, X, Psi, selection):
-        """The checks the two methods for rows with Psi of a covariance kind share, none of which touches a GPU: X, then where such
+        """The checks the three methods for rows with Psi of a covariance kind share, none of which touches a GPU: X, then where such
         rows go when this is not their route (no Psi, a full Psi cube, a diagonal kind, a shape outside predict_noisy_cov_fits of
         k_predict_noisy_cov.hip), then Psi's type, dtype and shape.  Returns X as n x d and Psi as n x 1 or n x d."""
         X = self._check_dev_rows(X, selection, what)
         name = f"{what}_noisy_cov_dev"
+        clean, diag = (f"{what}_dev(X, edges)", "stack_noisy_dev(X, Psi, edges)") if what == "stack" else \
+            (f"{what}_dev(X)", f"{what}_dev(X, Psi=Psi)")
         if Psi is None:
-            raise ValueError(f"{name} needs Psi: rows without input noise go to {what}_dev(X)")
+            raise ValueError(f"{name} needs Psi: rows without input noise go to {clean}")
         if np.ndim(Psi) == 3 or (hasattr(Psi, "dim") and Psi.dim() == 3):
             raise ValueError(f"{name} takes Psi as n x d, n x 1 or n variances: a full d x d x n Psi stays on "
                              "Predictor.predict(X, Psi=Psi)")
         if self._method[1] != "C":
-            raise ValueError(f"{name} is for the covariance kinds (GC, VC): a diagonal kind such as {self._method} goes to "
-                             f"{what}_dev(X, Psi=Psi)")
+            raise ValueError(f"{name} is for the covariance kinds (GC, VC): a diagonal kind such as {self._method} goes to {diag}")
         if not (1 <= self._d <= 10 and 1 <= self._k <= 8 and 1 <= self._m <= 256):
             raise ValueError(f"{name} needs a model inside predict_noisy_cov_fits: GC or VC, d <= 10, k <= 8 and m <= 256; this one is "
                              f"{self._method} with d = {self._d}, m = {self._m}, k = {self._k} (Predictor.predict takes Psi for every "
                              "shape)")
+        if what == "stack" and isinstance(Psi, np.ndarray):               # (no host stack takes Psi of a covariance kind)
+            raise TypeError(f"{name} takes Psi as a torch tensor on cuda:{self.device}; host arrays of a covariance kind stay on "
+                            "Predictor.predict(X, Psi=Psi)")
         return X, self._check_dev_psi(Psi, X.shape[0], what)
 
     def predict_noisy_cov_dev(self, X, Psi, selection=None):
@@ -764,7 +770,8 @@ class Predictor:
         predictCov.m on the handle's tiles by k_predict_noisy_cov_small, with the variances on the diagonal of each row's Psi as fixPsi
         puts them there.  A row's results do not depend on the tile size, the row order or the other rows of the call.  It needs a
         model inside predict_noisy_cov_fits (GC or VC, d <= 10, k <= 8, m <= 256), else ValueError; a full d x d x n Psi, PHI, host
-        arrays, stacks, gamma per draw and rows with missing values are not on this route (``Predictor.predict`` takes them).  Rows
+        arrays and rows with missing values are not on this route (``Predictor.predict`` takes them); the stack of such rows is
+        ``stack_noisy_cov_dev``'s and gamma per draw ``draws_noisy_cov_dev(..., return_gamma=True)``'s.  Rows
         with NaN and an element of Psi that is NaN, infinite or negative are refused (GpzError).  Type, dtype and shape are checked
         first, the device last, all before the GPU is touched."""
         self._check_open()
@@ -772,17 +779,32 @@ class Predictor:
         self._check_dev_device(X=X, selection=selection, Psi=Psi)
         return self._moments_dev(X, Psi, selection, False, cov=True)
 
-    def draws_noisy_cov_dev(self, X, Psi, n_draws, seed=0, Z=None, selection=None):
+    def draws_noisy_cov_dev(self, X, Psi, n_draws, seed=0, Z=None, selection=None, return_gamma=False):
         """``draws_dev(X, ..., Psi=Psi)`` for a covariance kind (gpz_predictor_draws_noisy_cov_dev): X, ``Psi`` and ``selection`` as for
         ``predict_noisy_cov_dev``, ``n_draws``, ``seed`` and ``Z`` as for ``draws_dev``.  Returns a float64 tensor of shape
         (n_draws, n, k) on the device: draws[s] is ``predict_noisy_cov_dev``'s mu under weight draw s, E_x[PHI] w_s + muY - the mean is
         linear in the weights, so this is exact.  E_x[PHI] of a tile comes from k_predict_noisy_cov_phi and meets the draws' weights on
-        the T-GEMM, whatever route the handle's noise-free draws take."""
+        the T-GEMM, whatever route the handle's noise-free draws take.
+        ``return_gamma=True`` (gpz_predictor_draws_gamma_noisy_cov_dev) returns ``(F, Gam)``: F with the bits it has without the keyword,
+        Gam a float64 tensor of shape (n_draws, n, k), predictNoisy's gamma of predictCov.m under the weights of draw s - the variance
+        of PHI(x) w_s over the input noise, not clamped at 0 (k_predict_noisy_cov_gamma).  A y-draw of row i under draw s has variance
+        beta_i + Gam[s, i].  A row's Gam has the same bits for any tile size, row order, other rows of the call and any n_draws > s."""
         self._check_open()
         X, Psi = self._check_noisy_cov("draws", X, Psi, selection)
         n_draws, z = self._check_draw_args(n_draws, seed, Z, 1)
         self._check_dev_device(X=X, selection=selection, Psi=Psi)
-        return self._draws_dev(X, Psi, selection, False, n_draws, seed, z, cov=True)
+        return self._draws_dev(X, Psi, selection, False, n_draws, seed, z, bool(return_gamma), cov=True)
+
+    def stack_noisy_cov_dev(self, X, Psi, edges, n_draws=0, seed=0, Z=None, groups=None, n_groups=None, weights=None, selection=None):
+        """``stack_noisy_dev`` for a covariance kind (GC, VC; gpz_predictor_stack_noisy_cov_dev): X, ``Psi`` and ``selection`` as for
+        ``predict_noisy_cov_dev``, everything else as for ``stack_dev``.  Returns a NumPy StackResult.  Column 0 uses
+        ``predict_noisy_cov_dev``'s mu and that call's sigma = (nu + beta_i) + gamma, bit for bit; column 1 + s
+        ``draws_noisy_cov_dev``'s draw s and the width beta_i + max(gamma_s, 0), where gamma_s is that method's ``return_gamma=True``.
+        The fields are plain sums over the rows, so calls over parts of a catalogue add.  It needs a model inside
+        predict_noisy_cov_fits (GC or VC, d <= 10, k <= 8, m <= 256), else ValueError, and takes any route of the handle; a diagonal
+        kind goes to ``stack_noisy_dev``.  Rows with NaN, a bad element of Psi, a label outside [-1, n_groups) and a negative or
+        non-finite weight are found on the device before the first tile and refused with a GpzError."""
+        return self._stack_dev(X, Psi, edges, n_draws, seed, Z, groups, n_groups, weights, selection, cov=True)
 
     def stack_dev(self, X, edges, n_draws=0, seed=0, Z=None, groups=None, n_groups=None, weights=None, selection=None):
         """``stack`` for a catalogue on the GPU (gpz_predictor_stack_dev): X and ``selection`` as for ``predict_dev``; ``groups`` an
@@ -831,20 +853,22 @@ class Predictor:
         the covariance kinds are not on the handle."""
         return self._stack_dev(X, Psi, edges, n_draws, seed, Z, groups, n_groups, weights, selection, missing=True, both=True)
 
-    def _stack_dev(self, X, Psi, edges, n_draws, seed, Z, groups, n_groups, weights, selection, missing=False, both=False):
-        """``stack_dev`` (Psi None), ``stack_noisy_dev``, ``stack_missing_dev`` and (``both``: Psi and ``missing`` together)
-        ``stack_noisy_missing_dev``: the checks, the device last, all before the GPU is touched; then the entry, or with ``missing``
+    def _stack_dev(self, X, Psi, edges, n_draws, seed, Z, groups, n_groups, weights, selection, missing=False, both=False, cov=False):
+        """``stack_dev`` (Psi None), ``stack_noisy_dev``, ``stack_missing_dev``, (``both``: Psi and ``missing`` together)
+        ``stack_noisy_missing_dev`` and (``cov``: Psi of a covariance kind) ``stack_noisy_cov_dev``: the checks, the device last, all before the GPU is touched; then the entry, or with ``missing``
         one entry per NaN-pattern group."""
         import torch
         self._check_open()
         if both:
             X, Psi = self._check_noisy_missing("stack", X, Psi, selection, draws=True)
+        elif cov:
+            X, Psi = self._check_noisy_cov("stack", X, Psi, selection)
         else:
             X = self._check_dev_rows(X, selection, "stack" if Psi is None else "stack_noisy")
         n_all = X.shape[0]
         if missing and not both:
             self._check_missing_model("stack_missing_dev", None)
-        if Psi is not None and not both:
+        if Psi is not None and not both and not cov:
             Psi = self._check_dev_psi(Psi, n_all, "stack_noisy")
             self._check_noisy_model("stack_noisy_dev", draws=True)
         e, B = self._check_edges(edges)
@@ -880,7 +904,7 @@ class Predictor:
             # X, lab and wt are referenced by this frame for the whole (host-synchronous) call: no record_stream needed
             for code, idx, Xg, Pg, lg, wg in self._dev_groups(X, missing, Psi, lab, wt):   # ascending code: one fixed order of the sums
                 part = totals if idx is None else self._stack_arrays(n_draws, G, B)
-                fn, lead, _ = self._dev_entry("stack", call, code, Xg, Pg)
+                fn, lead, _ = self._dev_entry("stack", call, code, Xg, Pg, cov)
                 _lib.check(fn(*lead, n_draws, int(seed), _lib.dptr(z), _lib.dptr(es), B, None if lg is None else lg.data_ptr(), G,
                               None if wg is None else wg.data_ptr(), *(_lib.dptr(a) for a in part), _lib.dptr(call.muY), call.stream))
                 self._merge(idx, totals, part, None)

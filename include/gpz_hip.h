@@ -396,6 +396,36 @@ int gpz_predictor_draws_gamma_noisy_dev(gpz_predictor *p, const void *X_d, int32
                                         const double *Z /* host: NULL or m x ndraws x k */, double *F_d /* ns x k x ndraws, column-major */,
                                         double *Gam_d /* ns x k x ndraws, column-major */, void *stream);
 
+/* The same for the covariance kinds: gpz_predictor_stack_noisy_dev and gpz_predictor_draws_gamma_noisy_dev for rows with a variance per
+ * input dimension on a GC or VC model, where predict_noisy_cov_fits holds (any other model returns GPZ_ERR_UNSUPPORTED and names that
+ * function) and on any route of the handle.  The arguments are exactly those of the two entries above.  Column 0: mu of
+ * gpz_predictor_run_noisy_cov_dev, width^2 = (nu + beta) + gamma, the bits of that call's sigma.  Column 1 + s: mu_s of
+ * gpz_predictor_draws_noisy_cov_dev, width^2 = beta_i + max(gamma_s,i, 0) with
+ *   gamma_s,i = sum_{a >= b} f_ab z_ab(x_i, psi_i) w_s,a w_s,b - mu_s,i^2,   z_ab = exp(lnZ_ab - q / 2) prod_c 1 / L_cc
+ * from the Cholesky factor L of C_ab + diag(psi_i): predictNoisy's gamma (predictCov.m:105-119) under the draw's weights.  Per tile
+ * k_predict_noisy_cov_gamma (k_predict_noisy_cov_gamma.hip: k_predict_noisy_gamma's f64 MFMA product with k_predict_noisy_cov_small's
+ * pair density, on the head of the handle's packed pair records) in front of the same finish and stack kernels.  Rows with NaN ->
+ * GPZ_ERR_UNSUPPORTED, a bad element of Psi, label or weight -> GPZ_ERR_ARG, all found before the first tile; in every refusal the
+ * outputs are untouched.  Gam_d is unclamped; a row's gamma_s has the same bits for any tile size, row order, split into calls and any
+ * ndraws > s.  The first of these calls adds to the handle what gpz_predictor_run_noisy_cov_dev adds and, with draws, what
+ * gpz_predictor_draws_noisy_cov_dev adds, plus the chunk slab of the pair sums (predict_gamma_chunks(m) x ndraws k x tile rows doubles)
+ * and, for the stack, the widths ((1 + ndraws) k x tile rows); ndraws = 0 forms no factors and takes no draws buffer and no slab.
+ * Nothing grows with ns, and gpz_predictor_route then ends in "; noise per draw: k_predict_noisy_cov_gamma (C pair chunks)", followed
+ * by " + k_stack_tile_w" once the stack entry has been called. */
+int gpz_predictor_stack_noisy_cov_dev(gpz_predictor *p, const void *X_d, int32_t x_type, int64_t ns, int64_t row_stride, int64_t col_stride,
+                                      const void *Psi_d, int32_t psi_type, int64_t psi_row_stride, int64_t psi_col_stride,
+                                      const double *muX, const double *sdX, const double *sd2,
+                                      int32_t ndraws, uint64_t seed, const double *Z, const double *edges, int32_t nbins,
+                                      const int32_t *group_d /* ns or NULL */, int32_t ngroups, const double *weight_d /* ns or NULL */,
+                                      double *hist, double *sum_w, double *sum_mu, double *sum_mu2, const double *mu_shift /* k or NULL */,
+                                      void *stream);
+int gpz_predictor_draws_gamma_noisy_cov_dev(gpz_predictor *p, const void *X_d, int32_t x_type, int64_t ns, int64_t row_stride,
+                                            int64_t col_stride, const void *Psi_d, int32_t psi_type, int64_t psi_row_stride,
+                                            int64_t psi_col_stride, const double *muX, const double *sdX, const double *sd2,
+                                            const double *muY /* k or NULL */, int32_t ndraws, uint64_t seed,
+                                            const double *Z /* host: NULL or m x ndraws x k */, double *F_d /* ns x k x ndraws, column-major */,
+                                            double *Gam_d /* ns x k x ndraws, column-major */, void *stream);
+
 /* ---- rows with missing inputs on the predictor handle ------------------------------------------------------------------------------
  * predictMissing (predictDiag.m:127-209) and the draws for ONE group of rows that share a NaN pattern, on the handle's own tiles,
  * where predict_missing_fits holds: a diagonal kind (GL, VL, GD, VD), d <= 20, k <= 8 and ceil16(m) <= 256, no Psi.  Any other shape
