@@ -134,6 +134,13 @@ SYMBOLS = {
     "gpz_predictor_draws_missing_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int64, c_double_p,
                                                   c_double_p, c_double_p, c_double_p, C.c_uint32, C.c_int32, C.c_uint64, c_double_p,
                                                   C.c_void_p, C.c_void_p]),
+    # the same for a covariance kind (GC, VC): exactly the arguments of the two entries above
+    "gpz_predictor_run_missing_cov_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int64, c_double_p,
+                                                    c_double_p, c_double_p, c_double_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                    C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gpz_predictor_draws_missing_cov_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int64, c_double_p,
+                                                      c_double_p, c_double_p, c_double_p, C.c_uint32, C.c_int32, C.c_uint64, c_double_p,
+                                                      C.c_void_p, C.c_void_p]),
     # gamma under every draw and the stack for such a group: the draws entry plus Gam; gpz_predictor_stack_dev plus the priors and the mask
     "gpz_predictor_draws_gamma_missing_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int64, c_double_p,
                                                         c_double_p, c_double_p, c_double_p, C.c_uint32, C.c_int32, C.c_uint64, c_double_p,

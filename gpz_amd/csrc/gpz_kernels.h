@@ -320,6 +320,34 @@ size_t predict_missing_gamma_lds(int m, int d, bool psi);   // dynamic LDS of th
 int launch_predict_missing_gamma(hipStream_t st, const double *Xc, const double *Psic, long ldx, int n, const double *Pio, int ldpio, int m,
                                  int d, int k, unsigned obs, const double *U, const double *rec, const double *W, int ldw, int ncol,
                                  int nchunk, double *part, long ldp);
+// ---- rows with missing inputs, covariance kinds (k_predict_missing_cov.hip; gpz_predictor_*_missing_cov_dev) --------------------------
+// One group of rows sharing a NaN pattern with no observed dimensions.  fits: GC or VC, 1 <= d <= 10, 1 <= k <= 8, ceil16(m) <= 256.
+// A record is predict_missing_cov_rec(no) = 1 + no + no (no + 1) / 2 doubles, [lnw | a | U]: -1/2 q = lnw - 1/2 |U (x_o - a)|^2.
+// launch_pmcv_tables (per pattern and priors; Sig m x d x d and lnS from launch_gen_prep): bas [m][predict_missing_cov_bas(d, no)],
+// the m Ex records, the m * m PHI records and, with coef, the 3 k coefficients of every pair as gpz_pair_coef writes them.
+// launch_pmcv_rows (per tile): Pio [m][ldr], Phi [nrow][mp] (rows >= n and columns >= m zero, what launch_tgemm takes) and hd [2k][ldh] =
+// PHI w | PHI v.  launch_predict_missing_cov_pairs: per slab of predict_missing_cov_slab_pairs(m, no) whole pairs (there are
+// predict_missing_cov_slabs(m, no) of them, at most 64 MB each) k_pmc_triples from raw (launch_pair_table's records, 1 + d + d d doubles)
+// into slab and k_predict_missing_cov_pairs, part [predict_missing_cov_chunks(m)][3k][ldp] -> out [4k][n] = mu | nu | beta | gamma
+// (launch_pmd_finish inside).  *slab_kept: the slab holds the pattern's whole table (one slab) and is not written again; the caller clears
+// it when bas or raw change.  Chunks and slabs are functions of m and no alone.  The launchers return -1 when a launch failed.
+bool predict_missing_cov_fits(int kind, int d, int m, int k);
+int predict_missing_cov_rec(int no);
+int predict_missing_cov_bas(int d, int no);
+int predict_missing_cov_chunks(int m);
+int predict_missing_cov_slabs(int m, int no);
+long predict_missing_cov_slab_pairs(int m, int no);
+size_t predict_missing_cov_lds(int m, int no, int k);   // dynamic LDS of the pair kernel, bytes
+int launch_pmcv_tables(hipStream_t st, int m, int d, int de, int k, unsigned obs, const double *P, const double *Sig, const double *lnS,
+                       const double *priors, const double *w, const double *v, const double *iS, double *bas, double *exrec,
+                       double *phirec, double *coef);
+int launch_pmcv_rows(hipStream_t st, const double *Xc, long ldx, int n, int nrow, int m, int mp, int d, int k, unsigned obs,
+                     const double *exrec, const double *phirec, const double *w, const double *v, double *Pio, long ldr, double *Phi,
+                     double *hd, long ldh);
+int launch_predict_missing_cov_pairs(hipStream_t st, const double *Xc, long ldx, int n, const double *Pio, long ldr, int m, int d, int k,
+                                     unsigned obs, const double *raw, const double *bas, const double *coef, double *slab,
+                                     bool *slab_kept, int nchunk, double *part, long ldp, const double *hd, long ldh, const double *bvec,
+                                     double *out);
 // B (rows x ld row-major) <- [iS (m x m column-major) | nw columns of W from column wcol | nv columns of V (nullptr: 0) from vcol | 0]
 void launch_pred_fill_b(hipStream_t st, const double *iS, const double *W, int nw, int wcol, const double *V, int nv, int vcol, int m,
                         int rows, int ld, double *B);

@@ -90,6 +90,15 @@ struct gpz_predictor {
     int cchunks = 0;               // predict_noisy_cov_chunks of the model
     double *cbrec = nullptr, *cprec = nullptr;   // the basis and pair records (k_noisy_cov_records): the model's alone, written once
     double *cphi = nullptr;        // the draws (and a stack with draws): E_x[PHI] of a tile, [tile_pad][mp] (the tile route's own Phi where there is one)
+    // ---- rows with missing inputs for the covariance kinds (gpz_predictor_*_missing_cov_dev): the tile buffers, the priors and the
+    // cache keys are the fields of the diagonal kinds' group above (mtile, mNo = PHI, mPio = [m][tile], mhd, mpart, mout, mpri, mtab_*;
+    // mchunks = predict_missing_cov_chunks), which a covariance handle has from nowhere else.  Beyond them only this exists, and not
+    // before the first of their calls
+    bool mcov_used = false;
+    double *mcSig = nullptr, *mclnS = nullptr, *mcraw = nullptr;   // the model's alone: Sigma_j, ln|Sigma_j|; with pairs launch_pair_table's records
+    double *mcbas = nullptr, *mcex = nullptr, *mcphi = nullptr;    // the pattern's: [R | CU | off] per basis function, the Ex and PHI records
+    double *mccoef = nullptr, *mcslab = nullptr;                   // with pairs: the 3k coefficients per pair, the slab of pair-component records
+    bool mcslab_kept = false;      // the slab holds the whole table of (mtab_obs, mtab_pri)
 };
 
 namespace gpzi {
@@ -97,13 +106,14 @@ namespace gpzi {
 // share the NaN pattern obs (the bit mask of the observed dimensions), with the priors of the set (m values, or nullptr for 1 / m).
 // Noisy missing: such a group with Psi in Psic[s] too (read in the observed dimensions only).  Noisy cov: complete rows with Psi of a
 // covariance kind (a handle has either this kind or the diagonal noisy one, never both).  What a tile is made of for a kind is answered by the rows_* functions below; the runners of every entry go through them.
-enum RowKind { ROWS_CLEAN = 0, ROWS_NOISY = 1, ROWS_MISSING = 2, ROWS_NOISY_MISSING = 3, ROWS_NOISY_COV = 4 };
+// Missing cov: a group without Psi on a covariance kind (moments and draws only: it has no slot in gam[]).
+enum RowKind { ROWS_CLEAN = 0, ROWS_NOISY = 1, ROWS_MISSING = 2, ROWS_NOISY_MISSING = 3, ROWS_NOISY_COV = 4, ROWS_MISSING_COV = 5 };
 struct Rows {
     RowKind kind = ROWS_CLEAN;
     uint32_t obs = 0;
     const double *priors = nullptr;
     bool psi() const { return kind == ROWS_NOISY || kind == ROWS_NOISY_MISSING || kind == ROWS_NOISY_COV; }   // Psic[s] is staged beside Xc[s]
-    bool group() const { return kind == ROWS_MISSING || kind == ROWS_NOISY_MISSING; }    // one NaN pattern, tiles of at most mtile rows
+    bool group() const { return kind == ROWS_MISSING || kind == ROWS_NOISY_MISSING || kind == ROWS_MISSING_COV; }    // one NaN pattern, tiles of at most mtile rows
 };
 
 // ---- what a kind of rows is made of (gpz_predictor.hip) ------------------------------------------------------------------------------

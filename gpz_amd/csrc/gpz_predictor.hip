@@ -48,6 +48,11 @@
 // shapes): gpz_predictor_run_missing_dev / _draws_missing_dev run predictMissing on tiles of at most GPZ_PREDICTOR_TILE_MISSING rows
 // (k_predict_missing.hip): No and Pio, PHI through k_tgemm, then the fused pair kernel, or for the draws k_tgemm against W.  The tables
 // of a pattern (NijS, the pair records, U) are kept until the pattern or the priors change; all of it is allocated on the first such call.
+// The covariance kinds have these two entries as gpz_predictor_run_missing_cov_dev / _draws_missing_cov_dev where
+// predict_missing_cov_fits holds (1 <= d <= 10, k <= 8, m <= 256; k_predict_missing_cov.hip): every density of predictMissing of
+// predictCov.m is a quadratic in the row's observed inputs, written once per pattern as a record; Ex, Pio and PHI per tile from the m
+// and m^2 records of the pattern, the pair sums from the m^2 (m + 1) / 2 pair-component records, which pass through a slab of at most
+// 64 MB (predictor_missing_cov_prepare, predictor_missing_cov_tile); the finish and the draws are the diagonal kinds'.
 // A group whose rows have Psi as well goes through gpz_predictor_run_noisy_missing_dev / _draws_noisy_missing_dev (predictNoisyMissing,
 // k_predict_noisy_missing.hip): the same tiles and tables with No widened by psi and a pair kernel whose epilogue is predictNoisy's, on a
 // second record table that is the model's alone.  gpz_predictor_stack_noisy_missing_dev stacks such a group as the two stacks above,
@@ -497,8 +502,19 @@ static int predictor_draws_tile(gpz_predictor *p, int s, int64_t nt, int ncol, i
 }
 
 // ---- rows with missing inputs on the handle -----------------------------------------------------------------------------------------
-static int predictor_missing_check(const char *who, const gpz_predictor *p, uint32_t obs) {
-    if (!predict_missing_fits(p->kind, p->de, p->m, p->k))
+// cov: the entries of the covariance kinds (ROWS_MISSING_COV); each of the two refuses the other's kinds and names their entry
+static int predictor_missing_check(const char *who, const gpz_predictor *p, uint32_t obs, bool cov) {
+    if (cov && p->kind != GPZ_KIND_COV)
+        return gpz_fail(GPZ_ERR_UNSUPPORTED,
+                        "%s: method %.2s is a diagonal kind: its rows with missing inputs go to gpz_predictor_run_missing_dev / "
+                        "_draws_missing_dev",
+                        who, p->desc.method);
+    if (cov && !predict_missing_cov_fits(p->kind, p->d, p->m, p->k))
+        return gpz_fail(GPZ_ERR_UNSUPPORTED,
+                        "%s: missing inputs for a covariance kind on the handle need predict_missing_cov_fits: GC or VC, 1 <= d <= 10, "
+                        "1 <= k <= 8 and ceil16(m) <= 256 (method %.2s, d %d, m %d, k %d); gpz_predict_missing takes every shape",
+                        who, p->desc.method, p->d, p->m, p->k);
+    if (!cov && !predict_missing_fits(p->kind, p->de, p->m, p->k))
         return gpz_fail(GPZ_ERR_UNSUPPORTED,
                         "%s: missing inputs on the handle need predict_missing_fits: a diagonal kind (GL, VL, GD, VD), d <= 20, k <= 8 and "
                         "ceil16(m) <= 256 (method %.2s, d %d, m %d, k %d); gpz_predict_missing takes every shape",
@@ -611,10 +627,109 @@ static int predictor_noisy_cov_draws_tile(gpz_predictor *p, const char *who, int
     return 0;
 }
 
+// ---- rows with missing inputs on the handle, covariance kinds -------------------------------------------------------------------------
+// The model's own tables, each where it is missing: Sigma_j and ln|Sigma_j| (launch_gen_prep) and, with pairs, launch_pair_table's
+// records [lnZ | c_ab | C_ab].  inv(Sigma_j) is a temporary of the call that makes the pair records.
+static int predictor_missing_cov_model(gpz_predictor *p, bool pairs) {
+    const size_t m = p->m, d = p->d, npair = m * (m + 1) / 2, nsig = m * d * d, rawrec = 1 + d + d * d;
+    hipStream_t st = p->s_cmp;
+    const bool sig = !p->mcSig, raw = pairs && !p->mcraw;
+    if (!sig && !raw) return 0;
+    int rc = 0;
+    double *Sig = p->mcSig, *lnS = p->mclnS, *rawt = nullptr, *tmp = nullptr;   // (where only raw is missing they are written again: the same values)
+    if (sig && ((rc = p->ar.alloc(&Sig, nsig)) || (rc = p->ar.alloc(&lnS, m)))) return rc;
+    if (raw && (rc = p->ar.alloc(&rawt, npair * rawrec))) return rc;
+    if (hipMalloc((void **)&tmp, (nsig + (d + 7) / 8) * sizeof(double)) != hipSuccess)
+        return gpz_fail(GPZ_ERR_ALLOC, "gpz_predictor: out of device memory");
+    unsigned char *pat = (unsigned char *)(tmp + nsig);   // one pattern: every dimension observed
+    if (hipMemsetAsync(pat, 1, d, st) != hipSuccess) rc = gpz_fail(GPZ_ERR_HIP, "gpz_predictor: memset failed");
+    if (!rc) {
+        launch_gen_prep(st, p->pr.G, p->m, p->d, p->de, Sig, tmp, pat, 1, lnS, nullptr);
+        if (raw) launch_pair_table(st, GPZ_KIND_COV, p->m, p->d, p->de, p->pr.P, p->pr.G, Sig, tmp, rawt, (int)rawrec, nullptr);
+        if (hipGetLastError() != hipSuccess) rc = gpz_fail(GPZ_ERR_HIP, "gpz_predictor: table launch failed");
+    }
+    if (hipStreamSynchronize(st) != hipSuccess && !rc) rc = gpz_fail(GPZ_ERR_HIP, "gpz_predictor: sync failed");
+    (void)hipFree(tmp);
+    if (rc) return rc;
+    if (sig) { p->mcSig = Sig; p->mclnS = lnS; }
+    if (raw) p->mcraw = rawt;
+    return 0;
+}
+
+// What a call for a group needs before its first tile, as predictor_missing_prepare: the tile buffers and the record tables sized for
+// the widest pattern of the model (so nothing grows with the patterns a handle sees), with pairs the pair records, coefficients, slab,
+// chunk partials and the output slot too; then the tables of (obs, priors), rebuilt where the handle holds another pattern's.
+static int predictor_missing_cov_prepare(gpz_predictor *p, const char *who, uint32_t obs, const double *priors, bool pairs) {
+    const size_t m = p->m, k = p->k, mp = p->mp, npair = m * (m + 1) / 2;
+    auto &ar = p->ar;
+    hipStream_t st = p->s_cmp;
+    int rc = 0;
+    if ((rc = predictor_missing_cov_model(p, pairs))) return rc;
+    if (!p->mtile) p->mtile = std::min<int64_t>(p->tile_rows, GPZ_PREDICTOR_TILE_MISSING);
+    const size_t mtp = (size_t)rup(p->mtile, 1024);
+    size_t rlmax = 0, nbmax = 0, slabmax = 0;   // over no = 0 .. d - 1
+    for (int no = 0; no < p->d; ++no) {
+        const size_t rl = (size_t)predict_missing_cov_rec(no);
+        rlmax = std::max(rlmax, rl);
+        nbmax = std::max(nbmax, (size_t)predict_missing_cov_bas(p->d, no));
+        slabmax = std::max(slabmax, (size_t)predict_missing_cov_slab_pairs(p->m, no) * m * rl);
+    }
+    p->mchunks = predict_missing_cov_chunks(p->m);
+    if (!p->mNo && (rc = ar.alloc(&p->mNo, mtp * mp))) return rc;
+    if (!p->mPio && (rc = ar.alloc(&p->mPio, mtp * mp))) return rc;
+    if (!p->mpri && (rc = ar.alloc(&p->mpri, m))) return rc;
+    if (!p->mhd && (rc = ar.alloc(&p->mhd, 2 * k * mtp))) return rc;
+    if (!p->mcbas && (rc = ar.alloc(&p->mcbas, m * nbmax))) return rc;
+    if (!p->mcex && (rc = ar.alloc(&p->mcex, m * rlmax))) return rc;
+    if (!p->mcphi && (rc = ar.alloc(&p->mcphi, m * m * rlmax))) return rc;
+    if (pairs) {
+        if (!p->mccoef && (rc = ar.alloc(&p->mccoef, npair * 3 * k))) return rc;
+        if (!p->mcslab && (rc = ar.alloc(&p->mcslab, slabmax))) return rc;
+        if (!p->mpart && (rc = ar.alloc(&p->mpart, (size_t)p->mchunks * 3 * k * mtp))) return rc;
+        if (!p->mout && (rc = ar.alloc(&p->mout, 4 * k * mtp))) return rc;
+    }
+    p->mcov_used = true;
+    const bool same_pri = priors ? (!p->mtab_uniform && p->mtab_pri.size() == m && std::equal(priors, priors + m, p->mtab_pri.begin()))
+                                 : p->mtab_uniform;
+    if (p->mtab_valid && p->mtab_obs == obs && same_pri && (p->mtab_pairs || !pairs)) return 0;
+    p->mtab_valid = false;
+    p->mcslab_kept = false;
+    p->mtab_uniform = priors == nullptr;
+    if (priors) {   // the handle's own copy: the upload may still be in flight when the caller has its memory back
+        p->mtab_pri.assign(priors, priors + m);
+        if (hipMemcpyAsync(p->mpri, p->mtab_pri.data(), m * sizeof(double), hipMemcpyHostToDevice, st) != hipSuccess)
+            return gpz_fail(GPZ_ERR_HIP, "%s: copy failed", who);
+    }
+    if (launch_pmcv_tables(st, p->m, p->d, p->de, p->k, obs, p->pr.P, p->mcSig, p->mclnS, priors ? p->mpri : nullptr, p->w_d,
+                           p->hetero ? p->pr.v : nullptr, p->iS_d, p->mcbas, p->mcex, p->mcphi, pairs ? p->mccoef : nullptr))
+        return gpz_fail(GPZ_ERR_HIP, "%s: table kernel launch failed", who);
+    p->mtab_obs = obs;
+    p->mtab_pairs = pairs;
+    p->mtab_valid = true;
+    return 0;
+}
+
+// predictMissing of one tile of nt rows of the group, covariance kinds: Xc[s] -> Pio in mPio ([m][tile]), PHI in mNo, mu | ElnS - b in mhd
+// and, with pairs, mout ([4k][nt] = mu | nu | beta | gamma)
+static int predictor_missing_cov_tile(gpz_predictor *p, const char *who, int s, int nt, uint32_t obs, bool pairs) {
+    hipStream_t st = p->s_cmp;
+    const int np = rup(nt, 128);   // the rows of the draws' product: k_tgemm's row tile
+    const long mtp = rup(p->mtile, 1024);
+    if (launch_pmcv_rows(st, p->Xc[s], p->tile_pad, nt, np, p->m, p->mp, p->d, p->k, obs, p->mcex, p->mcphi, p->w_d,
+                         p->hetero ? p->pr.v : nullptr, p->mPio, mtp, p->mNo, p->mhd, mtp))
+        return gpz_fail(GPZ_ERR_HIP, "%s: k_pmcv launch failed", who);
+    if (pairs && launch_predict_missing_cov_pairs(st, p->Xc[s], p->tile_pad, nt, p->mPio, mtp, p->m, p->d, p->k, obs, p->mcraw, p->mcbas,
+                                                  p->mccoef, p->mcslab, &p->mcslab_kept, p->mchunks, p->mpart, mtp, p->mhd, mtp, p->pr.b,
+                                                  p->mout))
+        return gpz_fail(GPZ_ERR_HIP, "%s: k_predict_missing_cov_pairs launch failed", who);
+    return 0;
+}
+
 // ---- what a kind of rows is made of ---------------------------------------------------------------------------------------------------
 // the kind's refusal of the model and, for a group, of its mask.  draws: the call has draws, which with Psi need the fused draws route
 int rows_check(const char *who, const gpz_predictor *p, const Rows &r, bool draws) {
-    if (r.group()) return predictor_missing_check(who, p, r.obs);   // (with Psi too: its product against W needs no fused draws route)
+    if (r.group())   // (with Psi too: its product against W needs no fused draws route)
+        return predictor_missing_check(who, p, r.obs, r.kind == ROWS_MISSING_COV);
     if (r.kind == ROWS_CLEAN) return 0;
     if (r.kind == ROWS_NOISY_COV) return predictor_noisy_cov_check(who, p);   // (its draws are a product on the T-GEMM: any route)
     if (int rc = predictor_noisy_check(who, p)) return rc;
@@ -626,6 +741,7 @@ int rows_check(const char *who, const gpz_predictor *p, const Rows &r, bool draw
 // What the call needs on the handle before its first tile.  pairs: it reads the kind's pair tables (the moments, gamma per draw, the
 // stack); the draws alone do not, and take the Psi slots or the group's tables without them.
 int rows_prepare(gpz_predictor *p, const char *who, const Rows &r, bool pairs) {
+    if (r.kind == ROWS_MISSING_COV) return predictor_missing_cov_prepare(p, who, r.obs, r.priors, pairs);
     if (r.group()) return predictor_missing_prepare(p, who, r.obs, r.priors, pairs, r.kind == ROWS_NOISY_MISSING);
     if (r.kind == ROWS_NOISY) return pairs ? predictor_noisy_prepare(p) : predictor_psi_slots(p);
     if (r.kind == ROWS_NOISY_COV) return predictor_noisy_cov_prepare(p, pairs);
@@ -638,6 +754,7 @@ int64_t rows_tile(const gpz_predictor *p, const Rows &r, int64_t T) { return r.g
 // the moments of one tile of nt rows in slot s -> rows_moments: [3k][nt] = mu | nu | beta for clean rows (and PHI when asked), else
 // [4k][nt] = mu | nu | beta | gamma
 int rows_moments_tile(gpz_predictor *p, const char *who, const Rows &r, int s, int nt, bool want_phi) {
+    if (r.kind == ROWS_MISSING_COV) return predictor_missing_cov_tile(p, who, s, nt, r.obs, true);
     if (r.group()) return predictor_missing_tile(p, who, s, nt, r.obs, true, r.psi() ? p->Psic[s] : nullptr);
     if (r.kind == ROWS_NOISY) return predictor_noisy_tile(p, who, s, nt);
     if (r.kind == ROWS_NOISY_COV) return predictor_noisy_cov_tile(p, who, s, nt);
@@ -651,7 +768,7 @@ const double *rows_moments(const gpz_predictor *p, const Rows &r, int s) {
 // the kind's tile for a call whose draws (or stack) would take *T rows, and for a group the output tile of its product PHI_missing W:
 // the tile route of the draws has one already, the fused route does not
 static int rows_fit_tile(gpz_predictor *p, const Rows &r, int ncol, int ldw, int64_t *T) {
-    *T = rows_tile(p, r, *T);
+    *T = rows_tile(p, r, *T);   // (ROWS_MISSING_COV is a group: its PHI_missing W takes the same output tile)
     if ((!r.group() && r.kind != ROWS_NOISY_COV) || ncol == 0) return 0;   // (a covariance kind with Psi: the output tile of E_x[PHI] W)
     if (r.kind == ROWS_NOISY_COV)   // (a call that reads the pairs too - gamma per draw, a stack with draws - has no PHI tile from rows_prepare)
         if (int rc = predictor_noisy_cov_phi_tile(p)) return rc;
@@ -670,8 +787,10 @@ int rows_draws_tile(gpz_predictor *p, const char *who, const Rows &r, int s, int
     if (r.kind == ROWS_CLEAN) return predictor_draws_tile(p, s, nt, ncol, ldw, after_moments && p->route == 1);
     if (r.kind == ROWS_NOISY) return predictor_draws_tile(p, s, nt, ncol, ldw, false, p->Psic[s]);
     if (r.kind == ROWS_NOISY_COV) return predictor_noisy_cov_draws_tile(p, who, s, nt, ncol, ldw);
-    if (!after_moments)
-        if (int rc = predictor_missing_tile(p, who, s, nt, r.obs, false, r.psi() ? p->Psic[s] : nullptr)) return rc;
+    if (!after_moments)   // (a covariance kind's PHI_missing lies in mNo as the diagonal kinds' does)
+        if (int rc = r.kind == ROWS_MISSING_COV ? predictor_missing_cov_tile(p, who, s, nt, r.obs, false)
+                                                : predictor_missing_tile(p, who, s, nt, r.obs, false, r.psi() ? p->Psic[s] : nullptr))
+            return rc;
     return predictor_missing_draws_tile(p, who, s, nt, ncol, ldw);
 }
 
@@ -929,6 +1048,10 @@ extern "C" int gpz_predictor_route(const gpz_predictor *p, char *buf, int cap) {
     }
     if (p->miss_used) {   // after the first call for a group of rows with missing inputs
         snprintf(tmp, sizeof tmp, "; missing: k_predict_missing_pairs (%d pair chunks), %lld-row tiles", p->mchunks, (long long)p->mtile);
+        r += tmp;
+    }
+    if (p->mcov_used) {   // after the first call for a group of rows with missing inputs on a covariance kind
+        snprintf(tmp, sizeof tmp, "; missing: k_predict_missing_cov_pairs (%d pair chunks)", p->mchunks);
         r += tmp;
     }
     if (p->gam[1].used) {   // after the first stack or gamma-per-draw call for such a group

@@ -50,6 +50,12 @@ static DevCall with_pattern(DevCall c, const double *priors, uint32_t obs_mask) 
     return c;
 }
 
+// such a group on a covariance kind
+static DevCall with_cov_pattern(DevCall c, const double *priors, uint32_t obs_mask) {
+    c.rows = Rows{ROWS_MISSING_COV, obs_mask, priors};
+    return c;
+}
+
 // a group whose rows have Psi too: with_psi first, then the pattern
 static DevCall with_noisy_pattern(DevCall c, const double *priors, uint32_t obs_mask) {
     c.rows = Rows{ROWS_NOISY_MISSING, obs_mask, priors};
@@ -205,7 +211,7 @@ static int predictor_run_dev(gpz_predictor *p, const char *who, DevCall &c, doub
     return rc;
 }
 
-// gpz_predictor_run_dev, _run_noisy_dev, _run_noisy_cov_dev, _run_missing_dev and _run_noisy_missing_dev
+// gpz_predictor_run_dev, _run_noisy_dev, _run_noisy_cov_dev, _run_missing_dev, _run_missing_cov_dev and _run_noisy_missing_dev
 static int run_dev_entry(const char *who, gpz_predictor *p, DevCall c, double *mu_d, double *sigma_d, double *nu_d, double *beta_d,
                          double *gamma_d, double *PHI_d) {
     if (int rc = predictor_check_call(who, p, c.x.ns)) return rc;
@@ -244,7 +250,7 @@ static int predictor_run_draws_dev(gpz_predictor *p, const char *who, DevCall &c
     return predictor_dev_sync(p, who, rc);
 }
 
-// gpz_predictor_draws_dev, _draws_noisy_dev, _draws_noisy_cov_dev, _draws_missing_dev, _draws_noisy_missing_dev and, with want_gamma, _draws_gamma_noisy_dev, _draws_gamma_noisy_cov_dev, _draws_gamma_missing_dev and _draws_gamma_noisy_missing_dev
+// gpz_predictor_draws_dev, _draws_noisy_dev, _draws_noisy_cov_dev, _draws_missing_dev, _draws_missing_cov_dev, _draws_noisy_missing_dev and, with want_gamma, _draws_gamma_noisy_dev, _draws_gamma_noisy_cov_dev, _draws_gamma_missing_dev and _draws_gamma_noisy_missing_dev
 static int draws_dev_entry(const char *who, gpz_predictor *p, DevCall c, int32_t ndraws, uint64_t seed, const double *Z, double *F_d,
                            double *Gam_d = nullptr, bool want_gamma = false) {
     if (int rc = predictor_check_call(who, p, c.x.ns)) return rc;
@@ -378,6 +384,23 @@ extern "C" int gpz_predictor_draws_missing_dev(gpz_predictor *p, const void *X_d
                                                double *F_d, void *stream) {
     const DevCall x = dev_call(X_d, x_type, ns, row_stride, col_stride, muX, sdX, muY, stream);
     return draws_dev_entry("gpz_predictor_draws_missing_dev", p, with_pattern(x, priors, obs_mask), ndraws, seed, Z, F_d);
+}
+
+extern "C" int gpz_predictor_run_missing_cov_dev(gpz_predictor *p, const void *X_d, int32_t x_type, int64_t ns, int64_t row_stride,
+                                                 int64_t col_stride, const double *muX, const double *sdX, const double *muY,
+                                                 const double *priors, uint32_t obs_mask, double *mu_d, double *sigma_d, double *nu_d,
+                                                 double *beta_d, double *gamma_d, void *stream) {
+    const DevCall x = dev_call(X_d, x_type, ns, row_stride, col_stride, muX, sdX, muY, stream);
+    return run_dev_entry("gpz_predictor_run_missing_cov_dev", p, with_cov_pattern(x, priors, obs_mask), mu_d, sigma_d, nu_d, beta_d,
+                         gamma_d, nullptr);
+}
+
+extern "C" int gpz_predictor_draws_missing_cov_dev(gpz_predictor *p, const void *X_d, int32_t x_type, int64_t ns, int64_t row_stride,
+                                                   int64_t col_stride, const double *muX, const double *sdX, const double *muY,
+                                                   const double *priors, uint32_t obs_mask, int32_t ndraws, uint64_t seed,
+                                                   const double *Z, double *F_d, void *stream) {
+    const DevCall x = dev_call(X_d, x_type, ns, row_stride, col_stride, muX, sdX, muY, stream);
+    return draws_dev_entry("gpz_predictor_draws_missing_cov_dev", p, with_cov_pattern(x, priors, obs_mask), ndraws, seed, Z, F_d);
 }
 
 extern "C" int gpz_predictor_run_noisy_missing_dev(gpz_predictor *p, const void *X_d, int32_t x_type, int64_t ns, int64_t row_stride,

@@ -2,7 +2,8 @@
 
 The methods ask one of four questions (run: the moments of ``predict``; draws; draws with gamma per draw; stack) of rows of one of four
 kinds (clean, noisy: with Psi, missing: one NaN-pattern group, noisy_missing: such a group with Psi); noisy_cov is the noisy kind of a
-covariance model (GC, VC), which has all four questions through methods of its own (``*_noisy_cov_dev``).
+covariance model (GC, VC), which has all four questions through methods of its own (``*_noisy_cov_dev``), and missing_cov the
+missing kind of such a model, which has the first two (``predict_missing_cov_dev``, ``draws_missing_cov_dev``).
 ``_DEV_ENTRIES`` names the device-resident entry of each pair, ``Predictor._dev_entry`` builds the arguments the entries of a pair
 share, and ``Predictor._dev_groups`` is the one loop over the groups of a call; the host methods choose between two entries each by
 whether Psi is there (``_HOST_ENTRIES``).  Everything numeric happens in the library; ``torch`` is only imported by the device methods.
@@ -28,6 +29,7 @@ _DEV_ENTRIES = {
     ("run", "clean"): "gpz_predictor_run_dev", ("run", "noisy"): "gpz_predictor_run_noisy_dev",
     ("run", "noisy_cov"): "gpz_predictor_run_noisy_cov_dev", ("draws", "noisy_cov"): "gpz_predictor_draws_noisy_cov_dev",
     ("run", "missing"): "gpz_predictor_run_missing_dev", ("run", "noisy_missing"): "gpz_predictor_run_noisy_missing_dev",
+    ("run", "missing_cov"): "gpz_predictor_run_missing_cov_dev", ("draws", "missing_cov"): "gpz_predictor_draws_missing_cov_dev",
     ("draws", "clean"): "gpz_predictor_draws_dev", ("draws", "noisy"): "gpz_predictor_draws_noisy_dev",
     ("draws", "missing"): "gpz_predictor_draws_missing_dev", ("draws", "noisy_missing"): "gpz_predictor_draws_noisy_missing_dev",
     ("draws_gamma", "noisy"): "gpz_predictor_draws_gamma_noisy_dev", ("draws_gamma", "missing"): "gpz_predictor_draws_gamma_missing_dev",
@@ -562,9 +564,11 @@ class Predictor:
         include/gpz_hip.h: the handle, the rows, Psi for rows with one, muX, sdX, sd2 for rows with Psi; then muY and, for a group with
         missing values, the priors and the mask of the observed dimensions.  ``run`` and ``draws`` take muY there, in front of the
         priors; ``stack`` takes the priors straight after sdX and muY at the end of its own arguments.  ``cov``: complete rows with Psi
-        of a covariance kind, whose entries take the noisy kind's arguments.  Returns (entry, arguments, row kind)."""
+        of a covariance kind, whose entries take the noisy kind's arguments, or a group with missing values of such a kind, whose
+        entries take the missing kind's.  Returns (entry, arguments, row kind)."""
         noisy = Pg is not None
-        kind = ("noisy_missing" if noisy else "missing") if code else (("noisy_cov" if cov else "noisy") if noisy else "clean")
+        kind = ("noisy_missing" if noisy else "missing_cov" if cov else "missing") if code else \
+            (("noisy_cov" if cov else "noisy") if noisy else "clean")
         lead = [call.h, *self._x_args(Xg)]
         if noisy:
             lead += self._psi_args(Pg, Xg.shape[0])
@@ -794,6 +798,64 @@ class Predictor:
         n_draws, z = self._check_draw_args(n_draws, seed, Z, 1)
         self._check_dev_device(X=X, selection=selection, Psi=Psi)
         return self._draws_dev(X, Psi, selection, False, n_draws, seed, z, bool(return_gamma), cov=True)
+
+    def _check_missing_cov(self, what, X, Psi, selection):
+        """The checks the two methods for rows with missing values of a covariance kind share, none of which touches a GPU: X by type,
+        dtype and shape, then where such rows go when this is not their route (Psi, a diagonal kind, a shape outside
+        predict_missing_cov_fits of k_predict_missing_cov.hip), then the priors.  Returns X as n x d."""
+        name = f"{what}_missing_cov_dev"
+        if isinstance(X, np.ndarray):
+            raise TypeError(f"{name} takes a torch tensor on cuda:{self.device}; a NumPy catalogue with missing values goes to "
+                            "Predictor.predict")
+        X = self._check_dev_rows(X, selection, what)
+        if Psi is not None:
+            raise ValueError(f"{name} does not take Psi: rows of a covariance kind with both input noise and missing values "
+                             "(predictNoisyMissing) go to Predictor.predict(X, Psi=Psi)")
+        if self._method[1] != "C":
+            raise ValueError(f"{name} is for the covariance kinds (GC, VC): a diagonal kind such as {self._method} goes to "
+                             f"{what}_dev(X, missing=True)")
+        if not (1 <= self._d <= 10 and 1 <= self._k <= 8 and 1 <= self._m <= 256):
+            raise ValueError(f"{name} needs a model inside predict_missing_cov_fits: GC or VC, d <= 10, k <= 8 and m <= 256; this one "
+                             f"is {self._method} with d = {self._d}, m = {self._m}, k = {self._k} (Predictor.predict takes rows with "
+                             "missing values for every shape)")
+        if self._priors.shape != (self._m,):
+            raise ValueError(f"the priors of the set must be {self._m} values, got {self._priors.size} (Predictor.predict reports "
+                             "the same for such rows)")
+        return X
+
+    def _check_missing_cov_device(self, X, selection):
+        """``_check_dev_device`` for those two methods, saying where a catalogue in host memory goes."""
+        try:
+            self._check_dev_device(X=X, selection=selection)
+        except ValueError as e:
+            raise ValueError(f"{e} (Predictor.predict takes a catalogue with missing values from host arrays)") from None
+
+    def predict_missing_cov_dev(self, X, selection=None, Psi=None):
+        """``predict_dev(X, missing=True)`` for a covariance kind (GC, VC; gpz_predictor_run_missing_cov_dev): X and ``selection`` as
+        for ``predict_dev``.  Returns mu, sigma, nu, beta_i, gamma as ``predict(X)`` does, as float64 tensors of shape (n, k) on the
+        device.  The rows are grouped by NaN pattern with torch on the device; complete rows go to gpz_predictor_run_dev and get
+        exactly what ``predict_dev`` gives them (gamma 0.0), every other group predictMissing of predictCov.m:134-232 on the handle's
+        tiles with the priors of the set (1 / m without any), gamma > 0 there.  A row's results do not depend on the tile size, the
+        row order or the other rows of the call.  It needs a model inside predict_missing_cov_fits (GC or VC, d <= 10, k <= 8,
+        m <= 256), else ValueError; ``Psi`` is refused (rows with both stay on ``Predictor.predict``, as host arrays and PHI do), and
+        a diagonal kind goes to ``predict_dev(X, missing=True)``.  Type, dtype and shape are checked first, the device last, all
+        before the GPU is touched."""
+        self._check_open()
+        X = self._check_missing_cov("predict", X, Psi, selection)
+        self._check_missing_cov_device(X, selection)
+        return self._moments_dev(X, None, selection, True, cov=True)
+
+    def draws_missing_cov_dev(self, X, n_draws, seed=0, Z=None, selection=None, Psi=None):
+        """``draws_dev(X, n_draws, missing=True)`` for a covariance kind (gpz_predictor_draws_missing_cov_dev): X and ``selection`` as
+        for ``predict_missing_cov_dev``, ``n_draws``, ``seed`` and ``Z`` as for ``draws_dev``.  Returns a float64 tensor of shape
+        (n_draws, n, k) on the device: for a row with missing values draws[s] is PHI_missing w_s + muY, ``predict_missing_cov_dev``'s
+        mu under weight draw s - the mean is linear in the weights, so this is exact.  One weight draw serves all rows of all groups;
+        complete rows get the bits of ``draws_dev`` on them alone."""
+        self._check_open()
+        X = self._check_missing_cov("draws", X, Psi, selection)
+        n_draws, z = self._check_draw_args(n_draws, seed, Z, 1)
+        self._check_missing_cov_device(X, selection)
+        return self._draws_dev(X, None, selection, True, n_draws, seed, z, cov=True)
 
     def stack_noisy_cov_dev(self, X, Psi, edges, n_draws=0, seed=0, Z=None, groups=None, n_groups=None, weights=None, selection=None):
         """``stack_noisy_dev`` for a covariance kind (GC, VC; gpz_predictor_stack_noisy_cov_dev): X, ``Psi`` and ``selection`` as for

@@ -453,6 +453,31 @@ int gpz_predictor_draws_missing_dev(gpz_predictor *p, const void *X_d, int32_t x
                                     int32_t ndraws, uint64_t seed, const double *Z /* host: NULL or m x ndraws x k */,
                                     double *F_d /* ns x k x ndraws, column-major */, void *stream);
 
+/* ---- rows with missing inputs on the predictor handle, covariance kinds ----------------------------------------------------------------
+ * predictMissing of GC and VC (predictCov.m:134-232) and the draws for ONE group of rows that share a NaN pattern, where
+ * predict_missing_cov_fits holds: GC or VC, 1 <= d <= 10, 1 <= k <= 8 and ceil16(m) <= 256, no Psi, device tensors.  Any other shape
+ * returns GPZ_ERR_UNSUPPORTED and names the condition (gpz_predict_missing takes every shape); a diagonal kind returns
+ * GPZ_ERR_UNSUPPORTED and names gpz_predictor_run_missing_dev.  The two entries take exactly the arguments of
+ * gpz_predictor_run_missing_dev / _draws_missing_dev, and priors, obs_mask, the scan of the pattern and every refusal are theirs.
+ * With no observed dimensions every density of predictMissing is exp(lnw - 1/2 |U (x_o - a)|^2) in the row's observed inputs x_o alone
+ * (a record of 1 + no + no (no + 1) / 2 doubles per centre and component, k_predict_missing_cov.hip), so a row costs
+ * m + m^2 + m^2 (m + 1) / 2 densities of no (no + 3) / 2 multiply-adds and one exp each.  Per pattern (kept until the pattern or the
+ * priors change): the m + m^2 records of Ex and PHI; per handle the model's Sigma_j and pair records (O(m^2 d^2) doubles), two
+ * [tile][mp] buffers with tile = min(tile_rows, 16384), predict_missing_cov_chunks(m) x 3k x tile partial sums and one slab of at most
+ * 64 MB through which the m^2 (m + 1) / 2 pair-component records pass, regenerated per tile (kept where they all fit).  All of it is
+ * allocated on the first such call, sized for the widest pattern, and does not grow with ns or the number of patterns; a handle that
+ * never sees such a call holds what it held.  A row's results have the same bits for any tile size, row order or split of the rows
+ * into calls.  gpz_predictor_route then ends in "; missing: k_predict_missing_cov_pairs (C pair chunks)". */
+int gpz_predictor_run_missing_cov_dev(gpz_predictor *p, const void *X_d, int32_t x_type, int64_t ns, int64_t row_stride,
+                                      int64_t col_stride, const double *muX, const double *sdX, const double *muY /* k or NULL */,
+                                      const double *priors /* m or NULL */, uint32_t obs_mask,
+                                      double *mu_d, double *sigma_d, double *nu_d, double *beta_d, double *gamma_d, void *stream);
+int gpz_predictor_draws_missing_cov_dev(gpz_predictor *p, const void *X_d, int32_t x_type, int64_t ns, int64_t row_stride,
+                                        int64_t col_stride, const double *muX, const double *sdX, const double *muY /* k or NULL */,
+                                        const double *priors /* m or NULL */, uint32_t obs_mask,
+                                        int32_t ndraws, uint64_t seed, const double *Z /* host: NULL or m x ndraws x k */,
+                                        double *F_d /* ns x k x ndraws, column-major */, void *stream);
+
 /* ---- stacked densities of rows with missing inputs, and gamma under every weight draw --------------------------------------------------
  * gpz_predictor_stack_dev for ONE group of rows that share a NaN pattern (non-detections), and gpz_predictor_draws_missing_dev with
  * gamma: the scope (predict_missing_fits), priors, obs_mask, the scan of the pattern and its refusals are those of the two entries
