@@ -34,12 +34,14 @@
 // The covariance kinds (GC, VC) have the same two questions where predict_noisy_cov_fits holds (1 <= d <= 10, k <= 8, m <= 256), for a
 // variance per input dimension: gpz_predictor_run_noisy_cov_dev runs k_predict_noisy_cov_small per tile (k_predict_noisy_cov.hip: a
 // packed Cholesky per row and record in registers) with the same finish, and gpz_predictor_draws_noisy_cov_dev E_x[PHI] of the tile
-// (k_predict_noisy_cov_phi) against W on k_tgemm.  Their record tables are written on the first such call (predictor_noisy_cov_prepare).
+// (k_predict_noisy_cov_phi) against W on k_tgemm.  Their record tables are written on the first such call (predictor_noisy_cov_prepare)
+// from Sigma_j, ln|Sigma_j| and the raw pair records of predictor_cov_model_tables, which the missing-input entries below keep on the handle.
 // gpz_predictor_stack_noisy_cov_dev / _draws_gamma_noisy_cov_dev answer the other two questions for them as the entries of the next
-// paragraph do for the diagonal kinds, with gamma under every draw from k_predict_noisy_cov_gamma.hip (the same f64 MFMA product with
-// that kernel's pair density) on the handle's packed pair records.
+// paragraph do for the diagonal kinds, with gamma under every draw from k_predict_noisy_cov_gamma.hip (the same frame,
+// k_predict_gamma_impl.h, with k_predict_noisy_cov_small's pair density) on the handle's packed pair records.
 // gpz_predictor_stack_noisy / _stack_noisy_dev stack rows with Psi of a diagonal kind: per tile predictNoisy, the draws with Psi, gamma under every draw
-// (k_predict_noisy_gamma.hip, an f64 MFMA product of pair densities and weight products), and k_stack_tile_w with a width per (column,
+// (k_predict_noisy_gamma.hip: predict_gamma_body of k_predict_gamma_impl.h, an f64 MFMA product of pair densities and weight products,
+// with k_predict_noisy_small's pair density), and k_stack_tile_w with a width per (column,
 // row); gpz_predictor_draws_gamma_noisy_dev returns that gamma beside the draws.  Their buffers are allocated on their first call.
 // gpz_predictor_stack_missing_dev stacks one group of rows with missing inputs in the same way, with gamma under every draw from
 // k_predict_missing_gamma.hip (the pair kernel's product chained into a second f64 MFMA against the weight products);
@@ -62,7 +64,8 @@
 // made of for each kind of rows (clean, with Psi, one NaN-pattern group: the rows_* functions), draws preparation and factorisation, the
 // stack's preparation and tile, the checks the entries share, route and info.  gpz_predictor_host.hip holds the host pipeline, its jobs
 // and the entries that take host arrays; gpz_predictor_dev.hip the device-resident entries.  Every entry is one check ladder and one
-// runner per question (moments, draws with or without gamma, stack) for every kind of rows.
+// runner per question (moments, draws with or without gamma, stack) for every kind of rows.  What two kinds of rows both need is
+// written once: predictor_phi_times_w (PHI W of the draws on k_tgemm), predictor_noisy_slots, predictor_cov_model_tables, PER_DRAW.
 #include <string>
 
 #include "gpz_predictor.h"
@@ -254,22 +257,29 @@ int predictor_psi_slots(gpz_predictor *p) {
     return 0;
 }
 
+// The 4k-row output slots and the chunk slab of predictNoisy's moments over nchunks pair chunks, each where it is missing
+static int predictor_noisy_slots(gpz_predictor *p, int nchunks) {
+    const size_t k = p->k, tp = (size_t)p->tile_pad;
+    int rc = 0;
+    for (int s = 0; s < 2; ++s)
+        if (!p->nout[s] && (rc = p->ar.alloc(&p->nout[s], 4 * k * tp))) return rc;
+    if (!p->npart && (rc = p->ar.alloc(&p->npart, (size_t)nchunks * 5 * k * tp))) return rc;
+    return 0;
+}
+
 // What the first predictNoisy call adds to the handle beyond that: the pair table [lnZ | c_ab | C_ab | coefficients] (the model's alone:
 // launch_pair_table needs only pr.P and pr.G for a diagonal kind), the 4k-row output slots and the chunk slab.  The draws read none of
 // these and do not come here.
 static int predictor_noisy_prepare(gpz_predictor *p) {
     if (p->noisy_ready) return 0;
-    const size_t m = p->m, k = p->k, tp = (size_t)p->tile_pad, npair = m * (m + 1) / 2;
+    const size_t m = p->m, npair = m * (m + 1) / 2;
     hipStream_t st = p->s_cmp;
-    auto &ar = p->ar;
     int rc = 0;
     if ((rc = predictor_psi_slots(p))) return rc;
     p->nchunks = predict_noisy_chunks(p->m, p->d, p->k);
     p->nrec = predict_noisy_rec(p->d, p->k);
-    if (!p->ptab && (rc = ar.alloc(&p->ptab, npair * p->nrec))) return rc;
-    for (int s = 0; s < 2; ++s)
-        if (!p->nout[s] && (rc = ar.alloc(&p->nout[s], 4 * k * tp))) return rc;
-    if (!p->npart && (rc = ar.alloc(&p->npart, (size_t)p->nchunks * 5 * k * tp))) return rc;
+    if (!p->ptab && (rc = p->ar.alloc(&p->ptab, npair * p->nrec))) return rc;
+    if ((rc = predictor_noisy_slots(p, p->nchunks))) return rc;
     launch_pair_table(st, GPZ_KIND_DIAG, p->m, p->d, p->de, p->pr.P, p->pr.G, nullptr, nullptr, p->ptab, p->nrec, nullptr);
     if (hipGetLastError() != hipSuccess ||
         launch_noisy_pair_coef(st, p->m, p->k, p->d, p->w_d, p->hetero ? p->pr.v : nullptr, p->iS_d, p->ptab, p->nrec))
@@ -298,27 +308,40 @@ static int predictor_noisy_cov_check(const char *who, const gpz_predictor *p) {
     return 0;
 }
 
-// The tables of the covariance kinds, the model's alone: Sigma_j and ln|Sigma_j| from Gamma_j (launch_gen_prep, as the evaluation has
-// them) and, with pairs, launch_pair_table's records, repacked by k_noisy_cov_records.  The d x d forms are temporaries of this call.
-static int predictor_noisy_cov_tables(gpz_predictor *p, bool pairs) {
-    const size_t m = p->m, d = p->d, npair = m * (m + 1) / 2, rawrec = 1 + d + d * d;
+// The model's own tables of a covariance kind, into the caller's blocks: Sigma_j (m d d doubles) and ln|Sigma_j| (m) from Gamma_j
+// (launch_gen_prep, as the evaluation has them) and, where raw is given, launch_pair_table's records [lnZ | c_ab | C_ab] (1 + d + d d a
+// pair).  inv(Sigma_j) and the pattern "every dimension observed" are temporaries of this call; it returns with the stream synchronised.
+static int predictor_cov_model_tables(gpz_predictor *p, double *Sig, double *lnS, double *raw) {
+    const size_t d = p->d, nsig = (size_t)p->m * d * d;
     hipStream_t st = p->s_cmp;
-    double *tmp = nullptr;
-    const size_t nsig = m * d * d, ntmp = 2 * nsig + m + (pairs ? npair * rawrec : 0) + (d + 7) / 8;
-    if (hipMalloc((void **)&tmp, ntmp * sizeof(double)) != hipSuccess) return gpz_fail(GPZ_ERR_ALLOC, "gpz_predictor: out of device memory");
-    double *Sig = tmp, *iSig = Sig + nsig, *lnS = iSig + nsig, *raw = lnS + m;
-    unsigned char *pat = (unsigned char *)(raw + (pairs ? npair * rawrec : 0));   // one pattern: every dimension observed
+    double *iSig = nullptr;
+    if (hipMalloc((void **)&iSig, (nsig + (d + 7) / 8) * sizeof(double)) != hipSuccess)
+        return gpz_fail(GPZ_ERR_ALLOC, "gpz_predictor: out of device memory");
+    unsigned char *pat = (unsigned char *)(iSig + nsig);
     int rc = 0;
     if (hipMemsetAsync(pat, 1, d, st) != hipSuccess) rc = gpz_fail(GPZ_ERR_HIP, "gpz_predictor: memset failed");
     if (!rc) {
         launch_gen_prep(st, p->pr.G, p->m, p->d, p->de, Sig, iSig, pat, 1, lnS, nullptr);
-        if (pairs) launch_pair_table(st, GPZ_KIND_COV, p->m, p->d, p->de, p->pr.P, p->pr.G, Sig, iSig, raw, (int)rawrec, nullptr);
-        if (hipGetLastError() != hipSuccess ||
-            launch_noisy_cov_records(st, p->m, p->d, p->de, p->k, p->pr.P, Sig, lnS, pairs ? raw : nullptr, p->w_d,
-                                     p->hetero ? p->pr.v : nullptr, p->iS_d, p->cbrec, pairs ? p->cprec : nullptr))
-            rc = gpz_fail(GPZ_ERR_HIP, "gpz_predictor: record table launch failed");
+        if (raw) launch_pair_table(st, GPZ_KIND_COV, p->m, p->d, p->de, p->pr.P, p->pr.G, Sig, iSig, raw, (int)(1 + d + d * d), nullptr);
+        if (hipGetLastError() != hipSuccess) rc = gpz_fail(GPZ_ERR_HIP, "gpz_predictor: table launch failed");
     }
     if (hipStreamSynchronize(st) != hipSuccess && !rc) rc = gpz_fail(GPZ_ERR_HIP, "gpz_predictor: sync failed");
+    (void)hipFree(iSig);
+    return rc;
+}
+
+// The record tables of rows with input noise on a covariance kind: predictor_cov_model_tables (with pairs, its pair records too) into
+// temporaries of this call, repacked by k_noisy_cov_records into the handle's basis records and, with pairs, pair records.
+static int predictor_noisy_cov_tables(gpz_predictor *p, bool pairs) {
+    const size_t m = p->m, d = p->d, nsig = m * d * d, nraw = pairs ? m * (m + 1) / 2 * (1 + d + d * d) : 0;
+    double *tmp = nullptr;
+    if (hipMalloc((void **)&tmp, (nsig + m + nraw) * sizeof(double)) != hipSuccess) return gpz_fail(GPZ_ERR_ALLOC, "gpz_predictor: out of device memory");
+    double *Sig = tmp, *lnS = Sig + nsig, *raw = pairs ? lnS + m : nullptr;
+    int rc = predictor_cov_model_tables(p, Sig, lnS, raw);
+    if (!rc && launch_noisy_cov_records(p->s_cmp, p->m, p->d, p->de, p->k, p->pr.P, Sig, lnS, raw, p->w_d, p->hetero ? p->pr.v : nullptr,
+                                        p->iS_d, p->cbrec, pairs ? p->cprec : nullptr))
+        rc = gpz_fail(GPZ_ERR_HIP, "gpz_predictor: record table launch failed");
+    if (hipStreamSynchronize(p->s_cmp) != hipSuccess && !rc) rc = gpz_fail(GPZ_ERR_HIP, "gpz_predictor: sync failed");
     (void)hipFree(tmp);
     return rc;
 }
@@ -338,7 +361,7 @@ static int predictor_noisy_cov_phi_tile(gpz_predictor *p) {
 // which a covariance kind has from nowhere else; without (the draws) the PHI tile, which a call with pairs and draws takes in
 // rows_fit_tile.
 static int predictor_noisy_cov_prepare(gpz_predictor *p, bool pairs) {
-    const size_t m = p->m, k = p->k, tp = (size_t)p->tile_pad, npair = m * (m + 1) / 2;
+    const size_t m = p->m, npair = m * (m + 1) / 2;
     auto &ar = p->ar;
     int rc = 0;
     if ((rc = predictor_psi_slots(p))) return rc;
@@ -349,9 +372,7 @@ static int predictor_noisy_cov_prepare(gpz_predictor *p, bool pairs) {
         if ((rc = predictor_noisy_cov_phi_tile(p))) return rc;
     } else {
         if (!p->cprec && (rc = ar.alloc(&p->cprec, npair * predict_noisy_cov_prec(p->d, p->k)))) return rc;
-        for (int s = 0; s < 2; ++s)
-            if (!p->nout[s] && (rc = ar.alloc(&p->nout[s], 4 * k * tp))) return rc;
-        if (!p->npart && (rc = ar.alloc(&p->npart, (size_t)p->cchunks * 5 * k * tp))) return rc;
+        if ((rc = predictor_noisy_slots(p, p->cchunks))) return rc;
     }
     if (basis || table)
         if ((rc = predictor_noisy_cov_tables(p, table))) return rc;
@@ -472,6 +493,15 @@ static int predictor_draws_prepare(gpz_predictor *p, int nd, unsigned long long 
     return 0;
 }
 
+// PHI of nt rows (np rows of mp doubles, the rows of k_tgemm's tile) against the handle's W on k_tgemm -> dout[s] ([ncol][nt], without
+// muY): T = PHI W with K = the rows of W (those >= m are zero) and ldw output columns, then transposed into the slot
+static int predictor_phi_times_w(gpz_predictor *p, const char *who, const double *Phi, long np, int s, int64_t nt, int ncol, int ldw) {
+    launch_tgemm(p->s_cmp, Phi, p->mp, p->Wd, ldw, p->Td, (int)np, ldw, nullptr, nullptr, p->m, 0, false, predictor_wrows(p), ldw);
+    launch_transpose_out(p->s_cmp, p->Td, ldw, nt, ncol, p->dout[s]);
+    if (hipGetLastError() != hipSuccess) return gpz_fail(GPZ_ERR_HIP, "%s: kernel launch failed", who);
+    return 0;
+}
+
 // the draws kernels of one tile of nt rows: Xc[s] -> dout[s] ([nd k][nt]).  phi_built: predictor_tile has just run on the same slot and
 // rows on the tile route, so p->Phi already holds this tile's PHI (the same launch_phi with the same arguments; launch_tgemm only reads it)
 // Psic: the tile's Psi slot for rows with input noise (fused route, diagonal kinds), else nullptr
@@ -491,14 +521,9 @@ static int predictor_draws_tile(gpz_predictor *p, int s, int64_t nt, int ncol, i
             return gpz_fail(GPZ_ERR_HIP, "gpz_predictor_draws: k_predict_draws launch failed");
         return 0;
     }
-    const long np = rup(nt, 1024);
     if (!phi_built && launch_phi(st, predictor_phi_args(p, s, (int)nt)))
         return gpz_fail(GPZ_ERR_UNSUPPORTED, "gpz_predictor_draws: PHI kernel not instantiated for d=%d", p->de);
-    // T = PHI W: K = mp (rows >= m of W are zero), ldw output columns
-    launch_tgemm(st, p->Phi, p->mp, p->Wd, ldw, p->Td, (int)np, ldw, nullptr, nullptr, m, 0, false, p->mp, ldw);
-    launch_transpose_out(st, p->Td, ldw, nt, ncol, p->dout[s]);
-    if (hipGetLastError() != hipSuccess) return gpz_fail(GPZ_ERR_HIP, "gpz_predictor_draws: kernel launch failed");
-    return 0;
+    return predictor_phi_times_w(p, "gpz_predictor_draws", p->Phi, rup(nt, 1024), s, nt, ncol, ldw);   // (K = mp on this route)
 }
 
 // ---- rows with missing inputs on the handle -----------------------------------------------------------------------------------------
@@ -607,11 +632,7 @@ static int predictor_missing_tile(gpz_predictor *p, const char *who, int s, int 
 // the draws of one tile of the group behind predictor_missing_tile: PHI_missing (mNo) against the handle's W on k_tgemm -> dout[s]
 // ([ncol][nt], without muY)
 static int predictor_missing_draws_tile(gpz_predictor *p, const char *who, int s, int nt, int ncol, int ldw) {
-    launch_tgemm(p->s_cmp, p->mNo, p->mp, p->Wd, ldw, p->Td, rup(nt, 128), ldw, nullptr, nullptr, p->m, 0, false,
-                 predictor_wrows(p), ldw);
-    launch_transpose_out(p->s_cmp, p->Td, ldw, nt, ncol, p->dout[s]);
-    if (hipGetLastError() != hipSuccess) return gpz_fail(GPZ_ERR_HIP, "%s: kernel launch failed", who);
-    return 0;
+    return predictor_phi_times_w(p, who, p->mNo, rup(nt, 128), s, nt, ncol, ldw);
 }
 
 // the draws of one tile of nt rows with Psi, covariance kinds: E_x[PHI] (k_predict_noisy_cov_phi, rows of the product padded with
@@ -621,36 +642,21 @@ static int predictor_noisy_cov_draws_tile(gpz_predictor *p, const char *who, int
     if (launch_predict_noisy_cov_phi(p->s_cmp, p->d, p->mid == 4, p->Xc[s], p->Psic[s], p->tile_pad, nt, np, p->m, p->mp, p->k, p->cbrec,
                                      p->cchunks, p->cphi))
         return gpz_fail(GPZ_ERR_HIP, "%s: k_predict_noisy_cov_phi launch failed", who);
-    launch_tgemm(p->s_cmp, p->cphi, p->mp, p->Wd, ldw, p->Td, np, ldw, nullptr, nullptr, p->m, 0, false, predictor_wrows(p), ldw);
-    launch_transpose_out(p->s_cmp, p->Td, ldw, nt, ncol, p->dout[s]);
-    if (hipGetLastError() != hipSuccess) return gpz_fail(GPZ_ERR_HIP, "%s: kernel launch failed", who);
-    return 0;
+    return predictor_phi_times_w(p, who, p->cphi, np, s, nt, ncol, ldw);
 }
 
 // ---- rows with missing inputs on the handle, covariance kinds -------------------------------------------------------------------------
-// The model's own tables, each where it is missing: Sigma_j and ln|Sigma_j| (launch_gen_prep) and, with pairs, launch_pair_table's
-// records [lnZ | c_ab | C_ab].  inv(Sigma_j) is a temporary of the call that makes the pair records.
+// The model's own tables on the handle, each where it is missing: Sigma_j and ln|Sigma_j| and, with pairs, the raw pair records
+// (predictor_cov_model_tables)
 static int predictor_missing_cov_model(gpz_predictor *p, bool pairs) {
-    const size_t m = p->m, d = p->d, npair = m * (m + 1) / 2, nsig = m * d * d, rawrec = 1 + d + d * d;
-    hipStream_t st = p->s_cmp;
+    const size_t m = p->m, d = p->d;
     const bool sig = !p->mcSig, raw = pairs && !p->mcraw;
     if (!sig && !raw) return 0;
     int rc = 0;
-    double *Sig = p->mcSig, *lnS = p->mclnS, *rawt = nullptr, *tmp = nullptr;   // (where only raw is missing they are written again: the same values)
-    if (sig && ((rc = p->ar.alloc(&Sig, nsig)) || (rc = p->ar.alloc(&lnS, m)))) return rc;
-    if (raw && (rc = p->ar.alloc(&rawt, npair * rawrec))) return rc;
-    if (hipMalloc((void **)&tmp, (nsig + (d + 7) / 8) * sizeof(double)) != hipSuccess)
-        return gpz_fail(GPZ_ERR_ALLOC, "gpz_predictor: out of device memory");
-    unsigned char *pat = (unsigned char *)(tmp + nsig);   // one pattern: every dimension observed
-    if (hipMemsetAsync(pat, 1, d, st) != hipSuccess) rc = gpz_fail(GPZ_ERR_HIP, "gpz_predictor: memset failed");
-    if (!rc) {
-        launch_gen_prep(st, p->pr.G, p->m, p->d, p->de, Sig, tmp, pat, 1, lnS, nullptr);
-        if (raw) launch_pair_table(st, GPZ_KIND_COV, p->m, p->d, p->de, p->pr.P, p->pr.G, Sig, tmp, rawt, (int)rawrec, nullptr);
-        if (hipGetLastError() != hipSuccess) rc = gpz_fail(GPZ_ERR_HIP, "gpz_predictor: table launch failed");
-    }
-    if (hipStreamSynchronize(st) != hipSuccess && !rc) rc = gpz_fail(GPZ_ERR_HIP, "gpz_predictor: sync failed");
-    (void)hipFree(tmp);
-    if (rc) return rc;
+    double *Sig = p->mcSig, *lnS = p->mclnS, *rawt = nullptr;   // (where only raw is missing they are written again: the same values)
+    if (sig && ((rc = p->ar.alloc(&Sig, m * d * d)) || (rc = p->ar.alloc(&lnS, m)))) return rc;
+    if (raw && (rc = p->ar.alloc(&rawt, m * (m + 1) / 2 * (1 + d + d * d)))) return rc;
+    if ((rc = predictor_cov_model_tables(p, Sig, lnS, rawt))) return rc;
     if (sig) { p->mcSig = Sig; p->mclnS = lnS; }
     if (raw) p->mcraw = rawt;
     return 0;
@@ -1017,6 +1023,18 @@ extern "C" int gpz_predictor_route(const gpz_predictor *p, char *buf, int cap) {
     else
         snprintf(tmp, sizeof tmp, "tiles: k_phi + k_tgemm, %lld-row tiles", (long long)p->tile_rows);
     std::string r = tmp;
+    // after the first stack or gamma-per-draw call for a kind of rows (gam[kind - 1]): its kernel and chunks (a group's: mchunks)
+    static const struct { const char *fmt; bool group; } PER_DRAW[4] = {
+        {"; noise per draw: k_predict_noisy_gamma (%d pair chunks)", false},
+        {"; missing per draw: k_predict_missing_gamma (%d pair chunks)", true},
+        {"; noisy missing per draw: k_predict_noisy_missing_gamma (%d pair chunks)", true},
+        {"; noise per draw: k_predict_noisy_cov_gamma (%d pair chunks)", false}};
+    auto per_draw = [&](int i) {
+        if (!p->gam[i].used) return;
+        snprintf(tmp, sizeof tmp, PER_DRAW[i].fmt, PER_DRAW[i].group ? p->mchunks : p->gchunks);
+        r += tmp;
+        if (p->gam[i].s2_d) r += " + k_stack_tile_w";   // the widths exist: a stack call was among them
+    };
     if (p->droute >= 0) {   // after a draws call: its route and each output's factor
         snprintf(tmp, sizeof tmp, "; draws: %s, %lld-row tiles, factors:", p->droute == 0 ? "fused k_predict_draws" : "tiles k_phi + k_tgemm",
                  (long long)p->dtile);
@@ -1036,16 +1054,8 @@ extern "C" int gpz_predictor_route(const gpz_predictor *p, char *buf, int cap) {
         snprintf(tmp, sizeof tmp, "; noise: k_predict_noisy_cov_small (%d pair chunks)", p->cchunks);
         r += tmp;
     }
-    if (p->gam[3].used) {   // after the first stack or gamma-per-draw call for such rows
-        snprintf(tmp, sizeof tmp, "; noise per draw: k_predict_noisy_cov_gamma (%d pair chunks)", p->gchunks);
-        r += tmp;
-        if (p->gam[3].s2_d) r += " + k_stack_tile_w";   // the widths exist: a stack call was among them
-    }
-    if (p->gam[0].used) {   // after the first stack or gamma-per-draw call for rows with input noise
-        snprintf(tmp, sizeof tmp, "; noise per draw: k_predict_noisy_gamma (%d pair chunks)", p->gchunks);
-        r += tmp;
-        if (p->gam[0].s2_d) r += " + k_stack_tile_w";   // the widths exist: a stack call was among them
-    }
+    per_draw(3);
+    per_draw(0);
     if (p->miss_used) {   // after the first call for a group of rows with missing inputs
         snprintf(tmp, sizeof tmp, "; missing: k_predict_missing_pairs (%d pair chunks), %lld-row tiles", p->mchunks, (long long)p->mtile);
         r += tmp;
@@ -1054,20 +1064,12 @@ extern "C" int gpz_predictor_route(const gpz_predictor *p, char *buf, int cap) {
         snprintf(tmp, sizeof tmp, "; missing: k_predict_missing_cov_pairs (%d pair chunks)", p->mchunks);
         r += tmp;
     }
-    if (p->gam[1].used) {   // after the first stack or gamma-per-draw call for such a group
-        snprintf(tmp, sizeof tmp, "; missing per draw: k_predict_missing_gamma (%d pair chunks)", p->mchunks);
-        r += tmp;
-        if (p->gam[1].s2_d) r += " + k_stack_tile_w";   // the widths exist: a stack call was among them
-    }
+    per_draw(1);
     if (p->nm_used) {   // after the first call for a group of rows with input noise and missing inputs
         snprintf(tmp, sizeof tmp, "; noisy missing: k_predict_noisy_missing_pairs (%d pair chunks)", p->mchunks);
         r += tmp;
     }
-    if (p->gam[2].used) {   // after the first stack or gamma-per-draw call for such a group
-        snprintf(tmp, sizeof tmp, "; noisy missing per draw: k_predict_noisy_missing_gamma (%d pair chunks)", p->mchunks);
-        r += tmp;
-        if (p->gam[2].s2_d) r += " + k_stack_tile_w";   // the widths exist: a stack call was among them
-    }
+    per_draw(2);
     snprintf(buf, (size_t)cap, "%s", r.c_str());
     return (int)r.size();
 }

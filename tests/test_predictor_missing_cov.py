@@ -363,3 +363,38 @@ def test_memory_is_added_once_and_never_grows_with_rows_or_patterns():
         assert p.info[1] == first                                            # eight patterns: the same bytes
         q.predict_dev(X); q.draws_dev(X[:50_000], nd)
         assert q.info[1] == held                                             # ... holds what it held
+
+
+# ---- 10. rows with input noise and rows with missing inputs on one handle ----------------------------------------------------------------------
+def test_noisy_and_missing_rows_share_a_handle_in_either_order():
+    """VC, m = 20, d = 3, k = 2, 300 rows on 256-row tiles.  predict_noisy_cov_dev and predict_missing_cov_dev take the model's Sigma_j,
+    ln|Sigma_j| and raw pair records from one helper, the first into temporaries of the call, the second into the handle: in either
+    order each call returns the bits of the same call on a fresh handle, and the handle grows by what the two calls add separately
+    (counted from a handle that has made a device call, predict_dev, as both do for their complete rows or their staging)."""
+    m, d, k, n = 20, 3, 2, 300
+    model = model_with_priors("VC", m, d, k, True, seed=4242)
+    X = catalogue(model, n, seed=3)
+    Xd, Xm = dev(X), dev(knock_out(X, seed=4, cols=((0, 0.3), (2, 0.2))))
+    Psi = dev(np.random.default_rng(5).gamma(1.0, 0.05, (n, d)))
+    calls = {"noisy": lambda p: p.predict_noisy_cov_dev(Xd, Psi), "missing": lambda p: p.predict_missing_cov_dev(Xm)}
+
+    def fresh():
+        p = gpz_amd.Predictor(model, tile_rows=256)
+        p.predict_dev(Xd)
+        return p
+
+    alone, added = {}, {}
+    for name, call in calls.items():
+        with fresh() as p:
+            base = p.info[1]
+            alone[name] = call(p)
+            added[name] = p.info[1] - base
+            assert added[name] > 0, name
+    for order in (("noisy", "missing"), ("missing", "noisy")):
+        with fresh() as p:
+            base = p.info[1]
+            for name in order:
+                same(calls[name](p), alone[name], (order, name))
+            print(order, p.info[1] - base, added)
+            assert p.info[1] - base == added["noisy"] + added["missing"], order
+            assert "k_predict_noisy_cov_small" in p.route and "k_predict_missing_cov_pairs" in p.route, p.route

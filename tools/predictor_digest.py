@@ -3,7 +3,9 @@
 profiles/r14_predictor_row_kinds.txt: before and after clean, noisy and missing rows were folded onto one set of runners and the unit
 was cut into gpz_predictor.hip, gpz_predictor_host.hip and gpz_predictor_dev.hip behind gpz_predictor.h;
 profiles/r18_predict_group_kernels.txt: before and after the four pair kernels of a group of rows with missing inputs were folded onto
-the one body of k_predict_group_impl.h).
+the one body of k_predict_group_impl.h;
+profiles/r20_predict_gamma_fold.txt: before and after k_predict_noisy_gamma and k_predict_noisy_cov_gamma were folded onto the one body
+of k_predict_gamma_impl.h and the host's covariance-kind model tables onto one helper).
 
     python tools/predictor_digest.py > digest.txt        # in each tree, on the same machine; then diff the two files
 
@@ -15,6 +17,12 @@ rows with four NaN patterns knocked out, predict_dev, draws_dev (with and withou
 and the same with Psi (predict_noisy_missing_dev, draws_noisy_missing_dev with and without gamma, stack_noisy_missing_dev plain, with
 draws and groups, and with Z and a selection); a third handle meets the missing stack first, then the noisy one, then predict.  One
 more VD model has m = 128 and k = 3: predict_missing_chunks is 8 there and the KM = 8 pair kernels walk more than one group per chunk.
+Then the entries of the covariance kinds and the gamma kernels at their edges (run_edges): GC and VC at d = 1, 7, 8, 9, 10 and VD at
+d = 1, 20, each with m = 20, k = 1 (one gamma chunk; 1, 64 and 129 or, from d = 8 on, 65 columns: one more than a pass holds) and
+m = 91, k = 3 (two gamma chunks, the last stage partial; 3 and 129 or 66 columns), 80 rows on 128-row tiles (a full workgroup and 16 rows)
+and one call over two tiles: predict_noisy_cov_dev, draws_noisy_cov_dev with and without gamma, stack_noisy_cov_dev,
+predict_missing_cov_dev and draws_missing_cov_dev (VD: gamma per draw and stack_noisy_dev), and two more handles that meet a call for
+rows with missing inputs first and one for rows with input noise second, and the other way round.
 After each call one line: the call, the digest of each array it returned, and the handle's route and info."""
 import hashlib
 import os
@@ -134,12 +142,64 @@ def run(method, k, force, M=M):
             report(f"{tag} third handle predict", p, p.predict(X))
 
 
+def run_edges(method, d, m, k):
+    tag = f"{method} d={d} m={m} k={k}"
+    cov = method != "VD"
+    model = synth_model(method, m, d, k, True, seed=1000 * d + 10 * m + k + (method == "GC"))
+    rng = np.random.default_rng(d + m)
+    X = catalogue(model, 200, seed=d)
+    Xm = X.copy()
+    Xm[0::3, 0] = np.nan
+    Xm[1::3, d - 1] = np.nan
+    Xd, Xmd, Pd = (torch.from_numpy(a).to(DEV) for a in (X, Xm, rng.gamma(1.0, 0.05, (200, d))))
+    edges = np.linspace(-3.0, 3.0, 13)
+    over = 65 if cov and d >= 8 else 129                                 # one column more than a pass of the gamma kernel holds
+    draws = (1, 64, over) if k == 1 else (1, -(-over // k))
+
+    def noisy(p, rows, nd):
+        x, psi = Xd[:rows], Pd[:rows]
+        if cov:
+            report(f"{tag} draws_noisy_cov_dev {nd} x {rows}", p, p.draws_noisy_cov_dev(x, psi, nd, seed=11))
+            report(f"{tag} draws_noisy_cov_dev gamma {nd} x {rows}", p, p.draws_noisy_cov_dev(x, psi, nd, seed=11, return_gamma=True))
+            report(f"{tag} stack_noisy_cov_dev {nd} x {rows}", p, tuple(p.stack_noisy_cov_dev(x, psi, edges, n_draws=nd, seed=11)))
+        else:
+            report(f"{tag} draws_dev psi gamma {nd} x {rows}", p, p.draws_dev(x, nd, seed=11, Psi=psi, return_gamma=True))
+            report(f"{tag} stack_noisy_dev {nd} x {rows}", p, tuple(p.stack_noisy_dev(x, psi, edges, n_draws=nd, seed=11)))
+
+    def missing(p, rows):
+        report(f"{tag} predict_missing_cov_dev x {rows}", p, p.predict_missing_cov_dev(Xmd[:rows]))
+        report(f"{tag} draws_missing_cov_dev x {rows}", p, p.draws_missing_cov_dev(Xmd[:rows], 3, seed=11))
+
+    with gpz_amd.Predictor(model, tile_rows=128) as p:
+        if cov:
+            report(f"{tag} predict_noisy_cov_dev", p, p.predict_noisy_cov_dev(Xd[:80], Pd[:80]))
+        for nd in draws:
+            noisy(p, 80, nd)
+        noisy(p, 200, draws[-1])                                         # two tiles
+        if cov:
+            missing(p, 80)
+            missing(p, 200)
+    if cov:
+        with gpz_amd.Predictor(model, tile_rows=128) as p:               # rows with missing inputs first, rows with input noise second
+            missing(p, 80)
+            report(f"{tag} missing first, predict_noisy_cov_dev", p, p.predict_noisy_cov_dev(Xd[:80], Pd[:80]))
+            noisy(p, 80, draws[0])
+        with gpz_amd.Predictor(model, tile_rows=128) as p:               # and the other way round, the draws (no pairs) in front
+            report(f"{tag} noisy first, draws_noisy_cov_dev", p, p.draws_noisy_cov_dev(Xd[:80], Pd[:80], 2, seed=11))
+            report(f"{tag} noisy first, predict_noisy_cov_dev", p, p.predict_noisy_cov_dev(Xd[:80], Pd[:80]))
+            missing(p, 80)
+
+
 def main():
     for method in ("VD", "VC"):
         for k in (1, 3):
             for force in (False, True):
                 run(method, k, force)
     run("VD", 3, False, M=128)
+    for method, widths in (("GC", (1, 7, 8, 9, 10)), ("VC", (1, 7, 8, 9, 10)), ("VD", (1, 20))):
+        for d in widths:
+            run_edges(method, d, 20, 1)
+            run_edges(method, d, 91, 3)
 
 
 if __name__ == "__main__":
