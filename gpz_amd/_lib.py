@@ -74,6 +74,7 @@ SYMBOLS = {
     "gpz_predict_missing": (C.c_int, [C.POINTER(gpz_desc), c_double_p, c_double_p, c_double_p, c_double_p, c_double_p,
                                       C.c_int64, c_double_p, C.c_int32, c_double_p, c_double_p, c_double_p, c_double_p,
                                       c_double_p]),
+    "gpz_predict_last_route": (C.c_int, [C.c_char_p, C.c_int64]),
     "gpz_predictor_create": (C.c_int, [C.POINTER(gpz_desc), c_double_p, c_double_p, c_double_p, C.c_int64, C.c_int32,
                                        C.POINTER(C.c_void_p)]),
     "gpz_predictor_destroy": (None, [C.c_void_p]),

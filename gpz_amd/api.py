@@ -638,6 +638,14 @@ def predict(X, model, whichSet="best", Psi=None, selection=None, device=0, n_gpu
     return mu, sigma, nu, beta_i, gamma, PHI, w, iS
 
 
+def predict_last_route():
+    """What the last one-shot prediction of this thread ran (gpz_predict_last_route), as one line of text; after ``predict`` on rows
+    of several NaN patterns it describes the last group."""
+    buf = C.create_string_buffer(1024)
+    _lib.load().gpz_predict_last_route(buf, 1024)
+    return buf.value.decode()
+
+
 def getPrior(X, Psi, theta, model, selection=None, device=0, return_iterations=False):
     """prior = getPrior(X,Sx,theta,model,set)   (getPrior.m:1); X / Psi already normalised as train.m passes them."""
     lib = _lib.load()

@@ -729,6 +729,10 @@ struct NormArgs {
 };
 void launch_phi_norm(hipStream_t st, const NormArgs &a);
 
+// gpz_predict_last_route (gpz_predict.hip): what the one-shot predict entries and the launchers that choose a kernel family note down,
+// host side and per thread.  A launcher called outside such an entry notes nothing (predict_route_add is a no-op then).
+void predict_route_add(const char *fmt, ...) __attribute__((format(printf, 1, 2)));
+
 // misc
 void launch_dxy(hipStream_t st, const double *X, long nx, const double *Y, long ny, int d, double *D);
 void launch_transpose_out(hipStream_t st, const double *src, int ld, long n, int m, double *dst /* n x m col-major */,

@@ -2,6 +2,33 @@
 // _missing, gpz_prior, gpz_inv_logdet, gpz_dxy, gpz_nan_groups (predict.m, predictDiag.m, predictCov.m, getPrior.m, inv_logdet.m, Dxy.m).
 #include "gpz_ctx.h"
 
+// ---- gpz_predict_last_route: which kernel family and which host-side counts the last gpz_predict_full / _noisy / _missing of this
+// thread ran.  The entry opens a RouteScope (the text starts anew), it and the launchers that choose a family add to it, and the
+// text stays readable after the entry has returned.  Host bookkeeping only: no kernel sees it.
+static thread_local std::string route_text;
+static thread_local bool route_open = false;
+void predict_route_add(const char *fmt, ...) {
+    if (!route_open || route_text.size() > 900) return;
+    char buf[256];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof buf, fmt, ap);
+    va_end(ap);
+    if (!route_text.empty()) route_text += ' ';
+    route_text += buf;
+}
+namespace {
+struct RouteScope {
+    explicit RouteScope(const char *entry) { route_text = entry; route_open = true; }
+    ~RouteScope() { route_open = false; }
+};
+}   // namespace
+extern "C" int gpz_predict_last_route(char *buf, int64_t cap) {
+    if (!buf || cap <= 0) return gpz_fail(GPZ_ERR_ARG, "gpz_predict_last_route: null argument");
+    snprintf(buf, (size_t)cap, "%s", route_text.c_str());
+    return (int)route_text.size();
+}
+
 namespace gpzi {
 // ---- stand-alone entry points --------------------------------------------------------------------
 // A throw-away context without targets: parameters + PHI on ns rows (all rows selected).
@@ -85,9 +112,11 @@ extern "C" int gpz_predict_full(const gpz_desc *desc, const double *theta, const
     gpz_ctx *c = nullptr;
     if (has_nan(Xs, ns * (int64_t)desc->d))
         return gpz_fail(GPZ_ERR_UNSUPPORTED, "gpz_predict_full: the rows have missing values (NaN): group them by pattern and call gpz_predict_missing (predict.m:45-69)");
+    RouteScope route("predict_full:");
     if (int e = make_eval_ctx(desc, Xs, ns, nullptr, 0, &c)) return e;
     gpz_opts_scope opts_scope(&c->opt);
     const size_t m = c->m, mp = c->mp, np = c->tr.n_pad, k = c->k;
+    predict_route_add("tgemm mp=%zu n_pad=%zu", mp, np);
     int rc = 0;
     double *T = nullptr, *Bext = nullptr, *wd = nullptr, *Sd = nullptr, *nud = nullptr, *dgi = nullptr, *tmp = nullptr;
     if (!rc) rc = c->ar.alloc(&T, np * mp);
@@ -154,6 +183,7 @@ extern "C" int gpz_predict_noisy(const gpz_desc *desc, const double *theta, cons
     if (has_nan(Xs, ns * (int64_t)desc->d))
         return gpz_fail(GPZ_ERR_UNSUPPORTED, "gpz_predict_noisy: the rows have missing values (NaN): group them by pattern and call gpz_predict_missing (predict.m:45-69)");
     gpz_ctx *c = nullptr;
+    RouteScope route("predict_noisy:");
     if (int e = make_eval_ctx(desc, Xs, ns, Psi, psi_kind, &c)) return e;
     gpz_opts_scope opts_scope(&c->opt);
     const size_t m = c->m, np = c->tr.n_pad, k = c->k;
@@ -170,6 +200,7 @@ extern "C" int gpz_predict_noisy(const gpz_desc *desc, const double *theta, cons
     if (nchunk < 1) nchunk = 1;
     const long ppc = (npair + nchunk - 1) / nchunk;
     nchunk = (int)((npair + ppc - 1) / ppc);
+    predict_route_add("nchunk=%d ppc=%ld n_pad=%zu", nchunk, ppc, np);
     if (!rc) rc = c->ar.alloc(&wd, m * k);
     if (!rc) rc = c->ar.alloc(&iSd, m * m * k);
     if (!rc) rc = c->ar.alloc(&phiw, np * k);
@@ -318,6 +349,7 @@ static int predict_missing_cov(const gpz_desc *desc, const std::vector<unsigned 
     int nchunk = (int)(npairs < want ? npairs : want);
     const long ppc = (npairs + nchunk - 1) / nchunk;
     nchunk = (int)((npairs + ppc - 1) / ppc);
+    predict_route_add("nchunk=%d ppc=%ld rows_blk=%d blocks=%d n_pad=%zu", nchunk, ppc, rows_blk, (n + rows_blk - 1) / rows_blk, np);
     double *wd = nullptr, *iSd = nullptr, *prd = nullptr, *rec = nullptr, *tab = nullptr, *Ex = nullptr, *Pio = nullptr,
            *Xhat = nullptr, *Phat = nullptr, *part = nullptr, *sums = nullptr, *phiw = nullptr, *outb = nullptr, *tmp = nullptr;
     if (!rc) rc = c->ar.alloc(&wd, m * k);
@@ -434,6 +466,7 @@ static int predict_missing_diag(const gpz_desc *desc, OBS obs, const std::vector
     int cw = 32;   // (8 until round 3: the 128-row GEMM of a small group ran 32 workgroups per launch)
     while (cw > 1 && (double)np * (double)(cw * mp) * 8.0 > 2e9) cw >>= 1;
     const size_t width = (size_t)rup((long)cw * (long)mp, 64);   // whole 64-pair blocks of the pair-table kernel
+    predict_route_add("%s cw=%d width=%zu n_pad=%zu", std::is_same<OBS, ObsFlags>::value ? "pm_diag_flags" : "pm_diag", cw, width, np);
     if (!rc) rc = c->ar.alloc(&No, np * mp);
     if (!rc) rc = c->ar.alloc(&Pio, np * mp);
     if (!rc) rc = c->ar.alloc(&B, mp * width);
@@ -469,14 +502,17 @@ static int predict_missing_diag(const gpz_desc *desc, OBS obs, const std::vector
                           c->lnbeta, nullptr, phiw);
         launch_zero(c->st, sums_s, (size_t)nsp * 3 * k * np);
         const long npairs = (long)m * (m + 1) / 2;
+        int passes = 0, last_npq = 0;                                                        // (for the route record)
         for (long q0 = 0; q0 < npairs; q0 += (long)width) {                                  // predictDiag.m:170-200
             const int npq = (int)((npairs - q0 < (long)width) ? npairs - q0 : (long)width);
+            ++passes; last_npq = npq;
             launch_pm_pairtab(c->st, q0, npairs, c->m, (int)mp, (int)width, d, de, c->k, obs, c->has_psi ? 1 : 0, c->pr.P,
                               c->pr.G, wd, c->hetero ? c->pr.v : nullptr, iSd, B, rec, nrec);
             launch_tgemm(c->st, Pio, (int)mp, B, (int)width, T, npg, (int)width, nullptr, nullptr, c->m, -1, false, (int)mp,
                          (int)width);
             launch_pm_accum(c->st, c->tr.Xr, Psir, de, n, (long)np, (int)width, d, c->k, obs, npq, T, rec, nrec, sums_s, nsp);
         }
+        predict_route_add("passes=%d last=%d npg=%d splits=%d", passes, last_npq, npg, nsp);
         launch_slab_sum(c->st, sums_s, nsp, 3 * k * np, sums);
         launch_predict_noisy_final(c->st, sums, (long)np, n, c->k, phiw, c->lnbeta, c->pr.b, outb, outb + k * np,
                                    outb + 2 * k * np);
@@ -512,6 +548,7 @@ extern "C" int gpz_predict_missing(const gpz_desc *desc, const double *theta, co
                                    double *mu, double *nu, double *beta_i, double *gamma, double *PHI) {
     if (!desc || !theta || !w || !iSigma_w || !priors || !Xs || ns < 1 || !mu || !nu || !beta_i || !gamma)
         return gpz_fail(GPZ_ERR_ARG, "gpz_predict_missing: null argument");
+    RouteScope route("predict_missing:");
     const int d = desc->d;
     const bool covk = method_id_of(desc->method) >= 4;
     // any d (the reference is generic in it): the tuned routes cover d <= 64 (GC/VC) and d <= GPZ_PM_MAXD_DIAG (GL/VL/GD/VD); wider

@@ -158,6 +158,7 @@ int launch_cpsi4_predict_noisy(hipStream_t st, int n, long ldx, int m, int d, in
                                long pairs_per_chunk, double *part, bool shared) {
     if (!cpsi4_available(d) || k > 8) return -1;
     if (n <= 0) return 0;
+    predict_route_add("cpsi4<%d,%d> shared=%d", (d + 3) / 4, k == 1 ? 1 : 8, shared ? 1 : 0);
 #define PN_CASE(ND)                                                                                                           \
     do {                                                                                                                      \
         if (k == 1 && shared)                                                                                                 \

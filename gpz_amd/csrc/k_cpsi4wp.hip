@@ -7,6 +7,7 @@ int launch_cpsi4w_predict_noisy(hipStream_t st, int n, long ldx, int m, int d, i
                                 long pairs_per_chunk, double *part, bool shared) {
     if (!cpsi4w_available(d) || k != 1) return -1;
     if (n <= 0) return 0;
+    predict_route_add("cpsi4w<%d,1> shared=%d", (d + 3) / 4, shared ? 1 : 0);
 #define PN_CASE(ND)                                                                                                           \
     do {                                                                                                                      \
         if (shared)                                                                                                           \

@@ -745,6 +745,7 @@ void launch_predict_noisy(hipStream_t st, int kind, int n, long ldx, int m, int 
         return;
     const long items = (((long)n + 63) / 64 * 64) * nchunk;
     const size_t lds = (size_t)3 * k * 64 * sizeof(double);
+    if (d <= GCAP) predict_route_add("gen<%d>", GCAP); else predict_route_add("gen_rt");
     GEN_LAUNCH(k_predict_noisy, items, lds, kind, n, ldx, m, d, de, k, Xr, Psir, Psi3, tab, rec, w, v, iS, pairs_per_chunk,
                part, nchunk);
 }

@@ -649,6 +649,13 @@ void launch_pmc(hipStream_t st, unsigned long long obs, int n, long ldx, int m, 
 #else
     const bool fast = pmc_fast(d, k) && work2 != nullptr && rows_blk <= 64 && !gpz_opts().pmc_scratch;
 #endif
+#ifdef PMC_WIDE
+    predict_route_add("pmc_wide");
+#else
+    const int phi_chunks = m < 256 ? m : 256;   // chunks of the PHI pass of the register-resident route
+    if (fast) predict_route_add("%s<%d> noisy=%d phi_chunks=%d", d <= 10 ? "pmc_fast" : "pmc4", d, Psi3 ? 1 : 0, phi_chunks);
+    else predict_route_add("pmc_scratch");
+#endif
 #ifndef PMC_WIDE
 #define PREP_CASE(DD) case DD: hipLaunchKernelGGL(k_pmc_prep_t<DD>, dim3((m + 63) / 64), dim3(64), 0, st, pt, m, Sig, rec, nrec); break;
     switch (gpz_opts().pmc_prep_scratch ? 0 : d) {
@@ -677,7 +684,7 @@ void launch_pmc(hipStream_t st, unsigned long long obs, int n, long ldx, int m, 
 #ifndef PMC_WIDE
         if (fast) {
             const double *PsT = Psi3 ? Phat : CUT;
-            pmc_sum(st, d, Psi3 != nullptr, nr, row0, m, ld, (long)m, m < 256 ? m : 256, ptab, d * d + d + 1, 0, Pio, Xhat, PsT,
+            pmc_sum(st, d, Psi3 != nullptr, nr, row0, m, ld, (long)m, phi_chunks, ptab, d * d + d + 1, 0, Pio, Xhat, PsT,
                     Phi, ldx, nullptr);
             pmc_sum(st, d, Psi3 != nullptr, nr, row0, m, ld, npairs, nchunk, tab, ntab, 3 * k, Pio, Xhat, PsT, nullptr, ldx,
                     part);

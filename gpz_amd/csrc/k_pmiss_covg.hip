@@ -320,6 +320,7 @@ void launch_pmc_generic(hipStream_t st, const unsigned char *obs_host, int n, lo
                                tab, ntab, q0, cnt, ws, wsp);
         }
     const int cpl = (int)(T / 64 < 1 ? 1 : T / 64);                           // pair chunks (waves) per accumulation launch
+    predict_route_add("pmc_generic ws_threads=%d chunks_per_launch=%d", T, cpl);
     for (int row = 0; row < n; ++row) {   // row block of one row: Ex / Pio / Xhat / Phat hold one row's tables (rr = 0)
         for (int b0 = 0; b0 < m; b0 += T) {
             const int cnt = m - b0 < T ? m - b0 : T;

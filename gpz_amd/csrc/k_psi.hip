@@ -396,6 +396,7 @@ int launch_predict_noisy_cov(hipStream_t st, int n, long ldx, int m, int d, int 
                        Psi3, tab, rec, w, v, iS, pairs_per_chunk, part)
 #define PN_CASE(DD)                                                                                                        \
     do {                                                                                                                   \
+        predict_route_add("psi<%d,%d> psi_diag=%d shared=%d", DD, k == 1 ? 1 : 8, dg ? 1 : 0, sh ? 1 : 0);                 \
         if (k == 1) {                                                                                                      \
             if (dg && sh) PN_LAUNCH(DD, true, true, 1); else if (dg) PN_LAUNCH(DD, true, false, 1);                        \
             else if (sh) PN_LAUNCH(DD, false, true, 1); else PN_LAUNCH(DD, false, false, 1);                               \
@@ -480,6 +481,7 @@ int launch_predict_noisy_diag(hipStream_t st, int n, long ldx, int m, int d, int
     if (n <= 0) return 0;
 #define PND(DD)                                                                                                              \
     do {                                                                                                                     \
+        predict_route_add("noisy_diag<%d,%d>", DD, k == 1 ? 1 : 8);                                                          \
         if (k == 1)                                                                                                          \
             hipLaunchKernelGGL((k_predict_noisy_diag<DD, 1>), dim3((n + 63) / 64, nchunk), dim3(64), 0, st, n, ldx, m, d, de, k, Xr, \
                                Psir, tab, rec, w, v, iS, pairs_per_chunk, part);                                             \

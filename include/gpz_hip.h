@@ -205,6 +205,12 @@ int gpz_predict_missing(const gpz_desc *desc, const double *theta, const double 
                         const double *priors, const double *Xs, int64_t ns, const double *Psi, int32_t psi_kind,
                         double *mu, double *nu, double *beta_i, double *gamma, double *PHI);
 
+/* Which kernels the last gpz_predict_full / _noisy / _missing of the CALLING THREAD ran, as one line of text: the entry, the kernel
+ * family with its template widths (noisy_diag<8,1>, psi<5,8>, cpsi4<3,8>, cpsi4w<9,1>, gen<20>, gen_rt, pmc_fast<5>, pmc4<12>,
+ * pmc_scratch, pmc_wide, pmc_generic, pm_diag, pm_diag_flags, tgemm) and the host-side counts (nchunk, ppc, rows_blk, blocks, width,
+ * passes, last, npg, n_pad).  Host bookkeeping for tests and diagnosis; empty before the first call.  Returns the text's full length. */
+int gpz_predict_last_route(char *buf, int64_t cap);
+
 /* ---- persistent streaming predictor: predictFull / predictNoisy for any number of rows --------------------------------------------
  * gpz_predictor_create does the once-per-model work on desc->device (theta unpacked, B_o = [inv(Sigma_o) | w | v] laid out for the
  * product) and allocates tile-sized buffers only: afterwards device memory does not depend on how many rows are predicted.  theta, w and
