@@ -150,6 +150,14 @@ SYMBOLS = {
                                                   c_double_p, c_double_p, C.c_uint32, C.c_int32, C.c_uint64, c_double_p, c_double_p,
                                                   C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, c_double_p, c_double_p, c_double_p,
                                                   c_double_p, c_double_p, C.c_void_p]),
+    # the same for a covariance kind (GC, VC): exactly the arguments of the two entries above
+    "gpz_predictor_draws_gamma_missing_cov_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int64, c_double_p,
+                                                            c_double_p, c_double_p, c_double_p, C.c_uint32, C.c_int32, C.c_uint64,
+                                                            c_double_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gpz_predictor_stack_missing_cov_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int64, c_double_p,
+                                                      c_double_p, c_double_p, C.c_uint32, C.c_int32, C.c_uint64, c_double_p, c_double_p,
+                                                      C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, c_double_p, c_double_p, c_double_p,
+                                                      c_double_p, c_double_p, C.c_void_p]),
     # such a group whose rows have Psi too: the noisy entries with the priors and the mask behind muY
     "gpz_predictor_run_noisy_missing_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_void_p,
                                                       C.c_int32, C.c_int64, C.c_int64, c_double_p, c_double_p, c_double_p, c_double_p,

@@ -344,10 +344,20 @@ int launch_pmcv_tables(hipStream_t st, int m, int d, int de, int k, unsigned obs
 int launch_pmcv_rows(hipStream_t st, const double *Xc, long ldx, int n, int nrow, int m, int mp, int d, int k, unsigned obs,
                      const double *exrec, const double *phirec, const double *w, const double *v, double *Pio, long ldr, double *Phi,
                      double *hd, long ldh);
+int launch_pmc_triples(hipStream_t st, int d, unsigned obs, long q0, long cnt, int m, const double *raw, const double *bas, double *slab);
 int launch_predict_missing_cov_pairs(hipStream_t st, const double *Xc, long ldx, int n, const double *Pio, long ldr, int m, int d, int k,
                                      unsigned obs, const double *raw, const double *bas, const double *coef, double *slab,
                                      bool *slab_kept, int nchunk, double *part, long ldp, const double *hd, long ldh, const double *bvec,
                                      double *out);
+// launch_predict_missing_cov_gamma (k_predict_missing_cov_gamma.hip; gpz_predictor_stack_missing_cov_dev, _draws_gamma_missing_cov_dev): the
+// pair sums of such a group under every column of W (ceil16(m) x ldw row-major, ncol <= ldw columns, ldw a multiple of 16) -> part
+// [predict_missing_cov_chunks(m)][ncol][ldp], from Pio of launch_pmcv_rows and the slabs as the pair kernel reads them: a slab that is not
+// kept is written here (launch_pmc_triples) and *slab_kept set as launch_predict_missing_cov_pairs sets it.  launch_gamma_finish_dev / _s2
+// take part from there.  Returns -1 when a launch failed.
+size_t predict_missing_cov_gamma_lds(int m, int no);   // dynamic LDS of the gamma kernel, bytes
+int launch_predict_missing_cov_gamma(hipStream_t st, const double *Xc, long ldx, int n, const double *Pio, long ldr, int m, int d,
+                                     unsigned obs, const double *raw, const double *bas, double *slab, bool *slab_kept, const double *W,
+                                     int ldw, int ncol, int nchunk, double *part, long ldp);
 // B (rows x ld row-major) <- [iS (m x m column-major) | nw columns of W from column wcol | nv columns of V (nullptr: 0) from vcol | 0]
 void launch_pred_fill_b(hipStream_t st, const double *iS, const double *W, int nw, int wcol, const double *V, int nv, int vcol, int m,
                         int rows, int ld, double *B);

@@ -61,7 +61,8 @@ struct gpz_predictor {
     // ---- gamma per draw and stacks of rows with input noise (gpz_predictor_stack_noisy*, _draws_gamma_noisy_dev) and of rows with missing
     // inputs (gpz_predictor_stack_missing_dev, _draws_gamma_missing_dev), of rows with both (gpz_predictor_stack_noisy_missing_dev,
     // _draws_gamma_noisy_missing_dev), and of rows with input noise on a covariance kind (gpz_predictor_stack_noisy_cov_dev,
-    // _draws_gamma_noisy_cov_dev): nothing of a kind before its first such call
+    // _draws_gamma_noisy_cov_dev), and of rows with missing inputs on a covariance kind (gpz_predictor_stack_missing_cov_dev,
+    // _draws_gamma_missing_cov_dev): nothing of a kind before its first such call
     int gchunks = 0;               // predict_gamma_chunks of the model (input noise, either kind; a group with missing inputs has mchunks)
     double *gpart = nullptr;       // [chunks][nd k][tile] pair sums per chunk, of either kind
     size_t gpart_cap = 0;          // doubles
@@ -69,7 +70,7 @@ struct gpz_predictor {
         bool used = false;
         double *s2_d = nullptr;    // [(1 + nd) k][tile] widths^2 of the stack
         size_t s2_cap = 0;         // doubles
-    } gam[4];                      // [ROWS_NOISY - 1], [ROWS_MISSING - 1], [ROWS_NOISY_MISSING - 1], [ROWS_NOISY_COV - 1]
+    } gam[5];                      // [ROWS_NOISY - 1], [ROWS_MISSING - 1], [ROWS_NOISY_MISSING - 1], [ROWS_NOISY_COV - 1], [ROWS_MISSING_COV - 1]
     // ---- rows with missing inputs on the handle (gpz_predictor_*_missing_dev): nothing of this exists before the first of their calls
     bool miss_used = false;
     int64_t mtile = 0;             // rows per tile of a group: min(tile_rows, GPZ_PREDICTOR_TILE_MISSING)
@@ -106,7 +107,7 @@ namespace gpzi {
 // share the NaN pattern obs (the bit mask of the observed dimensions), with the priors of the set (m values, or nullptr for 1 / m).
 // Noisy missing: such a group with Psi in Psic[s] too (read in the observed dimensions only).  Noisy cov: complete rows with Psi of a
 // covariance kind (a handle has either this kind or the diagonal noisy one, never both).  What a tile is made of for a kind is answered by the rows_* functions below; the runners of every entry go through them.
-// Missing cov: a group without Psi on a covariance kind (moments and draws only: it has no slot in gam[]).
+// Missing cov: a group without Psi on a covariance kind.
 enum RowKind { ROWS_CLEAN = 0, ROWS_NOISY = 1, ROWS_MISSING = 2, ROWS_NOISY_MISSING = 3, ROWS_NOISY_COV = 4, ROWS_MISSING_COV = 5 };
 struct Rows {
     RowKind kind = ROWS_CLEAN;

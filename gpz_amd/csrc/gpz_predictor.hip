@@ -532,7 +532,7 @@ static int predictor_missing_check(const char *who, const gpz_predictor *p, uint
     if (cov && p->kind != GPZ_KIND_COV)
         return gpz_fail(GPZ_ERR_UNSUPPORTED,
                         "%s: method %.2s is a diagonal kind: its rows with missing inputs go to gpz_predictor_run_missing_dev / "
-                        "_draws_missing_dev",
+                        "_draws_missing_dev / _draws_gamma_missing_dev / _stack_missing_dev",
                         who, p->desc.method);
     if (cov && !predict_missing_cov_fits(p->kind, p->d, p->m, p->k))
         return gpz_fail(GPZ_ERR_UNSUPPORTED,
@@ -822,6 +822,12 @@ int rows_gamma_tile(gpz_predictor *p, const char *who, const Rows &r, int s, int
             return gpz_fail(GPZ_ERR_HIP, "%s: k_predict_noisy_cov_gamma launch failed", who);
         return 0;
     }
+    if (r.kind == ROWS_MISSING_COV) {   // the slab of the pattern's pair records: kept, or written here as the pair kernel writes it
+        if (launch_predict_missing_cov_gamma(p->s_cmp, p->Xc[s], p->tile_pad, nt, p->mPio, rup(p->mtile, 1024), p->m, p->d, r.obs, p->mcraw,
+                                             p->mcbas, p->mcslab, &p->mcslab_kept, p->Wd, ldw, ncol, p->mchunks, p->gpart, nt))
+            return gpz_fail(GPZ_ERR_HIP, "%s: k_predict_missing_cov_gamma launch failed", who);
+        return 0;
+    }
     // a group with Psi: the second record table
     if (r.kind == ROWS_NOISY
             ? launch_predict_noisy_gamma(p->s_cmp, p->d, p->Xc[s], p->Psic[s], p->tile_pad, nt, p->m, p->ptab, p->nrec, p->Wd, ldw, ncol,
@@ -1024,11 +1030,12 @@ extern "C" int gpz_predictor_route(const gpz_predictor *p, char *buf, int cap) {
         snprintf(tmp, sizeof tmp, "tiles: k_phi + k_tgemm, %lld-row tiles", (long long)p->tile_rows);
     std::string r = tmp;
     // after the first stack or gamma-per-draw call for a kind of rows (gam[kind - 1]): its kernel and chunks (a group's: mchunks)
-    static const struct { const char *fmt; bool group; } PER_DRAW[4] = {
+    static const struct { const char *fmt; bool group; } PER_DRAW[5] = {
         {"; noise per draw: k_predict_noisy_gamma (%d pair chunks)", false},
         {"; missing per draw: k_predict_missing_gamma (%d pair chunks)", true},
         {"; noisy missing per draw: k_predict_noisy_missing_gamma (%d pair chunks)", true},
-        {"; noise per draw: k_predict_noisy_cov_gamma (%d pair chunks)", false}};
+        {"; noise per draw: k_predict_noisy_cov_gamma (%d pair chunks)", false},
+        {"; missing per draw: k_predict_missing_cov_gamma (%d pair chunks)", true}};
     auto per_draw = [&](int i) {
         if (!p->gam[i].used) return;
         snprintf(tmp, sizeof tmp, PER_DRAW[i].fmt, PER_DRAW[i].group ? p->mchunks : p->gchunks);
@@ -1064,6 +1071,7 @@ extern "C" int gpz_predictor_route(const gpz_predictor *p, char *buf, int cap) {
         snprintf(tmp, sizeof tmp, "; missing: k_predict_missing_cov_pairs (%d pair chunks)", p->mchunks);
         r += tmp;
     }
+    per_draw(4);
     per_draw(1);
     if (p->nm_used) {   // after the first call for a group of rows with input noise and missing inputs
         snprintf(tmp, sizeof tmp, "; noisy missing: k_predict_noisy_missing_pairs (%d pair chunks)", p->mchunks);

@@ -37,44 +37,10 @@
 // the same bits for any tile size, row order, company, position in its block and split into calls.
 #include "gpz_dev.h"
 #include "gpz_kernels.h"
+#include "k_pmcv_density.h"   // PMCV_MAXD, PMCV_SB, PmcvPat, pmcv_pat, pmcv_density, PMCV_CASES
 
-#define PMCV_MAXD 10
-#define PMCV_SB 16                    // records per wave and LDS stage of the pair kernel
 #define PMCV_ST 64                    // records per LDS stage of the Ex and PHI kernels
 #define PMCV_SLAB_BYTES (64L << 20)   // most bytes of a slab of pair-component records
-
-struct PmcvPat {
-    int d, no, nu;
-    int o[PMCV_MAXD], u[PMCV_MAXD];
-};
-
-static PmcvPat pmcv_pat(int d, unsigned obs) {
-    PmcvPat pt{};
-    pt.d = d;
-    for (int c = 0; c < d; ++c) {
-        if ((obs >> c) & 1u) pt.o[pt.no++] = c;
-        else pt.u[pt.nu++] = c;
-    }
-    return pt;
-}
-
-// ---- the density every tile kernel shares ----------------------------------------------------------------------------------------------
-template <int NO>
-__device__ __forceinline__ double pmcv_density(const double *t, const double (&x)[NO ? NO : 1]) {
-    double xa[NO ? NO : 1];
-#pragma unroll
-    for (int c = 0; c < NO; ++c) xa[c] = x[c] - t[1 + c];
-    double q = 0.0;
-    int e = 1 + NO;
-#pragma unroll
-    for (int r = 0; r < NO; ++r) {
-        double y = 0.0;
-#pragma unroll
-        for (int c = r; c < NO; ++c) y = fma(t[e++], xa[c], y);
-        q = fma(y, y, q);
-    }
-    return exp(t[0] - 0.5 * q);
-}
 
 // ---- records ---------------------------------------------------------------------------------------------------------------------------
 // S: n x n, lower triangle read, leading dimension PMCV_MAXD, destroyed.  V: columns 0 .. no - 1 the map, column no the offset, each of
@@ -439,14 +405,6 @@ static PmcvArgs pmcv_args(const PmcvPat &pt, const double *Xc, long ldx, int n, 
     return a;
 }
 
-#define PMCV_CASES(MACRO)                                                                                  \
-    switch (pt.no) {                                                                                       \
-        case 0: MACRO(0); break; case 1: MACRO(1); break; case 2: MACRO(2); break; case 3: MACRO(3); break; \
-        case 4: MACRO(4); break; case 5: MACRO(5); break; case 6: MACRO(6); break; case 7: MACRO(7); break; \
-        case 8: MACRO(8); break; case 9: MACRO(9); break;                                                  \
-        default: return -1;                                                                                \
-    }
-
 int launch_pmcv_rows(hipStream_t st, const double *Xc, long ldx, int n, int nrow, int m, int mp, int d, int k, unsigned obs,
                      const double *exrec, const double *phirec, const double *w, const double *v, double *Pio, long ldr, double *Phi,
                      double *hd, long ldh) {
@@ -465,6 +423,16 @@ int launch_pmcv_rows(hipStream_t st, const double *Xc, long ldx, int n, int nrow
     PMCV_CASES(PMCV_ROWS)
 #undef PMCV_ROWS
     hipLaunchKernelGGL(k_pmcv_hd, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, (const double *)Phi, n, m, mp, k, w, v, hd, ldh);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+// records [0, cnt * m) of the slab that starts at pair q0 (k_pmc_triples), for the units that read a slab without the pair kernel
+int launch_pmc_triples(hipStream_t st, int d, unsigned obs, long q0, long cnt, int m, const double *raw, const double *bas, double *slab) {
+    if (cnt <= 0) return 0;
+    if (d < 1 || d > PMCV_MAXD || m < 1) return -1;
+    const PmcvPat pt = pmcv_pat(d, obs);
+    hipLaunchKernelGGL(k_pmc_triples, dim3((unsigned)((cnt * m + 63) / 64)), dim3(64), 0, st, pt, q0, cnt, m, raw, bas,
+                       predict_missing_cov_bas(d, pt.no), slab, predict_missing_cov_rec(pt.no));
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

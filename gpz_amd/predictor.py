@@ -3,7 +3,8 @@
 The methods ask one of four questions (run: the moments of ``predict``; draws; draws with gamma per draw; stack) of rows of one of four
 kinds (clean, noisy: with Psi, missing: one NaN-pattern group, noisy_missing: such a group with Psi); noisy_cov is the noisy kind of a
 covariance model (GC, VC), which has all four questions through methods of its own (``*_noisy_cov_dev``), and missing_cov the
-missing kind of such a model, which has the first two (``predict_missing_cov_dev``, ``draws_missing_cov_dev``).
+missing kind of such a model, which has all four too (``predict_missing_cov_dev``, ``draws_missing_cov_dev`` with ``return_gamma``,
+``stack_missing_cov_dev``).
 ``_DEV_ENTRIES`` names the device-resident entry of each pair, ``Predictor._dev_entry`` builds the arguments the entries of a pair
 share, and ``Predictor._dev_groups`` is the one loop over the groups of a call; the host methods choose between two entries each by
 whether Psi is there (``_HOST_ENTRIES``).  Everything numeric happens in the library; ``torch`` is only imported by the device methods.
@@ -37,6 +38,7 @@ _DEV_ENTRIES = {
     ("draws_gamma", "noisy_cov"): "gpz_predictor_draws_gamma_noisy_cov_dev", ("stack", "noisy_cov"): "gpz_predictor_stack_noisy_cov_dev",
     ("stack", "clean"): "gpz_predictor_stack_dev", ("stack", "noisy"): "gpz_predictor_stack_noisy_dev",
     ("stack", "missing"): "gpz_predictor_stack_missing_dev", ("stack", "noisy_missing"): "gpz_predictor_stack_noisy_missing_dev",
+    ("draws_gamma", "missing_cov"): "gpz_predictor_draws_gamma_missing_cov_dev", ("stack", "missing_cov"): "gpz_predictor_stack_missing_cov_dev",
 }
 # (question, Psi there) -> the host entry
 _HOST_ENTRIES = {("draws", False): "gpz_predictor_draws", ("draws", True): "gpz_predictor_draws_noisy",
@@ -650,7 +652,8 @@ class Predictor:
         gamma under the weights of draw s: the variance of PHI(x) w_s over the missing dimensions of the row, exactly 0.0 on complete
         rows.  A row's Gam has the same bits for any tile size, row order, other rows of the call and any n_draws > s.  The scope is
         that of ``missing=True`` (diagonal kinds, d <= 20, k <= 8, m <= 256); the covariance kinds and host arrays are not on the handle
-        (gamma per draw over the input noise of a covariance kind is ``draws_noisy_cov_dev(..., return_gamma=True)``'s);
+        (gamma per draw over the input noise of a covariance kind is ``draws_noisy_cov_dev(..., return_gamma=True)``'s, over its
+        missing dimensions ``draws_missing_cov_dev(..., return_gamma=True)``'s);
         gamma per draw for ``Psi`` together with missing values is ``draws_noisy_missing_dev(..., return_gamma=True)``'s.  With neither ``Psi`` nor ``missing``, or with both, it is a ValueError."""
         self._check_open()
         X = self._check_dev_rows(X, selection, "draws")
@@ -800,7 +803,7 @@ class Predictor:
         return self._draws_dev(X, Psi, selection, False, n_draws, seed, z, bool(return_gamma), cov=True)
 
     def _check_missing_cov(self, what, X, Psi, selection):
-        """The checks the two methods for rows with missing values of a covariance kind share, none of which touches a GPU: X by type,
+        """The checks the three methods for rows with missing values of a covariance kind share, none of which touches a GPU: X by type,
         dtype and shape, then where such rows go when this is not their route (Psi, a diagonal kind, a shape outside
         predict_missing_cov_fits of k_predict_missing_cov.hip), then the priors.  Returns X as n x d."""
         name = f"{what}_missing_cov_dev"
@@ -812,8 +815,8 @@ class Predictor:
             raise ValueError(f"{name} does not take Psi: rows of a covariance kind with both input noise and missing values "
                              "(predictNoisyMissing) go to Predictor.predict(X, Psi=Psi)")
         if self._method[1] != "C":
-            raise ValueError(f"{name} is for the covariance kinds (GC, VC): a diagonal kind such as {self._method} goes to "
-                             f"{what}_dev(X, missing=True)")
+            raise ValueError(f"{name} is for the covariance kinds (GC, VC): a diagonal kind such as {self._method} goes to " +
+                             ("stack_missing_dev(X, edges)" if what == "stack" else f"{what}_dev(X, missing=True)"))
         if not (1 <= self._d <= 10 and 1 <= self._k <= 8 and 1 <= self._m <= 256):
             raise ValueError(f"{name} needs a model inside predict_missing_cov_fits: GC or VC, d <= 10, k <= 8 and m <= 256; this one "
                              f"is {self._method} with d = {self._d}, m = {self._m}, k = {self._k} (Predictor.predict takes rows with "
@@ -845,17 +848,36 @@ class Predictor:
         self._check_missing_cov_device(X, selection)
         return self._moments_dev(X, None, selection, True, cov=True)
 
-    def draws_missing_cov_dev(self, X, n_draws, seed=0, Z=None, selection=None, Psi=None):
+    def draws_missing_cov_dev(self, X, n_draws, seed=0, Z=None, selection=None, Psi=None, return_gamma=False):
         """``draws_dev(X, n_draws, missing=True)`` for a covariance kind (gpz_predictor_draws_missing_cov_dev): X and ``selection`` as
         for ``predict_missing_cov_dev``, ``n_draws``, ``seed`` and ``Z`` as for ``draws_dev``.  Returns a float64 tensor of shape
         (n_draws, n, k) on the device: for a row with missing values draws[s] is PHI_missing w_s + muY, ``predict_missing_cov_dev``'s
         mu under weight draw s - the mean is linear in the weights, so this is exact.  One weight draw serves all rows of all groups;
-        complete rows get the bits of ``draws_dev`` on them alone."""
+        complete rows get the bits of ``draws_dev`` on them alone.
+        ``return_gamma=True`` (gpz_predictor_draws_gamma_missing_cov_dev) returns ``(F, Gam)``: F with the bits it has without the keyword,
+        Gam a float64 tensor of shape (n_draws, n, k), predictMissing's gamma of predictCov.m under the weights of draw s - the variance
+        of PHI(x) w_s over the missing dimensions of the row, not clamped at 0 and exactly 0.0 on complete rows
+        (k_predict_missing_cov_gamma).  A y-draw of row i under draw s has variance beta_i + Gam[s, i].  A row's Gam has the same bits
+        for any tile size, row order, other rows of the call and any n_draws > s."""
         self._check_open()
         X = self._check_missing_cov("draws", X, Psi, selection)
         n_draws, z = self._check_draw_args(n_draws, seed, Z, 1)
         self._check_missing_cov_device(X, selection)
-        return self._draws_dev(X, None, selection, True, n_draws, seed, z, cov=True)
+        return self._draws_dev(X, None, selection, True, n_draws, seed, z, bool(return_gamma), cov=True)
+
+    def stack_missing_cov_dev(self, X, edges, n_draws=0, seed=0, Z=None, groups=None, n_groups=None, weights=None, selection=None):
+        """``stack_missing_dev`` for a covariance kind (GC, VC; gpz_predictor_stack_missing_cov_dev): arguments and result as for
+        ``stack_dev``.  The rows are grouped by NaN pattern with torch on the device, as ``predict_missing_cov_dev`` groups them.  The
+        complete rows go to gpz_predictor_stack_dev (a catalogue without NaN gives ``stack_dev``'s bits), every other group with its
+        labels and weights to gpz_predictor_stack_missing_cov_dev, and the groups' results are added field by field in ascending order
+        of the pattern code, so the call equals the ``+=`` of the single-pattern calls bit for bit.  For a row with missing values
+        column 0 uses ``predict_missing_cov_dev``'s mu and that call's sigma = (nu + beta_i) + gamma, bit for bit; column 1 + s
+        ``draws_missing_cov_dev``'s draw s and the width beta_i + max(gamma_s, 0), where gamma_s is that method's ``return_gamma=True``.
+        ``n_groups`` and the range of the labels are decided over all rows.  It needs a model inside predict_missing_cov_fits (GC or
+        VC, d <= 10, k <= 8, m <= 256), else ValueError; a diagonal kind goes to ``stack_missing_dev``, and host arrays and ``Psi``
+        together with missing values are not on the handle (``Predictor.predict`` takes such rows).  A label outside [-1, n_groups)
+        and a negative or non-finite weight are found on the device before the first tile and refused with a GpzError."""
+        return self._stack_dev(X, None, edges, n_draws, seed, Z, groups, n_groups, weights, selection, missing=True, cov=True)
 
     def stack_noisy_cov_dev(self, X, Psi, edges, n_draws=0, seed=0, Z=None, groups=None, n_groups=None, weights=None, selection=None):
         """``stack_noisy_dev`` for a covariance kind (GC, VC; gpz_predictor_stack_noisy_cov_dev): X, ``Psi`` and ``selection`` as for
@@ -895,8 +917,8 @@ class Predictor:
         column 1 + s ``draws_dev(X, ..., missing=True)``'s draw s and the width beta_i + max(gamma_s, 0), where gamma_s is
         predictMissing's gamma under the weights of draw s (``draws_dev(..., missing=True, return_gamma=True)`` returns it).
         ``n_groups`` and the range of the labels are decided over all rows.  It needs a model inside predict_missing_fits (a diagonal
-        kind, d <= 20, k <= 8, m <= 256), else ValueError; host arrays, ``Psi`` together with missing values and the covariance
-        kinds are not on the handle (``Predictor.predict`` takes such rows)."""
+        kind, d <= 20, k <= 8, m <= 256), else ValueError; host arrays and ``Psi`` together with missing values are not on the handle
+        (``Predictor.predict`` takes such rows), and the covariance kinds go to ``stack_missing_cov_dev``."""
         return self._stack_dev(X, None, edges, n_draws, seed, Z, groups, n_groups, weights, selection, missing=True)
 
     def stack_noisy_missing_dev(self, X, Psi, edges, n_draws=0, seed=0, Z=None, groups=None, n_groups=None, weights=None,
@@ -917,18 +939,21 @@ class Predictor:
 
     def _stack_dev(self, X, Psi, edges, n_draws, seed, Z, groups, n_groups, weights, selection, missing=False, both=False, cov=False):
         """``stack_dev`` (Psi None), ``stack_noisy_dev``, ``stack_missing_dev``, (``both``: Psi and ``missing`` together)
-        ``stack_noisy_missing_dev`` and (``cov``: Psi of a covariance kind) ``stack_noisy_cov_dev``: the checks, the device last, all before the GPU is touched; then the entry, or with ``missing``
+        ``stack_noisy_missing_dev``, (``cov``: Psi of a covariance kind) ``stack_noisy_cov_dev`` and (``cov`` with ``missing``)
+        ``stack_missing_cov_dev``: the checks, the device last, all before the GPU is touched; then the entry, or with ``missing``
         one entry per NaN-pattern group."""
         import torch
         self._check_open()
         if both:
             X, Psi = self._check_noisy_missing("stack", X, Psi, selection, draws=True)
+        elif cov and missing:
+            X = self._check_missing_cov("stack", X, Psi, selection)
         elif cov:
             X, Psi = self._check_noisy_cov("stack", X, Psi, selection)
         else:
             X = self._check_dev_rows(X, selection, "stack" if Psi is None else "stack_noisy")
         n_all = X.shape[0]
-        if missing and not both:
+        if missing and not both and not cov:
             self._check_missing_model("stack_missing_dev", None)
         if Psi is not None and not both and not cov:
             Psi = self._check_dev_psi(Psi, n_all, "stack_noisy")
@@ -947,7 +972,12 @@ class Predictor:
             raise ValueError(f"n_groups must be a positive integer, got {n_groups!r}")
         if n_groups is not None and int(n_groups) * B > GPZ_STACK_MAX_GROUP_BINS:
             raise ValueError(f"n_groups * bins = {int(n_groups) * B} is over the limit of {GPZ_STACK_MAX_GROUP_BINS} per call")
-        self._check_dev_device(X=X, selection=selection, groups=groups, weights=weights, Psi=Psi)
+        try:
+            self._check_dev_device(X=X, selection=selection, groups=groups, weights=weights, Psi=Psi)
+        except ValueError as err:
+            if not (cov and missing):
+                raise
+            raise ValueError(f"{err} (Predictor.predict takes a catalogue with missing values from host arrays)") from None
         lab = wt = None
         X, Psi = self._selected(selection, X, Psi)
         if groups is not None:

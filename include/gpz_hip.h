@@ -519,6 +519,35 @@ int gpz_predictor_stack_missing_dev(gpz_predictor *p, const void *X_d, int32_t x
                                     double *hist, double *sum_w, double *sum_mu, double *sum_mu2, const double *mu_shift /* k or NULL */,
                                     void *stream);
 
+/* ---- the same for a covariance kind -----------------------------------------------------------------------------------------------------
+ * gpz_predictor_stack_missing_dev and gpz_predictor_draws_gamma_missing_dev for ONE group of rows of a GC or VC model that share a NaN
+ * pattern, with exactly those entries' arguments; the scope (predict_missing_cov_fits), priors, obs_mask, the scan of the pattern and
+ * every refusal are those of gpz_predictor_run_missing_cov_dev / _draws_missing_cov_dev (a diagonal kind is sent to the two entries
+ * above by name).  Column 0: mu of gpz_predictor_run_missing_cov_dev, width^2 = (nu + beta) + gamma, the bits of that call's sigma.
+ * Column 1 + s: mu_s of gpz_predictor_draws_missing_cov_dev, width^2 = beta_i + max(gamma_s,i, 0) with
+ *   gamma_s,i = sum_{a >= b} f_ab z_ab(x_i) w_s,a w_s,b - mu_s,i^2,   z_ab(x) = sum_l Pio_l(x) exp(lnw_abl - 1/2 |U_abl (x_o - a_abl)|^2),
+ * predictMissing's gamma (predictCov.m:183-216) under the draw's weights, returned unclamped in Gam_d.  k_predict_missing_cov_gamma
+ * forms z from the records of gpz_predictor_run_missing_cov_dev's pair kernel (m exp per pair and row) and multiplies it into all
+ * draws at once on the f64 MFMA; a stack therefore forms every z twice, once per kernel.  A row's gamma_s has the same bits for any
+ * tile size, row order, position among other rows, split into calls and any ndraws > s.  The first of these calls adds to the handle
+ * what the two covariance entries above add, plus the chunk slab of the pair sums (predict_missing_cov_chunks(m) x ndraws k x tile
+ * rows doubles) and, for the stack, the widths ((1 + ndraws) k x tile rows) and gpz_predictor_stack_dev's accumulators and slabs;
+ * nothing grows with ns or the number of patterns, and gpz_predictor_route then holds "; missing per draw: k_predict_missing_cov_gamma
+ * (C pair chunks)", followed by " + k_stack_tile_w" once the stack entry has been called. */
+int gpz_predictor_draws_gamma_missing_cov_dev(gpz_predictor *p, const void *X_d, int32_t x_type, int64_t ns, int64_t row_stride,
+                                              int64_t col_stride, const double *muX, const double *sdX, const double *muY /* k or NULL */,
+                                              const double *priors /* m or NULL */, uint32_t obs_mask,
+                                              int32_t ndraws, uint64_t seed, const double *Z /* host: NULL or m x ndraws x k */,
+                                              double *F_d /* ns x k x ndraws, column-major */,
+                                              double *Gam_d /* ns x k x ndraws, column-major */, void *stream);
+int gpz_predictor_stack_missing_cov_dev(gpz_predictor *p, const void *X_d, int32_t x_type, int64_t ns, int64_t row_stride, int64_t col_stride,
+                                        const double *muX, const double *sdX,
+                                        const double *priors /* m or NULL */, uint32_t obs_mask,
+                                        int32_t ndraws, uint64_t seed, const double *Z, const double *edges, int32_t nbins,
+                                        const int32_t *group_d /* ns or NULL */, int32_t ngroups, const double *weight_d /* ns or NULL */,
+                                        double *hist, double *sum_w, double *sum_mu, double *sum_mu2, const double *mu_shift /* k or NULL */,
+                                        void *stream);
+
 /* ---- rows with input noise AND missing inputs on the predictor handle -------------------------------------------------------------------
  * predictNoisyMissing (predictDiag.m:211-297) and the draws for ONE group of rows that share a NaN pattern and carry a variance per
  * input dimension, on the handle's own tiles, where predict_missing_fits holds (a diagonal kind, d <= 20, k <= 8, ceil16(m) <= 256);

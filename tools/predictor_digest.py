@@ -22,7 +22,10 @@ d = 1, 20, each with m = 20, k = 1 (one gamma chunk; 1, 64 and 129 or, from d = 
 m = 91, k = 3 (two gamma chunks, the last stage partial; 3 and 129 or 66 columns), 80 rows on 128-row tiles (a full workgroup and 16 rows)
 and one call over two tiles: predict_noisy_cov_dev, draws_noisy_cov_dev with and without gamma, stack_noisy_cov_dev,
 predict_missing_cov_dev and draws_missing_cov_dev (VD: gamma per draw and stack_noisy_dev), and two more handles that meet a call for
-rows with missing inputs first and one for rows with input noise second, and the other way round.
+rows with missing inputs first and one for rows with input noise second, and the other way round.  Behind them, on handles of their
+own so that the lines above stay what they were (profiles/r21_predict_stack_missing_cov.txt): draws_missing_cov_dev with gamma (the
+first call of its handle, then predict_missing_cov_dev, which reads the slab that call filled) and stack_missing_cov_dev with 1 and
+with 129 or 66 columns, groups and weights, and a handle that meets stack_noisy_cov_dev first and stack_missing_cov_dev second.
 After each call one line: the call, the digest of each array it returned, and the handle's route and info."""
 import hashlib
 import os
@@ -188,6 +191,18 @@ def run_edges(method, d, m, k):
             report(f"{tag} noisy first, draws_noisy_cov_dev", p, p.draws_noisy_cov_dev(Xd[:80], Pd[:80], 2, seed=11))
             report(f"{tag} noisy first, predict_noisy_cov_dev", p, p.predict_noisy_cov_dev(Xd[:80], Pd[:80]))
             missing(p, 80)
+        gd = torch.from_numpy(rng.integers(-1, 3, 200)).to(DEV)
+        wd = torch.from_numpy(rng.uniform(0.5, 1.5, 200)).to(DEV)
+        with gpz_amd.Predictor(model, tile_rows=128) as p:               # gamma per draw and the stack of rows with missing inputs
+            for nd in (draws[0], draws[-1]):
+                report(f"{tag} draws_missing_cov_dev gamma {nd} x 200", p, p.draws_missing_cov_dev(Xmd, nd, seed=11, return_gamma=True))
+                missing(p, 200)
+                report(f"{tag} stack_missing_cov_dev {nd} x 200", p,
+                       tuple(p.stack_missing_cov_dev(Xmd, edges, n_draws=nd, seed=11, groups=gd, n_groups=3, weights=wd)))
+            report(f"{tag} stack_missing_cov_dev plain x 80", p, tuple(p.stack_missing_cov_dev(Xmd[:80], edges)))
+        with gpz_amd.Predictor(model, tile_rows=128) as p:               # the noisy stack first, the missing one second: gpart is shared
+            report(f"{tag} noisy first, stack_noisy_cov_dev", p, tuple(p.stack_noisy_cov_dev(Xd[:80], Pd[:80], edges, n_draws=3, seed=11)))
+            report(f"{tag} noisy first, stack_missing_cov_dev", p, tuple(p.stack_missing_cov_dev(Xmd, edges, n_draws=draws[-1], seed=11)))
 
 
 def main():
