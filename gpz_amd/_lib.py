@@ -167,6 +167,15 @@ SYMBOLS = {
                                                         C.c_int32, C.c_int64, C.c_int64, c_double_p, c_double_p, c_double_p, c_double_p,
                                                         c_double_p, C.c_uint32, C.c_int32, C.c_uint64, c_double_p, C.c_void_p,
                                                         C.c_void_p]),
+    # ... on a covariance kind: exactly their arguments
+    "gpz_predictor_run_noisy_missing_cov_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_void_p,
+                                                          C.c_int32, C.c_int64, C.c_int64, c_double_p, c_double_p, c_double_p, c_double_p,
+                                                          c_double_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                          C.c_void_p, C.c_void_p]),
+    "gpz_predictor_draws_noisy_missing_cov_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_void_p,
+                                                            C.c_int32, C.c_int64, C.c_int64, c_double_p, c_double_p, c_double_p,
+                                                            c_double_p, c_double_p, C.c_uint32, C.c_int32, C.c_uint64, c_double_p,
+                                                            C.c_void_p, C.c_void_p]),
     "gpz_predictor_draws_gamma_noisy_missing_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int64,
                                                               C.c_void_p, C.c_int32, C.c_int64, C.c_int64, c_double_p, c_double_p,
                                                               c_double_p, c_double_p, c_double_p, C.c_uint32, C.c_int32, C.c_uint64,

@@ -358,6 +358,26 @@ size_t predict_missing_cov_gamma_lds(int m, int no);   // dynamic LDS of the gam
 int launch_predict_missing_cov_gamma(hipStream_t st, const double *Xc, long ldx, int n, const double *Pio, long ldr, int m, int d,
                                      unsigned obs, const double *raw, const double *bas, double *slab, bool *slab_kept, const double *W,
                                      int ldw, int ncol, int nchunk, double *part, long ldp);
+int launch_pmcv_hd(hipStream_t st, const double *Phi, int n, int m, int mp, int k, const double *w, const double *v, double *hd, long ldh);
+// ---- rows with input noise and missing inputs, covariance kinds (k_predict_noisy_missing_cov.hip; gpz_predictor_*_noisy_missing_cov_dev)
+// The launchers above with Psic [d][ldx] beside Xc and records of predict_noisy_missing_cov_rec(d, no) doubles, [lnw | -j | M packed lower
+// triangle | J | A2 | b2] (the unit's head says what they are).  launch_pnmc_tables: the Ex and PHI tables of the pattern from bas as
+// launch_pmcv_tables left it (coef is that launcher's too).  The pair launcher writes each slab itself (k_pnmc_triples):
+// predict_noisy_missing_cov_slabs(m, d, no) slabs of predict_noisy_missing_cov_slab_pairs whole pairs, at most 64 MB each; chunks:
+// predict_missing_cov_chunks(m).  Patterns with 1 <= no < d only.  The launchers return -1 when a launch failed.
+int predict_noisy_missing_cov_rec(int d, int no);
+int predict_noisy_missing_cov_slabs(int m, int d, int no);
+long predict_noisy_missing_cov_slab_pairs(int m, int d, int no);
+size_t predict_noisy_missing_cov_lds(int m, int d, int no, int k);   // dynamic LDS of the pair kernel, bytes
+int launch_pnmc_tables(hipStream_t st, int m, int d, int de, unsigned obs, const double *P, const double *Sig, const double *lnS,
+                       const double *priors, const double *bas, double *exrec, double *phirec);
+int launch_pnmc_rows(hipStream_t st, const double *Xc, const double *Psic, long ldx, int n, int nrow, int m, int mp, int d, int k,
+                     unsigned obs, const double *exrec, const double *phirec, const double *w, const double *v, double *Pio, long ldr,
+                     double *Phi, double *hd, long ldh);
+int launch_predict_noisy_missing_cov_pairs(hipStream_t st, const double *Xc, const double *Psic, long ldx, int n, const double *Pio,
+                                           long ldr, int m, int d, int k, unsigned obs, const double *raw, const double *bas,
+                                           const double *coef, double *slab, bool *slab_kept, int nchunk, double *part, long ldp,
+                                           const double *hd, long ldh, const double *bvec, double *out);
 // B (rows x ld row-major) <- [iS (m x m column-major) | nw columns of W from column wcol | nv columns of V (nullptr: 0) from vcol | 0]
 void launch_pred_fill_b(hipStream_t st, const double *iS, const double *W, int nw, int wcol, const double *V, int nv, int vcol, int m,
                         int rows, int ld, double *B);

@@ -100,6 +100,13 @@ struct gpz_predictor {
     double *mcbas = nullptr, *mcex = nullptr, *mcphi = nullptr;    // the pattern's: [R | CU | off] per basis function, the Ex and PHI records
     double *mccoef = nullptr, *mcslab = nullptr;                   // with pairs: the 3k coefficients per pair, the slab of pair-component records
     bool mcslab_kept = false;      // the slab holds the whole table of (mtab_obs, mtab_pri)
+    // ---- rows with input noise and missing inputs for the covariance kinds (gpz_predictor_*_noisy_missing_cov_dev): everything of the
+    // group above and the Psi slots, each taken where the handle does not hold it yet.  Beyond them only this exists, and not before the
+    // first of their calls
+    bool nmcov_used = false;
+    double *nmcex = nullptr, *nmcphi = nullptr, *nmcslab = nullptr;   // the Ex and PHI records and the slab in the form of k_predict_noisy_missing_cov.hip
+    bool nmtab_valid = false;      // nmcex and nmcphi hold the records of (mtab_obs, mtab_pri); cleared where the tables above are written
+    bool nmcslab_kept = false;     // nmcslab holds the whole pair-component table of (mtab_obs, mtab_pri)
 };
 
 namespace gpzi {
@@ -107,14 +114,23 @@ namespace gpzi {
 // share the NaN pattern obs (the bit mask of the observed dimensions), with the priors of the set (m values, or nullptr for 1 / m).
 // Noisy missing: such a group with Psi in Psic[s] too (read in the observed dimensions only).  Noisy cov: complete rows with Psi of a
 // covariance kind (a handle has either this kind or the diagonal noisy one, never both).  What a tile is made of for a kind is answered by the rows_* functions below; the runners of every entry go through them.
-// Missing cov: a group without Psi on a covariance kind.
-enum RowKind { ROWS_CLEAN = 0, ROWS_NOISY = 1, ROWS_MISSING = 2, ROWS_NOISY_MISSING = 3, ROWS_NOISY_COV = 4, ROWS_MISSING_COV = 5 };
+// Missing cov: a group without Psi on a covariance kind.  Noisy missing cov: such a group with Psi in Psic[s] too; with nothing observed
+// (obs = 0) there is no Psi to read and the group is the missing cov kind's in all but the name of its entry.
+enum RowKind {
+    ROWS_CLEAN = 0, ROWS_NOISY = 1, ROWS_MISSING = 2, ROWS_NOISY_MISSING = 3, ROWS_NOISY_COV = 4, ROWS_MISSING_COV = 5,
+    ROWS_NOISY_MISSING_COV = 6
+};
 struct Rows {
     RowKind kind = ROWS_CLEAN;
     uint32_t obs = 0;
     const double *priors = nullptr;
-    bool psi() const { return kind == ROWS_NOISY || kind == ROWS_NOISY_MISSING || kind == ROWS_NOISY_COV; }   // Psic[s] is staged beside Xc[s]
-    bool group() const { return kind == ROWS_MISSING || kind == ROWS_NOISY_MISSING || kind == ROWS_MISSING_COV; }    // one NaN pattern, tiles of at most mtile rows
+    bool psi() const {   // Psic[s] is staged beside Xc[s]
+        return kind == ROWS_NOISY || kind == ROWS_NOISY_MISSING || kind == ROWS_NOISY_COV || (kind == ROWS_NOISY_MISSING_COV && obs != 0);
+    }
+    bool group() const {   // one NaN pattern, tiles of at most mtile rows
+        return kind == ROWS_MISSING || kind == ROWS_NOISY_MISSING || kind == ROWS_MISSING_COV || kind == ROWS_NOISY_MISSING_COV;
+    }
+    bool cov_group() const { return kind == ROWS_MISSING_COV || kind == ROWS_NOISY_MISSING_COV; }   // such a group on a covariance kind
 };
 
 // ---- what a kind of rows is made of (gpz_predictor.hip) ------------------------------------------------------------------------------

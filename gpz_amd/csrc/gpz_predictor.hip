@@ -60,6 +60,9 @@
 // second record table that is the model's alone.  gpz_predictor_stack_noisy_missing_dev stacks such a group as the two stacks above,
 // with gamma under every draw from k_predict_noisy_missing_gamma.hip (k_predict_missing_gamma's two chained products with that
 // epilogue between them); gpz_predictor_draws_gamma_noisy_missing_dev returns that gamma beside the draws.
+// The covariance kinds have the first two of these as gpz_predictor_run_noisy_missing_cov_dev / _draws_noisy_missing_cov_dev
+// (k_predict_noisy_missing_cov.hip): the frame, tile buffers and pattern tables of the missing_cov entries, with record tables of
+// their own whose density is a packed no x no Cholesky of M + diag(psi_o) per row (predictor_noisy_missing_cov_prepare).
 // Layout: gpz_predictor.h holds the handle and what the three units share.  This unit holds the handle's life and setup, what a tile is
 // made of for each kind of rows (clean, with Psi, one NaN-pattern group: the rows_* functions), draws preparation and factorisation, the
 // stack's preparation and tile, the checks the entries share, route and info.  gpz_predictor_host.hip holds the host pipeline, its jobs
@@ -528,7 +531,13 @@ static int predictor_draws_tile(gpz_predictor *p, int s, int64_t nt, int ncol, i
 
 // ---- rows with missing inputs on the handle -----------------------------------------------------------------------------------------
 // cov: the entries of the covariance kinds (ROWS_MISSING_COV); each of the two refuses the other's kinds and names their entry
-static int predictor_missing_check(const char *who, const gpz_predictor *p, uint32_t obs, bool cov) {
+// noisy (with cov): the entries for such a group with Psi (ROWS_NOISY_MISSING_COV), whose diagonal kinds have gpz_predictor_*_noisy_missing_dev
+static int predictor_missing_check(const char *who, const gpz_predictor *p, uint32_t obs, bool cov, bool noisy = false) {
+    if (cov && noisy && p->kind != GPZ_KIND_COV)
+        return gpz_fail(GPZ_ERR_UNSUPPORTED,
+                        "%s: method %.2s is a diagonal kind: its rows with input noise and missing inputs go to "
+                        "gpz_predictor_run_noisy_missing_dev / _draws_noisy_missing_dev",
+                        who, p->desc.method);
     if (cov && p->kind != GPZ_KIND_COV)
         return gpz_fail(GPZ_ERR_UNSUPPORTED,
                         "%s: method %.2s is a diagonal kind: its rows with missing inputs go to gpz_predictor_run_missing_dev / "
@@ -700,6 +709,8 @@ static int predictor_missing_cov_prepare(gpz_predictor *p, const char *who, uint
     if (p->mtab_valid && p->mtab_obs == obs && same_pri && (p->mtab_pairs || !pairs)) return 0;
     p->mtab_valid = false;
     p->mcslab_kept = false;
+    p->nmtab_valid = false;   // the records of k_predict_noisy_missing_cov.hip are made from these tables
+    p->nmcslab_kept = false;
     p->mtab_uniform = priors == nullptr;
     if (priors) {   // the handle's own copy: the upload may still be in flight when the caller has its memory back
         p->mtab_pri.assign(priors, priors + m);
@@ -715,12 +726,55 @@ static int predictor_missing_cov_prepare(gpz_predictor *p, const char *who, uint
     return 0;
 }
 
+// Such a group whose rows have Psi too (ROWS_NOISY_MISSING_COV with something observed): the Psi slots, everything above (the tile
+// buffers, [R | CU | off] and the coefficients of the pattern are shared, and the tables above stay valid for the entries that read
+// them), and the Ex and PHI records and the slab in the form of k_predict_noisy_missing_cov.hip, sized for the widest pattern of the
+// model and kept until the tables above are written again.
+static int predictor_noisy_missing_cov_prepare(gpz_predictor *p, const char *who, uint32_t obs, const double *priors, bool pairs) {
+    const size_t m = p->m;
+    int rc = 0;
+    if ((rc = predictor_psi_slots(p))) return rc;
+    const bool had = p->mcov_used;   // (the route text of the entries without Psi is theirs)
+    rc = predictor_missing_cov_prepare(p, who, obs, priors, pairs);
+    p->mcov_used = had;
+    if (rc) return rc;
+    size_t rlmax = 0, slabmax = 0;   // over no = 1 .. d - 1
+    for (int no = 1; no < p->d; ++no) {
+        const size_t rl = (size_t)predict_noisy_missing_cov_rec(p->d, no);
+        rlmax = std::max(rlmax, rl);
+        slabmax = std::max(slabmax, (size_t)predict_noisy_missing_cov_slab_pairs(p->m, p->d, no) * m * rl);
+    }
+    if (!p->nmcex && (rc = p->ar.alloc(&p->nmcex, m * rlmax))) return rc;
+    if (!p->nmcphi && (rc = p->ar.alloc(&p->nmcphi, m * m * rlmax))) return rc;
+    if (pairs && !p->nmcslab && (rc = p->ar.alloc(&p->nmcslab, slabmax))) return rc;
+    if (p->nmtab_valid) return 0;
+    p->nmcslab_kept = false;
+    if (launch_pnmc_tables(p->s_cmp, p->m, p->d, p->de, obs, p->pr.P, p->mcSig, p->mclnS, priors ? p->mpri : nullptr, p->mcbas, p->nmcex,
+                           p->nmcphi))
+        return gpz_fail(GPZ_ERR_HIP, "%s: table kernel launch failed", who);
+    p->nmtab_valid = true;
+    return 0;
+}
+
 // predictMissing of one tile of nt rows of the group, covariance kinds: Xc[s] -> Pio in mPio ([m][tile]), PHI in mNo, mu | ElnS - b in mhd
 // and, with pairs, mout ([4k][nt] = mu | nu | beta | gamma)
-static int predictor_missing_cov_tile(gpz_predictor *p, const char *who, int s, int nt, uint32_t obs, bool pairs) {
+// Psic: the tile's Psi slot for a group with input noise too (predictNoisyMissing: the kernels of k_predict_noisy_missing_cov.hip on
+// their own record tables), else nullptr
+static int predictor_missing_cov_tile(gpz_predictor *p, const char *who, int s, int nt, uint32_t obs, bool pairs,
+                                      const double *Psic = nullptr) {
     hipStream_t st = p->s_cmp;
     const int np = rup(nt, 128);   // the rows of the draws' product: k_tgemm's row tile
     const long mtp = rup(p->mtile, 1024);
+    if (Psic) {
+        if (launch_pnmc_rows(st, p->Xc[s], Psic, p->tile_pad, nt, np, p->m, p->mp, p->d, p->k, obs, p->nmcex, p->nmcphi, p->w_d,
+                             p->hetero ? p->pr.v : nullptr, p->mPio, mtp, p->mNo, p->mhd, mtp))
+            return gpz_fail(GPZ_ERR_HIP, "%s: k_pnmc launch failed", who);
+        if (pairs && launch_predict_noisy_missing_cov_pairs(st, p->Xc[s], Psic, p->tile_pad, nt, p->mPio, mtp, p->m, p->d, p->k, obs,
+                                                            p->mcraw, p->mcbas, p->mccoef, p->nmcslab, &p->nmcslab_kept, p->mchunks,
+                                                            p->mpart, mtp, p->mhd, mtp, p->pr.b, p->mout))
+            return gpz_fail(GPZ_ERR_HIP, "%s: k_predict_noisy_missing_cov_pairs launch failed", who);
+        return 0;
+    }
     if (launch_pmcv_rows(st, p->Xc[s], p->tile_pad, nt, np, p->m, p->mp, p->d, p->k, obs, p->mcex, p->mcphi, p->w_d,
                          p->hetero ? p->pr.v : nullptr, p->mPio, mtp, p->mNo, p->mhd, mtp))
         return gpz_fail(GPZ_ERR_HIP, "%s: k_pmcv launch failed", who);
@@ -735,7 +789,7 @@ static int predictor_missing_cov_tile(gpz_predictor *p, const char *who, int s, 
 // the kind's refusal of the model and, for a group, of its mask.  draws: the call has draws, which with Psi need the fused draws route
 int rows_check(const char *who, const gpz_predictor *p, const Rows &r, bool draws) {
     if (r.group())   // (with Psi too: its product against W needs no fused draws route)
-        return predictor_missing_check(who, p, r.obs, r.kind == ROWS_MISSING_COV);
+        return predictor_missing_check(who, p, r.obs, r.cov_group(), r.kind == ROWS_NOISY_MISSING_COV);
     if (r.kind == ROWS_CLEAN) return 0;
     if (r.kind == ROWS_NOISY_COV) return predictor_noisy_cov_check(who, p);   // (its draws are a product on the T-GEMM: any route)
     if (int rc = predictor_noisy_check(who, p)) return rc;
@@ -747,7 +801,13 @@ int rows_check(const char *who, const gpz_predictor *p, const Rows &r, bool draw
 // What the call needs on the handle before its first tile.  pairs: it reads the kind's pair tables (the moments, gamma per draw, the
 // stack); the draws alone do not, and take the Psi slots or the group's tables without them.
 int rows_prepare(gpz_predictor *p, const char *who, const Rows &r, bool pairs) {
-    if (r.kind == ROWS_MISSING_COV) return predictor_missing_cov_prepare(p, who, r.obs, r.priors, pairs);
+    if (r.cov_group()) {
+        if (int rc = r.psi() ? predictor_noisy_missing_cov_prepare(p, who, r.obs, r.priors, pairs)
+                             : predictor_missing_cov_prepare(p, who, r.obs, r.priors, pairs))
+            return rc;
+        if (r.kind == ROWS_NOISY_MISSING_COV) p->nmcov_used = true;
+        return 0;
+    }
     if (r.group()) return predictor_missing_prepare(p, who, r.obs, r.priors, pairs, r.kind == ROWS_NOISY_MISSING);
     if (r.kind == ROWS_NOISY) return pairs ? predictor_noisy_prepare(p) : predictor_psi_slots(p);
     if (r.kind == ROWS_NOISY_COV) return predictor_noisy_cov_prepare(p, pairs);
@@ -760,7 +820,7 @@ int64_t rows_tile(const gpz_predictor *p, const Rows &r, int64_t T) { return r.g
 // the moments of one tile of nt rows in slot s -> rows_moments: [3k][nt] = mu | nu | beta for clean rows (and PHI when asked), else
 // [4k][nt] = mu | nu | beta | gamma
 int rows_moments_tile(gpz_predictor *p, const char *who, const Rows &r, int s, int nt, bool want_phi) {
-    if (r.kind == ROWS_MISSING_COV) return predictor_missing_cov_tile(p, who, s, nt, r.obs, true);
+    if (r.cov_group()) return predictor_missing_cov_tile(p, who, s, nt, r.obs, true, r.psi() ? p->Psic[s] : nullptr);
     if (r.group()) return predictor_missing_tile(p, who, s, nt, r.obs, true, r.psi() ? p->Psic[s] : nullptr);
     if (r.kind == ROWS_NOISY) return predictor_noisy_tile(p, who, s, nt);
     if (r.kind == ROWS_NOISY_COV) return predictor_noisy_cov_tile(p, who, s, nt);
@@ -794,8 +854,8 @@ int rows_draws_tile(gpz_predictor *p, const char *who, const Rows &r, int s, int
     if (r.kind == ROWS_NOISY) return predictor_draws_tile(p, s, nt, ncol, ldw, false, p->Psic[s]);
     if (r.kind == ROWS_NOISY_COV) return predictor_noisy_cov_draws_tile(p, who, s, nt, ncol, ldw);
     if (!after_moments)   // (a covariance kind's PHI_missing lies in mNo as the diagonal kinds' does)
-        if (int rc = r.kind == ROWS_MISSING_COV ? predictor_missing_cov_tile(p, who, s, nt, r.obs, false)
-                                                : predictor_missing_tile(p, who, s, nt, r.obs, false, r.psi() ? p->Psic[s] : nullptr))
+        if (int rc = r.cov_group() ? predictor_missing_cov_tile(p, who, s, nt, r.obs, false, r.psi() ? p->Psic[s] : nullptr)
+                                   : predictor_missing_tile(p, who, s, nt, r.obs, false, r.psi() ? p->Psic[s] : nullptr))
             return rc;
     return predictor_missing_draws_tile(p, who, s, nt, ncol, ldw);
 }
@@ -1078,6 +1138,10 @@ extern "C" int gpz_predictor_route(const gpz_predictor *p, char *buf, int cap) {
         r += tmp;
     }
     per_draw(2);
+    if (p->nmcov_used) {   // after the first call for such a group on a covariance kind
+        snprintf(tmp, sizeof tmp, "; noisy missing: k_predict_noisy_missing_cov_pairs (%d pair chunks)", p->mchunks);
+        r += tmp;
+    }
     snprintf(buf, (size_t)cap, "%s", r.c_str());
     return (int)r.size();
 }

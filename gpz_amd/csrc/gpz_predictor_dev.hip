@@ -62,6 +62,12 @@ static DevCall with_noisy_pattern(DevCall c, const double *priors, uint32_t obs_
     return c;
 }
 
+// such a group with Psi on a covariance kind: with_psi first, then the pattern
+static DevCall with_noisy_cov_pattern(DevCall c, const double *priors, uint32_t obs_mask) {
+    c.rows = Rows{ROWS_NOISY_MISSING_COV, obs_mask, priors};
+    return c;
+}
+
 static int predictor_dev_args(const char *who, const gpz_predictor *p, const DevRows &x, const double *muX, const double *sdX) {
     if (x.type != GPZ_X_F64 && x.type != GPZ_X_F32)
         return gpz_fail(GPZ_ERR_ARG, "%s: x_type %d is neither GPZ_X_F64 nor GPZ_X_F32", who, (int)x.type);
@@ -211,7 +217,8 @@ static int predictor_run_dev(gpz_predictor *p, const char *who, DevCall &c, doub
     return rc;
 }
 
-// gpz_predictor_run_dev, _run_noisy_dev, _run_noisy_cov_dev, _run_missing_dev, _run_missing_cov_dev and _run_noisy_missing_dev
+// gpz_predictor_run_dev, _run_noisy_dev, _run_noisy_cov_dev, _run_missing_dev, _run_missing_cov_dev, _run_noisy_missing_dev and
+// _run_noisy_missing_cov_dev
 static int run_dev_entry(const char *who, gpz_predictor *p, DevCall c, double *mu_d, double *sigma_d, double *nu_d, double *beta_d,
                          double *gamma_d, double *PHI_d) {
     if (int rc = predictor_check_call(who, p, c.x.ns)) return rc;
@@ -443,6 +450,28 @@ extern "C" int gpz_predictor_draws_noisy_missing_dev(gpz_predictor *p, const voi
     return draws_dev_entry("gpz_predictor_draws_noisy_missing_dev", p,
                            with_noisy_pattern(with_psi(x, Psi_d, psi_type, psi_row_stride, psi_col_stride, sd2), priors, obs_mask), ndraws,
                            seed, Z, F_d);
+}
+
+extern "C" int gpz_predictor_run_noisy_missing_cov_dev(gpz_predictor *p, const void *X_d, int32_t x_type, int64_t ns, int64_t row_stride,
+                                                       int64_t col_stride, const void *Psi_d, int32_t psi_type, int64_t psi_row_stride,
+                                                       int64_t psi_col_stride, const double *muX, const double *sdX, const double *sd2,
+                                                       const double *muY, const double *priors, uint32_t obs_mask, double *mu_d,
+                                                       double *sigma_d, double *nu_d, double *beta_d, double *gamma_d, void *stream) {
+    const DevCall x = dev_call(X_d, x_type, ns, row_stride, col_stride, muX, sdX, muY, stream);
+    return run_dev_entry("gpz_predictor_run_noisy_missing_cov_dev", p,
+                         with_noisy_cov_pattern(with_psi(x, Psi_d, psi_type, psi_row_stride, psi_col_stride, sd2), priors, obs_mask), mu_d,
+                         sigma_d, nu_d, beta_d, gamma_d, nullptr);
+}
+
+extern "C" int gpz_predictor_draws_noisy_missing_cov_dev(gpz_predictor *p, const void *X_d, int32_t x_type, int64_t ns, int64_t row_stride,
+                                                         int64_t col_stride, const void *Psi_d, int32_t psi_type, int64_t psi_row_stride,
+                                                         int64_t psi_col_stride, const double *muX, const double *sdX, const double *sd2,
+                                                         const double *muY, const double *priors, uint32_t obs_mask, int32_t ndraws,
+                                                         uint64_t seed, const double *Z, double *F_d, void *stream) {
+    const DevCall x = dev_call(X_d, x_type, ns, row_stride, col_stride, muX, sdX, muY, stream);
+    return draws_dev_entry("gpz_predictor_draws_noisy_missing_cov_dev", p,
+                           with_noisy_cov_pattern(with_psi(x, Psi_d, psi_type, psi_row_stride, psi_col_stride, sd2), priors, obs_mask),
+                           ndraws, seed, Z, F_d);
 }
 
 extern "C" int gpz_predictor_stack_dev(gpz_predictor *p, const void *X_d, int32_t x_type, int64_t ns, int64_t row_stride,

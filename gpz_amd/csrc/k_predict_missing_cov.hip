@@ -405,6 +405,13 @@ static PmcvArgs pmcv_args(const PmcvPat &pt, const double *Xc, long ldx, int n, 
     return a;
 }
 
+// hd [2k][ldh] = PHI w | PHI v of n rows (k_pmcv_hd), for the units that build PHI of a group themselves
+int launch_pmcv_hd(hipStream_t st, const double *Phi, int n, int m, int mp, int k, const double *w, const double *v, double *hd, long ldh) {
+    if (n <= 0) return 0;
+    hipLaunchKernelGGL(k_pmcv_hd, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, Phi, n, m, mp, k, w, v, hd, ldh);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
 int launch_pmcv_rows(hipStream_t st, const double *Xc, long ldx, int n, int nrow, int m, int mp, int d, int k, unsigned obs,
                      const double *exrec, const double *phirec, const double *w, const double *v, double *Pio, long ldr, double *Phi,
                      double *hd, long ldh) {
@@ -422,8 +429,8 @@ int launch_pmcv_rows(hipStream_t st, const double *Xc, long ldx, int n, int nrow
     } while (0)
     PMCV_CASES(PMCV_ROWS)
 #undef PMCV_ROWS
-    hipLaunchKernelGGL(k_pmcv_hd, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, (const double *)Phi, n, m, mp, k, w, v, hd, ldh);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
+    if (hipGetLastError() != hipSuccess) return -1;
+    return launch_pmcv_hd(st, Phi, n, m, mp, k, w, v, hd, ldh);
 }
 
 // records [0, cnt * m) of the slab that starts at pair q0 (k_pmc_triples), for the units that read a slab without the pair kernel

@@ -4,7 +4,8 @@ The methods ask one of four questions (run: the moments of ``predict``; draws; d
 kinds (clean, noisy: with Psi, missing: one NaN-pattern group, noisy_missing: such a group with Psi); noisy_cov is the noisy kind of a
 covariance model (GC, VC), which has all four questions through methods of its own (``*_noisy_cov_dev``), and missing_cov the
 missing kind of such a model, which has all four too (``predict_missing_cov_dev``, ``draws_missing_cov_dev`` with ``return_gamma``,
-``stack_missing_cov_dev``).
+``stack_missing_cov_dev``); noisy_missing_cov is such a group with Psi, with the first two questions
+(``predict_noisy_missing_cov_dev``, ``draws_noisy_missing_cov_dev``).
 ``_DEV_ENTRIES`` names the device-resident entry of each pair, ``Predictor._dev_entry`` builds the arguments the entries of a pair
 share, and ``Predictor._dev_groups`` is the one loop over the groups of a call; the host methods choose between two entries each by
 whether Psi is there (``_HOST_ENTRIES``).  Everything numeric happens in the library; ``torch`` is only imported by the device methods.
@@ -39,6 +40,8 @@ _DEV_ENTRIES = {
     ("stack", "clean"): "gpz_predictor_stack_dev", ("stack", "noisy"): "gpz_predictor_stack_noisy_dev",
     ("stack", "missing"): "gpz_predictor_stack_missing_dev", ("stack", "noisy_missing"): "gpz_predictor_stack_noisy_missing_dev",
     ("draws_gamma", "missing_cov"): "gpz_predictor_draws_gamma_missing_cov_dev", ("stack", "missing_cov"): "gpz_predictor_stack_missing_cov_dev",
+    ("run", "noisy_missing_cov"): "gpz_predictor_run_noisy_missing_cov_dev",
+    ("draws", "noisy_missing_cov"): "gpz_predictor_draws_noisy_missing_cov_dev",
 }
 # (question, Psi there) -> the host entry
 _HOST_ENTRIES = {("draws", False): "gpz_predictor_draws", ("draws", True): "gpz_predictor_draws_noisy",
@@ -567,9 +570,9 @@ class Predictor:
         missing values, the priors and the mask of the observed dimensions.  ``run`` and ``draws`` take muY there, in front of the
         priors; ``stack`` takes the priors straight after sdX and muY at the end of its own arguments.  ``cov``: complete rows with Psi
         of a covariance kind, whose entries take the noisy kind's arguments, or a group with missing values of such a kind, whose
-        entries take the missing kind's.  Returns (entry, arguments, row kind)."""
+        entries take the missing kind's (with Psi too: the noisy missing kind's).  Returns (entry, arguments, row kind)."""
         noisy = Pg is not None
-        kind = ("noisy_missing" if noisy else "missing_cov" if cov else "missing") if code else \
+        kind = (("noisy_missing_cov" if cov else "noisy_missing") if noisy else "missing_cov" if cov else "missing") if code else \
             (("noisy_cov" if cov else "noisy") if noisy else "clean")
         lead = [call.h, *self._x_args(Xg)]
         if noisy:
@@ -801,6 +804,66 @@ class Predictor:
         n_draws, z = self._check_draw_args(n_draws, seed, Z, 1)
         self._check_dev_device(X=X, selection=selection, Psi=Psi)
         return self._draws_dev(X, Psi, selection, False, n_draws, seed, z, bool(return_gamma), cov=True)
+
+    def _check_noisy_missing_cov(self, what, X, Psi, selection):
+        """The checks the two methods for rows with Psi and missing values of a covariance kind share, none of which touches a GPU: X by
+        type, dtype and shape, then where such rows go when this is not their route (no Psi, a full Psi cube, a diagonal kind, a shape
+        outside predict_missing_cov_fits of k_predict_missing_cov.hip), then Psi's type, dtype and shape and the priors.  Returns X as
+        n x d and Psi as n x 1 or n x d."""
+        name = f"{what}_noisy_missing_cov_dev"
+        if isinstance(X, np.ndarray):
+            raise TypeError(f"{name} takes a torch tensor on cuda:{self.device}; a NumPy catalogue with input noise and missing values "
+                            "goes to Predictor.predict(X, Psi=Psi)")
+        X = self._check_dev_rows(X, selection, what)
+        if Psi is None:
+            raise ValueError(f"{name} needs Psi: rows of a covariance kind without input noise go to {what}_missing_cov_dev(X)")
+        if np.ndim(Psi) == 3 or (hasattr(Psi, "dim") and Psi.dim() == 3):
+            raise ValueError(f"{name} takes Psi as n x d, n x 1 or n variances: a full d x d x n Psi stays on "
+                             "Predictor.predict(X, Psi=Psi)")
+        if self._method[1] != "C":
+            raise ValueError(f"{name} is for the covariance kinds (GC, VC): a diagonal kind such as {self._method} goes to "
+                             f"{what}_noisy_missing_dev(X, Psi)")
+        if not (1 <= self._d <= 10 and 1 <= self._k <= 8 and 1 <= self._m <= 256):
+            raise ValueError(f"{name} needs a model inside predict_missing_cov_fits: GC or VC, d <= 10, k <= 8 and m <= 256; this one "
+                             f"is {self._method} with d = {self._d}, m = {self._m}, k = {self._k} (Predictor.predict takes rows with "
+                             "input noise and missing values for every shape)")
+        Psi = self._check_dev_psi(Psi, X.shape[0], what)
+        if self._priors.shape != (self._m,):
+            raise ValueError(f"the priors of the set must be {self._m} values, got {self._priors.size} (Predictor.predict reports "
+                             "the same for such rows)")
+        return X, Psi
+
+    def predict_noisy_missing_cov_dev(self, X, Psi, selection=None):
+        """``predict_noisy_missing_dev`` for a covariance kind (GC, VC; gpz_predictor_run_noisy_missing_cov_dev): a catalogue whose rows
+        have input noise and, some of them, missing values.  X, ``selection`` and ``Psi`` (variances per input dimension, (n, d),
+        (n, 1) or (n,), float64 or float32, any strides) as for ``predict_noisy_cov_dev``.  Returns mu, sigma, nu, beta_i, gamma as
+        ``predict(X, Psi=Psi)`` does, as float64 tensors of shape (n, k) on the device.  The rows are grouped by NaN pattern with torch
+        on the device: the complete rows go to gpz_predictor_run_noisy_cov_dev and get the bits of ``predict_noisy_cov_dev`` on them
+        alone; every other group is gathered with its Psi and gets predictNoisyMissing of predictCov.m:233-337 on the handle's tiles
+        (k_predict_noisy_missing_cov_pairs) with the priors of the set (1 / m without any).  Psi must be finite and >= 0 in a row's
+        observed dimensions (else GpzError); in its missing dimensions it is not read, whatever it holds, and a row with nothing
+        observed gets the bits of ``predict_missing_cov_dev``.  It needs a model inside predict_missing_cov_fits (GC or VC, d <= 10,
+        k <= 8, m <= 256), else ValueError; a full d x d x n Psi, PHI and host arrays stay on ``Predictor.predict``, a diagonal kind
+        goes to ``predict_noisy_missing_dev`` and rows without Psi to ``predict_missing_cov_dev``.  A row's results do not depend on the
+        tile size, the row order or the other rows of the call.  Type, dtype and shape are checked first, the device last, all before
+        the GPU is touched."""
+        self._check_open()
+        X, Psi = self._check_noisy_missing_cov("predict", X, Psi, selection)
+        self._check_dev_device(X=X, selection=selection, Psi=Psi)
+        return self._moments_dev(X, Psi, selection, True, cov=True)
+
+    def draws_noisy_missing_cov_dev(self, X, Psi, n_draws, seed=0, Z=None, selection=None):
+        """``draws_noisy_missing_dev`` for a covariance kind (gpz_predictor_draws_noisy_missing_cov_dev): X, ``Psi`` and ``selection`` as
+        for ``predict_noisy_missing_cov_dev``, ``n_draws``, ``seed`` and ``Z`` as for ``draws_dev``.  Returns a float64 tensor of shape
+        (n_draws, n, k) on the device: draws[s] is ``predict_noisy_missing_cov_dev``'s mu under weight draw s, PHI w_s + muY with the PHI
+        of predictNoisy or predictNoisyMissing - the mean is linear in the weights, so this is exact.  One weight draw serves all rows
+        of all groups; complete rows get the bits of ``draws_noisy_cov_dev`` on them alone.  Gamma per draw and the stack of such rows
+        are not on the handle."""
+        self._check_open()
+        X, Psi = self._check_noisy_missing_cov("draws", X, Psi, selection)
+        n_draws, z = self._check_draw_args(n_draws, seed, Z, 1)
+        self._check_dev_device(X=X, selection=selection, Psi=Psi)
+        return self._draws_dev(X, Psi, selection, True, n_draws, seed, z, False, cov=True)
 
     def _check_missing_cov(self, what, X, Psi, selection):
         """The checks the three methods for rows with missing values of a covariance kind share, none of which touches a GPU: X by type,

@@ -578,6 +578,41 @@ int gpz_predictor_draws_noisy_missing_dev(gpz_predictor *p, const void *X_d, int
                                           int32_t ndraws, uint64_t seed, const double *Z /* host: NULL or m x ndraws x k */,
                                           double *F_d /* ns x k x ndraws, column-major */, void *stream);
 
+/* ---- rows with input noise AND missing inputs on the predictor handle, covariance kinds -------------------------------------------------
+ * predictNoisyMissing of predictCov.m:233-337 and the draws of its mean for ONE group of rows that share a NaN pattern and carry a
+ * variance per input dimension (entering as psi / sd2[c] on the diagonal of the row's Psi, as fixPsi puts it there; a full d x d x n
+ * cube stays on gpz_predict_missing), where predict_missing_cov_fits holds (GC or VC, 1 <= d <= 10, k <= 8, ceil16(m) <= 256); any
+ * other shape returns GPZ_ERR_UNSUPPORTED and names the function, a diagonal kind GPZ_ERR_UNSUPPORTED naming
+ * gpz_predictor_run_noisy_missing_dev.  The arguments are exactly those of gpz_predictor_run_noisy_missing_dev /
+ * _draws_noisy_missing_dev, and the scans before the first tile are theirs: a row whose NaN pattern differs from the mask and an
+ * element of Psi that is NaN, negative or infinite IN AN OBSERVED DIMENSION are GPZ_ERR_ARG with their texts, outputs untouched.  Psi
+ * in a missing dimension is never read; a group with nothing observed (obs_mask 0) reads no Psi at all and gets the bits of
+ * gpz_predictor_run_missing_cov_dev / _draws_missing_cov_dev.  Complete rows go to gpz_predictor_run_noisy_cov_dev /
+ * _draws_noisy_cov_dev.
+ * Every density of predictNoisyMissing is N(T x_o + s - c ; S + G Psi_oo G') with S, T and s of predictMissing and G the rows of T where
+ * predictCov.m:271-273 scatters them through `unshuffle` (kept as written: G = T only where [observed | missing] is its own inverse).
+ * Whitened by S and split by a QR of G, the exponent is a sum of d - no squares and one no x no form in (M + Psi_oo)^-1, written once
+ * per pattern as a record of 1 + no + no (no + 1) / 2 + no no + (d - no)(no + 1) doubles (k_predict_noisy_missing_cov.hip), so a
+ * density costs a packed no x no Cholesky of M + diag(psi_o) and a forward substitution in registers, not a d x d factorisation.
+ * The tile buffers, the pattern's [R | CU | off] and coefficients, the chunks and the order of every sum are those of the missing_cov
+ * entries, whose own tables stay valid; the first call adds the Psi slots where the handle has none, the Ex and PHI records and a
+ * slab of at most 64 MB in this form, sized for the widest pattern of the model.
+ * Nothing grows with ns or the number of patterns, a handle that never makes such a call holds what it held, and a row's results
+ * have the same bits for any tile size, row order, company or split of the rows into calls.  The draws are PHI W + muY with the
+ * handle's weight draws.  gpz_predictor_route then holds "; noisy missing: k_predict_noisy_missing_cov_pairs (C pair chunks)".
+ * The stack and gamma per draw of such rows, host arrays and PHI are not on the handle. */
+int gpz_predictor_run_noisy_missing_cov_dev(gpz_predictor *p, const void *X_d, int32_t x_type, int64_t ns, int64_t row_stride,
+                                            int64_t col_stride, const void *Psi_d, int32_t psi_type, int64_t psi_row_stride,
+                                            int64_t psi_col_stride, const double *muX, const double *sdX, const double *sd2,
+                                            const double *muY /* k or NULL */, const double *priors /* m or NULL */, uint32_t obs_mask,
+                                            double *mu_d, double *sigma_d, double *nu_d, double *beta_d, double *gamma_d, void *stream);
+int gpz_predictor_draws_noisy_missing_cov_dev(gpz_predictor *p, const void *X_d, int32_t x_type, int64_t ns, int64_t row_stride,
+                                              int64_t col_stride, const void *Psi_d, int32_t psi_type, int64_t psi_row_stride,
+                                              int64_t psi_col_stride, const double *muX, const double *sdX, const double *sd2,
+                                              const double *muY /* k or NULL */, const double *priors /* m or NULL */, uint32_t obs_mask,
+                                              int32_t ndraws, uint64_t seed, const double *Z /* host: NULL or m x ndraws x k */,
+                                              double *F_d /* ns x k x ndraws, column-major */, void *stream);
+
 /* ---- stacked densities of rows with input noise AND missing inputs, and gamma under every weight draw ----------------------------------
  * gpz_predictor_stack_noisy_dev for ONE group of rows that share a NaN pattern and carry a variance per input dimension, and
  * gpz_predictor_draws_noisy_missing_dev with gamma: the scope (predict_missing_fits), Psi, priors, obs_mask, the scans of the pattern
