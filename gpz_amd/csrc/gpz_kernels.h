@@ -378,6 +378,16 @@ int launch_predict_noisy_missing_cov_pairs(hipStream_t st, const double *Xc, con
                                            long ldr, int m, int d, int k, unsigned obs, const double *raw, const double *bas,
                                            const double *coef, double *slab, bool *slab_kept, int nchunk, double *part, long ldp,
                                            const double *hd, long ldh, const double *bvec, double *out);
+// launch_pnmc_triples: the records of cnt whole pairs from pair q0 into slab, as the pair launcher writes them (launch_pmc_triples' twin).
+// launch_predict_noisy_missing_cov_gamma (k_predict_noisy_missing_cov_gamma.hip; gpz_predictor_stack_noisy_missing_cov_dev,
+// _draws_gamma_noisy_missing_cov_dev): launch_predict_missing_cov_gamma with Psic and this unit's records and slabs -> part
+// [predict_missing_cov_chunks(m)][ncol][ldp], from Pio of launch_pnmc_rows; a slab that is not kept is written here and *slab_kept set
+// as launch_predict_noisy_missing_cov_pairs sets it.  Returns -1 when a launch failed.
+int launch_pnmc_triples(hipStream_t st, int d, unsigned obs, long q0, long cnt, int m, const double *raw, const double *bas, double *slab);
+size_t predict_noisy_missing_cov_gamma_lds(int m, int d, int no);   // dynamic LDS of the gamma kernel, bytes
+int launch_predict_noisy_missing_cov_gamma(hipStream_t st, const double *Xc, const double *Psic, long ldx, int n, const double *Pio,
+                                           long ldr, int m, int d, unsigned obs, const double *raw, const double *bas, double *slab,
+                                           bool *slab_kept, const double *W, int ldw, int ncol, int nchunk, double *part, long ldp);
 // B (rows x ld row-major) <- [iS (m x m column-major) | nw columns of W from column wcol | nv columns of V (nullptr: 0) from vcol | 0]
 void launch_pred_fill_b(hipStream_t st, const double *iS, const double *W, int nw, int wcol, const double *V, int nv, int vcol, int m,
                         int rows, int ld, double *B);

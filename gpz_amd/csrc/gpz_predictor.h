@@ -62,7 +62,8 @@ struct gpz_predictor {
     // inputs (gpz_predictor_stack_missing_dev, _draws_gamma_missing_dev), of rows with both (gpz_predictor_stack_noisy_missing_dev,
     // _draws_gamma_noisy_missing_dev), and of rows with input noise on a covariance kind (gpz_predictor_stack_noisy_cov_dev,
     // _draws_gamma_noisy_cov_dev), and of rows with missing inputs on a covariance kind (gpz_predictor_stack_missing_cov_dev,
-    // _draws_gamma_missing_cov_dev): nothing of a kind before its first such call
+    // _draws_gamma_missing_cov_dev), and of such rows with input noise too (gpz_predictor_stack_noisy_missing_cov_dev,
+    // _draws_gamma_noisy_missing_cov_dev): nothing of a kind before its first such call
     int gchunks = 0;               // predict_gamma_chunks of the model (input noise, either kind; a group with missing inputs has mchunks)
     double *gpart = nullptr;       // [chunks][nd k][tile] pair sums per chunk, of either kind
     size_t gpart_cap = 0;          // doubles
@@ -70,7 +71,8 @@ struct gpz_predictor {
         bool used = false;
         double *s2_d = nullptr;    // [(1 + nd) k][tile] widths^2 of the stack
         size_t s2_cap = 0;         // doubles
-    } gam[5];                      // [ROWS_NOISY - 1], [ROWS_MISSING - 1], [ROWS_NOISY_MISSING - 1], [ROWS_NOISY_COV - 1], [ROWS_MISSING_COV - 1]
+    } gam[6];                      // [ROWS_NOISY - 1], [ROWS_MISSING - 1], [ROWS_NOISY_MISSING - 1], [ROWS_NOISY_COV - 1], [ROWS_MISSING_COV - 1],
+                                   // [ROWS_NOISY_MISSING_COV - 1]
     // ---- rows with missing inputs on the handle (gpz_predictor_*_missing_dev): nothing of this exists before the first of their calls
     bool miss_used = false;
     int64_t mtile = 0;             // rows per tile of a group: min(tile_rows, GPZ_PREDICTOR_TILE_MISSING)

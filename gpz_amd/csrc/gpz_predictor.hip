@@ -62,7 +62,9 @@
 // epilogue between them); gpz_predictor_draws_gamma_noisy_missing_dev returns that gamma beside the draws.
 // The covariance kinds have the first two of these as gpz_predictor_run_noisy_missing_cov_dev / _draws_noisy_missing_cov_dev
 // (k_predict_noisy_missing_cov.hip): the frame, tile buffers and pattern tables of the missing_cov entries, with record tables of
-// their own whose density is a packed no x no Cholesky of M + diag(psi_o) per row (predictor_noisy_missing_cov_prepare).
+// their own whose density is a packed no x no Cholesky of M + diag(psi_o) per row (predictor_noisy_missing_cov_prepare), and the other
+// two as gpz_predictor_stack_noisy_missing_cov_dev / _draws_gamma_noisy_missing_cov_dev, with gamma under every draw from
+// k_predict_noisy_missing_cov_gamma.hip (k_predict_missing_cov_gamma's frame on those records and that slab).
 // Layout: gpz_predictor.h holds the handle and what the three units share.  This unit holds the handle's life and setup, what a tile is
 // made of for each kind of rows (clean, with Psi, one NaN-pattern group: the rows_* functions), draws preparation and factorisation, the
 // stack's preparation and tile, the checks the entries share, route and info.  gpz_predictor_host.hip holds the host pipeline, its jobs
@@ -888,6 +890,16 @@ int rows_gamma_tile(gpz_predictor *p, const char *who, const Rows &r, int s, int
             return gpz_fail(GPZ_ERR_HIP, "%s: k_predict_missing_cov_gamma launch failed", who);
         return 0;
     }
+    if (r.kind == ROWS_NOISY_MISSING_COV) {   // its own records and slab; nothing observed: no Psi to read, the group is the kind's above
+        if (!r.psi() ? launch_predict_missing_cov_gamma(p->s_cmp, p->Xc[s], p->tile_pad, nt, p->mPio, rup(p->mtile, 1024), p->m, p->d, r.obs,
+                                                        p->mcraw, p->mcbas, p->mcslab, &p->mcslab_kept, p->Wd, ldw, ncol, p->mchunks,
+                                                        p->gpart, nt)
+                     : launch_predict_noisy_missing_cov_gamma(p->s_cmp, p->Xc[s], p->Psic[s], p->tile_pad, nt, p->mPio, rup(p->mtile, 1024),
+                                                              p->m, p->d, r.obs, p->mcraw, p->mcbas, p->nmcslab, &p->nmcslab_kept, p->Wd,
+                                                              ldw, ncol, p->mchunks, p->gpart, nt))
+            return gpz_fail(GPZ_ERR_HIP, "%s: k_predict_noisy_missing_cov_gamma launch failed", who);
+        return 0;
+    }
     // a group with Psi: the second record table
     if (r.kind == ROWS_NOISY
             ? launch_predict_noisy_gamma(p->s_cmp, p->d, p->Xc[s], p->Psic[s], p->tile_pad, nt, p->m, p->ptab, p->nrec, p->Wd, ldw, ncol,
@@ -1090,12 +1102,13 @@ extern "C" int gpz_predictor_route(const gpz_predictor *p, char *buf, int cap) {
         snprintf(tmp, sizeof tmp, "tiles: k_phi + k_tgemm, %lld-row tiles", (long long)p->tile_rows);
     std::string r = tmp;
     // after the first stack or gamma-per-draw call for a kind of rows (gam[kind - 1]): its kernel and chunks (a group's: mchunks)
-    static const struct { const char *fmt; bool group; } PER_DRAW[5] = {
+    static const struct { const char *fmt; bool group; } PER_DRAW[6] = {
         {"; noise per draw: k_predict_noisy_gamma (%d pair chunks)", false},
         {"; missing per draw: k_predict_missing_gamma (%d pair chunks)", true},
         {"; noisy missing per draw: k_predict_noisy_missing_gamma (%d pair chunks)", true},
         {"; noise per draw: k_predict_noisy_cov_gamma (%d pair chunks)", false},
-        {"; missing per draw: k_predict_missing_cov_gamma (%d pair chunks)", true}};
+        {"; missing per draw: k_predict_missing_cov_gamma (%d pair chunks)", true},
+        {"; noisy missing per draw: k_predict_noisy_missing_cov_gamma (%d pair chunks)", true}};
     auto per_draw = [&](int i) {
         if (!p->gam[i].used) return;
         snprintf(tmp, sizeof tmp, PER_DRAW[i].fmt, PER_DRAW[i].group ? p->mchunks : p->gchunks);
@@ -1142,6 +1155,7 @@ extern "C" int gpz_predictor_route(const gpz_predictor *p, char *buf, int cap) {
         snprintf(tmp, sizeof tmp, "; noisy missing: k_predict_noisy_missing_cov_pairs (%d pair chunks)", p->mchunks);
         r += tmp;
     }
+    per_draw(5);
     snprintf(buf, (size_t)cap, "%s", r.c_str());
     return (int)r.size();
 }

@@ -257,7 +257,7 @@ static int predictor_run_draws_dev(gpz_predictor *p, const char *who, DevCall &c
     return predictor_dev_sync(p, who, rc);
 }
 
-// gpz_predictor_draws_dev, _draws_noisy_dev, _draws_noisy_cov_dev, _draws_missing_dev, _draws_missing_cov_dev, _draws_noisy_missing_dev and, with want_gamma, _draws_gamma_noisy_dev, _draws_gamma_noisy_cov_dev, _draws_gamma_missing_dev, _draws_gamma_missing_cov_dev and _draws_gamma_noisy_missing_dev
+// gpz_predictor_draws_dev, _draws_noisy_dev, _draws_noisy_cov_dev, _draws_missing_dev, _draws_missing_cov_dev, _draws_noisy_missing_dev and, with want_gamma, _draws_gamma_noisy_dev, _draws_gamma_noisy_cov_dev, _draws_gamma_missing_dev, _draws_gamma_missing_cov_dev, _draws_gamma_noisy_missing_dev and _draws_gamma_noisy_missing_cov_dev
 static int draws_dev_entry(const char *who, gpz_predictor *p, DevCall c, int32_t ndraws, uint64_t seed, const double *Z, double *F_d,
                            double *Gam_d = nullptr, bool want_gamma = false) {
     if (int rc = predictor_check_call(who, p, c.x.ns)) return rc;
@@ -287,7 +287,7 @@ static int predictor_run_stack_dev(gpz_predictor *p, const char *who, DevCall &c
     return predictor_dev_sync(p, who, rc);
 }
 
-// gpz_predictor_stack_dev, _stack_noisy_dev, _stack_noisy_cov_dev, _stack_missing_dev, _stack_missing_cov_dev and _stack_noisy_missing_dev
+// gpz_predictor_stack_dev, _stack_noisy_dev, _stack_noisy_cov_dev, _stack_missing_dev, _stack_missing_cov_dev, _stack_noisy_missing_dev and _stack_noisy_missing_cov_dev
 static int stack_dev_entry(const char *who, gpz_predictor *p, DevCall c, const StackArgs &a) {
     return stack_entry(
         who, p, c.x.ns, c.x.X, a, false,
@@ -548,4 +548,29 @@ extern "C" int gpz_predictor_stack_noisy_missing_dev(gpz_predictor *p, const voi
     const StackArgs a{ndraws, seed, Z, edges, nbins, group_d, ngroups, weight_d, hist, sum_w, sum_mu, sum_mu2, mu_shift};
     return stack_dev_entry("gpz_predictor_stack_noisy_missing_dev", p,
                            with_noisy_pattern(with_psi(x, Psi_d, psi_type, psi_row_stride, psi_col_stride, sd2), priors, obs_mask), a);
+}
+
+extern "C" int gpz_predictor_draws_gamma_noisy_missing_cov_dev(gpz_predictor *p, const void *X_d, int32_t x_type, int64_t ns,
+                                                               int64_t row_stride, int64_t col_stride, const void *Psi_d, int32_t psi_type,
+                                                               int64_t psi_row_stride, int64_t psi_col_stride, const double *muX,
+                                                               const double *sdX, const double *sd2, const double *muY,
+                                                               const double *priors, uint32_t obs_mask, int32_t ndraws, uint64_t seed,
+                                                               const double *Z, double *F_d, double *Gam_d, void *stream) {
+    const DevCall x = dev_call(X_d, x_type, ns, row_stride, col_stride, muX, sdX, muY, stream);
+    return draws_dev_entry("gpz_predictor_draws_gamma_noisy_missing_cov_dev", p,
+                           with_noisy_cov_pattern(with_psi(x, Psi_d, psi_type, psi_row_stride, psi_col_stride, sd2), priors, obs_mask),
+                           ndraws, seed, Z, F_d, Gam_d, true);
+}
+
+extern "C" int gpz_predictor_stack_noisy_missing_cov_dev(gpz_predictor *p, const void *X_d, int32_t x_type, int64_t ns, int64_t row_stride,
+                                                         int64_t col_stride, const void *Psi_d, int32_t psi_type, int64_t psi_row_stride,
+                                                         int64_t psi_col_stride, const double *muX, const double *sdX, const double *sd2,
+                                                         const double *priors, uint32_t obs_mask, int32_t ndraws, uint64_t seed,
+                                                         const double *Z, const double *edges, int32_t nbins, const int32_t *group_d,
+                                                         int32_t ngroups, const double *weight_d, double *hist, double *sum_w,
+                                                         double *sum_mu, double *sum_mu2, const double *mu_shift, void *stream) {
+    const DevCall x = dev_call(X_d, x_type, ns, row_stride, col_stride, muX, sdX, nullptr, stream);
+    const StackArgs a{ndraws, seed, Z, edges, nbins, group_d, ngroups, weight_d, hist, sum_w, sum_mu, sum_mu2, mu_shift};
+    return stack_dev_entry("gpz_predictor_stack_noisy_missing_cov_dev", p,
+                           with_noisy_cov_pattern(with_psi(x, Psi_d, psi_type, psi_row_stride, psi_col_stride, sd2), priors, obs_mask), a);
 }

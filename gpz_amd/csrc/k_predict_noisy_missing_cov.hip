@@ -34,10 +34,11 @@
 // k_pmcv_hd, k_pmcv_coef, k_pmd_finish and the draws' product are k_predict_missing_cov.hip's.  No atomics; every sum starts from zero
 // in an order fixed by m, d and no: the same bits for any tile size, row order, company, position in the block and split into calls.
 // A group with nothing observed (no = 0) has no Psi to read and is k_predict_missing_cov.hip's own (the host sends it there).
+// pnmc_density<NO>, the density of one record that every tile kernel here shares, and the switch over NO live in k_pnmc_density.h:
+// k_predict_noisy_missing_cov_gamma.hip (gamma under every weight draw) forms its densities with them from this unit's slabs.
 #include "gpz_dev.h"
 #include "gpz_kernels.h"
-#include "k_pmcv_density.h"   // PMCV_MAXD, PmcvPat, pmcv_pat
-#include "k_ncov_density.h"   // ncov_factor, ncov_density, LT
+#include "k_pnmc_density.h"   // pnmc_density, PNMC_CASES; PMCV_MAXD, PmcvPat, pmcv_pat; LT
 
 #define PNMC_STD 2048                 // doubles per LDS stage of the Ex and PHI kernels (whole records: at least 13)
 #define PNMC_SB 4                     // records per LDS stage of a wave of the pair kernel
@@ -182,40 +183,6 @@ __global__ __launch_bounds__(64) void k_pnmc_triples(PmcvPat pt, long q0, long c
     const double *t = raw + (size_t)(q0 + q) * (1 + pt.d + pt.d * pt.d);
     pnmc_cond_record(pt, t + 1 + pt.d, t + 1, t[0], bas + (size_t)l * nb, slab + (size_t)e * rl);
 }
-
-// ---- the density every tile kernel shares ----------------------------------------------------------------------------------------------
-// t: the record, the same address in every lane; x, ps: the row's observed inputs and their variances; nu: the missing dimensions
-template <int NO>
-__device__ __forceinline__ double pnmc_density(const double *t, int nu, const double (&x)[NO], const double (&ps)[NO]) {
-    constexpr int TRI = NO * (NO + 1) / 2;
-    const double *J = t + 1 + NO + TRI, *A2 = J + NO * NO, *b2 = A2 + nu * NO;
-    double w[NO], q2 = 0.0;
-#pragma unroll
-    for (int r = 0; r < NO; ++r) {
-        double s = 0.0;
-#pragma unroll
-        for (int c = 0; c < NO; ++c) s = fma(J[r * NO + c], x[c], s);
-        w[r] = s;
-    }
-#pragma unroll 1
-    for (int r = 0; r < nu; ++r) {
-        double s = b2[r];
-#pragma unroll
-        for (int c = 0; c < NO; ++c) s = fma(A2[r * NO + c], x[c], s);
-        q2 = fma(s, s, q2);
-    }
-    double M[TRI], rd[NO], prd;
-    ncov_factor<NO>(t + 1 + NO, ps, M, rd, &prd);
-    return ncov_density<NO>(t + 1, t[0] - 0.5 * q2, w, M, rd, prd);
-}
-
-#define PNMC_CASES(MACRO)                                                                                  \
-    switch (pt.no) {                                                                                       \
-        case 1: MACRO(1); break; case 2: MACRO(2); break; case 3: MACRO(3); break; case 4: MACRO(4); break; \
-        case 5: MACRO(5); break; case 6: MACRO(6); break; case 7: MACRO(7); break; case 8: MACRO(8); break; \
-        case 9: MACRO(9); break;                                                                           \
-        default: return -1;                                                                                \
-    }
 
 // ---- the tile kernels ------------------------------------------------------------------------------------------------------------------
 struct PnmcArgs {
@@ -428,6 +395,17 @@ int launch_pnmc_rows(hipStream_t st, const double *Xc, const double *Psic, long 
     return launch_pmcv_hd(st, Phi, n, m, mp, k, w, v, hd, ldh);
 }
 
+// records [0, cnt * m) of the slab that starts at pair q0 (k_predict_noisy_missing_cov_gamma.hip fills a slab through it too)
+int launch_pnmc_triples(hipStream_t st, int d, unsigned obs, long q0, long cnt, int m, const double *raw, const double *bas, double *slab) {
+    if (cnt <= 0) return 0;
+    if (d < 1 || d > PMCV_MAXD || m < 1) return -1;
+    const PmcvPat pt = pmcv_pat(d, obs);
+    if (pt.no < 1 || pt.nu < 1) return -1;
+    hipLaunchKernelGGL(k_pnmc_triples, dim3((unsigned)((cnt * m + 63) / 64)), dim3(64), 0, st, pt, q0, cnt, m, raw, bas,
+                       predict_missing_cov_bas(d, pt.no), slab, predict_noisy_missing_cov_rec(d, pt.no));
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
 // per launch, not once per process: the attribute belongs to the current device's copy of the kernel
 template <int NO, int KM>
 static int pnmc_launch_pairs(hipStream_t st, dim3 grid, size_t lds, const PnmcArgs &a) {
@@ -450,7 +428,7 @@ int launch_predict_noisy_missing_cov_pairs(hipStream_t st, const double *Xc, con
         return -1;
     const PmcvPat pt = pmcv_pat(d, obs);
     if (pt.nu < 1 || pt.no < 1) return -1;
-    const int nb = predict_missing_cov_bas(d, pt.no), nslab = predict_noisy_missing_cov_slabs(m, d, pt.no);
+    const int nslab = predict_noisy_missing_cov_slabs(m, d, pt.no);
     const long npair = (long)m * (m + 1) / 2, sp = predict_noisy_missing_cov_slab_pairs(m, d, pt.no);
     PnmcArgs a = pnmc_args(pt, Xc, Psic, ldx, n, m, k, const_cast<double *>(Pio), ldr, slab);
     a.coef = coef; a.part = part; a.ldp = ldp;
@@ -459,11 +437,8 @@ int launch_predict_noisy_missing_cov_pairs(hipStream_t st, const double *Xc, con
     for (int s = 0; s < nslab; ++s) {
         const long q0 = s * sp, cnt = (npair - q0 < sp) ? npair - q0 : sp;
         if (cnt <= 0) break;
-        if (!(nslab == 1 && *slab_kept)) {   // the whole table is one slab: it stays until the pattern's tables change
-            hipLaunchKernelGGL(k_pnmc_triples, dim3((unsigned)((cnt * m + 63) / 64)), dim3(64), 0, st, pt, q0, cnt, m, raw, bas, nb, slab,
-                               a.rl);
-            if (hipGetLastError() != hipSuccess) return -1;
-        }
+        // the whole table is one slab: it stays until the pattern's tables change, whichever kernel filled it
+        if (!(nslab == 1 && *slab_kept) && launch_pnmc_triples(st, d, obs, q0, cnt, m, raw, bas, slab)) return -1;
         a.q0 = q0; a.cnt = (int)cnt; a.ppc = (int)((cnt + nchunk - 1) / nchunk); a.first = s == 0;
         int rc;
 #define PNMC_PAIRS(NN) rc = k == 1 ? pnmc_launch_pairs<NN, 1>(st, grid, lds, a) : pnmc_launch_pairs<NN, 8>(st, grid, lds, a)

@@ -4,8 +4,8 @@ The methods ask one of four questions (run: the moments of ``predict``; draws; d
 kinds (clean, noisy: with Psi, missing: one NaN-pattern group, noisy_missing: such a group with Psi); noisy_cov is the noisy kind of a
 covariance model (GC, VC), which has all four questions through methods of its own (``*_noisy_cov_dev``), and missing_cov the
 missing kind of such a model, which has all four too (``predict_missing_cov_dev``, ``draws_missing_cov_dev`` with ``return_gamma``,
-``stack_missing_cov_dev``); noisy_missing_cov is such a group with Psi, with the first two questions
-(``predict_noisy_missing_cov_dev``, ``draws_noisy_missing_cov_dev``).
+``stack_missing_cov_dev``); noisy_missing_cov is such a group with Psi, with all four as well
+(``predict_noisy_missing_cov_dev``, ``draws_noisy_missing_cov_dev`` with ``return_gamma``, ``stack_noisy_missing_cov_dev``).
 ``_DEV_ENTRIES`` names the device-resident entry of each pair, ``Predictor._dev_entry`` builds the arguments the entries of a pair
 share, and ``Predictor._dev_groups`` is the one loop over the groups of a call; the host methods choose between two entries each by
 whether Psi is there (``_HOST_ENTRIES``).  Everything numeric happens in the library; ``torch`` is only imported by the device methods.
@@ -42,6 +42,8 @@ _DEV_ENTRIES = {
     ("draws_gamma", "missing_cov"): "gpz_predictor_draws_gamma_missing_cov_dev", ("stack", "missing_cov"): "gpz_predictor_stack_missing_cov_dev",
     ("run", "noisy_missing_cov"): "gpz_predictor_run_noisy_missing_cov_dev",
     ("draws", "noisy_missing_cov"): "gpz_predictor_draws_noisy_missing_cov_dev",
+    ("draws_gamma", "noisy_missing_cov"): "gpz_predictor_draws_gamma_noisy_missing_cov_dev",
+    ("stack", "noisy_missing_cov"): "gpz_predictor_stack_noisy_missing_cov_dev",
 }
 # (question, Psi there) -> the host entry
 _HOST_ENTRIES = {("draws", False): "gpz_predictor_draws", ("draws", True): "gpz_predictor_draws_noisy",
@@ -806,7 +808,7 @@ class Predictor:
         return self._draws_dev(X, Psi, selection, False, n_draws, seed, z, bool(return_gamma), cov=True)
 
     def _check_noisy_missing_cov(self, what, X, Psi, selection):
-        """The checks the two methods for rows with Psi and missing values of a covariance kind share, none of which touches a GPU: X by
+        """The checks the three methods for rows with Psi and missing values of a covariance kind share, none of which touches a GPU: X by
         type, dtype and shape, then where such rows go when this is not their route (no Psi, a full Psi cube, a diagonal kind, a shape
         outside predict_missing_cov_fits of k_predict_missing_cov.hip), then Psi's type, dtype and shape and the priors.  Returns X as
         n x d and Psi as n x 1 or n x d."""
@@ -852,18 +854,41 @@ class Predictor:
         self._check_dev_device(X=X, selection=selection, Psi=Psi)
         return self._moments_dev(X, Psi, selection, True, cov=True)
 
-    def draws_noisy_missing_cov_dev(self, X, Psi, n_draws, seed=0, Z=None, selection=None):
+    def draws_noisy_missing_cov_dev(self, X, Psi, n_draws, seed=0, Z=None, selection=None, return_gamma=False):
         """``draws_noisy_missing_dev`` for a covariance kind (gpz_predictor_draws_noisy_missing_cov_dev): X, ``Psi`` and ``selection`` as
         for ``predict_noisy_missing_cov_dev``, ``n_draws``, ``seed`` and ``Z`` as for ``draws_dev``.  Returns a float64 tensor of shape
         (n_draws, n, k) on the device: draws[s] is ``predict_noisy_missing_cov_dev``'s mu under weight draw s, PHI w_s + muY with the PHI
         of predictNoisy or predictNoisyMissing - the mean is linear in the weights, so this is exact.  One weight draw serves all rows
-        of all groups; complete rows get the bits of ``draws_noisy_cov_dev`` on them alone.  Gamma per draw and the stack of such rows
-        are not on the handle."""
+        of all groups; complete rows get the bits of ``draws_noisy_cov_dev`` on them alone.
+        ``return_gamma=True`` (gpz_predictor_draws_gamma_noisy_missing_cov_dev) returns ``(F, Gam)``: F with the bits it has without the
+        keyword, Gam a float64 tensor of shape (n_draws, n, k), predictNoisyMissing's gamma of predictCov.m under the weights of draw
+        s - the variance of PHI(x) w_s over the input noise and the missing dimensions together, not clamped at 0
+        (k_predict_noisy_missing_cov_gamma); complete rows get ``draws_noisy_cov_dev(..., return_gamma=True)``'s and rows with nothing
+        observed ``draws_missing_cov_dev(..., return_gamma=True)``'s.  A y-draw of row i under draw s has variance beta_i + Gam[s, i].
+        A row's Gam has the same bits for any tile size, row order, other rows of the call and any n_draws > s."""
         self._check_open()
         X, Psi = self._check_noisy_missing_cov("draws", X, Psi, selection)
         n_draws, z = self._check_draw_args(n_draws, seed, Z, 1)
         self._check_dev_device(X=X, selection=selection, Psi=Psi)
-        return self._draws_dev(X, Psi, selection, True, n_draws, seed, z, False, cov=True)
+        return self._draws_dev(X, Psi, selection, True, n_draws, seed, z, bool(return_gamma), cov=True)
+
+    def stack_noisy_missing_cov_dev(self, X, Psi, edges, n_draws=64, seed=0, Z=None, groups=None, n_groups=None, weights=None,
+                                    selection=None):
+        """``stack_noisy_missing_dev`` for a covariance kind (GC, VC; gpz_predictor_stack_noisy_missing_cov_dev): a catalogue whose rows
+        have input noise and, some of them, missing values.  X, ``Psi`` and ``selection`` as for ``predict_noisy_missing_cov_dev``
+        (Psi is not read in a row's missing dimensions), everything else as for ``stack_dev``; ``n_draws`` defaults to 64.  The rows are
+        grouped by NaN pattern with torch on the device.  The complete rows go to gpz_predictor_stack_noisy_cov_dev (a catalogue
+        without NaN gives ``stack_noisy_cov_dev``'s bits), every other group with its Psi, labels and weights to
+        gpz_predictor_stack_noisy_missing_cov_dev (rows with nothing observed get ``stack_missing_cov_dev``'s), and the groups' results
+        are added field by field in ascending order of the pattern code, so the call equals the ``+=`` of the single-pattern calls bit
+        for bit; one weight draw serves all groups.  For a row with missing values column 0 uses ``predict_noisy_missing_cov_dev``'s mu
+        and that call's sigma = (nu + beta_i) + gamma, bit for bit; column 1 + s ``draws_noisy_missing_cov_dev``'s draw s and the width
+        beta_i + max(gamma_s, 0), where gamma_s is that method's ``return_gamma=True``.  ``n_groups`` and the range of the labels are
+        decided over all rows.  It needs a model inside predict_missing_cov_fits (GC or VC, d <= 10, k <= 8, m <= 256), else
+        ValueError; a diagonal kind goes to ``stack_noisy_missing_dev``, rows without Psi to ``stack_missing_cov_dev``, and a full
+        d x d x n Psi and host arrays stay on ``Predictor.predict``.  A label outside [-1, n_groups) and a negative or non-finite
+        weight are found on the device before the first tile and refused with a GpzError."""
+        return self._stack_dev(X, Psi, edges, n_draws, seed, Z, groups, n_groups, weights, selection, missing=True, both=True, cov=True)
 
     def _check_missing_cov(self, what, X, Psi, selection):
         """The checks the three methods for rows with missing values of a covariance kind share, none of which touches a GPU: X by type,
@@ -937,8 +962,8 @@ class Predictor:
         column 0 uses ``predict_missing_cov_dev``'s mu and that call's sigma = (nu + beta_i) + gamma, bit for bit; column 1 + s
         ``draws_missing_cov_dev``'s draw s and the width beta_i + max(gamma_s, 0), where gamma_s is that method's ``return_gamma=True``.
         ``n_groups`` and the range of the labels are decided over all rows.  It needs a model inside predict_missing_cov_fits (GC or
-        VC, d <= 10, k <= 8, m <= 256), else ValueError; a diagonal kind goes to ``stack_missing_dev``, and host arrays and ``Psi``
-        together with missing values are not on the handle (``Predictor.predict`` takes such rows).  A label outside [-1, n_groups)
+        VC, d <= 10, k <= 8, m <= 256), else ValueError; a diagonal kind goes to ``stack_missing_dev``, rows with ``Psi`` to
+        ``stack_noisy_missing_cov_dev``, and host arrays are not on the handle (``Predictor.predict`` takes such rows).  A label outside [-1, n_groups)
         and a negative or non-finite weight are found on the device before the first tile and refused with a GpzError."""
         return self._stack_dev(X, None, edges, n_draws, seed, Z, groups, n_groups, weights, selection, missing=True, cov=True)
 
@@ -996,18 +1021,20 @@ class Predictor:
         column 1 + s ``draws_noisy_missing_dev``'s draw s and the width beta_i + max(gamma_s, 0), where gamma_s is
         predictNoisyMissing's gamma under the weights of draw s (``draws_noisy_missing_dev(..., return_gamma=True)`` returns it).
         ``n_groups`` and the range of the labels are decided over all rows.  It needs a model inside predict_missing_fits (a diagonal
-        kind, d <= 20, k <= 8, m <= 256), else ValueError, and a predictor that was not made with force_tiles=True; host arrays and
-        the covariance kinds are not on the handle."""
+        kind, d <= 20, k <= 8, m <= 256), else ValueError, and a predictor that was not made with force_tiles=True; host arrays are
+        not on the handle, and the covariance kinds go to ``stack_noisy_missing_cov_dev``."""
         return self._stack_dev(X, Psi, edges, n_draws, seed, Z, groups, n_groups, weights, selection, missing=True, both=True)
 
     def _stack_dev(self, X, Psi, edges, n_draws, seed, Z, groups, n_groups, weights, selection, missing=False, both=False, cov=False):
         """``stack_dev`` (Psi None), ``stack_noisy_dev``, ``stack_missing_dev``, (``both``: Psi and ``missing`` together)
-        ``stack_noisy_missing_dev``, (``cov``: Psi of a covariance kind) ``stack_noisy_cov_dev`` and (``cov`` with ``missing``)
-        ``stack_missing_cov_dev``: the checks, the device last, all before the GPU is touched; then the entry, or with ``missing``
+        ``stack_noisy_missing_dev``, (``cov``: Psi of a covariance kind) ``stack_noisy_cov_dev``, (``cov`` with ``missing``)
+        ``stack_missing_cov_dev`` and (``cov`` with ``both``) ``stack_noisy_missing_cov_dev``: the checks, the device last, all before the GPU is touched; then the entry, or with ``missing``
         one entry per NaN-pattern group."""
         import torch
         self._check_open()
-        if both:
+        if both and cov:
+            X, Psi = self._check_noisy_missing_cov("stack", X, Psi, selection)
+        elif both:
             X, Psi = self._check_noisy_missing("stack", X, Psi, selection, draws=True)
         elif cov and missing:
             X = self._check_missing_cov("stack", X, Psi, selection)
@@ -1038,7 +1065,7 @@ class Predictor:
         try:
             self._check_dev_device(X=X, selection=selection, groups=groups, weights=weights, Psi=Psi)
         except ValueError as err:
-            if not (cov and missing):
+            if not (cov and missing) or both:
                 raise
             raise ValueError(f"{err} (Predictor.predict takes a catalogue with missing values from host arrays)") from None
         lab = wt = None

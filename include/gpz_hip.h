@@ -600,7 +600,7 @@ int gpz_predictor_draws_noisy_missing_dev(gpz_predictor *p, const void *X_d, int
  * Nothing grows with ns or the number of patterns, a handle that never makes such a call holds what it held, and a row's results
  * have the same bits for any tile size, row order, company or split of the rows into calls.  The draws are PHI W + muY with the
  * handle's weight draws.  gpz_predictor_route then holds "; noisy missing: k_predict_noisy_missing_cov_pairs (C pair chunks)".
- * The stack and gamma per draw of such rows, host arrays and PHI are not on the handle. */
+ * The stack and gamma per draw of such rows follow at the end of the predictor's entries; host arrays and PHI are not on the handle. */
 int gpz_predictor_run_noisy_missing_cov_dev(gpz_predictor *p, const void *X_d, int32_t x_type, int64_t ns, int64_t row_stride,
                                             int64_t col_stride, const void *Psi_d, int32_t psi_type, int64_t psi_row_stride,
                                             int64_t psi_col_stride, const double *muX, const double *sdX, const double *sd2,
@@ -649,6 +649,45 @@ int gpz_predictor_stack_noisy_missing_dev(gpz_predictor *p, const void *X_d, int
                                           const int32_t *group_d /* ns or NULL */, int32_t ngroups, const double *weight_d /* ns or NULL */,
                                           double *hist, double *sum_w, double *sum_mu, double *sum_mu2,
                                           const double *mu_shift /* k or NULL */, void *stream);
+
+/* ---- stacked densities of rows with input noise AND missing inputs on a covariance kind, and gamma under every weight draw -------------
+ * gpz_predictor_stack_noisy_missing_dev and gpz_predictor_draws_gamma_noisy_missing_dev for a covariance kind: the arguments are exactly
+ * theirs; the scope (predict_missing_cov_fits), Psi, priors, obs_mask, the scans of the pattern and of Psi in the observed dimensions and
+ * every refusal are those of gpz_predictor_run_noisy_missing_cov_dev / _draws_noisy_missing_cov_dev (a diagonal kind is sent to the two
+ * entries above by name), made before the first tile with the outputs untouched; no host-array entry.  Column 0: mu of
+ * gpz_predictor_run_noisy_missing_cov_dev, width^2 = (nu + beta) + gamma, the bits of that call's sigma.  Column 1 + s: mu_s of
+ * gpz_predictor_draws_noisy_missing_cov_dev, width^2 = beta_i + max(gamma_s,i, 0) with
+ *   gamma_s,i = sum_{a >= b} f_ab z_ab(x_i, psi_i) w_s,a w_s,b - mu_s,i^2   (f_ab = 2 off the diagonal, 1 on it),
+ * predictNoisyMissing's gamma of predictCov.m:308-320 under the draw's weights, z_ab the pair quantity of
+ * k_predict_noisy_missing_cov_pairs.  k_predict_noisy_missing_cov_gamma forms z from that kernel's slab records and the tile's Pio (m
+ * densities per pair and row, each a packed no x no Cholesky of M + diag(psi_o)) and multiplies it into all draws at once on the f64
+ * MFMA, up to 128 columns per pass (64 with seven observed dimensions).  A table of one slab is kept on the handle, whichever kernel
+ * filled it; with several slabs they are generated again per tile behind the pair kernel's own pass.  A group with nothing observed
+ * (obs_mask 0) reads no Psi and gets the bits of gpz_predictor_draws_gamma_missing_cov_dev / _stack_missing_cov_dev.  Complete rows go
+ * to gpz_predictor_draws_gamma_noisy_cov_dev / _stack_noisy_cov_dev.  Everything else - edges, groups, weights, mu_shift, layouts,
+ * additivity over calls - is gpz_predictor_stack's.  gpz_predictor_draws_gamma_noisy_missing_cov_dev: Gam_d (ns x k x ndraws
+ * column-major, device) <- gamma_s, unclamped; F_d has the bits of gpz_predictor_draws_noisy_missing_cov_dev.  A row's gamma_s has the
+ * same bits for any tile size, row order, position among other rows, split into calls and any ndraws > s.  The first of these calls
+ * adds to the handle what the two entries above add, plus the chunk slab of the pair sums and, for the stack, the widths and
+ * gpz_predictor_stack_dev's accumulators and slabs; nothing grows with ns or the number of patterns, and gpz_predictor_route then
+ * holds "; noisy missing per draw: k_predict_noisy_missing_cov_gamma (C pair chunks)", followed by " + k_stack_tile_w" once the stack
+ * entry has been called. */
+int gpz_predictor_draws_gamma_noisy_missing_cov_dev(gpz_predictor *p, const void *X_d, int32_t x_type, int64_t ns, int64_t row_stride,
+                                                    int64_t col_stride, const void *Psi_d, int32_t psi_type, int64_t psi_row_stride,
+                                                    int64_t psi_col_stride, const double *muX, const double *sdX, const double *sd2,
+                                                    const double *muY /* k or NULL */, const double *priors /* m or NULL */,
+                                                    uint32_t obs_mask, int32_t ndraws, uint64_t seed,
+                                                    const double *Z /* host: NULL or m x ndraws x k */,
+                                                    double *F_d /* ns x k x ndraws, column-major */,
+                                                    double *Gam_d /* ns x k x ndraws, column-major */, void *stream);
+int gpz_predictor_stack_noisy_missing_cov_dev(gpz_predictor *p, const void *X_d, int32_t x_type, int64_t ns, int64_t row_stride,
+                                              int64_t col_stride, const void *Psi_d, int32_t psi_type, int64_t psi_row_stride,
+                                              int64_t psi_col_stride, const double *muX, const double *sdX, const double *sd2,
+                                              const double *priors /* m or NULL */, uint32_t obs_mask,
+                                              int32_t ndraws, uint64_t seed, const double *Z, const double *edges, int32_t nbins,
+                                              const int32_t *group_d /* ns or NULL */, int32_t ngroups, const double *weight_d /* ns or NULL */,
+                                              double *hist, double *sum_w, double *sum_mu, double *sum_mu2,
+                                              const double *mu_shift /* k or NULL */, void *stream);
 
 /* ---- device-resident L-BFGS memory: minFunc's lbfgsAdd.m / lbfgsProd.m (mex/lbfgsAddC.c, mex/lbfgsProdC.c) ----
  * S and Y (p x corrections) live on the device; all vector arguments are device pointers.

@@ -26,6 +26,8 @@ rows with missing inputs first and one for rows with input noise second, and the
 own so that the lines above stay what they were (profiles/r21_predict_stack_missing_cov.txt): draws_missing_cov_dev with gamma (the
 first call of its handle, then predict_missing_cov_dev, which reads the slab that call filled) and stack_missing_cov_dev with 1 and
 with 129 or 66 columns, groups and weights, and a handle that meets stack_noisy_cov_dev first and stack_missing_cov_dev second.
+Behind those again, on one more handle (profiles/r23_predict_stack_noisy_missing_cov.txt): the same rows with Psi through
+draws_noisy_missing_cov_dev with gamma (the first call of its handle), predict_noisy_missing_cov_dev and stack_noisy_missing_cov_dev.
 After each call one line: the call, the digest of each array it returned, and the handle's route and info."""
 import hashlib
 import os
@@ -203,6 +205,14 @@ def run_edges(method, d, m, k):
         with gpz_amd.Predictor(model, tile_rows=128) as p:               # the noisy stack first, the missing one second: gpart is shared
             report(f"{tag} noisy first, stack_noisy_cov_dev", p, tuple(p.stack_noisy_cov_dev(Xd[:80], Pd[:80], edges, n_draws=3, seed=11)))
             report(f"{tag} noisy first, stack_missing_cov_dev", p, tuple(p.stack_missing_cov_dev(Xmd, edges, n_draws=draws[-1], seed=11)))
+        with gpz_amd.Predictor(model, tile_rows=128) as p:               # the same with Psi: gamma first, then the moments, which read its slab
+            for nd in (draws[0], draws[-1]):
+                report(f"{tag} draws_noisy_missing_cov_dev gamma {nd} x 200", p,
+                       p.draws_noisy_missing_cov_dev(Xmd, Pd, nd, seed=11, return_gamma=True))
+                report(f"{tag} predict_noisy_missing_cov_dev x 200", p, p.predict_noisy_missing_cov_dev(Xmd, Pd))
+                report(f"{tag} stack_noisy_missing_cov_dev {nd} x 200", p,
+                       tuple(p.stack_noisy_missing_cov_dev(Xmd, Pd, edges, n_draws=nd, seed=11, groups=gd, n_groups=3, weights=wd)))
+            report(f"{tag} stack_noisy_missing_cov_dev plain x 80", p, tuple(p.stack_noisy_missing_cov_dev(Xmd[:80], Pd[:80], edges, n_draws=0)))
 
 
 def main():
