@@ -108,6 +108,22 @@ SYMBOLS = {
     "gpz_predictor_draws_noisy_cov_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_void_p,
                                                     C.c_int32, C.c_int64, C.c_int64, c_double_p, c_double_p, c_double_p, c_double_p,
                                                     C.c_int32, C.c_uint64, c_double_p, C.c_void_p, C.c_void_p]),
+    # a full d x d Psi per row on a covariance kind: the four noisy_cov entries with three Psi strides (matrix row, matrix column,
+    # catalogue row) and the divisor triangle sdX[r] sdX[c] (host or device) in place of sd2
+    "gpz_predictor_run_psi_cube_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_void_p,
+                                                 C.c_int32, C.c_int64, C.c_int64, C.c_int64, c_double_p, c_double_p, c_double_p,
+                                                 c_double_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gpz_predictor_draws_psi_cube_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_void_p,
+                                                   C.c_int32, C.c_int64, C.c_int64, C.c_int64, c_double_p, c_double_p, c_double_p,
+                                                   c_double_p, C.c_int32, C.c_uint64, c_double_p, C.c_void_p, C.c_void_p]),
+    "gpz_predictor_draws_gamma_psi_cube_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_void_p,
+                                                         C.c_int32, C.c_int64, C.c_int64, C.c_int64, c_double_p, c_double_p,
+                                                         c_double_p, c_double_p, C.c_int32, C.c_uint64, c_double_p, C.c_void_p,
+                                                         C.c_void_p, C.c_void_p]),
+    "gpz_predictor_stack_psi_cube_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_void_p,
+                                                   C.c_int32, C.c_int64, C.c_int64, C.c_int64, c_double_p, c_double_p, c_double_p,
+                                                   C.c_int32, C.c_uint64, c_double_p, c_double_p, C.c_int32, C.c_void_p, C.c_int32,
+                                                   C.c_void_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, C.c_void_p]),
     # stacks of rows with input noise and gamma under every draw: the stack / draws entries with Psi as the noisy draws take it
     "gpz_predictor_stack_noisy": (C.c_int, [C.c_void_p, c_double_p, C.c_int64, c_double_p, C.c_int32, C.c_uint64, c_double_p, c_double_p,
                                             C.c_int32, c_int32_p, C.c_int32, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p,

@@ -273,6 +273,25 @@ int launch_stack_tile_w(hipStream_t st, const double *out, const double *s2, con
 // Returns -1 when the launch failed or d is outside 1 .. 10.
 int launch_predict_noisy_cov_gamma(hipStream_t st, int d, bool shared, const double *Xc, const double *Psic, long ldx, int n, int m,
                                    const double *tab, int rec, const double *W, int ldw, int ncol, int nchunk, double *part, long ldp);
+// ---- a full input-noise covariance per row, covariance kinds (k_predict_psi_cube.hip, k_predict_psi_cube_gamma.hip;
+// gpz_predictor_*_psi_cube_dev) ----
+// The launchers of the three groups above with Psic [d (d + 1) / 2][ldx]: column LT(r, c) holds element (r, c), r >= c, of every row's
+// Psi (after fixPsi's division), and the density's matrix is S + Psi_i over the whole packed triangle.  Tables, chunk counts
+// (predict_noisy_cov_chunks, predict_gamma_chunks), partial sums and finish kernels are theirs.  check: word 3 of rec is set when an
+// element of a lower triangle is NaN or infinite, itself or divided by div[LT(r, c)] (device, nullptr: no division), or a diagonal
+// element is negative.  stage: element (r, c) of row i at Psi[r sr + c sc + i sn] -> Psic.  All return -1 when a launch failed or d is
+// outside 1 .. 10.
+int launch_pred_check_psi_cube(hipStream_t st, const void *Psi, int f32, long ns, int d, long sr, long sc, long sn, const double *div,
+                               unsigned *rec);
+int launch_pred_stage_psi_cube(hipStream_t st, const void *Psi, int f32, long sr, long sc, long sn, long r0, int nt, int d,
+                               const double *div, double *Psic, long ldx);
+int launch_predict_psi_cube_small(hipStream_t st, int d, bool shared, const double *Xc, const double *Psic, long ldx, int n, int m, int k,
+                                  const double *brec, const double *prec, const double *bvec, int nchunk, double *part, long ldp,
+                                  double *out);
+int launch_predict_psi_cube_phi(hipStream_t st, int d, bool shared, const double *Xc, const double *Psic, long ldx, int n, int nrow, int m,
+                                int mp, int k, const double *brec, int nchunk, double *Phi);
+int launch_predict_psi_cube_gamma(hipStream_t st, int d, bool shared, const double *Xc, const double *Psic, long ldx, int n, int m,
+                                  const double *tab, int rec, const double *W, int ldw, int ncol, int nchunk, double *part, long ldp);
 // ---- rows with missing inputs through the streaming predictor, with or without input noise (k_predict_missing.hip,
 // k_predict_noisy_missing.hip, the pair kernels' body in k_predict_group_impl.h; gpz_predictor_*_missing_dev, _*_noisy_missing_dev) ----
 // One group of rows sharing a NaN pattern; obs: bit c set = dimension c observed.  fits: a diagonal kind, an instantiated de <= 20,

@@ -73,6 +73,9 @@ struct gpz_predictor {
         size_t s2_cap = 0;         // doubles
     } gam[6];                      // [ROWS_NOISY - 1], [ROWS_MISSING - 1], [ROWS_NOISY_MISSING - 1], [ROWS_NOISY_COV - 1], [ROWS_MISSING_COV - 1],
                                    // [ROWS_NOISY_MISSING_COV - 1]
+    PerDraw gamq;                  // rows with a full Psi each (kind 7, ROWS_PSI_CUBE)
+    PerDraw &per_draw(int kind) { return kind == 7 ? gamq : gam[kind - 1]; }
+    const PerDraw &per_draw(int kind) const { return kind == 7 ? gamq : gam[kind - 1]; }
     // ---- rows with missing inputs on the handle (gpz_predictor_*_missing_dev): nothing of this exists before the first of their calls
     bool miss_used = false;
     int64_t mtile = 0;             // rows per tile of a group: min(tile_rows, GPZ_PREDICTOR_TILE_MISSING)
@@ -90,9 +93,16 @@ struct gpz_predictor {
     // ---- input noise for the covariance kinds (gpz_predictor_*_noisy_cov_dev): beyond the Psi slots and, for the moments, nout and npart
     // (which a covariance kind has from nowhere else), only this exists, and not before the first of their calls
     bool ncov_ready = false;       // the pair records, the output slots and the chunk slab exist (the first call that reads the pairs)
+    bool ncov_used = false;        // such a call (a variance per dimension) was the one that read them (the route text)
     int cchunks = 0;               // predict_noisy_cov_chunks of the model
     double *cbrec = nullptr, *cprec = nullptr;   // the basis and pair records (k_noisy_cov_records): the model's alone, written once
     double *cphi = nullptr;        // the draws (and a stack with draws): E_x[PHI] of a tile, [tile_pad][mp] (the tile route's own Phi where there is one)
+    // ---- a full input-noise covariance per row for the covariance kinds (gpz_predictor_*_psi_cube_dev): the records, output slots, chunk
+    // slab and PHI tile are the group's above, each taken where the handle does not hold it yet (the Psi slots of that group are not
+    // needed and not taken).  Beyond them only this exists, and not before the first of their calls
+    bool cube_used = false;        // a call that reads the pairs has run (the route text)
+    double *Psiq[2] = {};          // the tile's packed lower triangles, [d (d + 1) / 2][tile_pad]
+    double *div_d = nullptr;       // the divisors sdX[r] sdX[c] in LT order, d (d + 1) / 2
     // ---- rows with missing inputs for the covariance kinds (gpz_predictor_*_missing_cov_dev): the tile buffers, the priors and the
     // cache keys are the fields of the diagonal kinds' group above (mtile, mNo = PHI, mPio = [m][tile], mhd, mpart, mout, mpri, mtab_*;
     // mchunks = predict_missing_cov_chunks), which a covariance handle has from nowhere else.  Beyond them only this exists, and not
@@ -118,9 +128,11 @@ namespace gpzi {
 // covariance kind (a handle has either this kind or the diagonal noisy one, never both).  What a tile is made of for a kind is answered by the rows_* functions below; the runners of every entry go through them.
 // Missing cov: a group without Psi on a covariance kind.  Noisy missing cov: such a group with Psi in Psic[s] too; with nothing observed
 // (obs = 0) there is no Psi to read and the group is the missing cov kind's in all but the name of its entry.
+// Psi cube: complete rows of a covariance kind with a full d x d Psi each, its packed lower triangle in Psiq[s] beside Xc[s]; the tables
+// are the noisy cov kind's.
 enum RowKind {
     ROWS_CLEAN = 0, ROWS_NOISY = 1, ROWS_MISSING = 2, ROWS_NOISY_MISSING = 3, ROWS_NOISY_COV = 4, ROWS_MISSING_COV = 5,
-    ROWS_NOISY_MISSING_COV = 6
+    ROWS_NOISY_MISSING_COV = 6, ROWS_PSI_CUBE = 7
 };
 struct Rows {
     RowKind kind = ROWS_CLEAN;
@@ -132,6 +144,7 @@ struct Rows {
     bool group() const {   // one NaN pattern, tiles of at most mtile rows
         return kind == ROWS_MISSING || kind == ROWS_NOISY_MISSING || kind == ROWS_MISSING_COV || kind == ROWS_NOISY_MISSING_COV;
     }
+    bool cube() const { return kind == ROWS_PSI_CUBE; }   // Psiq[s] is staged beside Xc[s]
     bool cov_group() const { return kind == ROWS_MISSING_COV || kind == ROWS_NOISY_MISSING_COV; }   // such a group on a covariance kind
 };
 

@@ -21,7 +21,9 @@ struct DevCall {
     Rows rows;
     DevRows psi;
     const double *sd2;
-    const double *muX_d, *sdX_d, *muY_d, *sd2_d;
+    int64_t psi_mr;      // a cube: the stride between the rows of a matrix (psi.cs: between its columns, psi.rs: between catalogue rows)
+    const double *div;   // a cube: the divisors sdX[r] sdX[c] in LT order, host or device (nullptr with sdX: none)
+    const double *muX_d, *sdX_d, *muY_d, *sd2_d, *div_d;
 };
 
 static DevCall dev_call(const void *X_d, int32_t x_type, int64_t ns, int64_t rs, int64_t cs, const double *muX, const double *sdX,
@@ -36,6 +38,15 @@ static DevCall with_psi(DevCall c, const void *Psi_d, int32_t psi_type, int64_t 
     c.rows.kind = ROWS_NOISY;
     c.psi = DevRows{Psi_d, psi_type, c.x.ns, rs, cs};
     c.sd2 = sd2;
+    return c;
+}
+
+// complete rows of a covariance kind with a full d x d Psi each: element (r, c) of row i at Psi[r mr + c mc + i rs]
+static DevCall with_cube(DevCall c, const void *Psi_d, int32_t psi_type, int64_t mr, int64_t mc, int64_t rs, const double *div) {
+    c.rows.kind = ROWS_PSI_CUBE;
+    c.psi = DevRows{Psi_d, psi_type, c.x.ns, rs, mc};
+    c.psi_mr = mr;
+    c.div = div;
     return c;
 }
 
@@ -91,8 +102,23 @@ static int predictor_dev_psi_args(const char *who, const DevRows &psi, const dou
     return 0;
 }
 
+// the caller's cube: only the lower triangle is read, so a 1 x 1 matrix needs no matrix stride
+static int predictor_dev_cube_args(const char *who, const gpz_predictor *p, const DevCall &c) {
+    const DevRows &psi = c.psi;
+    if (psi.type != GPZ_X_F64 && psi.type != GPZ_X_F32)
+        return gpz_fail(GPZ_ERR_ARG, "%s: psi_type %d is neither GPZ_X_F64 nor GPZ_X_F32", who, (int)psi.type);
+    if ((c.sdX != nullptr) != (c.div != nullptr))
+        return gpz_fail(GPZ_ERR_ARG, "%s: sdX and the divisor triangle go together (both or neither)", who);
+    if (psi.ns > 0 && !psi.X) return gpz_fail(GPZ_ERR_ARG, "%s: null Psi", who);
+    if (c.psi_mr < 0 || psi.cs < 0 || psi.rs < 0 || (psi.ns > 1 && psi.rs == 0) || (p->d > 1 && (c.psi_mr == 0 || psi.cs == 0)))
+        return gpz_fail(GPZ_ERR_ARG, "%s: Psi strides (%lld, %lld, %lld) of %lld matrices: a stride must be positive", who,
+                        (long long)c.psi_mr, (long long)psi.cs, (long long)psi.rs, (long long)psi.ns);
+    return 0;
+}
+
 static int predictor_dev_check(const char *who, const gpz_predictor *p, const DevCall &c) {
     if (int rc = predictor_dev_args(who, p, c.x, c.muX, c.sdX)) return rc;
+    if (c.rows.cube()) return predictor_dev_cube_args(who, p, c);
     return c.rows.psi() ? predictor_dev_psi_args(who, c.psi, c.sdX, c.sd2) : 0;
 }
 
@@ -148,6 +174,11 @@ static int predictor_dev_begin(gpz_predictor *p, const char *who, DevCall &c, co
         ((sd2 && hipMemcpyAsync(p->sd2_d, sd2, d * sizeof(double), hipMemcpyHostToDevice, st) != hipSuccess) ||
          launch_pred_check_psi(st, psi->X, psi->f32(), psi->ns, p->d, psi->rs, psi->cs, sd2 ? *std::min_element(sd2, sd2 + d) : 1.0, rec)))
         rc = gpz_fail(GPZ_ERR_HIP, "%s: k_pred_check_psi launch failed", who);
+    // a full Psi per row: the divisor triangle up (from the host or the device), then the scan of every lower triangle
+    if (!rc && c.rows.cube() &&
+        ((c.div && hipMemcpyAsync(p->div_d, c.div, d * (d + 1) / 2 * sizeof(double), hipMemcpyDefault, st) != hipSuccess) ||
+         launch_pred_check_psi_cube(st, c.psi.X, c.psi.f32(), c.psi.ns, p->d, c.psi_mr, c.psi.cs, c.psi.rs, c.div ? p->div_d : nullptr, rec)))
+        rc = gpz_fail(GPZ_ERR_HIP, "%s: k_pred_check_psi_cube launch failed", who);
     if (!rc && hipMemcpyAsync(verdict, rec, sizeof verdict, hipMemcpyDeviceToHost, st) != hipSuccess)
         rc = gpz_fail(GPZ_ERR_HIP, "%s: copy failed", who);
     if (hipStreamSynchronize(st) != hipSuccess && !rc) rc = gpz_fail(GPZ_ERR_HIP, "%s: sync failed", who);
@@ -157,6 +188,9 @@ static int predictor_dev_begin(gpz_predictor *p, const char *who, DevCall &c, co
     if (verdict[0] && pattern)
         return gpz_fail(GPZ_ERR_ARG, "%s: the rows of a group must share one NaN pattern, the one of the mask", who);
     if (verdict[0]) return gpz_fail(GPZ_ERR_UNSUPPORTED, "%s: %s", who, nan_text);
+    if (verdict[3] && c.rows.cube())
+        return gpz_fail(GPZ_ERR_ARG, "%s: the lower triangle of Psi has an element that is NaN or infinite, or a negative diagonal element",
+                        who);
     if (verdict[3]) return gpz_fail(GPZ_ERR_ARG, "%s: Psi has an element that is NaN, infinite or negative", who);
     c.muX_d = muX ? p->par_d : nullptr;
     c.sdX_d = muX ? p->par_d + d : nullptr;
@@ -167,6 +201,7 @@ static int predictor_dev_begin(gpz_predictor *p, const char *who, DevCall &c, co
             return predictor_dev_sync(p, who, gpz_fail(GPZ_ERR_HIP, "%s: copy failed", who));
     }
     c.sd2_d = sd2 ? p->sd2_d : nullptr;   // (a group's first call with Psi has it from rows_prepare only)
+    c.div_d = c.div ? p->div_d : nullptr;
     return 0;
 }
 
@@ -183,6 +218,9 @@ static int predictor_dev_tiles(gpz_predictor *p, const char *who, const DevCall 
         if (c.rows.psi() &&
             launch_pred_stage_psi(st, psi.X, psi.f32(), psi.rs, psi.cs, r0, nt, p->d, c.sd2_d, p->Psic[s], p->tile_pad))
             return gpz_fail(GPZ_ERR_HIP, "%s: k_pred_stage_psi launch failed", who);
+        if (c.rows.cube() && launch_pred_stage_psi_cube(st, psi.X, psi.f32(), c.psi_mr, psi.cs, psi.rs, r0, nt, p->d, c.div_d, p->Psiq[s],
+                                                        p->tile_pad))
+            return gpz_fail(GPZ_ERR_HIP, "%s: k_pred_stage_psi_cube launch failed", who);
         if (int rc = body(s, r0, nt)) return rc;
     }
     return 0;
@@ -198,7 +236,7 @@ static int predictor_run_dev(gpz_predictor *p, const char *who, DevCall &c, doub
     int rc = PHI ? predictor_want_phi(p, false) : 0;
     if (!rc)
         rc = predictor_dev_begin(p, who, c, nullptr, 0, nullptr,
-                                 r.psi()
+                                 r.psi() || r.cube()
                                      ? "the rows have missing values (NaN): input noise on the handle is for complete rows"
                                      : "the rows have missing values (NaN): group them by pattern and call gpz_predict_missing (predict.m:45-69)",
                                  true);
@@ -217,7 +255,7 @@ static int predictor_run_dev(gpz_predictor *p, const char *who, DevCall &c, doub
     return rc;
 }
 
-// gpz_predictor_run_dev, _run_noisy_dev, _run_noisy_cov_dev, _run_missing_dev, _run_missing_cov_dev, _run_noisy_missing_dev and
+// gpz_predictor_run_dev, _run_noisy_dev, _run_noisy_cov_dev, _run_psi_cube_dev, _run_missing_dev, _run_missing_cov_dev, _run_noisy_missing_dev and
 // _run_noisy_missing_cov_dev
 static int run_dev_entry(const char *who, gpz_predictor *p, DevCall c, double *mu_d, double *sigma_d, double *nu_d, double *beta_d,
                          double *gamma_d, double *PHI_d) {
@@ -374,6 +412,51 @@ extern "C" int gpz_predictor_stack_noisy_cov_dev(gpz_predictor *p, const void *X
     const StackArgs a{ndraws, seed, Z, edges, nbins, group_d, ngroups, weight_d, hist, sum_w, sum_mu, sum_mu2, mu_shift};
     return stack_dev_entry("gpz_predictor_stack_noisy_cov_dev", p,
                            with_cov(with_psi(x, Psi_d, psi_type, psi_row_stride, psi_col_stride, sd2)), a);
+}
+
+extern "C" int gpz_predictor_run_psi_cube_dev(gpz_predictor *p, const void *X_d, int32_t x_type, int64_t ns, int64_t row_stride,
+                                              int64_t col_stride, const void *Psi_d, int32_t psi_type, int64_t psi_mrow_stride,
+                                              int64_t psi_mcol_stride, int64_t psi_row_stride, const double *muX, const double *sdX,
+                                              const double *div, const double *muY, double *mu_d, double *sigma_d, double *nu_d,
+                                              double *beta_d, double *gamma_d, void *stream) {
+    const DevCall x = dev_call(X_d, x_type, ns, row_stride, col_stride, muX, sdX, muY, stream);
+    return run_dev_entry("gpz_predictor_run_psi_cube_dev", p,
+                         with_cube(x, Psi_d, psi_type, psi_mrow_stride, psi_mcol_stride, psi_row_stride, div), mu_d, sigma_d, nu_d, beta_d,
+                         gamma_d, nullptr);
+}
+
+extern "C" int gpz_predictor_draws_psi_cube_dev(gpz_predictor *p, const void *X_d, int32_t x_type, int64_t ns, int64_t row_stride,
+                                                int64_t col_stride, const void *Psi_d, int32_t psi_type, int64_t psi_mrow_stride,
+                                                int64_t psi_mcol_stride, int64_t psi_row_stride, const double *muX, const double *sdX,
+                                                const double *div, const double *muY, int32_t ndraws, uint64_t seed, const double *Z,
+                                                double *F_d, void *stream) {
+    const DevCall x = dev_call(X_d, x_type, ns, row_stride, col_stride, muX, sdX, muY, stream);
+    return draws_dev_entry("gpz_predictor_draws_psi_cube_dev", p,
+                           with_cube(x, Psi_d, psi_type, psi_mrow_stride, psi_mcol_stride, psi_row_stride, div), ndraws, seed, Z, F_d);
+}
+
+extern "C" int gpz_predictor_draws_gamma_psi_cube_dev(gpz_predictor *p, const void *X_d, int32_t x_type, int64_t ns, int64_t row_stride,
+                                                      int64_t col_stride, const void *Psi_d, int32_t psi_type, int64_t psi_mrow_stride,
+                                                      int64_t psi_mcol_stride, int64_t psi_row_stride, const double *muX,
+                                                      const double *sdX, const double *div, const double *muY, int32_t ndraws,
+                                                      uint64_t seed, const double *Z, double *F_d, double *Gam_d, void *stream) {
+    const DevCall x = dev_call(X_d, x_type, ns, row_stride, col_stride, muX, sdX, muY, stream);
+    return draws_dev_entry("gpz_predictor_draws_gamma_psi_cube_dev", p,
+                           with_cube(x, Psi_d, psi_type, psi_mrow_stride, psi_mcol_stride, psi_row_stride, div), ndraws, seed, Z, F_d,
+                           Gam_d, true);
+}
+
+extern "C" int gpz_predictor_stack_psi_cube_dev(gpz_predictor *p, const void *X_d, int32_t x_type, int64_t ns, int64_t row_stride,
+                                                int64_t col_stride, const void *Psi_d, int32_t psi_type, int64_t psi_mrow_stride,
+                                                int64_t psi_mcol_stride, int64_t psi_row_stride, const double *muX, const double *sdX,
+                                                const double *div, int32_t ndraws, uint64_t seed, const double *Z, const double *edges,
+                                                int32_t nbins, const int32_t *group_d, int32_t ngroups, const double *weight_d,
+                                                double *hist, double *sum_w, double *sum_mu, double *sum_mu2, const double *mu_shift,
+                                                void *stream) {
+    const DevCall x = dev_call(X_d, x_type, ns, row_stride, col_stride, muX, sdX, nullptr, stream);
+    const StackArgs a{ndraws, seed, Z, edges, nbins, group_d, ngroups, weight_d, hist, sum_w, sum_mu, sum_mu2, mu_shift};
+    return stack_dev_entry("gpz_predictor_stack_psi_cube_dev", p,
+                           with_cube(x, Psi_d, psi_type, psi_mrow_stride, psi_mcol_stride, psi_row_stride, div), a);
 }
 
 extern "C" int gpz_predictor_run_missing_dev(gpz_predictor *p, const void *X_d, int32_t x_type, int64_t ns, int64_t row_stride,

@@ -1,5 +1,6 @@
-// The frame of the two kernels that form gamma under every weight draw for rows with input noise: k_predict_noisy_gamma<DT>
-// (k_predict_noisy_gamma.hip, the diagonal kinds) and k_predict_noisy_cov_gamma<D, SHARED> (k_predict_noisy_cov_gamma.hip, GC and VC).
+// The frame of the kernels that form gamma under every weight draw for rows with input noise: k_predict_noisy_gamma<DT>
+// (k_predict_noisy_gamma.hip, the diagonal kinds), k_predict_noisy_cov_gamma<D, SHARED> (k_predict_noisy_cov_gamma.hip, GC and VC) and
+// k_predict_psi_cube_gamma<D, SHARED> (k_predict_psi_cube_gamma.hip, GC and VC with a full d x d Psi per row).
 // Each is a thin __global__ wrapper of predict_gamma_body<Density>; what differs between them is the Density policy of its file.
 //
 //   predict_gamma_body<Density>
@@ -19,12 +20,14 @@
 //   Density    a struct without virtuals: D (the dimension), RL (the doubles of a record head that are staged), NB (16-column blocks
 //              of accumulators per pass), its members (what a lane keeps across K steps), init(tab, ps) once per row before the
 //              loop, and z(t, x, ps) for one staged head t.
+//              Optional: PW, the values of Psi per row where that is not D (gamma_psi_width below), with bind(P, ldx).
 // No atomics; every sum starts from zero and runs in one order that the model's shape fixes (pairs in table order, four per K step from
 // the chunk's first pair, chunks in chunk order): a row's gamma_s has the same bits for any tile size, row order, position in its block,
 // other rows of the call and any number of draws > s.
 #pragma once
 #include "gpz_dev.h"
 #include "gpz_kernels.h"
+#include <type_traits>
 
 #define GPZ_GAMMA_TP 32   // pair records per LDS stage: 8 K steps
 #define GPZ_GAMMA_PF 4    // the blocks whose W rows are fetched ahead of the density work (64 columns: the usual 64 draws)
@@ -56,19 +59,46 @@ static inline dim3 predict_gamma_grid(const PredGammaArgs &a, int nchunk, int nb
     return dim3((unsigned)((a.n + 63) / 64), (unsigned)nchunk, (unsigned)((a.nbw + nb - 1) / nb));
 }
 
+// The values of Psi a lane loads for its row: Density::D columns of Psic, or Density::PW where a policy declares it (a packed triangle is
+// wider than D).  A policy with PW also has bind(P, ldx), called before init with the lane's place in Psic, for what it reads there
+// itself.
+template <class Density, class = void>
+struct gamma_psi_width {
+    static constexpr int value = Density::D;
+    static constexpr bool bind = false;
+};
+template <class Density>
+struct gamma_psi_width<Density, std::void_t<decltype(Density::PW)>> {
+    static constexpr int value = Density::PW;
+    static constexpr bool bind = true;
+};
+
 template <class Density>
 __device__ __forceinline__ void predict_gamma_body(const PredGammaArgs &a) {
     constexpr int D = Density::D, RL = Density::RL, NB = Density::NB, NST = GPZ_GAMMA_TP * RL, NPRE = (NST + 255) / 256;
+    constexpr int PW = gamma_psi_width<Density>::value;
     __shared__ double sT[NST];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, g = lane >> 4, lr = lane & 15;
     const long i = ((long)blockIdx.x * 4 + wv) * 16 + lr;
     const bool act = i < a.n;
     const long ic = act ? i : a.n - 1;
-    double x[D], ps[D];
+    double x[D], ps[PW];
+    if constexpr (PW == D) {
 #pragma unroll
-    for (int c = 0; c < D; ++c) {
-        x[c] = a.Xc[(size_t)c * a.ldx + ic];
-        ps[c] = a.Psic[(size_t)c * a.ldx + ic];
+        for (int c = 0; c < D; ++c) {
+            x[c] = a.Xc[(size_t)c * a.ldx + ic];
+            ps[c] = a.Psic[(size_t)c * a.ldx + ic];
+        }
+    } else {   // a policy whose row has more (or fewer) values of Psi than dimensions
+#pragma unroll
+        for (int c = 0; c < D; ++c) x[c] = a.Xc[(size_t)c * a.ldx + ic];
+        const double *pq = a.Psic + ic;   // stepped in vector registers: PW uniform offsets at once would not fit the scalar file
+#pragma unroll
+        for (int c = 0; c < PW; ++c) {
+            ps[c] = *pq;
+            pq += a.ldx;
+            asm volatile("" : "+v"(pq));
+        }
     }
     const int ch = blockIdx.y, cb0 = blockIdx.z * NB;
     const int nb = __builtin_amdgcn_readfirstlane(a.nbw - cb0 < NB ? a.nbw - cb0 : NB);
@@ -88,6 +118,7 @@ __device__ __forceinline__ void predict_gamma_body(const PredGammaArgs &a) {
     for (int q = 0; q < NB; ++q) acc[q] = (d4_t){0.0, 0.0, 0.0, 0.0};
     const double *wl = a.W + (size_t)cb0 * 16 + lr;
     Density den;
+    if constexpr (gamma_psi_width<Density>::bind) den.bind(a.Psic + ic, a.ldx);
     den.init(a.tab, ps);
     double pre[NPRE];
     // the heads of the records [pbase, pbase + 32) of the chunk (clamped to its last one, so that every slot of a stage holds a record)

@@ -5,7 +5,9 @@ kinds (clean, noisy: with Psi, missing: one NaN-pattern group, noisy_missing: su
 covariance model (GC, VC), which has all four questions through methods of its own (``*_noisy_cov_dev``), and missing_cov the
 missing kind of such a model, which has all four too (``predict_missing_cov_dev``, ``draws_missing_cov_dev`` with ``return_gamma``,
 ``stack_missing_cov_dev``); noisy_missing_cov is such a group with Psi, with all four as well
-(``predict_noisy_missing_cov_dev``, ``draws_noisy_missing_cov_dev`` with ``return_gamma``, ``stack_noisy_missing_cov_dev``).
+(``predict_noisy_missing_cov_dev``, ``draws_noisy_missing_cov_dev`` with ``return_gamma``, ``stack_noisy_missing_cov_dev``);
+psi_cube is the noisy kind of a covariance model whose rows have a full d x d Psi each, the d x d x n cube, with all four
+(``predict_psi_cube_dev``, ``draws_psi_cube_dev`` with ``return_gamma``, ``stack_psi_cube_dev``).
 ``_DEV_ENTRIES`` names the device-resident entry of each pair, ``Predictor._dev_entry`` builds the arguments the entries of a pair
 share, and ``Predictor._dev_groups`` is the one loop over the groups of a call; the host methods choose between two entries each by
 whether Psi is there (``_HOST_ENTRIES``).  Everything numeric happens in the library; ``torch`` is only imported by the device methods.
@@ -44,12 +46,14 @@ _DEV_ENTRIES = {
     ("draws", "noisy_missing_cov"): "gpz_predictor_draws_noisy_missing_cov_dev",
     ("draws_gamma", "noisy_missing_cov"): "gpz_predictor_draws_gamma_noisy_missing_cov_dev",
     ("stack", "noisy_missing_cov"): "gpz_predictor_stack_noisy_missing_cov_dev",
+    ("run", "psi_cube"): "gpz_predictor_run_psi_cube_dev", ("draws", "psi_cube"): "gpz_predictor_draws_psi_cube_dev",
+    ("draws_gamma", "psi_cube"): "gpz_predictor_draws_gamma_psi_cube_dev", ("stack", "psi_cube"): "gpz_predictor_stack_psi_cube_dev",
 }
 # (question, Psi there) -> the host entry
 _HOST_ENTRIES = {("draws", False): "gpz_predictor_draws", ("draws", True): "gpz_predictor_draws_noisy",
                  ("stack", False): "gpz_predictor_stack", ("stack", True): "gpz_predictor_stack_noisy"}
 # what the entries of one *_dev call share: the handle, torch's current stream and the normalisation vectors (host, float64)
-_DevCall = namedtuple("_DevCall", ["h", "stream", "muX", "sdX", "sd2", "muY"])
+_DevCall = namedtuple("_DevCall", ["h", "stream", "muX", "sdX", "sd2", "muY", "div"])
 
 
 class Predictor:
@@ -532,8 +536,10 @@ class Predictor:
 
     @staticmethod
     def _selected(selection, X, Psi):
-        """The rows and their Psi under the mask (predict.m:25-33): as they are without one."""
-        return (X, Psi) if selection is None else (X[selection], None if Psi is None else Psi[selection])
+        """The rows and their Psi under the mask (predict.m:25-33): as they are without one.  A d x d x n cube has its rows last."""
+        if selection is None:
+            return X, Psi
+        return X[selection], None if Psi is None else Psi[:, :, selection] if Psi.dim() == 3 else Psi[selection]
 
     def _dev_begin(self, device):
         """What the entries of one *_dev call share: the normalisation vectors (sd2 for fixPsi.m's Psi ./ sdX.^2), the handle and
@@ -541,7 +547,13 @@ class Predictor:
         import torch
         muX, sdX, muY = self._norm_vectors()
         h = self._handle()
-        return _DevCall(h, torch.cuda.current_stream(device).cuda_stream, muX, sdX, np.ascontiguousarray(sdX ** 2), muY)
+        sd2 = np.ascontiguousarray(sdX ** 2)
+        # fixPsi.m:36's divisors sdX' sdX of a Psi cube as the packed lower triangle, (r, c) at r (r + 1) / 2 + c; on the diagonal they
+        # must be the sd2 that a variance per dimension is divided by, so that a cube of diagonals gets that route's bits
+        r, c = np.tril_indices(self._d)
+        div = np.ascontiguousarray(sdX[r] * sdX[c])
+        assert np.array_equal(div[r == c], sd2), "the divisor triangle's diagonal must be sdX ** 2 bit for bit"
+        return _DevCall(h, torch.cuda.current_stream(device).cuda_stream, muX, sdX, sd2, muY, div)
 
     def _dev_groups(self, X, missing, *per_row):
         """The one loop over the groups of a *_dev call: yields (code, idx, Xg, the per-row tensors of the group ...).  Without
@@ -574,14 +586,19 @@ class Predictor:
         of a covariance kind, whose entries take the noisy kind's arguments, or a group with missing values of such a kind, whose
         entries take the missing kind's (with Psi too: the noisy missing kind's).  Returns (entry, arguments, row kind)."""
         noisy = Pg is not None
-        kind = (("noisy_missing_cov" if cov else "noisy_missing") if noisy else "missing_cov" if cov else "missing") if code else \
+        cube = cov == "cube"   # complete rows with a d x d x n Psi: three strides, the divisor triangle in place of sd2
+        kind = "psi_cube" if cube else \
+            (("noisy_missing_cov" if cov else "noisy_missing") if noisy else "missing_cov" if cov else "missing") if code else \
             (("noisy_cov" if cov else "noisy") if noisy else "clean")
         lead = [call.h, *self._x_args(Xg)]
-        if noisy:
+        if cube:
+            import torch
+            lead += [Pg.data_ptr(), 1 if Pg.dtype == torch.float32 else 0, Pg.stride(0), Pg.stride(1), Pg.stride(2)]
+        elif noisy:
             lead += self._psi_args(Pg, Xg.shape[0])
         lead += [_lib.dptr(call.muX), _lib.dptr(call.sdX)]
         if noisy:
-            lead.append(_lib.dptr(call.sd2))
+            lead.append(_lib.dptr(call.div if cube else call.sd2))
         if question != "stack":
             lead.append(_lib.dptr(call.muY))
         if code:
@@ -806,6 +823,82 @@ class Predictor:
         n_draws, z = self._check_draw_args(n_draws, seed, Z, 1)
         self._check_dev_device(X=X, selection=selection, Psi=Psi)
         return self._draws_dev(X, Psi, selection, False, n_draws, seed, z, bool(return_gamma), cov=True)
+
+    def _check_psi_cube(self, what, X, Psi, selection):
+        """The checks the three methods for rows with a d x d x n Psi of a covariance kind share, none of which touches a GPU, in the
+        order of ``_check_noisy_cov``: X, then where such rows go when this is not their route (no Psi, a variance per dimension, a
+        diagonal kind, a shape outside predict_noisy_cov_fits), then Psi's type, dtype and shape.  Returns X as n x d and Psi."""
+        import torch
+        X = self._check_dev_rows(X, selection, what)
+        name, d, n = f"{what}_psi_cube_dev", self._d, X.shape[0]
+        clean, diag = (f"{what}_dev(X, edges)", "stack_noisy_dev(X, Psi, edges)") if what == "stack" else \
+            (f"{what}_dev(X)", f"{what}_dev(X, Psi=Psi)")
+        if Psi is None:
+            raise ValueError(f"{name} needs Psi: rows without input noise go to {clean}")
+        ndim = Psi.dim() if hasattr(Psi, "dim") else np.ndim(Psi)
+        if ndim in (1, 2):
+            raise ValueError(f"{name} takes Psi as the d x d x n cube: n x d, n x 1 or n variances go to {what}_noisy_cov_dev")
+        if self._method[1] != "C":
+            raise ValueError(f"{name} is for the covariance kinds (GC, VC): fixPsi gives a diagonal kind such as {self._method} only "
+                             f"the cube's diagonal, which goes to {diag}")
+        if not (1 <= d <= 10 and 1 <= self._k <= 8 and 1 <= self._m <= 256):
+            raise ValueError(f"{name} needs a model inside predict_noisy_cov_fits: GC or VC, d <= 10, k <= 8 and m <= 256; this one is "
+                             f"{self._method} with d = {d}, m = {self._m}, k = {self._k} (Predictor.predict takes Psi for every shape)")
+        if isinstance(Psi, np.ndarray):
+            raise TypeError(f"{name} takes Psi as a torch tensor on cuda:{self.device}; host arrays stay on "
+                            "Predictor.predict(X, Psi=Psi)")
+        if not isinstance(Psi, torch.Tensor):
+            raise TypeError(f"Psi must be a torch.Tensor on cuda:{self.device}, got {type(Psi).__name__}")
+        if Psi.dtype not in (torch.float64, torch.float32):
+            raise TypeError(f"Psi must be float64 or float32, got {Psi.dtype}")
+        if tuple(Psi.shape) != (d, d, n):
+            raise ValueError(f"Psi must be d x d x n (d = {d}, n = {n}; an n x d x d tensor goes in as .permute(1, 2, 0)), got shape "
+                             f"{tuple(Psi.shape)}")
+        return X, Psi
+
+    def predict_psi_cube_dev(self, X, Psi, selection=None):
+        """``predict_noisy_cov_dev`` for rows with a full input-noise covariance each (GC, VC; gpz_predictor_run_psi_cube_dev): ``Psi``
+        is a float64 or float32 tensor of shape (d, d, n) on the device, the reference's cube (fixPsi.m, predictCov.m:109), with any
+        strides - an (n, d, d) tensor under ``.permute(1, 2, 0)`` is read where it lies.  Only the lower triangle (row >= column) of
+        each row's matrix is read and scanned; the upper triangle may hold anything.  Element (r, c) enters the kernels as
+        double(Psi[r, c, i]) / (sdX[r] * sdX[c]), fixPsi.m:36's bits.  Returns mu, sigma, nu, beta_i, gamma as
+        ``predict(X, Psi=Psi)`` does, float64 (n, k) on the device, from k_predict_psi_cube_small on the handle's tiles: the packed
+        Cholesky of S + Psi_i per row and record.  A cube with zeros off the diagonal gives the bits of ``predict_noisy_cov_dev`` on
+        its diagonal; a row's results do not depend on the tile size, the row order or the other rows of the call.  An element of a
+        lower triangle that is NaN or infinite (itself or after its division), a negative diagonal element and rows with NaN in X are
+        refused (GpzError), outputs untouched.  A matrix that passes this scan but is not positive semidefinite is the caller's error:
+        that row's results are unspecified, and no other row is affected.  It needs a model inside predict_noisy_cov_fits (GC or VC,
+        d <= 10, k <= 8, m <= 256), else ValueError; a diagonal kind takes the cube's diagonal through ``predict_dev(X, Psi=)``; rows
+        with NaN together with a cube, PHI and host arrays stay on ``Predictor.predict``.  Type, dtype and shape are checked first,
+        the device last, all before the GPU is touched."""
+        self._check_open()
+        X, Psi = self._check_psi_cube("predict", X, Psi, selection)
+        self._check_dev_device(X=X, selection=selection, Psi=Psi)
+        return self._moments_dev(X, Psi, selection, False, cov="cube")
+
+    def draws_psi_cube_dev(self, X, Psi, n_draws, seed=0, Z=None, selection=None, return_gamma=False):
+        """``draws_noisy_cov_dev`` for such rows (gpz_predictor_draws_psi_cube_dev): X, ``Psi`` (d x d x n, its lower triangles read)
+        and ``selection`` as for ``predict_psi_cube_dev``, everything else and the result as for ``draws_noisy_cov_dev``: draws[s] is
+        ``predict_psi_cube_dev``'s mu under weight draw s, E_x[PHI] w_s + muY with E_x[PHI] from k_predict_psi_cube_phi.
+        ``return_gamma=True`` (gpz_predictor_draws_gamma_psi_cube_dev) returns ``(F, Gam)``: Gam[s] is predictNoisy's gamma of
+        predictCov.m under the weights of draw s, not clamped at 0 (k_predict_psi_cube_gamma).  A row's F and Gam have the same bits
+        for any tile size, row order, other rows of the call and any n_draws > s; a matrix that is not positive semidefinite makes its
+        own row's results unspecified and touches no other row."""
+        self._check_open()
+        X, Psi = self._check_psi_cube("draws", X, Psi, selection)
+        n_draws, z = self._check_draw_args(n_draws, seed, Z, 1)
+        self._check_dev_device(X=X, selection=selection, Psi=Psi)
+        return self._draws_dev(X, Psi, selection, False, n_draws, seed, z, bool(return_gamma), cov="cube")
+
+    def stack_psi_cube_dev(self, X, Psi, edges, n_draws=0, seed=0, Z=None, groups=None, n_groups=None, weights=None, selection=None):
+        """``stack_noisy_cov_dev`` for such rows (gpz_predictor_stack_psi_cube_dev): X, ``Psi`` (d x d x n, its lower triangles read)
+        and ``selection`` as for ``predict_psi_cube_dev``, everything else as for ``stack_dev``.  Returns a NumPy StackResult.  Column 0
+        uses ``predict_psi_cube_dev``'s mu and that call's sigma = (nu + beta_i) + gamma, bit for bit; column 1 + s
+        ``draws_psi_cube_dev``'s draw s and the width beta_i + max(gamma_s, 0), where gamma_s is that method's ``return_gamma=True``.
+        The fields are plain sums over the rows, so calls over parts of a catalogue add.  Rows with NaN, a bad element of a lower
+        triangle, a label outside [-1, n_groups) and a negative or non-finite weight are found on the device before the first tile and
+        refused with a GpzError; a matrix that is not positive semidefinite makes its own row's contribution unspecified."""
+        return self._stack_dev(X, Psi, edges, n_draws, seed, Z, groups, n_groups, weights, selection, cov="cube")
 
     def _check_noisy_missing_cov(self, what, X, Psi, selection):
         """The checks the three methods for rows with Psi and missing values of a covariance kind share, none of which touches a GPU: X by
@@ -1036,6 +1129,8 @@ class Predictor:
             X, Psi = self._check_noisy_missing_cov("stack", X, Psi, selection)
         elif both:
             X, Psi = self._check_noisy_missing("stack", X, Psi, selection, draws=True)
+        elif cov == "cube":
+            X, Psi = self._check_psi_cube("stack", X, Psi, selection)
         elif cov and missing:
             X = self._check_missing_cov("stack", X, Psi, selection)
         elif cov:

@@ -432,6 +432,53 @@ int gpz_predictor_draws_gamma_noisy_cov_dev(gpz_predictor *p, const void *X_d, i
                                             const double *Z /* host: NULL or m x ndraws x k */, double *F_d /* ns x k x ndraws, column-major */,
                                             double *Gam_d /* ns x k x ndraws, column-major */, void *stream);
 
+/* ---- a full input-noise covariance per row on the predictor handle, covariance kinds --------------------------------------------------
+ * The four questions of the *_noisy_cov_dev entries for rows whose Psi is a d x d matrix each, the d x d x n cube that fixPsi.m and
+ * predictCov.m:109 take: gpz_predictor_run_psi_cube_dev (the moments), _draws_psi_cube_dev, _draws_gamma_psi_cube_dev and
+ * _stack_psi_cube_dev, where predict_noisy_cov_fits holds (any other model returns GPZ_ERR_UNSUPPORTED and names that function).  Each
+ * has the arguments of its noisy_cov twin with three Psi strides in place of two - element (r, c) of row i lies at
+ * Psi_d[r psi_mrow_stride + c psi_mcol_stride + i psi_row_stride], so the reference's column-major d x d x n cube is (1, d, d d) and an
+ * n x d x d array is read where it lies - and div in place of sd2: the d (d + 1) / 2 divisors sdX[r] sdX[c] at r (r + 1) / 2 + c, a host
+ * or a device pointer (NULL together with muX / sdX: no normalisation).  Only the lower triangle (r >= c) of a row's matrix is read and
+ * scanned; it enters the kernels as double(psi) / div, a plain f64 division (fixPsi.m:36).  An element of a lower triangle that is NaN
+ * or infinite, itself or after its division, or a negative diagonal element -> GPZ_ERR_ARG; rows with NaN -> GPZ_ERR_UNSUPPORTED; a bad
+ * label or weight -> GPZ_ERR_ARG; all found before the first tile (k_pred_check_psi_cube), outputs untouched.  A matrix that passes the
+ * scan but is not positive semidefinite is the caller's error: that row's results are unspecified (NaN where a pivot of
+ * S + Psi_i is not positive) and no other row is affected.
+ * Per tile k_pred_stage_psi_cube packs the lower triangles into [d (d + 1) / 2][tile rows] and k_predict_psi_cube_small / _phi / _gamma
+ * (k_predict_psi_cube.hip, k_predict_psi_cube_gamma.hip) are the noisy_cov kernels with the packed Cholesky of S + Psi_i over the whole
+ * triangle, on the same records, chunk counts, finish kernels, T-GEMM and stack kernel.  A cube with zeros off the diagonal returns the
+ * bits of the noisy_cov entries on its diagonal.  Same bits for any tile size, row order, split into calls and any ndraws > s.  The
+ * first call adds to the handle what the twin adds except the Psi slots, and in their place two slots of d (d + 1) / 2 x tile rows
+ * doubles and the divisor triangle; on a handle that has served the twin it adds only these.  Nothing grows with ns, and
+ * gpz_predictor_route then holds "; noise cube: k_predict_psi_cube_small (C pair chunks)" and, after gamma per draw or a stack,
+ * "; noise cube per draw: k_predict_psi_cube_gamma (C pair chunks)" (" + k_stack_tile_w" once the stack entry has been called). */
+int gpz_predictor_run_psi_cube_dev(gpz_predictor *p, const void *X_d, int32_t x_type, int64_t ns, int64_t row_stride, int64_t col_stride,
+                                   const void *Psi_d, int32_t psi_type, int64_t psi_mrow_stride, int64_t psi_mcol_stride,
+                                   int64_t psi_row_stride, const double *muX, const double *sdX,
+                                   const double *div /* d (d + 1) / 2, host or device */, const double *muY /* k or NULL */,
+                                   double *mu_d, double *sigma_d, double *nu_d, double *beta_d, double *gamma_d, void *stream);
+int gpz_predictor_draws_psi_cube_dev(gpz_predictor *p, const void *X_d, int32_t x_type, int64_t ns, int64_t row_stride,
+                                     int64_t col_stride, const void *Psi_d, int32_t psi_type, int64_t psi_mrow_stride,
+                                     int64_t psi_mcol_stride, int64_t psi_row_stride, const double *muX, const double *sdX,
+                                     const double *div, const double *muY /* k or NULL */, int32_t ndraws, uint64_t seed,
+                                     const double *Z /* host: NULL or m x ndraws x k */,
+                                     double *F_d /* ns x k x ndraws, column-major */, void *stream);
+int gpz_predictor_draws_gamma_psi_cube_dev(gpz_predictor *p, const void *X_d, int32_t x_type, int64_t ns, int64_t row_stride,
+                                           int64_t col_stride, const void *Psi_d, int32_t psi_type, int64_t psi_mrow_stride,
+                                           int64_t psi_mcol_stride, int64_t psi_row_stride, const double *muX, const double *sdX,
+                                           const double *div, const double *muY /* k or NULL */, int32_t ndraws, uint64_t seed,
+                                           const double *Z /* host: NULL or m x ndraws x k */,
+                                           double *F_d /* ns x k x ndraws, column-major */,
+                                           double *Gam_d /* ns x k x ndraws, column-major */, void *stream);
+int gpz_predictor_stack_psi_cube_dev(gpz_predictor *p, const void *X_d, int32_t x_type, int64_t ns, int64_t row_stride, int64_t col_stride,
+                                     const void *Psi_d, int32_t psi_type, int64_t psi_mrow_stride, int64_t psi_mcol_stride,
+                                     int64_t psi_row_stride, const double *muX, const double *sdX, const double *div,
+                                     int32_t ndraws, uint64_t seed, const double *Z, const double *edges, int32_t nbins,
+                                     const int32_t *group_d /* ns or NULL */, int32_t ngroups, const double *weight_d /* ns or NULL */,
+                                     double *hist, double *sum_w, double *sum_mu, double *sum_mu2, const double *mu_shift /* k or NULL */,
+                                     void *stream);
+
 /* ---- rows with missing inputs on the predictor handle ------------------------------------------------------------------------------
  * predictMissing (predictDiag.m:127-209) and the draws for ONE group of rows that share a NaN pattern, on the handle's own tiles,
  * where predict_missing_fits holds: a diagonal kind (GL, VL, GD, VD), d <= 20, k <= 8 and ceil16(m) <= 256, no Psi.  Any other shape
