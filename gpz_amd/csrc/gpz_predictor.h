@@ -71,11 +71,7 @@ struct gpz_predictor {
         bool used = false;
         double *s2_d = nullptr;    // [(1 + nd) k][tile] widths^2 of the stack
         size_t s2_cap = 0;         // doubles
-    } gam[6];                      // [ROWS_NOISY - 1], [ROWS_MISSING - 1], [ROWS_NOISY_MISSING - 1], [ROWS_NOISY_COV - 1], [ROWS_MISSING_COV - 1],
-                                   // [ROWS_NOISY_MISSING_COV - 1]
-    PerDraw gamq;                  // rows with a full Psi each (kind 7, ROWS_PSI_CUBE)
-    PerDraw &per_draw(int kind) { return kind == 7 ? gamq : gam[kind - 1]; }
-    const PerDraw &per_draw(int kind) const { return kind == 7 ? gamq : gam[kind - 1]; }
+    } gam[7];                      // [kind - 1] of the call's RowKind: ROWS_NOISY .. ROWS_PSI_CUBE (clean rows have no gamma per draw)
     // ---- rows with missing inputs on the handle (gpz_predictor_*_missing_dev): nothing of this exists before the first of their calls
     bool miss_used = false;
     int64_t mtile = 0;             // rows per tile of a group: min(tile_rows, GPZ_PREDICTOR_TILE_MISSING)
@@ -145,6 +141,7 @@ struct Rows {
         return kind == ROWS_MISSING || kind == ROWS_NOISY_MISSING || kind == ROWS_MISSING_COV || kind == ROWS_NOISY_MISSING_COV;
     }
     bool cube() const { return kind == ROWS_PSI_CUBE; }   // Psiq[s] is staged beside Xc[s]
+    bool ncov() const { return kind == ROWS_NOISY_COV || kind == ROWS_PSI_CUBE; }   // complete rows of a covariance kind with Psi, either form
     bool cov_group() const { return kind == ROWS_MISSING_COV || kind == ROWS_NOISY_MISSING_COV; }   // such a group on a covariance kind
 };
 

@@ -375,11 +375,11 @@ static int predictor_noisy_cov_phi_tile(gpz_predictor *p) {
 // pairs (the moments, gamma per draw, the stack) the pair records, the 4k-row output slots and the chunk slab of predictor_noisy_prepare,
 // which a covariance kind has from nowhere else; without (the draws) the PHI tile, which a call with pairs and draws takes in
 // rows_fit_tile.
-static int predictor_noisy_cov_prepare(gpz_predictor *p, bool pairs, bool cube = false) {
+static int predictor_noisy_cov_prepare(gpz_predictor *p, const Rows &r, bool pairs) {
     const size_t m = p->m, npair = m * (m + 1) / 2;
     auto &ar = p->ar;
     int rc = 0;
-    if ((rc = cube ? predictor_cube_slots(p) : predictor_psi_slots(p))) return rc;
+    if ((rc = r.cube() ? predictor_cube_slots(p) : predictor_psi_slots(p))) return rc;
     p->cchunks = predict_noisy_cov_chunks(p->m, p->d, p->k);
     const bool basis = !p->cbrec, table = pairs && !p->ncov_ready;
     if (basis && (rc = ar.alloc(&p->cbrec, m * predict_noisy_cov_brec(p->d, p->k)))) return rc;
@@ -395,17 +395,26 @@ static int predictor_noisy_cov_prepare(gpz_predictor *p, bool pairs, bool cube =
     return 0;
 }
 
-// predictNoisy of one tile of nt rows: Xc[s], Psic[s] -> nout[s] ([4k][nt] = mu | nu | beta | gamma); cube: Psiq[s], a full Psi per row
-static int predictor_noisy_cov_tile(gpz_predictor *p, const char *who, int s, int nt, bool cube = false) {
-    if (cube) {
-        if (launch_predict_psi_cube_small(p->s_cmp, p->d, p->mid == 4, p->Xc[s], p->Psiq[s], p->tile_pad, nt, p->m, p->k, p->cbrec,
-                                          p->cprec, p->pr.b, p->cchunks, p->npart, p->tile_pad, p->nout[s]))
-            return gpz_fail(GPZ_ERR_HIP, "%s: k_predict_psi_cube_small launch failed", who);
-        return 0;
-    }
-    if (launch_predict_noisy_cov_small(p->s_cmp, p->d, p->mid == 4, p->Xc[s], p->Psic[s], p->tile_pad, nt, p->m, p->k, p->cbrec, p->cprec,
-                                       p->pr.b, p->cchunks, p->npart, p->tile_pad, p->nout[s]))
-        return gpz_fail(GPZ_ERR_HIP, "%s: k_predict_noisy_cov_small launch failed", who);
+// The two forms of Psi on complete rows of a covariance kind (Rows::ncov()) differ on the host in the tile's Psi slot, in the launchers of
+// their three kernels (the same signatures: k_predict_noisy_cov*.hip and k_predict_psi_cube*.hip) and in the names of those kernels
+struct NcovForm {
+    double *const *Psi;               // Psic: a variance per dimension; Psiq: the packed triangle of a full matrix per row
+    decltype(&launch_predict_noisy_cov_small) small;
+    decltype(&launch_predict_noisy_cov_phi) phi;
+    decltype(&launch_predict_noisy_cov_gamma) gamma;
+    const char *name;                 // k_predict_<name>_small, _phi, _gamma
+};
+static NcovForm ncov_form(const gpz_predictor *p, const Rows &r) {
+    if (r.cube()) return {p->Psiq, launch_predict_psi_cube_small, launch_predict_psi_cube_phi, launch_predict_psi_cube_gamma, "psi_cube"};
+    return {p->Psic, launch_predict_noisy_cov_small, launch_predict_noisy_cov_phi, launch_predict_noisy_cov_gamma, "noisy_cov"};
+}
+
+// predictNoisy of one tile of nt rows: Xc[s] and the form's Psi slot -> nout[s] ([4k][nt] = mu | nu | beta | gamma)
+static int predictor_noisy_cov_tile(gpz_predictor *p, const char *who, const Rows &r, int s, int nt) {
+    const NcovForm f = ncov_form(p, r);
+    if (f.small(p->s_cmp, p->d, p->mid == 4, p->Xc[s], f.Psi[s], p->tile_pad, nt, p->m, p->k, p->cbrec, p->cprec, p->pr.b, p->cchunks,
+                p->npart, p->tile_pad, p->nout[s]))
+        return gpz_fail(GPZ_ERR_HIP, "%s: k_predict_%s_small launch failed", who, f.name);
     return 0;
 }
 
@@ -662,19 +671,13 @@ static int predictor_missing_draws_tile(gpz_predictor *p, const char *who, int s
     return predictor_phi_times_w(p, who, p->mNo, rup(nt, 128), s, nt, ncol, ldw);
 }
 
-// the draws of one tile of nt rows with Psi, covariance kinds: E_x[PHI] (k_predict_noisy_cov_phi, rows of the product padded with
-// zeros) against the handle's W on k_tgemm -> dout[s] ([ncol][nt], without muY)
-static int predictor_noisy_cov_draws_tile(gpz_predictor *p, const char *who, int s, int nt, int ncol, int ldw, bool cube = false) {
+// the draws of one tile of nt rows with Psi, covariance kinds: E_x[PHI] (k_predict_noisy_cov_phi or k_predict_psi_cube_phi, rows of the
+// product padded with zeros) against the handle's W on k_tgemm -> dout[s] ([ncol][nt], without muY)
+static int predictor_noisy_cov_draws_tile(gpz_predictor *p, const char *who, const Rows &r, int s, int nt, int ncol, int ldw) {
     const int np = rup(nt, 128);   // the rows of the product: k_tgemm's row tile
-    if (cube) {   // a full Psi per row in Psiq[s]
-        if (launch_predict_psi_cube_phi(p->s_cmp, p->d, p->mid == 4, p->Xc[s], p->Psiq[s], p->tile_pad, nt, np, p->m, p->mp, p->k, p->cbrec,
-                                        p->cchunks, p->cphi))
-            return gpz_fail(GPZ_ERR_HIP, "%s: k_predict_psi_cube_phi launch failed", who);
-        return predictor_phi_times_w(p, who, p->cphi, np, s, nt, ncol, ldw);
-    }
-    if (launch_predict_noisy_cov_phi(p->s_cmp, p->d, p->mid == 4, p->Xc[s], p->Psic[s], p->tile_pad, nt, np, p->m, p->mp, p->k, p->cbrec,
-                                     p->cchunks, p->cphi))
-        return gpz_fail(GPZ_ERR_HIP, "%s: k_predict_noisy_cov_phi launch failed", who);
+    const NcovForm f = ncov_form(p, r);
+    if (f.phi(p->s_cmp, p->d, p->mid == 4, p->Xc[s], f.Psi[s], p->tile_pad, nt, np, p->m, p->mp, p->k, p->cbrec, p->cchunks, p->cphi))
+        return gpz_fail(GPZ_ERR_HIP, "%s: k_predict_%s_phi launch failed", who, f.name);
     return predictor_phi_times_w(p, who, p->cphi, np, s, nt, ncol, ldw);
 }
 
@@ -815,7 +818,7 @@ int rows_check(const char *who, const gpz_predictor *p, const Rows &r, bool draw
     if (r.group())   // (with Psi too: its product against W needs no fused draws route)
         return predictor_missing_check(who, p, r.obs, r.cov_group(), r.kind == ROWS_NOISY_MISSING_COV);
     if (r.kind == ROWS_CLEAN) return 0;
-    if (r.kind == ROWS_NOISY_COV || r.cube()) return predictor_noisy_cov_check(who, p);   // (its draws are a product on the T-GEMM: any route)
+    if (r.ncov()) return predictor_noisy_cov_check(who, p);   // (its draws are a product on the T-GEMM: any route)
     if (int rc = predictor_noisy_check(who, p)) return rc;
     if (draws && p->force_tiles)
         return gpz_fail(GPZ_ERR_UNSUPPORTED, "%s: input noise needs the fused draws route (GPZ_PREDICT_FORCE_TILES is set)", who);
@@ -834,14 +837,9 @@ int rows_prepare(gpz_predictor *p, const char *who, const Rows &r, bool pairs) {
     }
     if (r.group()) return predictor_missing_prepare(p, who, r.obs, r.priors, pairs, r.kind == ROWS_NOISY_MISSING);
     if (r.kind == ROWS_NOISY) return pairs ? predictor_noisy_prepare(p) : predictor_psi_slots(p);
-    if (r.kind == ROWS_NOISY_COV) {
-        if (int rc = predictor_noisy_cov_prepare(p, pairs)) return rc;
-        if (pairs) p->ncov_used = true;
-        return 0;
-    }
-    if (r.cube()) {
-        if (int rc = predictor_noisy_cov_prepare(p, pairs, true)) return rc;
-        if (pairs) p->cube_used = true;
+    if (r.ncov()) {
+        if (int rc = predictor_noisy_cov_prepare(p, r, pairs)) return rc;
+        if (pairs) (r.cube() ? p->cube_used : p->ncov_used) = true;   // (two flags: the route text has a line for each form)
     }
     return 0;
 }
@@ -855,7 +853,7 @@ int rows_moments_tile(gpz_predictor *p, const char *who, const Rows &r, int s, i
     if (r.cov_group()) return predictor_missing_cov_tile(p, who, s, nt, r.obs, true, r.psi() ? p->Psic[s] : nullptr);
     if (r.group()) return predictor_missing_tile(p, who, s, nt, r.obs, true, r.psi() ? p->Psic[s] : nullptr);
     if (r.kind == ROWS_NOISY) return predictor_noisy_tile(p, who, s, nt);
-    if (r.kind == ROWS_NOISY_COV || r.cube()) return predictor_noisy_cov_tile(p, who, s, nt, r.cube());
+    if (r.ncov()) return predictor_noisy_cov_tile(p, who, r, s, nt);
     return predictor_tile(p, s, nt, want_phi);
 }
 
@@ -867,8 +865,8 @@ const double *rows_moments(const gpz_predictor *p, const Rows &r, int s) {
 // the tile route of the draws has one already, the fused route does not
 static int rows_fit_tile(gpz_predictor *p, const Rows &r, int ncol, int ldw, int64_t *T) {
     *T = rows_tile(p, r, *T);   // (ROWS_MISSING_COV is a group: its PHI_missing W takes the same output tile)
-    if ((!r.group() && r.kind != ROWS_NOISY_COV && !r.cube()) || ncol == 0) return 0;   // (a covariance kind with Psi: the output tile of E_x[PHI] W)
-    if (r.kind == ROWS_NOISY_COV || r.cube())   // (a call that reads the pairs too - gamma per draw, a stack with draws - has no PHI tile from rows_prepare)
+    if ((!r.group() && !r.ncov()) || ncol == 0) return 0;   // (a covariance kind with Psi: the output tile of E_x[PHI] W)
+    if (r.ncov())   // (a call that reads the pairs too - gamma per draw, a stack with draws - has no PHI tile from rows_prepare)
         if (int rc = predictor_noisy_cov_phi_tile(p)) return rc;
     return predictor_grow(p, &p->Td, &p->t_cap, (size_t)rup(*T, 1024) * ldw);
 }
@@ -884,7 +882,7 @@ int rows_draws_prepare(gpz_predictor *p, const Rows &r, int nd, unsigned long lo
 int rows_draws_tile(gpz_predictor *p, const char *who, const Rows &r, int s, int nt, int ncol, int ldw, bool after_moments) {
     if (r.kind == ROWS_CLEAN) return predictor_draws_tile(p, s, nt, ncol, ldw, after_moments && p->route == 1);
     if (r.kind == ROWS_NOISY) return predictor_draws_tile(p, s, nt, ncol, ldw, false, p->Psic[s]);
-    if (r.kind == ROWS_NOISY_COV || r.cube()) return predictor_noisy_cov_draws_tile(p, who, s, nt, ncol, ldw, r.cube());
+    if (r.ncov()) return predictor_noisy_cov_draws_tile(p, who, r, s, nt, ncol, ldw);
     if (!after_moments)   // (a covariance kind's PHI_missing lies in mNo as the diagonal kinds' does)
         if (int rc = r.cov_group() ? predictor_missing_cov_tile(p, who, s, nt, r.obs, false, r.psi() ? p->Psic[s] : nullptr)
                                    : predictor_missing_tile(p, who, s, nt, r.obs, false, r.psi() ? p->Psic[s] : nullptr))
@@ -897,9 +895,9 @@ int rows_chunks(const gpz_predictor *p, const Rows &r) { return r.group() ? p->m
 // What a call that needs gamma under nd draws on tiles of T rows adds to the handle (after rows_prepare with pairs: the pair table, or U
 // and the records): the chunk slab of the pair sums and, for a stack of Q column-outputs, the kind's widths.  nd = 0 takes no slab.
 int rows_gamma_prepare(gpz_predictor *p, const Rows &r, int ncol, int Q, int64_t T) {
-    gpz_predictor::PerDraw &g = p->per_draw(r.kind);
+    gpz_predictor::PerDraw &g = p->gam[r.kind - 1];
     int rc = 0;
-    if (r.kind == ROWS_NOISY || r.kind == ROWS_NOISY_COV || r.cube()) p->gchunks = predict_gamma_chunks(p->m);   // (a handle has one of the two kinds)
+    if (r.kind == ROWS_NOISY || r.ncov()) p->gchunks = predict_gamma_chunks(p->m);   // (a handle has one of the two kinds)
     if (ncol > 0 && (rc = predictor_grow(p, &p->gpart, &p->gpart_cap, (size_t)rows_chunks(p, r) * ncol * T))) return rc;
     if (Q > 0 && (rc = predictor_grow(p, &g.s2_d, &g.s2_cap, (size_t)Q * T))) return rc;
     g.used = true;
@@ -908,16 +906,11 @@ int rows_gamma_prepare(gpz_predictor *p, const Rows &r, int ncol, int Q, int64_t
 
 // the pair sums under every draw of one tile of nt rows (a group: after predictor_missing_tile, mPio): -> gpart ([chunks][ncol][nt])
 int rows_gamma_tile(gpz_predictor *p, const char *who, const Rows &r, int s, int nt, int ncol, int ldw) {
-    if (r.kind == ROWS_NOISY_COV) {   // the head of the packed pair records, read with the table's stride
-        if (launch_predict_noisy_cov_gamma(p->s_cmp, p->d, p->mid == 4, p->Xc[s], p->Psic[s], p->tile_pad, nt, p->m, p->cprec,
-                                           predict_noisy_cov_prec(p->d, p->k), p->Wd, ldw, ncol, p->gchunks, p->gpart, nt))
-            return gpz_fail(GPZ_ERR_HIP, "%s: k_predict_noisy_cov_gamma launch failed", who);
-        return 0;
-    }
-    if (r.cube()) {   // the same records, a full Psi per row in Psiq[s]
-        if (launch_predict_psi_cube_gamma(p->s_cmp, p->d, p->mid == 4, p->Xc[s], p->Psiq[s], p->tile_pad, nt, p->m, p->cprec,
-                                          predict_noisy_cov_prec(p->d, p->k), p->Wd, ldw, ncol, p->gchunks, p->gpart, nt))
-            return gpz_fail(GPZ_ERR_HIP, "%s: k_predict_psi_cube_gamma launch failed", who);
+    if (r.ncov()) {   // the head of the packed pair records, read with the table's stride; Psi in the form's slot
+        const NcovForm f = ncov_form(p, r);
+        if (f.gamma(p->s_cmp, p->d, p->mid == 4, p->Xc[s], f.Psi[s], p->tile_pad, nt, p->m, p->cprec, predict_noisy_cov_prec(p->d, p->k),
+                    p->Wd, ldw, ncol, p->gchunks, p->gpart, nt))
+            return gpz_fail(GPZ_ERR_HIP, "%s: k_predict_%s_gamma launch failed", who, f.name);
         return 0;
     }
     if (r.kind == ROWS_MISSING_COV) {   // the slab of the pattern's pair records: kept, or written here as the pair kernel writes it
@@ -1001,7 +994,7 @@ int predictor_stack_tile(gpz_predictor *p, const char *who, const Rows &r, const
     if (r.kind == ROWS_CLEAN) {
         bad = launch_stack_tile(st, mom, F, lab, wt, p->edges_d, sh, nt, p->k, c.nd, c.B, c.G, c.R, p->slab_d);
     } else {
-        double *s2 = p->per_draw(r.kind).s2_d;
+        double *s2 = p->gam[r.kind - 1].s2_d;
         if (c.nd > 0 && (rc = rows_gamma_tile(p, who, r, s, (int)nt, c.ncol, c.ldw))) return rc;
         if (launch_gamma_finish_s2(st, p->gpart, rows_chunks(p, r), nt, mom, F, (int)nt, p->k, c.nd, s2))
             return gpz_fail(GPZ_ERR_HIP, "%s: k_gamma_finish_s2 launch failed", who);
@@ -1137,7 +1130,7 @@ extern "C" int gpz_predictor_route(const gpz_predictor *p, char *buf, int cap) {
     else
         snprintf(tmp, sizeof tmp, "tiles: k_phi + k_tgemm, %lld-row tiles", (long long)p->tile_rows);
     std::string r = tmp;
-    // after the first stack or gamma-per-draw call for a kind of rows (per_draw(kind)): its kernel and chunks (a group's: mchunks)
+    // after the first stack or gamma-per-draw call for a kind of rows (gam[kind - 1]): its kernel and chunks (a group's: mchunks)
     static const struct { const char *fmt; bool group; } PER_DRAW[7] = {
         {"; noise per draw: k_predict_noisy_gamma (%d pair chunks)", false},
         {"; missing per draw: k_predict_missing_gamma (%d pair chunks)", true},
@@ -1146,8 +1139,8 @@ extern "C" int gpz_predictor_route(const gpz_predictor *p, char *buf, int cap) {
         {"; missing per draw: k_predict_missing_cov_gamma (%d pair chunks)", true},
         {"; noisy missing per draw: k_predict_noisy_missing_cov_gamma (%d pair chunks)", true},
         {"; noise cube per draw: k_predict_psi_cube_gamma (%d pair chunks)", false}};
-    auto per_draw = [&](int i) {
-        const gpz_predictor::PerDraw &g = p->per_draw(i + 1);
+    auto gamma_line = [&](int i) {
+        const gpz_predictor::PerDraw &g = p->gam[i];
         if (!g.used) return;
         snprintf(tmp, sizeof tmp, PER_DRAW[i].fmt, PER_DRAW[i].group ? p->mchunks : p->gchunks);
         r += tmp;
@@ -1172,13 +1165,13 @@ extern "C" int gpz_predictor_route(const gpz_predictor *p, char *buf, int cap) {
         snprintf(tmp, sizeof tmp, "; noise: k_predict_noisy_cov_small (%d pair chunks)", p->cchunks);
         r += tmp;
     }
-    per_draw(3);
+    gamma_line(3);
     if (p->cube_used) {   // after the first call with a full Psi per row that reads the pairs
         snprintf(tmp, sizeof tmp, "; noise cube: k_predict_psi_cube_small (%d pair chunks)", p->cchunks);
         r += tmp;
     }
-    per_draw(6);
-    per_draw(0);
+    gamma_line(6);
+    gamma_line(0);
     if (p->miss_used) {   // after the first call for a group of rows with missing inputs
         snprintf(tmp, sizeof tmp, "; missing: k_predict_missing_pairs (%d pair chunks), %lld-row tiles", p->mchunks, (long long)p->mtile);
         r += tmp;
@@ -1187,18 +1180,18 @@ extern "C" int gpz_predictor_route(const gpz_predictor *p, char *buf, int cap) {
         snprintf(tmp, sizeof tmp, "; missing: k_predict_missing_cov_pairs (%d pair chunks)", p->mchunks);
         r += tmp;
     }
-    per_draw(4);
-    per_draw(1);
+    gamma_line(4);
+    gamma_line(1);
     if (p->nm_used) {   // after the first call for a group of rows with input noise and missing inputs
         snprintf(tmp, sizeof tmp, "; noisy missing: k_predict_noisy_missing_pairs (%d pair chunks)", p->mchunks);
         r += tmp;
     }
-    per_draw(2);
+    gamma_line(2);
     if (p->nmcov_used) {   // after the first call for such a group on a covariance kind
         snprintf(tmp, sizeof tmp, "; noisy missing: k_predict_noisy_missing_cov_pairs (%d pair chunks)", p->mchunks);
         r += tmp;
     }
-    per_draw(5);
+    gamma_line(5);
     snprintf(buf, (size_t)cap, "%s", r.c_str());
     return (int)r.size();
 }

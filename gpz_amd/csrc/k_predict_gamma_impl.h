@@ -17,17 +17,16 @@
 //       its pair's (a, b) and steps them by 4 pairs.
 //       Density::NB blocks of accumulators per pass; more columns are further passes on gridDim.z that form z again.  gridDim.y: the
 //       pair chunks, predict_gamma_chunks(m) of the model's shape alone; chunk c writes its partial sums to part [C][ncol][ldp].
-//   Density    a struct without virtuals: D (the dimension), RL (the doubles of a record head that are staged), NB (16-column blocks
+//   Density    a struct without virtuals: D (the dimension), PW (the values of Psi a lane loads for its row: D columns of Psic, or
+//              more where a row's Psi is a packed triangle), RL (the doubles of a record head that are staged), NB (16-column blocks
 //              of accumulators per pass), its members (what a lane keeps across K steps), init(tab, ps) once per row before the
 //              loop, and z(t, x, ps) for one staged head t.
-//              Optional: PW, the values of Psi per row where that is not D (gamma_psi_width below), with bind(P, ldx).
 // No atomics; every sum starts from zero and runs in one order that the model's shape fixes (pairs in table order, four per K step from
 // the chunk's first pair, chunks in chunk order): a row's gamma_s has the same bits for any tile size, row order, position in its block,
 // other rows of the call and any number of draws > s.
 #pragma once
 #include "gpz_dev.h"
 #include "gpz_kernels.h"
-#include <type_traits>
 
 #define GPZ_GAMMA_TP 32   // pair records per LDS stage: 8 K steps
 #define GPZ_GAMMA_PF 4    // the blocks whose W rows are fetched ahead of the density work (64 columns: the usual 64 draws)
@@ -59,24 +58,9 @@ static inline dim3 predict_gamma_grid(const PredGammaArgs &a, int nchunk, int nb
     return dim3((unsigned)((a.n + 63) / 64), (unsigned)nchunk, (unsigned)((a.nbw + nb - 1) / nb));
 }
 
-// The values of Psi a lane loads for its row: Density::D columns of Psic, or Density::PW where a policy declares it (a packed triangle is
-// wider than D).  A policy with PW also has bind(P, ldx), called before init with the lane's place in Psic, for what it reads there
-// itself.
-template <class Density, class = void>
-struct gamma_psi_width {
-    static constexpr int value = Density::D;
-    static constexpr bool bind = false;
-};
-template <class Density>
-struct gamma_psi_width<Density, std::void_t<decltype(Density::PW)>> {
-    static constexpr int value = Density::PW;
-    static constexpr bool bind = true;
-};
-
 template <class Density>
 __device__ __forceinline__ void predict_gamma_body(const PredGammaArgs &a) {
-    constexpr int D = Density::D, RL = Density::RL, NB = Density::NB, NST = GPZ_GAMMA_TP * RL, NPRE = (NST + 255) / 256;
-    constexpr int PW = gamma_psi_width<Density>::value;
+    constexpr int D = Density::D, PW = Density::PW, RL = Density::RL, NB = Density::NB, NST = GPZ_GAMMA_TP * RL, NPRE = (NST + 255) / 256;
     __shared__ double sT[NST];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, g = lane >> 4, lr = lane & 15;
     const long i = ((long)blockIdx.x * 4 + wv) * 16 + lr;
@@ -118,7 +102,6 @@ __device__ __forceinline__ void predict_gamma_body(const PredGammaArgs &a) {
     for (int q = 0; q < NB; ++q) acc[q] = (d4_t){0.0, 0.0, 0.0, 0.0};
     const double *wl = a.W + (size_t)cb0 * 16 + lr;
     Density den;
-    if constexpr (gamma_psi_width<Density>::bind) den.bind(a.Psic + ic, a.ldx);
     den.init(a.tab, ps);
     double pre[NPRE];
     // the heads of the records [pbase, pbase + 32) of the chunk (clamped to its last one, so that every slot of a stage holds a record)

@@ -4,39 +4,24 @@
 //
 //   k_predict_noisy_cov_gamma<D, SHARED>
 //       predict_gamma_body (k_predict_gamma_impl.h: k_predict_noisy_gamma's frame, the f64 MFMA product of pair densities and weight
-//       products, its LDS stages, chunks and passes) with GammaCov<D, SHARED>.  The density is k_predict_noisy_cov_small's
-//       (ncov_factor / ncov_density, k_ncov_density.h): the packed Cholesky of C_ab + diag(psi_i) and a forward substitution,
+//       products, its LDS stages, chunks and passes) with GammaNcov<PsiDiag<D>, SHARED, ncg_blocks(D)> (k_ncov_density.h).  The density
+//       is k_predict_noisy_cov_small's: the packed Cholesky of C_ab + diag(psi_i) and a forward substitution,
 //       z = exp(lnZ - 1/2 q) prod(1 / L_cc), from the record head [lnZ | c_ab | C_ab packed lower], the first 1 + d + d (d + 1) / 2
-//       doubles of the handle's packed pair records.  A lane keeps the factor M, rd, prd across K steps.
-//       SHARED (GC): every C_ab is one matrix, so a lane factorises C + psi of its row once, from record 0, before the loop (the same
-//       bits in every chunk and pass), and a K step is the substitution alone.
+//       doubles of the handle's packed pair records.
 //       ncg_blocks(D) 16-column blocks of accumulators per pass: 8 (128 columns) for d <= 7, 4 for d >= 8, where the packed triangle
 //       leaves the accumulators less room.
 // k_gamma_finish_dev / k_gamma_finish_s2 (k_predict_noisy_gamma.hip) add the chunks and take mu_s^2 off.
 #include "k_predict_gamma_impl.h"
-#include "k_ncov_density.h"   // ncov_factor, ncov_density
+#include "k_ncov_density.h"   // GammaNcov, PsiDiag
 
 // 16-column blocks of accumulators per pass
 constexpr int ncg_blocks(int d) { return d <= 7 ? 8 : 4; }
-
-template <int DD, bool SHARED>
-struct GammaCov {
-    static constexpr int D = DD, NP = DD * (DD + 1) / 2, RL = 1 + DD + NP, NB = ncg_blocks(DD);
-    double M[NP], rd[DD], prd;
-    __device__ __forceinline__ void init(const double *tab, const double (&ps)[DD]) {
-        if (SHARED) ncov_factor<DD>(tab + 1 + DD, ps, M, rd, &prd);   // C + Psi of the row, once                  predictCov.m:109
-    }
-    __device__ __forceinline__ double z(const double *t, const double (&x)[DD], const double (&ps)[DD]) {
-        if (!SHARED) ncov_factor<DD>(t + 1 + DD, ps, M, rd, &prd);    // Cij + Psi                                 :109
-        return ncov_density<DD>(t + 1, t[0], x, M, rd, prd);          //                                           :111
-    }
-};
 
 // D = 9 is held to 256 registers (two workgroups per compute unit) by the second launch bound: left alone it takes 252 (VC) and 258
 // (GC).  D = 10 does not fit 256 without scratch and keeps one workgroup per compute unit.
 template <int D, bool SHARED>
 __global__ __launch_bounds__(256, D == 9 ? 2 : 1) void k_predict_noisy_cov_gamma(PredGammaArgs a) {
-    predict_gamma_body<GammaCov<D, SHARED>>(a);
+    predict_gamma_body<GammaNcov<PsiDiag<D>, SHARED, ncg_blocks(D)>>(a);
 }
 
 template <int D>

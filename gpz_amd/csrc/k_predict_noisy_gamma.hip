@@ -16,7 +16,7 @@
 
 template <int DT>
 struct GammaDiag {
-    static constexpr int D = DT, RL = 1 + 2 * DT, NB = GPZ_GAMMA_NB;
+    static constexpr int D = DT, PW = DT, RL = 1 + 2 * DT, NB = GPZ_GAMMA_NB;
     __device__ __forceinline__ void init(const double *, const double (&)[DT]) {}
     __device__ __forceinline__ double z(const double *t, const double (&x)[DT], const double (&ps)[DT]) const {
         double q = 0.0, rp = 1.0;

@@ -4,48 +4,22 @@
 //
 //   k_predict_psi_cube_gamma<D, SHARED>
 //       predict_gamma_body (k_predict_gamma_impl.h: the f64 MFMA product of pair densities and weight products, its LDS stages, chunks
-//       and passes) with GammaCube<D, SHARED>: k_predict_noisy_cov_gamma's policy with M = C_ab + Psi_i over the whole packed triangle
-//       (ncov_factor_tri / ncov_density, k_ncov_density.h), the density of k_predict_psi_cube_small.  The row's triangle is the
-//       d (d + 1) / 2 columns of the tile's Psic at the lane's row.
-//       SHARED (GC): the body loads the triangle, init factorises C + Psi_i once from record 0 and nothing of it is live in the loop.
-//       VC: in registers beside M up to D = GPZ_PSI_CUBE_REG_D (psi_cube_regs); above it z() reads the columns again at every K step
-//       (the 16 rows of a wave are 128 contiguous bytes of a column).
+//       and passes) with GammaNcov<PsiTri<D>, SHARED, pcg_blocks(D)> (k_ncov_density.h): k_predict_noisy_cov_gamma's policy with
+//       M = C_ab + Psi_i over the whole packed triangle, the density of k_predict_psi_cube_small.  The row's triangle is the
+//       d (d + 1) / 2 columns of the tile's Psic at the lane's row, which the body loads into registers.
 //       pcg_blocks(D) 16-column blocks of accumulators per pass.
 // k_gamma_finish_dev / k_gamma_finish_s2 (k_predict_noisy_gamma.hip) add the chunks and take mu_s^2 off.  The chunk count is the
 // caller's predict_gamma_chunks(m).
 #include "k_predict_gamma_impl.h"
-#include "k_ncov_density.h"   // ncov_factor_tri, ncov_density, psi_cube_regs
+#include "k_ncov_density.h"   // GammaNcov, PsiTri
 
 // 16-column blocks of accumulators per pass: 8 (128 columns) up to d = 6, then 4 - one width earlier than k_predict_noisy_cov_gamma,
 // so that d = 7 with the row's triangle beside M stays within 256 registers (two workgroups per compute unit)
 constexpr int pcg_blocks(int d) { return d <= 6 ? 8 : 4; }
 
-template <int DD, bool SHARED>
-struct GammaCube {
-    static constexpr int D = DD, NP = DD * (DD + 1) / 2, RL = 1 + DD + NP, NB = pcg_blocks(DD);
-    static constexpr bool REG = SHARED || psi_cube_regs(DD);   // the body loads the triangle into the lane's registers
-    static constexpr int PW = REG ? NP : 1;
-    double M[NP], rd[DD], prd;
-    const double *P;   // the lane's place in Psic, element q at P[q ldx]
-    long ldx;
-    __device__ __forceinline__ void bind(const double *P_, long ldx_) {
-        if constexpr (!REG) { P = P_; ldx = ldx_; }
-    }
-    __device__ __forceinline__ void init(const double *tab, const double (&ps)[PW]) {
-        if constexpr (SHARED) ncov_factor_tri<DD>(tab + 1 + DD, ps, 1, M, rd, &prd);   // C + Psi_i of the row, once       predictCov.m:109
-    }
-    __device__ __forceinline__ double z(const double *t, const double (&x)[DD], const double (&ps)[PW]) {
-        if constexpr (!SHARED) {
-            if constexpr (REG) ncov_factor_tri<DD>(t + 1 + DD, ps, 1, M, rd, &prd);     // Cij + Psi_i                     :109
-            else ncov_factor_tri<DD>(t + 1 + DD, P, ldx, M, rd, &prd);
-        }
-        return ncov_density<DD>(t + 1, t[0], x, M, rd, prd);                            //                                 :111
-    }
-};
-
 template <int D, bool SHARED>
 __global__ __launch_bounds__(256) void k_predict_psi_cube_gamma(PredGammaArgs a) {
-    predict_gamma_body<GammaCube<D, SHARED>>(a);
+    predict_gamma_body<GammaNcov<PsiTri<D>, SHARED, pcg_blocks(D)>>(a);
 }
 
 template <int D>

@@ -35,7 +35,8 @@ def test_header_binding_library_and_entry_table_agree():
     E = gpz_amd.predictor._DEV_ENTRIES
     assert E["run", "noisy_cov"] == "gpz_predictor_run_noisy_cov_dev" and E["draws", "noisy_cov"] == "gpz_predictor_draws_noisy_cov_dev"
     assert E["run", "noisy"] == "gpz_predictor_run_noisy_dev" and E["draws", "noisy"] == "gpz_predictor_draws_noisy_dev"
-    assert "k_predict_noisy_cov " in open(os.path.join(ROOT, "build.sh")).read()
+    build = open(os.path.join(ROOT, "build.sh")).read()
+    assert "k_predict_noisy_cov " in build and "$SRC/k_predict_ncov_impl.h" in build   # the unit and the header that holds its kernels' bodies
 
 
 @pytest.mark.skipif(shutil.which("hipcc") is None, reason="needs hipcc")

@@ -1,9 +1,10 @@
 """CPU-side checks of rows with a full input-noise covariance on the predictor handle (Predictor.predict_psi_cube_dev /
 draws_psi_cube_dev / stack_psi_cube_dev; gpz_predictor_run_psi_cube_dev, _draws_psi_cube_dev, _draws_gamma_psi_cube_dev and
 _stack_psi_cube_dev of the C ABI): the entries are declared with their twins' arguments but three Psi strides and the divisor triangle,
-bound, exported and in the entry table; the factor step has one definition and the new units no chunk rule; k_predict_psi_cube.hip and
-k_predict_psi_cube_gamma.hip compile for gfx950 to complete instantiation sets without scratch, spills or atomics, inside the register
-bounds of DESIGN.md section 33; and every refusal of the three methods fires before the GPU is touched."""
+bound, exported and in the entry table; the factor step, the Psi policy and each kernel body have one definition and the units no
+chunk rule; k_predict_psi_cube.hip and k_predict_psi_cube_gamma.hip compile for gfx950 to complete instantiation sets without scratch,
+spills or atomics, inside the register bounds of DESIGN.md section 33; and every refusal of the three methods fires before the GPU is
+touched."""
 import os
 import re
 import shutil
@@ -61,30 +62,84 @@ def test_header_binding_library_and_entry_table_agree():
                                                                                               ENTRIES))
     build = open(os.path.join(ROOT, "build.sh")).read()
     assert " k_predict_psi_cube " in build and " k_predict_psi_cube_gamma " in build and "k_ncov_density.h" in build
+    assert "$SRC/k_predict_ncov_impl.h" in build                          # a change to the shared bodies rebuilds the units
     for m in ("predict_psi_cube_dev", "draws_psi_cube_dev", "stack_psi_cube_dev"):
         assert callable(getattr(gpz_amd.Predictor, m))
 
 
+def _sources():
+    return {f: open(os.path.join(CSRC, f)).read() for f in sorted(os.listdir(CSRC))}
+
+
 def test_the_factor_has_one_definition_and_the_units_no_chunk_rule():
-    head = open(os.path.join(CSRC, "k_ncov_density.h")).read()
+    """The factor, the density and the Psi policy live in k_ncov_density.h alone; both units take their kernels from the bodies of
+    k_predict_ncov_impl.h (the tile kernels) and from GammaNcov (the gamma kernel) with PsiTri, which is where ncov_factor_tri is
+    called; neither has a chunk rule; and the host passes the handle's chunk counts to the form's launchers."""
+    src = _sources()
+    head = src["k_ncov_density.h"]
     assert len(re.findall(r"__device__[^;{]*\bncov_factor_tri\s*\(", head)) == 1
-    for f in os.listdir(CSRC):
+    for f, text in src.items():
         if f != "k_ncov_density.h":
-            assert not re.search(r"__device__[^;{]*\bncov_factor_tri\s*\(", open(os.path.join(CSRC, f)).read()), f
-    for unit in UNITS:
-        text = open(os.path.join(CSRC, unit)).read()
-        assert re.search(r'#include\s+"k_ncov_density\.h"', text), unit
-        code = re.sub(r"//.*", "", text)
-        assert "ncov_factor_tri<" in code and "ncov_density<" in code, unit
+            assert not re.search(r"__device__[^;{]*\bncov_factor_tri\s*\(", text), f
+            assert "ncov_factor_tri<" not in re.sub(r"//.*", "", text), f     # reached through PsiTri alone
+    tri = re.search(r"struct PsiTri \{.*?\n\};", head, flags=re.S).group(0)
+    assert "ncov_factor_tri<DD>(S, ps, 1, M, rd, prd)" in tri and "W = DD * (DD + 1) / 2" in tri
+    impl = re.sub(r"//.*", "", src["k_predict_ncov_impl.h"])
+    assert re.search(r'#include\s+"k_ncov_density\.h"', impl) and "Psi::factor(" in impl and "ncov_density<" in impl
+    policy = re.search(r"struct GammaNcov \{.*?\n\};", head, flags=re.S).group(0)
+    assert "Psi::factor(" in policy and "ncov_density<" in policy
+    for unit, needs in ((UNITS[0], ('#include "k_predict_ncov_impl.h"', "predict_ncov_small_body<PsiTri<D>, SHARED, KM>(a)",
+                                    "predict_ncov_phi_body<PsiTri<D>, SHARED>(a)")),
+                        (UNITS[1], ('#include "k_ncov_density.h"', "predict_gamma_body<GammaNcov<PsiTri<D>, SHARED, pcg_blocks(D)>>(a)"))):
+        code = re.sub(r"//.*", "", src[unit])
+        for word in needs:
+            assert word in code, (unit, word)
         assert not re.search(r"__device__[^;{]*\b(ncov_(factor|density)|chol_packed_rd)\s*\(", code), unit
         assert not re.search(r"\bint\s+\w*chunks\s*\(", code) and "predict_gamma_chunks" not in code, unit
         assert "predict_noisy_cov_chunks" not in code, unit
-    host = re.sub(r"//.*", "", open(os.path.join(CSRC, "gpz_predictor.hip")).read())
-    assert re.search(r"launch_predict_psi_cube_small\([^;]*p->cchunks", host, flags=re.S)
-    assert re.search(r"launch_predict_psi_cube_phi\([^;]*p->cchunks", host, flags=re.S)
-    assert re.search(r"launch_predict_psi_cube_gamma\([^;]*p->gchunks[^;]*p->gpart", host, flags=re.S)
+    assert not re.search(r"\bint\s+\w*chunks\s*\(", impl) and "predict_noisy_cov_chunks" not in impl
+    host = re.sub(r"//.*", "", src["gpz_predictor.hip"])
+    form = re.search(r"static NcovForm ncov_form\(.*?\n\}", host, flags=re.S).group(0)
+    assert re.search(r"r\.cube\(\)\) return \{p->Psiq, launch_predict_psi_cube_small, launch_predict_psi_cube_phi, "
+                     r"launch_predict_psi_cube_gamma, \"psi_cube\"\}", form)
+    assert re.search(r"\bf\.small\([^;]*f\.Psi\[s\][^;]*p->cchunks", host, flags=re.S)
+    assert re.search(r"\bf\.phi\([^;]*f\.Psi\[s\][^;]*p->cchunks", host, flags=re.S)
+    assert re.search(r"\bf\.gamma\([^;]*f\.Psi\[s\][^;]*p->gchunks[^;]*p->gpart", host, flags=re.S)
     prep = re.search(r"int rows_gamma_prepare\(.*?\n\}", host, flags=re.S).group(0)
-    assert re.search(r"r\.cube\(\)[^;]*gchunks\s*=\s*predict_gamma_chunks\(p->m\)", prep)
+    assert re.search(r"r\.ncov\(\)[^;]*gchunks\s*=\s*predict_gamma_chunks\(p->m\)", prep)
+    assert re.search(r"bool ncov\(\) const \{ return kind == ROWS_NOISY_COV \|\| kind == ROWS_PSI_CUBE; \}", src["gpz_predictor.h"])
+
+
+def test_each_body_has_one_definition_and_the_host_no_cube_flag():
+    """The record loops of the four tile kernels are the two bodies of k_predict_ncov_impl.h and the two gamma policies are GammaNcov:
+    each is defined once in the tree, the four units hold wrappers only, and the host tells the two forms apart by the kind of rows."""
+    src = _sources()
+    code = {f: re.sub(r"//.*", "", t) for f, t in src.items()}
+    for body, home in (("predict_ncov_small_body", "k_predict_ncov_impl.h"), ("predict_ncov_phi_body", "k_predict_ncov_impl.h"),
+                       ("struct GammaNcov", "k_ncov_density.h"), ("struct PsiDiag", "k_ncov_density.h"), ("struct PsiTri", "k_ncov_density.h")):
+        pat = re.escape(body) + (r"\s*\{" if body.startswith("struct") else r"\s*\(const PredNcovArgs &a\)\s*\{")
+        assert [f for f, t in code.items() if re.search(pat, t)] == [home], body
+    # the record loops themselves: the calls that form a density per record stand in the two headers and nowhere else
+    assert sorted(f for f, t in code.items() if "Psi::factor(" in t) == ["k_ncov_density.h", "k_predict_ncov_impl.h"]
+    assert not [f for f, t in code.items() if "ncov_density<" in t and re.match(r"k_predict_(noisy_cov|psi_cube)", f)]
+    for unit, kernels in (("k_predict_noisy_cov.hip", ("k_predict_noisy_cov_small", "k_predict_noisy_cov_phi")),
+                          ("k_predict_psi_cube.hip", ("k_predict_psi_cube_small", "k_predict_psi_cube_phi")),
+                          ("k_predict_noisy_cov_gamma.hip", ("k_predict_noisy_cov_gamma",)),
+                          ("k_predict_psi_cube_gamma.hip", ("k_predict_psi_cube_gamma",))):
+        for kname in kernels:
+            m = re.search(r"__global__[^{;]*\bvoid " + kname + r"\((?:PredNcovArgs|PredGammaArgs) a\) \{\s*(.*?)\s*\}", code[unit], flags=re.S)
+            assert m and re.fullmatch(r"predict_\w+_body<[^;]*>\(a\);", m.group(1)), (unit, kname)   # a wrapper: one call
+        assert "__syncthreads" not in code[unit] and "__shared__" not in code[unit], unit   # no staging loop of its own
+        for word in ("struct GammaCov", "struct GammaCube", "PredNoisyCovArgs", "PredPsiCubeArgs"):
+            assert word not in code[unit], (unit, word)
+    for f, t in code.items():
+        for word in ("GPZ_PSI_CUBE_REG_D", "psi_cube_regs", "gamq", "per_draw("):
+            assert word not in t, (f, word)
+        assert not re.search(r"\bbool cube\b(?!\()", t), f              # no flag parameter (Rows::cube() and cube_used are not one)
+    assert "den.bind(" not in code["k_predict_gamma_impl.h"] and "gamma_psi_width" not in code["k_predict_gamma_impl.h"]
+    host = code["gpz_predictor.hip"]
+    assert len(re.findall(r"ROWS_NOISY_COV\s*\|\|", host + code["gpz_predictor_dev.hip"] + code["gpz_predictor_host.hip"])) == 0
+    assert "} gam[7];" in src["gpz_predictor.h"] and "p->gam[r.kind - 1]" in host
 
 
 def _compile(unit, tmp_path):

@@ -43,21 +43,39 @@ def test_header_binding_library_and_entry_table_agree():
 
 
 def test_the_density_is_shared_and_the_chunks_are_the_existing_function():
-    """Both units take ncov_factor / ncov_density from one header and define neither; the new unit has no chunk rule of its own and the
-    host takes this kind's chunks from predict_gamma_chunks."""
+    """Both units take ncov_factor / ncov_density from one header and define neither (the tile kernels through the bodies of
+    k_predict_ncov_impl.h, the gamma kernel through the one policy GammaNcov, each with PsiDiag, which is where ncov_factor is called);
+    the gamma unit has no chunk rule of its own and the host takes this kind's chunks from predict_gamma_chunks."""
     head = open(os.path.join(CSRC, "k_ncov_density.h")).read()
-    assert re.search(r"\bncov_factor\s*\(", head) and re.search(r"\bncov_density\s*\(", head)
-    for unit in ("k_predict_noisy_cov.hip", "k_predict_noisy_cov_gamma.hip"):
+    assert len(re.findall(r"__device__[^;{]*\bncov_factor\s*\(", head)) == 1 and len(re.findall(r"__device__[^;{]*\bncov_density\s*\(", head)) == 1
+    diag = re.search(r"struct PsiDiag \{.*?\n\};", head, flags=re.S).group(0)
+    assert "ncov_factor<DD>(S, ps, M, rd, prd)" in diag and "W = DD;" in diag
+    for unit in sorted(os.listdir(CSRC)):
         text = open(os.path.join(CSRC, unit)).read()
-        assert re.search(r'#include\s+"k_ncov_density\.h"', text), unit
-        assert not re.search(r"__device__[^;{]*\bncov_(factor|density)\s*\(", text), unit   # no second definition
+        if unit != "k_ncov_density.h":
+            assert not re.search(r"__device__[^;{]*\bncov_(factor|density)\s*\(", text), unit   # no second definition
+            if re.match(r"k_predict_(noisy_cov|psi_cube|ncov_impl)", unit):                       # these reach it through PsiDiag alone
+                assert "ncov_factor<" not in re.sub(r"//.*", "", text), unit
+    impl = open(os.path.join(CSRC, "k_predict_ncov_impl.h")).read()
+    assert re.search(r'#include\s+"k_ncov_density\.h"', impl)
+    tile = re.sub(r"//.*", "", open(os.path.join(CSRC, "k_predict_noisy_cov.hip")).read())
+    assert '#include "k_predict_ncov_impl.h"' in tile
+    assert "predict_ncov_small_body<PsiDiag<D>, SHARED, KM>(a)" in tile and "predict_ncov_phi_body<PsiDiag<D>, SHARED>(a)" in tile
     code = re.sub(r"//.*", "", open(SRC).read())
+    assert re.search(r'#include\s+"k_ncov_density\.h"', code)
+    assert "predict_gamma_body<GammaNcov<PsiDiag<D>, SHARED, ncg_blocks(D)>>(a)" in code
+    assert "__launch_bounds__(256, D == 9 ? 2 : 1) void k_predict_noisy_cov_gamma(" in code
     assert "predict_gamma_chunks" not in code and not re.search(r"\bint\s+\w*chunks\s*\(", code)
     host = re.sub(r"//.*", "", open(os.path.join(CSRC, "gpz_predictor.hip")).read())
     prep = re.search(r"int rows_gamma_prepare\(.*?\n\}", host, flags=re.S).group(0)
-    assert re.search(r"ROWS_NOISY_COV[^;]*gchunks\s*=\s*predict_gamma_chunks\(p->m\)", prep)
+    assert re.search(r"r\.ncov\(\)[^;]*gchunks\s*=\s*predict_gamma_chunks\(p->m\)", prep)
+    assert re.search(r"bool ncov\(\) const \{ return kind == ROWS_NOISY_COV \|\|", open(os.path.join(CSRC, "gpz_predictor.h")).read())
+    form = re.search(r"static NcovForm ncov_form\(.*?\n\}", host, flags=re.S).group(0)
+    assert re.search(r"return \{p->Psic, launch_predict_noisy_cov_small, launch_predict_noisy_cov_phi, launch_predict_noisy_cov_gamma, "
+                     r"\"noisy_cov\"\}", form)
     tile = re.search(r"int rows_gamma_tile\(.*?\n\}", host, flags=re.S).group(0)
-    assert re.search(r"launch_predict_noisy_cov_gamma\([^;]*p->gchunks[^;]*p->gpart", tile, flags=re.S)
+    assert re.search(r"\bf\.gamma\([^;]*f\.Psi\[s\][^;]*p->gchunks[^;]*p->gpart", tile, flags=re.S)
+    assert '"%s: k_predict_%s_gamma launch failed", who, f.name' in tile
 
 
 @pytest.mark.skipif(shutil.which("hipcc") is None, reason="needs hipcc")

@@ -58,7 +58,7 @@ def test_header_binding_library_and_entry_table_agree():
     host = open(os.path.join(CSRC, "gpz_predictor.hip")).read()
     assert "; noisy missing per draw: k_predict_noisy_missing_cov_gamma (%d pair chunks)" in host
     assert "p->nmcslab, &p->nmcslab_kept, p->Wd" in host                  # the pair kernel's own slab and its state
-    assert "} gam[6];" in open(os.path.join(CSRC, "gpz_predictor.h")).read()
+    assert "} gam[7];" in open(os.path.join(CSRC, "gpz_predictor.h")).read()   # one slot per kind of rows with gamma per draw, this kind's the sixth
     old = open(OLD).read()                                               # one generation kernel, reached through its launcher
     assert old.count("void k_pnmc_triples(") == 1 and "k_pnmc_triples" not in open(SRC).read().replace("launch_pnmc_triples", "")
     assert "pnmc_density(" not in old.replace("pnmc_density<NO>(", "") and "#define PNMC_CASES" not in old   # they moved to the header

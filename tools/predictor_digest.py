@@ -5,7 +5,9 @@ was cut into gpz_predictor.hip, gpz_predictor_host.hip and gpz_predictor_dev.hip
 profiles/r18_predict_group_kernels.txt: before and after the four pair kernels of a group of rows with missing inputs were folded onto
 the one body of k_predict_group_impl.h;
 profiles/r20_predict_gamma_fold.txt: before and after k_predict_noisy_gamma and k_predict_noisy_cov_gamma were folded onto the one body
-of k_predict_gamma_impl.h and the host's covariance-kind model tables onto one helper).
+of k_predict_gamma_impl.h and the host's covariance-kind model tables onto one helper;
+profiles/r25_predict_ncov_fold.txt: before and after the tile kernels and gamma policies of GC / VC rows with Psi, a variance per
+dimension or a full matrix per row, were folded onto the bodies of k_predict_ncov_impl.h and one Psi policy).
 
     python tools/predictor_digest.py > digest.txt        # in each tree, on the same machine; then diff the two files
 
@@ -28,6 +30,12 @@ first call of its handle, then predict_missing_cov_dev, which reads the slab tha
 with 129 or 66 columns, groups and weights, and a handle that meets stack_noisy_cov_dev first and stack_missing_cov_dev second.
 Behind those again, on one more handle (profiles/r23_predict_stack_noisy_missing_cov.txt): the same rows with Psi through
 draws_noisy_missing_cov_dev with gamma (the first call of its handle), predict_noisy_missing_cov_dev and stack_noisy_missing_cov_dev.
+Last, on handles of their own again (run_cube, profiles/r25_predict_ncov_fold.txt): rows with a full Psi each, Psi_i = u_i u_i' +
+diag(g_i) as tools/predict_psi_cube_timing.py draws it, on GC and VC at d = 1 (no off-diagonal element), 6 and 7 (pcg_blocks changes
+between them), 9, 10 (the widths above 256 registers), each with m = 20, k = 1 and m = 91, k = 3, 80 rows on 128-row tiles and 200 rows
+over two tiles: predict_psi_cube_dev, draws_psi_cube_dev with and without gamma, stack_psi_cube_dev with 1 draw and with one column
+more than a gamma pass holds; one handle that meets a cube call first and predict_noisy_cov_dev / stack_noisy_cov_dev second, and one
+the other way round (the two kinds share cbrec, cprec, nout, npart, cphi and gpart).
 After each call one line: the call, the digest of each array it returned, and the handle's route and info."""
 import hashlib
 import os
@@ -215,6 +223,40 @@ def run_edges(method, d, m, k):
             report(f"{tag} stack_noisy_missing_cov_dev plain x 80", p, tuple(p.stack_noisy_missing_cov_dev(Xmd[:80], Pd[:80], edges, n_draws=0)))
 
 
+def run_cube(method, d, m, k):
+    from predict_psi_cube_timing import catalogue as cube_rows           # (X, the variances g, the cube u u' + diag(g), groups), seed 2
+    tag = f"{method} d={d} m={m} k={k} cube"
+    model = synth_model(method, m, d, k, True, seed=1000 * d + 10 * m + k + (method == "GC"))
+    Xd = torch.from_numpy(catalogue(model, 200, seed=d)).to(DEV)
+    _, Pd, Cd, _ = cube_rows(200, d, torch.device(DEV))
+    edges = np.linspace(-3.0, 3.0, 13)
+    over = 65 if d >= 7 else 129                                         # one column more than a pass of k_predict_psi_cube_gamma holds
+    draws = (1, over) if k == 1 else (1, -(-over // k))
+
+    def cube(p, rows, nd, pre=""):
+        x, c = Xd[:rows], Cd[:, :, :rows]
+        report(f"{tag} {pre}predict_psi_cube_dev x {rows}", p, p.predict_psi_cube_dev(x, c))
+        report(f"{tag} {pre}draws_psi_cube_dev {nd} x {rows}", p, p.draws_psi_cube_dev(x, c, nd, seed=11))
+        report(f"{tag} {pre}draws_psi_cube_dev gamma {nd} x {rows}", p, p.draws_psi_cube_dev(x, c, nd, seed=11, return_gamma=True))
+        report(f"{tag} {pre}stack_psi_cube_dev {nd} x {rows}", p, tuple(p.stack_psi_cube_dev(x, c, edges, n_draws=nd, seed=11)))
+
+    def diagonal(p, rows, nd, pre=""):
+        x, psi = Xd[:rows], Pd[:rows]
+        report(f"{tag} {pre}predict_noisy_cov_dev x {rows}", p, p.predict_noisy_cov_dev(x, psi))
+        report(f"{tag} {pre}stack_noisy_cov_dev {nd} x {rows}", p, tuple(p.stack_noisy_cov_dev(x, psi, edges, n_draws=nd, seed=11)))
+
+    with gpz_amd.Predictor(model, tile_rows=128) as p:
+        for nd in draws:
+            cube(p, 80, nd)
+        cube(p, 200, draws[-1])                                          # two tiles
+    with gpz_amd.Predictor(model, tile_rows=128) as p:                   # a full Psi first, a variance per dimension second
+        cube(p, 80, draws[0], "cube first, ")
+        diagonal(p, 80, draws[-1], "cube first, ")
+    with gpz_amd.Predictor(model, tile_rows=128) as p:                   # and the other way round
+        diagonal(p, 80, draws[0], "diagonal first, ")
+        cube(p, 80, draws[-1], "diagonal first, ")
+
+
 def main():
     for method in ("VD", "VC"):
         for k in (1, 3):
@@ -225,6 +267,10 @@ def main():
         for d in widths:
             run_edges(method, d, 20, 1)
             run_edges(method, d, 91, 3)
+    for method in ("GC", "VC"):
+        for d in (1, 6, 7, 9, 10):
+            run_cube(method, d, 20, 1)
+            run_cube(method, d, 91, 3)
 
 
 if __name__ == "__main__":
