@@ -210,6 +210,25 @@ SYMBOLS = {
                                                             c_double_p, c_double_p, C.c_uint32, C.c_int32, C.c_uint64, c_double_p,
                                                             c_double_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, c_double_p,
                                                             c_double_p, c_double_p, c_double_p, c_double_p, C.c_void_p]),
+    # such a group whose rows have a full d x d Psi each: the four noisy_missing_cov entries with three Psi strides (matrix row, matrix
+    # column, catalogue row) and the divisor triangle in place of sd2, as the psi_cube entries take a cube
+    "gpz_predictor_run_psi_cube_missing_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_void_p,
+                                                         C.c_int32, C.c_int64, C.c_int64, C.c_int64, c_double_p, c_double_p, c_double_p,
+                                                         c_double_p, c_double_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                         C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gpz_predictor_draws_psi_cube_missing_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_void_p,
+                                                           C.c_int32, C.c_int64, C.c_int64, C.c_int64, c_double_p, c_double_p,
+                                                           c_double_p, c_double_p, c_double_p, C.c_uint32, C.c_int32, C.c_uint64,
+                                                           c_double_p, C.c_void_p, C.c_void_p]),
+    "gpz_predictor_draws_gamma_psi_cube_missing_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int64,
+                                                                 C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int64, c_double_p,
+                                                                 c_double_p, c_double_p, c_double_p, c_double_p, C.c_uint32, C.c_int32,
+                                                                 C.c_uint64, c_double_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gpz_predictor_stack_psi_cube_missing_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int64,
+                                                           C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int64, c_double_p,
+                                                           c_double_p, c_double_p, c_double_p, C.c_uint32, C.c_int32, C.c_uint64,
+                                                           c_double_p, c_double_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p,
+                                                           c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, C.c_void_p]),
     "gpz_prior": (C.c_int, [C.POINTER(gpz_desc), c_double_p, c_double_p, C.c_int64, c_double_p, C.c_int32, c_double_p,
                             c_int32_p]),
     "gpz_inv_logdet": (C.c_int, [c_double_p, C.c_int32, C.c_int32, c_double_p, c_double_p, c_int32_p]),

@@ -407,6 +407,29 @@ size_t predict_noisy_missing_cov_gamma_lds(int m, int d, int no);   // dynamic L
 int launch_predict_noisy_missing_cov_gamma(hipStream_t st, const double *Xc, const double *Psic, long ldx, int n, const double *Pio,
                                            long ldr, int m, int d, unsigned obs, const double *raw, const double *bas, double *slab,
                                            bool *slab_kept, const double *W, int ldw, int ncol, int nchunk, double *part, long ldp);
+// ---- such a group whose rows have a full d x d Psi each (k_predict_psi_cube_missing.hip, k_predict_psi_cube_missing_gamma.hip;
+// gpz_predictor_*_psi_cube_missing_dev) ----
+// The launchers of the group above with Psio [no (no + 1) / 2][ldx] in place of Psic: column LT(ro, co) holds element (o[ro], o[co]),
+// ro >= co, of every row's Psi (after fixPsi's division), o the observed dimensions in ascending order, and the density's matrix is
+// M + Psi_oo over the whole packed triangle.  Records, tables, slabs (the same slab and *slab_kept: the records do not depend on Psi),
+// chunk counts, LDS figures and finish kernels are that group's.  check: word 3 of rec is set when an element of the lower triangle of an
+// observed x observed block is NaN or infinite, itself or divided by div[LT(r, c)] (the whole d x d triangle of divisors on the device,
+// nullptr: no division), or a diagonal element is negative; nothing observed: nothing is launched.  stage: element (r, c) of row i at
+// Psi[r sr + c sc + i sn] -> Psio.  All return -1 when a launch failed or a shape is outside predict_missing_cov_fits.
+int launch_pcm_check_psi(hipStream_t st, const void *Psi, int f32, long ns, int d, unsigned obs, long sr, long sc, long sn,
+                         const double *div, unsigned *rec);
+int launch_pcm_stage_psi(hipStream_t st, const void *Psi, int f32, long sr, long sc, long sn, long r0, int nt, int d, unsigned obs,
+                         const double *div, double *Psio, long ldx);
+int launch_pcm_rows(hipStream_t st, const double *Xc, const double *Psio, long ldx, int n, int nrow, int m, int mp, int d, int k,
+                    unsigned obs, const double *exrec, const double *phirec, const double *w, const double *v, double *Pio, long ldr,
+                    double *Phi, double *hd, long ldh);
+int launch_predict_psi_cube_missing_pairs(hipStream_t st, const double *Xc, const double *Psio, long ldx, int n, const double *Pio,
+                                          long ldr, int m, int d, int k, unsigned obs, const double *raw, const double *bas,
+                                          const double *coef, double *slab, bool *slab_kept, int nchunk, double *part, long ldp,
+                                          const double *hd, long ldh, const double *bvec, double *out);
+int launch_predict_psi_cube_missing_gamma(hipStream_t st, const double *Xc, const double *Psio, long ldx, int n, const double *Pio,
+                                          long ldr, int m, int d, unsigned obs, const double *raw, const double *bas, double *slab,
+                                          bool *slab_kept, const double *W, int ldw, int ncol, int nchunk, double *part, long ldp);
 // B (rows x ld row-major) <- [iS (m x m column-major) | nw columns of W from column wcol | nv columns of V (nullptr: 0) from vcol | 0]
 void launch_pred_fill_b(hipStream_t st, const double *iS, const double *W, int nw, int wcol, const double *V, int nv, int vcol, int m,
                         int rows, int ld, double *B);

@@ -72,6 +72,7 @@ struct gpz_predictor {
         double *s2_d = nullptr;    // [(1 + nd) k][tile] widths^2 of the stack
         size_t s2_cap = 0;         // doubles
     } gam[7];                      // [kind - 1] of the call's RowKind: ROWS_NOISY .. ROWS_PSI_CUBE (clean rows have no gamma per draw)
+    PerDraw gam_pcm;               // the same for ROWS_PSI_CUBE_MISSING, the eighth kind with gamma per draw (rows_gamma_state picks)
     // ---- rows with missing inputs on the handle (gpz_predictor_*_missing_dev): nothing of this exists before the first of their calls
     bool miss_used = false;
     int64_t mtile = 0;             // rows per tile of a group: min(tile_rows, GPZ_PREDICTOR_TILE_MISSING)
@@ -115,6 +116,10 @@ struct gpz_predictor {
     double *nmcex = nullptr, *nmcphi = nullptr, *nmcslab = nullptr;   // the Ex and PHI records and the slab in the form of k_predict_noisy_missing_cov.hip
     bool nmtab_valid = false;      // nmcex and nmcphi hold the records of (mtab_obs, mtab_pri); cleared where the tables above are written
     bool nmcslab_kept = false;     // nmcslab holds the whole pair-component table of (mtab_obs, mtab_pri)
+    // ---- such rows with a full input-noise covariance each (gpz_predictor_*_psi_cube_missing_dev): everything of the group above but its
+    // Psi slots (the records do not depend on Psi: a handle that has served that group on the same pattern builds nothing twice), and
+    // Psiq and div_d of the cube kind, whose first no (no + 1) / 2 columns hold the observed triangles.  Beyond them only this exists
+    bool pcm_used = false;         // such a call has run (the route text)
 };
 
 namespace gpzi {
@@ -125,10 +130,12 @@ namespace gpzi {
 // Missing cov: a group without Psi on a covariance kind.  Noisy missing cov: such a group with Psi in Psic[s] too; with nothing observed
 // (obs = 0) there is no Psi to read and the group is the missing cov kind's in all but the name of its entry.
 // Psi cube: complete rows of a covariance kind with a full d x d Psi each, its packed lower triangle in Psiq[s] beside Xc[s]; the tables
-// are the noisy cov kind's.
+// are the noisy cov kind's.  Psi cube missing: a group on a covariance kind whose rows have a full d x d Psi each; the lower triangle of
+// its observed x observed block lies packed in Psiq[s] (no (no + 1) / 2 columns), the tables are the noisy missing cov kind's, and with
+// nothing observed there is no Psi to read and the group is the missing cov kind's, as for that kind.
 enum RowKind {
     ROWS_CLEAN = 0, ROWS_NOISY = 1, ROWS_MISSING = 2, ROWS_NOISY_MISSING = 3, ROWS_NOISY_COV = 4, ROWS_MISSING_COV = 5,
-    ROWS_NOISY_MISSING_COV = 6, ROWS_PSI_CUBE = 7
+    ROWS_NOISY_MISSING_COV = 6, ROWS_PSI_CUBE = 7, ROWS_PSI_CUBE_MISSING = 8
 };
 struct Rows {
     RowKind kind = ROWS_CLEAN;
@@ -138,11 +145,16 @@ struct Rows {
         return kind == ROWS_NOISY || kind == ROWS_NOISY_MISSING || kind == ROWS_NOISY_COV || (kind == ROWS_NOISY_MISSING_COV && obs != 0);
     }
     bool group() const {   // one NaN pattern, tiles of at most mtile rows
-        return kind == ROWS_MISSING || kind == ROWS_NOISY_MISSING || kind == ROWS_MISSING_COV || kind == ROWS_NOISY_MISSING_COV;
+        return kind == ROWS_MISSING || kind == ROWS_NOISY_MISSING || kind == ROWS_MISSING_COV || kind == ROWS_NOISY_MISSING_COV ||
+               kind == ROWS_PSI_CUBE_MISSING;
     }
     bool cube() const { return kind == ROWS_PSI_CUBE; }   // Psiq[s] is staged beside Xc[s]
     bool ncov() const { return kind == ROWS_NOISY_COV || kind == ROWS_PSI_CUBE; }   // complete rows of a covariance kind with Psi, either form
-    bool cov_group() const { return kind == ROWS_MISSING_COV || kind == ROWS_NOISY_MISSING_COV; }   // such a group on a covariance kind
+    bool cov_group() const {   // such a group on a covariance kind
+        return kind == ROWS_MISSING_COV || kind == ROWS_NOISY_MISSING_COV || kind == ROWS_PSI_CUBE_MISSING;
+    }
+    bool cube_obs() const { return kind == ROWS_PSI_CUBE_MISSING && obs != 0; }   // Psiq[s] holds the observed sub-triangle of each row's Psi
+    bool group_psi() const { return cube_obs() || (kind == ROWS_NOISY_MISSING_COV && obs != 0); }   // a covariance group with Psi, either form
 };
 
 // ---- what a kind of rows is made of (gpz_predictor.hip) ------------------------------------------------------------------------------

@@ -65,6 +65,9 @@
 // their own whose density is a packed no x no Cholesky of M + diag(psi_o) per row (predictor_noisy_missing_cov_prepare), and the other
 // two as gpz_predictor_stack_noisy_missing_cov_dev / _draws_gamma_noisy_missing_cov_dev, with gamma under every draw from
 // k_predict_noisy_missing_cov_gamma.hip (k_predict_missing_cov_gamma's frame on those records and that slab).
+// Such a group whose rows have a full d x d Psi each has all four as gpz_predictor_run_psi_cube_missing_dev / _draws_ / _draws_gamma_ /
+// _stack_psi_cube_missing_dev (k_predict_psi_cube_missing.hip, k_predict_psi_cube_missing_gamma.hip): the same records, slabs and tile
+// buffers, the packed Cholesky of M + Psi_oo over the observed triangle of the row's matrix, which k_pcm_stage_psi packs into Psiq.
 // Layout: gpz_predictor.h holds the handle and what the three units share.  This unit holds the handle's life and setup, what a tile is
 // made of for each kind of rows (clean, with Psi, one NaN-pattern group: the rows_* functions), draws preparation and factorisation, the
 // stack's preparation and tile, the checks the entries share, route and info.  gpz_predictor_host.hip holds the host pipeline, its jobs
@@ -757,10 +760,14 @@ static int predictor_missing_cov_prepare(gpz_predictor *p, const char *who, uint
 // buffers, [R | CU | off] and the coefficients of the pattern are shared, and the tables above stay valid for the entries that read
 // them), and the Ex and PHI records and the slab in the form of k_predict_noisy_missing_cov.hip, sized for the widest pattern of the
 // model and kept until the tables above are written again.
-static int predictor_noisy_missing_cov_prepare(gpz_predictor *p, const char *who, uint32_t obs, const double *priors, bool pairs) {
+// A full Psi per row (ROWS_PSI_CUBE_MISSING) takes the cube kind's slots in place of the Psi slots and nothing else of its own: the
+// records do not depend on Psi, so the two forms share nmcex, nmcphi, nmcslab and their flags.
+static int predictor_noisy_missing_cov_prepare(gpz_predictor *p, const char *who, const Rows &r, bool pairs) {
     const size_t m = p->m;
+    const uint32_t obs = r.obs;
+    const double *priors = r.priors;
     int rc = 0;
-    if ((rc = predictor_psi_slots(p))) return rc;
+    if ((rc = r.cube_obs() ? predictor_cube_slots(p) : predictor_psi_slots(p))) return rc;
     const bool had = p->mcov_used;   // (the route text of the entries without Psi is theirs)
     rc = predictor_missing_cov_prepare(p, who, obs, priors, pairs);
     p->mcov_used = had;
@@ -785,13 +792,24 @@ static int predictor_noisy_missing_cov_prepare(gpz_predictor *p, const char *who
 
 // predictMissing of one tile of nt rows of the group, covariance kinds: Xc[s] -> Pio in mPio ([m][tile]), PHI in mNo, mu | ElnS - b in mhd
 // and, with pairs, mout ([4k][nt] = mu | nu | beta | gamma)
-// Psic: the tile's Psi slot for a group with input noise too (predictNoisyMissing: the kernels of k_predict_noisy_missing_cov.hip on
-// their own record tables), else nullptr
-static int predictor_missing_cov_tile(gpz_predictor *p, const char *who, int s, int nt, uint32_t obs, bool pairs,
-                                      const double *Psic = nullptr) {
+// A group with input noise too (predictNoisyMissing) runs the kernels of k_predict_noisy_missing_cov.hip on their own record tables with
+// the tile's Psi slot, or, with a full Psi per row, those of k_predict_psi_cube_missing.hip on the same tables with the observed triangles
+static int predictor_missing_cov_tile(gpz_predictor *p, const char *who, const Rows &r, int s, int nt, bool pairs) {
     hipStream_t st = p->s_cmp;
     const int np = rup(nt, 128);   // the rows of the draws' product: k_tgemm's row tile
     const long mtp = rup(p->mtile, 1024);
+    const uint32_t obs = r.obs;
+    const double *Psic = r.psi() ? p->Psic[s] : nullptr;
+    if (r.cube_obs()) {
+        if (launch_pcm_rows(st, p->Xc[s], p->Psiq[s], p->tile_pad, nt, np, p->m, p->mp, p->d, p->k, obs, p->nmcex, p->nmcphi, p->w_d,
+                            p->hetero ? p->pr.v : nullptr, p->mPio, mtp, p->mNo, p->mhd, mtp))
+            return gpz_fail(GPZ_ERR_HIP, "%s: k_pcm launch failed", who);
+        if (pairs && launch_predict_psi_cube_missing_pairs(st, p->Xc[s], p->Psiq[s], p->tile_pad, nt, p->mPio, mtp, p->m, p->d, p->k, obs,
+                                                           p->mcraw, p->mcbas, p->mccoef, p->nmcslab, &p->nmcslab_kept, p->mchunks,
+                                                           p->mpart, mtp, p->mhd, mtp, p->pr.b, p->mout))
+            return gpz_fail(GPZ_ERR_HIP, "%s: k_predict_psi_cube_missing_pairs launch failed", who);
+        return 0;
+    }
     if (Psic) {
         if (launch_pnmc_rows(st, p->Xc[s], Psic, p->tile_pad, nt, np, p->m, p->mp, p->d, p->k, obs, p->nmcex, p->nmcphi, p->w_d,
                              p->hetero ? p->pr.v : nullptr, p->mPio, mtp, p->mNo, p->mhd, mtp))
@@ -815,6 +833,11 @@ static int predictor_missing_cov_tile(gpz_predictor *p, const char *who, int s, 
 // ---- what a kind of rows is made of ---------------------------------------------------------------------------------------------------
 // the kind's refusal of the model and, for a group, of its mask.  draws: the call has draws, which with Psi need the fused draws route
 int rows_check(const char *who, const gpz_predictor *p, const Rows &r, bool draws) {
+    if (r.kind == ROWS_PSI_CUBE_MISSING && p->kind != GPZ_KIND_COV)
+        return gpz_fail(GPZ_ERR_UNSUPPORTED,
+                        "%s: method %.2s is a diagonal kind: fixPsi gives it the cube's diagonal, and its rows with input noise and "
+                        "missing inputs go to gpz_predictor_run_noisy_missing_dev / _draws_noisy_missing_dev",
+                        who, p->desc.method);
     if (r.group())   // (with Psi too: its product against W needs no fused draws route)
         return predictor_missing_check(who, p, r.obs, r.cov_group(), r.kind == ROWS_NOISY_MISSING_COV);
     if (r.kind == ROWS_CLEAN) return 0;
@@ -829,10 +852,11 @@ int rows_check(const char *who, const gpz_predictor *p, const Rows &r, bool draw
 // stack); the draws alone do not, and take the Psi slots or the group's tables without them.
 int rows_prepare(gpz_predictor *p, const char *who, const Rows &r, bool pairs) {
     if (r.cov_group()) {
-        if (int rc = r.psi() ? predictor_noisy_missing_cov_prepare(p, who, r.obs, r.priors, pairs)
-                             : predictor_missing_cov_prepare(p, who, r.obs, r.priors, pairs))
+        if (int rc = r.group_psi() ? predictor_noisy_missing_cov_prepare(p, who, r, pairs)
+                                   : predictor_missing_cov_prepare(p, who, r.obs, r.priors, pairs))
             return rc;
         if (r.kind == ROWS_NOISY_MISSING_COV) p->nmcov_used = true;
+        if (r.kind == ROWS_PSI_CUBE_MISSING) p->pcm_used = true;
         return 0;
     }
     if (r.group()) return predictor_missing_prepare(p, who, r.obs, r.priors, pairs, r.kind == ROWS_NOISY_MISSING);
@@ -850,7 +874,7 @@ int64_t rows_tile(const gpz_predictor *p, const Rows &r, int64_t T) { return r.g
 // the moments of one tile of nt rows in slot s -> rows_moments: [3k][nt] = mu | nu | beta for clean rows (and PHI when asked), else
 // [4k][nt] = mu | nu | beta | gamma
 int rows_moments_tile(gpz_predictor *p, const char *who, const Rows &r, int s, int nt, bool want_phi) {
-    if (r.cov_group()) return predictor_missing_cov_tile(p, who, s, nt, r.obs, true, r.psi() ? p->Psic[s] : nullptr);
+    if (r.cov_group()) return predictor_missing_cov_tile(p, who, r, s, nt, true);
     if (r.group()) return predictor_missing_tile(p, who, s, nt, r.obs, true, r.psi() ? p->Psic[s] : nullptr);
     if (r.kind == ROWS_NOISY) return predictor_noisy_tile(p, who, s, nt);
     if (r.ncov()) return predictor_noisy_cov_tile(p, who, r, s, nt);
@@ -884,7 +908,7 @@ int rows_draws_tile(gpz_predictor *p, const char *who, const Rows &r, int s, int
     if (r.kind == ROWS_NOISY) return predictor_draws_tile(p, s, nt, ncol, ldw, false, p->Psic[s]);
     if (r.ncov()) return predictor_noisy_cov_draws_tile(p, who, r, s, nt, ncol, ldw);
     if (!after_moments)   // (a covariance kind's PHI_missing lies in mNo as the diagonal kinds' does)
-        if (int rc = r.cov_group() ? predictor_missing_cov_tile(p, who, s, nt, r.obs, false, r.psi() ? p->Psic[s] : nullptr)
+        if (int rc = r.cov_group() ? predictor_missing_cov_tile(p, who, r, s, nt, false)
                                    : predictor_missing_tile(p, who, s, nt, r.obs, false, r.psi() ? p->Psic[s] : nullptr))
             return rc;
     return predictor_missing_draws_tile(p, who, s, nt, ncol, ldw);
@@ -894,8 +918,12 @@ int rows_chunks(const gpz_predictor *p, const Rows &r) { return r.group() ? p->m
 
 // What a call that needs gamma under nd draws on tiles of T rows adds to the handle (after rows_prepare with pairs: the pair table, or U
 // and the records): the chunk slab of the pair sums and, for a stack of Q column-outputs, the kind's widths.  nd = 0 takes no slab.
+static gpz_predictor::PerDraw &rows_gamma_state(gpz_predictor *p, const Rows &r) {
+    return r.kind == ROWS_PSI_CUBE_MISSING ? p->gam_pcm : p->gam[r.kind - 1];
+}
+
 int rows_gamma_prepare(gpz_predictor *p, const Rows &r, int ncol, int Q, int64_t T) {
-    gpz_predictor::PerDraw &g = p->gam[r.kind - 1];
+    gpz_predictor::PerDraw &g = rows_gamma_state(p, r);
     int rc = 0;
     if (r.kind == ROWS_NOISY || r.ncov()) p->gchunks = predict_gamma_chunks(p->m);   // (a handle has one of the two kinds)
     if (ncol > 0 && (rc = predictor_grow(p, &p->gpart, &p->gpart_cap, (size_t)rows_chunks(p, r) * ncol * T))) return rc;
@@ -927,6 +955,16 @@ int rows_gamma_tile(gpz_predictor *p, const char *who, const Rows &r, int s, int
                                                               p->m, p->d, r.obs, p->mcraw, p->mcbas, p->nmcslab, &p->nmcslab_kept, p->Wd,
                                                               ldw, ncol, p->mchunks, p->gpart, nt))
             return gpz_fail(GPZ_ERR_HIP, "%s: k_predict_noisy_missing_cov_gamma launch failed", who);
+        return 0;
+    }
+    if (r.kind == ROWS_PSI_CUBE_MISSING) {   // that kind's records and slab with the observed triangles; nothing observed: as above
+        if (!r.cube_obs() ? launch_predict_missing_cov_gamma(p->s_cmp, p->Xc[s], p->tile_pad, nt, p->mPio, rup(p->mtile, 1024), p->m, p->d,
+                                                             r.obs, p->mcraw, p->mcbas, p->mcslab, &p->mcslab_kept, p->Wd, ldw, ncol,
+                                                             p->mchunks, p->gpart, nt)
+                          : launch_predict_psi_cube_missing_gamma(p->s_cmp, p->Xc[s], p->Psiq[s], p->tile_pad, nt, p->mPio,
+                                                                  rup(p->mtile, 1024), p->m, p->d, r.obs, p->mcraw, p->mcbas, p->nmcslab,
+                                                                  &p->nmcslab_kept, p->Wd, ldw, ncol, p->mchunks, p->gpart, nt))
+            return gpz_fail(GPZ_ERR_HIP, "%s: k_predict_psi_cube_missing_gamma launch failed", who);
         return 0;
     }
     // a group with Psi: the second record table
@@ -994,7 +1032,7 @@ int predictor_stack_tile(gpz_predictor *p, const char *who, const Rows &r, const
     if (r.kind == ROWS_CLEAN) {
         bad = launch_stack_tile(st, mom, F, lab, wt, p->edges_d, sh, nt, p->k, c.nd, c.B, c.G, c.R, p->slab_d);
     } else {
-        double *s2 = p->gam[r.kind - 1].s2_d;
+        double *s2 = rows_gamma_state(p, r).s2_d;
         if (c.nd > 0 && (rc = rows_gamma_tile(p, who, r, s, (int)nt, c.ncol, c.ldw))) return rc;
         if (launch_gamma_finish_s2(st, p->gpart, rows_chunks(p, r), nt, mom, F, (int)nt, p->k, c.nd, s2))
             return gpz_fail(GPZ_ERR_HIP, "%s: k_gamma_finish_s2 launch failed", who);
@@ -1131,16 +1169,17 @@ extern "C" int gpz_predictor_route(const gpz_predictor *p, char *buf, int cap) {
         snprintf(tmp, sizeof tmp, "tiles: k_phi + k_tgemm, %lld-row tiles", (long long)p->tile_rows);
     std::string r = tmp;
     // after the first stack or gamma-per-draw call for a kind of rows (gam[kind - 1]): its kernel and chunks (a group's: mchunks)
-    static const struct { const char *fmt; bool group; } PER_DRAW[7] = {
+    static const struct { const char *fmt; bool group; } PER_DRAW[8] = {
         {"; noise per draw: k_predict_noisy_gamma (%d pair chunks)", false},
         {"; missing per draw: k_predict_missing_gamma (%d pair chunks)", true},
         {"; noisy missing per draw: k_predict_noisy_missing_gamma (%d pair chunks)", true},
         {"; noise per draw: k_predict_noisy_cov_gamma (%d pair chunks)", false},
         {"; missing per draw: k_predict_missing_cov_gamma (%d pair chunks)", true},
         {"; noisy missing per draw: k_predict_noisy_missing_cov_gamma (%d pair chunks)", true},
-        {"; noise cube per draw: k_predict_psi_cube_gamma (%d pair chunks)", false}};
-    auto gamma_line = [&](int i) {
-        const gpz_predictor::PerDraw &g = p->gam[i];
+        {"; noise cube per draw: k_predict_psi_cube_gamma (%d pair chunks)", false},
+        {"; noise cube missing per draw: k_predict_psi_cube_missing_gamma (%d pair chunks)", true}};
+    auto gamma_line = [&](int i) {   // (the eighth kind's state is gam_pcm)
+        const gpz_predictor::PerDraw &g = i < 7 ? p->gam[i] : p->gam_pcm;
         if (!g.used) return;
         snprintf(tmp, sizeof tmp, PER_DRAW[i].fmt, PER_DRAW[i].group ? p->mchunks : p->gchunks);
         r += tmp;
@@ -1192,6 +1231,11 @@ extern "C" int gpz_predictor_route(const gpz_predictor *p, char *buf, int cap) {
         r += tmp;
     }
     gamma_line(5);
+    if (p->pcm_used) {   // after the first call for such a group with a full Psi per row
+        snprintf(tmp, sizeof tmp, "; noise cube missing: k_predict_psi_cube_missing_pairs (%d pair chunks)", p->mchunks);
+        r += tmp;
+    }
+    gamma_line(7);
     snprintf(buf, (size_t)cap, "%s", r.c_str());
     return (int)r.size();
 }

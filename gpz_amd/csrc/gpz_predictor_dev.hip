@@ -79,6 +79,12 @@ static DevCall with_noisy_cov_pattern(DevCall c, const double *priors, uint32_t 
     return c;
 }
 
+// such a group whose rows have a full d x d Psi each: with_cube first, then the pattern
+static DevCall with_cube_pattern(DevCall c, const double *priors, uint32_t obs_mask) {
+    c.rows = Rows{ROWS_PSI_CUBE_MISSING, obs_mask, priors};
+    return c;
+}
+
 static int predictor_dev_args(const char *who, const gpz_predictor *p, const DevRows &x, const double *muX, const double *sdX) {
     if (x.type != GPZ_X_F64 && x.type != GPZ_X_F32)
         return gpz_fail(GPZ_ERR_ARG, "%s: x_type %d is neither GPZ_X_F64 nor GPZ_X_F32", who, (int)x.type);
@@ -118,7 +124,7 @@ static int predictor_dev_cube_args(const char *who, const gpz_predictor *p, cons
 
 static int predictor_dev_check(const char *who, const gpz_predictor *p, const DevCall &c) {
     if (int rc = predictor_dev_args(who, p, c.x, c.muX, c.sdX)) return rc;
-    if (c.rows.cube()) return predictor_dev_cube_args(who, p, c);
+    if (c.rows.cube() || c.rows.cube_obs()) return predictor_dev_cube_args(who, p, c);   // (nothing observed: no Psi is read)
     return c.rows.psi() ? predictor_dev_psi_args(who, c.psi, c.sdX, c.sd2) : 0;
 }
 
@@ -146,6 +152,8 @@ static int predictor_dev_begin(gpz_predictor *p, const char *who, DevCall &c, co
     hipStream_t st = p->s_cmp;
     if (!p->par_d)
         if (int rc = p->ar.alloc(&p->par_d, 2 * d + k + 2)) return rc;
+    if (c.rows.cube_obs() && !p->div_d)   // (the scan of such a group divides on the device: the one table it takes before its verdict)
+        if (int rc = p->ar.alloc(&p->div_d, d * (d + 1) / 2)) return rc;
     if (!p->ev_dev) HIPCHK(hipEventCreateWithFlags(&p->ev_dev, hipEventDisableTiming));
     p->dev_used = true;
     unsigned *rec = (unsigned *)(p->par_d + 2 * d + k);
@@ -179,6 +187,11 @@ static int predictor_dev_begin(gpz_predictor *p, const char *who, DevCall &c, co
         ((c.div && hipMemcpyAsync(p->div_d, c.div, d * (d + 1) / 2 * sizeof(double), hipMemcpyDefault, st) != hipSuccess) ||
          launch_pred_check_psi_cube(st, c.psi.X, c.psi.f32(), c.psi.ns, p->d, c.psi_mr, c.psi.cs, c.psi.rs, c.div ? p->div_d : nullptr, rec)))
         rc = gpz_fail(GPZ_ERR_HIP, "%s: k_pred_check_psi_cube launch failed", who);
+    // such a group with a full Psi per row: the same, over the lower triangle of the observed x observed block only
+    if (!rc && c.rows.cube_obs() &&
+        ((c.div && hipMemcpyAsync(p->div_d, c.div, d * (d + 1) / 2 * sizeof(double), hipMemcpyDefault, st) != hipSuccess) ||
+         launch_pcm_check_psi(st, c.psi.X, c.psi.f32(), c.psi.ns, p->d, obs, c.psi_mr, c.psi.cs, c.psi.rs, c.div ? p->div_d : nullptr, rec)))
+        rc = gpz_fail(GPZ_ERR_HIP, "%s: k_pcm_check_psi launch failed", who);
     if (!rc && hipMemcpyAsync(verdict, rec, sizeof verdict, hipMemcpyDeviceToHost, st) != hipSuccess)
         rc = gpz_fail(GPZ_ERR_HIP, "%s: copy failed", who);
     if (hipStreamSynchronize(st) != hipSuccess && !rc) rc = gpz_fail(GPZ_ERR_HIP, "%s: sync failed", who);
@@ -190,6 +203,11 @@ static int predictor_dev_begin(gpz_predictor *p, const char *who, DevCall &c, co
     if (verdict[0]) return gpz_fail(GPZ_ERR_UNSUPPORTED, "%s: %s", who, nan_text);
     if (verdict[3] && c.rows.cube())
         return gpz_fail(GPZ_ERR_ARG, "%s: the lower triangle of Psi has an element that is NaN or infinite, or a negative diagonal element",
+                        who);
+    if (verdict[3] && c.rows.cube_obs())
+        return gpz_fail(GPZ_ERR_ARG,
+                        "%s: the lower triangle of Psi over the observed dimensions has an element that is NaN or infinite, or a negative "
+                        "diagonal element",
                         who);
     if (verdict[3]) return gpz_fail(GPZ_ERR_ARG, "%s: Psi has an element that is NaN, infinite or negative", who);
     c.muX_d = muX ? p->par_d : nullptr;
@@ -221,6 +239,9 @@ static int predictor_dev_tiles(gpz_predictor *p, const char *who, const DevCall 
         if (c.rows.cube() && launch_pred_stage_psi_cube(st, psi.X, psi.f32(), c.psi_mr, psi.cs, psi.rs, r0, nt, p->d, c.div_d, p->Psiq[s],
                                                         p->tile_pad))
             return gpz_fail(GPZ_ERR_HIP, "%s: k_pred_stage_psi_cube launch failed", who);
+        if (c.rows.cube_obs() && launch_pcm_stage_psi(st, psi.X, psi.f32(), c.psi_mr, psi.cs, psi.rs, r0, nt, p->d, c.rows.obs, c.div_d,
+                                                      p->Psiq[s], p->tile_pad))
+            return gpz_fail(GPZ_ERR_HIP, "%s: k_pcm_stage_psi launch failed", who);
         if (int rc = body(s, r0, nt)) return rc;
     }
     return 0;
@@ -656,4 +677,59 @@ extern "C" int gpz_predictor_stack_noisy_missing_cov_dev(gpz_predictor *p, const
     const StackArgs a{ndraws, seed, Z, edges, nbins, group_d, ngroups, weight_d, hist, sum_w, sum_mu, sum_mu2, mu_shift};
     return stack_dev_entry("gpz_predictor_stack_noisy_missing_cov_dev", p,
                            with_noisy_cov_pattern(with_psi(x, Psi_d, psi_type, psi_row_stride, psi_col_stride, sd2), priors, obs_mask), a);
+}
+
+extern "C" int gpz_predictor_run_psi_cube_missing_dev(gpz_predictor *p, const void *X_d, int32_t x_type, int64_t ns, int64_t row_stride,
+                                                      int64_t col_stride, const void *Psi_d, int32_t psi_type, int64_t psi_mrow_stride,
+                                                      int64_t psi_mcol_stride, int64_t psi_row_stride, const double *muX,
+                                                      const double *sdX, const double *div, const double *muY, const double *priors,
+                                                      uint32_t obs_mask, double *mu_d, double *sigma_d, double *nu_d, double *beta_d,
+                                                      double *gamma_d, void *stream) {
+    const DevCall x = dev_call(X_d, x_type, ns, row_stride, col_stride, muX, sdX, muY, stream);
+    return run_dev_entry("gpz_predictor_run_psi_cube_missing_dev", p,
+                         with_cube_pattern(with_cube(x, Psi_d, psi_type, psi_mrow_stride, psi_mcol_stride, psi_row_stride, div), priors,
+                                           obs_mask),
+                         mu_d, sigma_d, nu_d, beta_d, gamma_d, nullptr);
+}
+
+extern "C" int gpz_predictor_draws_psi_cube_missing_dev(gpz_predictor *p, const void *X_d, int32_t x_type, int64_t ns, int64_t row_stride,
+                                                        int64_t col_stride, const void *Psi_d, int32_t psi_type, int64_t psi_mrow_stride,
+                                                        int64_t psi_mcol_stride, int64_t psi_row_stride, const double *muX,
+                                                        const double *sdX, const double *div, const double *muY, const double *priors,
+                                                        uint32_t obs_mask, int32_t ndraws, uint64_t seed, const double *Z, double *F_d,
+                                                        void *stream) {
+    const DevCall x = dev_call(X_d, x_type, ns, row_stride, col_stride, muX, sdX, muY, stream);
+    return draws_dev_entry("gpz_predictor_draws_psi_cube_missing_dev", p,
+                           with_cube_pattern(with_cube(x, Psi_d, psi_type, psi_mrow_stride, psi_mcol_stride, psi_row_stride, div), priors,
+                                             obs_mask),
+                           ndraws, seed, Z, F_d);
+}
+
+extern "C" int gpz_predictor_draws_gamma_psi_cube_missing_dev(gpz_predictor *p, const void *X_d, int32_t x_type, int64_t ns,
+                                                              int64_t row_stride, int64_t col_stride, const void *Psi_d, int32_t psi_type,
+                                                              int64_t psi_mrow_stride, int64_t psi_mcol_stride, int64_t psi_row_stride,
+                                                              const double *muX, const double *sdX, const double *div, const double *muY,
+                                                              const double *priors, uint32_t obs_mask, int32_t ndraws, uint64_t seed,
+                                                              const double *Z, double *F_d, double *Gam_d, void *stream) {
+    const DevCall x = dev_call(X_d, x_type, ns, row_stride, col_stride, muX, sdX, muY, stream);
+    return draws_dev_entry("gpz_predictor_draws_gamma_psi_cube_missing_dev", p,
+                           with_cube_pattern(with_cube(x, Psi_d, psi_type, psi_mrow_stride, psi_mcol_stride, psi_row_stride, div), priors,
+                                             obs_mask),
+                           ndraws, seed, Z, F_d, Gam_d, true);
+}
+
+extern "C" int gpz_predictor_stack_psi_cube_missing_dev(gpz_predictor *p, const void *X_d, int32_t x_type, int64_t ns, int64_t row_stride,
+                                                        int64_t col_stride, const void *Psi_d, int32_t psi_type, int64_t psi_mrow_stride,
+                                                        int64_t psi_mcol_stride, int64_t psi_row_stride, const double *muX,
+                                                        const double *sdX, const double *div, const double *priors, uint32_t obs_mask,
+                                                        int32_t ndraws, uint64_t seed, const double *Z, const double *edges, int32_t nbins,
+                                                        const int32_t *group_d, int32_t ngroups, const double *weight_d, double *hist,
+                                                        double *sum_w, double *sum_mu, double *sum_mu2, const double *mu_shift,
+                                                        void *stream) {
+    const DevCall x = dev_call(X_d, x_type, ns, row_stride, col_stride, muX, sdX, nullptr, stream);
+    const StackArgs a{ndraws, seed, Z, edges, nbins, group_d, ngroups, weight_d, hist, sum_w, sum_mu, sum_mu2, mu_shift};
+    return stack_dev_entry("gpz_predictor_stack_psi_cube_missing_dev", p,
+                           with_cube_pattern(with_cube(x, Psi_d, psi_type, psi_mrow_stride, psi_mcol_stride, psi_row_stride, div), priors,
+                                             obs_mask),
+                           a);
 }

@@ -4,13 +4,16 @@
 #pragma once
 #include "gpz_dev.h"
 #include "k_pmcv_density.h"   // PMCV_MAXD, PmcvPat, pmcv_pat
-#include "k_ncov_density.h"   // ncov_factor, ncov_density, LT
+#include "k_ncov_density.h"   // PsiDiag, PsiTri, ncov_density, LT
 
 // ---- the density every tile kernel shares ----------------------------------------------------------------------------------------------
-// t: the record, the same address in every lane; x, ps: the row's observed inputs and their variances; nu: the missing dimensions
-template <int NO>
-__device__ __forceinline__ double pnmc_density(const double *t, int nu, const double (&x)[NO], const double (&ps)[NO]) {
-    constexpr int TRI = NO * (NO + 1) / 2;
+// t: the record, the same address in every lane; x: the row's observed inputs; nu: the missing dimensions.  P: the policy of
+// k_ncov_density.h for the row's Psi_oo over the NO = P::D observed dimensions, ps its P::W values - PsiDiag<NO> a variance per observed
+// dimension (k_predict_noisy_missing_cov*.hip), PsiTri<NO> the packed lower triangle of the observed x observed block of a full matrix
+// (k_predict_psi_cube_missing*.hip).  The policy's factor step is all that differs: J x, the nu squares and ncov_density are the same.
+template <class P>
+__device__ __forceinline__ double pnmc_density(const double *t, int nu, const double (&x)[P::D], const double (&ps)[P::W]) {
+    constexpr int NO = P::D, TRI = NO * (NO + 1) / 2;
     const double *J = t + 1 + NO + TRI, *A2 = J + NO * NO, *b2 = A2 + nu * NO;
     double w[NO], q2 = 0.0;
 #pragma unroll
@@ -28,8 +31,14 @@ __device__ __forceinline__ double pnmc_density(const double *t, int nu, const do
         q2 = fma(s, s, q2);
     }
     double M[TRI], rd[NO], prd;
-    ncov_factor<NO>(t + 1 + NO, ps, M, rd, &prd);
+    P::factor(t + 1 + NO, ps, M, rd, &prd);
     return ncov_density<NO>(t + 1, t[0] - 0.5 * q2, w, M, rd, prd);
+}
+
+// a variance per observed dimension: the spelling of the units that were there first
+template <int NO>
+__device__ __forceinline__ double pnmc_density(const double *t, int nu, const double (&x)[NO], const double (&ps)[NO]) {
+    return pnmc_density<PsiDiag<NO>>(t, nu, x, ps);
 }
 
 #define PNMC_CASES(MACRO)                                                                                  \

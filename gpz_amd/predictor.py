@@ -7,7 +7,9 @@ missing kind of such a model, which has all four too (``predict_missing_cov_dev`
 ``stack_missing_cov_dev``); noisy_missing_cov is such a group with Psi, with all four as well
 (``predict_noisy_missing_cov_dev``, ``draws_noisy_missing_cov_dev`` with ``return_gamma``, ``stack_noisy_missing_cov_dev``);
 psi_cube is the noisy kind of a covariance model whose rows have a full d x d Psi each, the d x d x n cube, with all four
-(``predict_psi_cube_dev``, ``draws_psi_cube_dev`` with ``return_gamma``, ``stack_psi_cube_dev``).
+(``predict_psi_cube_dev``, ``draws_psi_cube_dev`` with ``return_gamma``, ``stack_psi_cube_dev``); psi_cube_missing is a NaN-pattern
+group of such rows, with all four (``predict_psi_cube_missing_dev``, ``draws_psi_cube_missing_dev`` with ``return_gamma``,
+``stack_psi_cube_missing_dev``).
 ``_DEV_ENTRIES`` names the device-resident entry of each pair, ``Predictor._dev_entry`` builds the arguments the entries of a pair
 share, and ``Predictor._dev_groups`` is the one loop over the groups of a call; the host methods choose between two entries each by
 whether Psi is there (``_HOST_ENTRIES``).  Everything numeric happens in the library; ``torch`` is only imported by the device methods.
@@ -48,6 +50,10 @@ _DEV_ENTRIES = {
     ("stack", "noisy_missing_cov"): "gpz_predictor_stack_noisy_missing_cov_dev",
     ("run", "psi_cube"): "gpz_predictor_run_psi_cube_dev", ("draws", "psi_cube"): "gpz_predictor_draws_psi_cube_dev",
     ("draws_gamma", "psi_cube"): "gpz_predictor_draws_gamma_psi_cube_dev", ("stack", "psi_cube"): "gpz_predictor_stack_psi_cube_dev",
+    ("run", "psi_cube_missing"): "gpz_predictor_run_psi_cube_missing_dev",
+    ("draws", "psi_cube_missing"): "gpz_predictor_draws_psi_cube_missing_dev",
+    ("draws_gamma", "psi_cube_missing"): "gpz_predictor_draws_gamma_psi_cube_missing_dev",
+    ("stack", "psi_cube_missing"): "gpz_predictor_stack_psi_cube_missing_dev",
 }
 # (question, Psi there) -> the host entry
 _HOST_ENTRIES = {("draws", False): "gpz_predictor_draws", ("draws", True): "gpz_predictor_draws_noisy",
@@ -559,12 +565,13 @@ class Predictor:
         """The one loop over the groups of a *_dev call: yields (code, idx, Xg, the per-row tensors of the group ...).  Without
         ``missing`` the rows are not looked at and the whole call is the one group (0, None, X, ...); rows with NaN are then refused by
         the entry.  With it the groups of ``_nan_groups_dev`` in ascending code order, gathered by idx (None, and nothing gathered,
-        where all rows share one pattern).  A per-row tensor that is None stays None."""
+        where all rows share one pattern).  A per-row tensor that is None stays None; a d x d x n cube has its rows last."""
         if not missing:
             yield (0, None, X) + per_row
             return
         for code, idx in self._nan_groups_dev(X):
-            yield (code, idx, X if idx is None else X[idx]) + tuple(t if idx is None or t is None else t[idx] for t in per_row)
+            yield (code, idx, X if idx is None else X[idx]) + tuple(
+                t if idx is None or t is None else t[:, :, idx] if t.dim() == 3 else t[idx] for t in per_row)
 
     @staticmethod
     def _merge(idx, whole, part, axis):
@@ -584,10 +591,15 @@ class Predictor:
         missing values, the priors and the mask of the observed dimensions.  ``run`` and ``draws`` take muY there, in front of the
         priors; ``stack`` takes the priors straight after sdX and muY at the end of its own arguments.  ``cov``: complete rows with Psi
         of a covariance kind, whose entries take the noisy kind's arguments, or a group with missing values of such a kind, whose
-        entries take the missing kind's (with Psi too: the noisy missing kind's).  Returns (entry, arguments, row kind)."""
+        entries take the missing kind's (with Psi too: the noisy missing kind's).  ``cov == "cube"``: a d x d x n Psi, three strides
+        and the divisor triangle in place of sd2, for complete rows and for a group with missing values; a group with nothing observed
+        has no Psi to read and is the missing kind's of the model.  Returns (entry, arguments, row kind)."""
+        cube = cov == "cube"
+        if cube and code == (1 << self._d) - 1:
+            Pg = None
         noisy = Pg is not None
-        cube = cov == "cube"   # complete rows with a d x d x n Psi: three strides, the divisor triangle in place of sd2
-        kind = "psi_cube" if cube else \
+        cube = cube and noisy
+        kind = ("psi_cube_missing" if code else "psi_cube") if cube else \
             (("noisy_missing_cov" if cov else "noisy_missing") if noisy else "missing_cov" if cov else "missing") if code else \
             (("noisy_cov" if cov else "noisy") if noisy else "clean")
         lead = [call.h, *self._x_args(Xg)]
@@ -900,6 +912,98 @@ class Predictor:
         refused with a GpzError; a matrix that is not positive semidefinite makes its own row's contribution unspecified."""
         return self._stack_dev(X, Psi, edges, n_draws, seed, Z, groups, n_groups, weights, selection, cov="cube")
 
+    def _check_psi_cube_missing(self, what, X, Psi, selection):
+        """The checks the three methods for rows with a d x d x n Psi and missing values of a covariance kind share, none of which
+        touches a GPU, in the order of ``_check_psi_cube``: X, then where such rows go when this is not their route (no Psi, a variance
+        per dimension, a diagonal kind, a shape outside predict_missing_cov_fits), then Psi's type, dtype and shape and the priors.
+        Returns X as n x d and Psi."""
+        import torch
+        name = f"{what}_psi_cube_missing_dev"
+        if isinstance(X, np.ndarray):
+            raise TypeError(f"{name} takes a torch tensor on cuda:{self.device}; a NumPy catalogue with a Psi cube and missing values "
+                            "goes to Predictor.predict(X, Psi=Psi)")
+        X = self._check_dev_rows(X, selection, what)
+        d, n = self._d, X.shape[0]
+        if Psi is None:
+            raise ValueError(f"{name} needs Psi: rows of a covariance kind without input noise go to {what}_missing_cov_dev(X)")
+        ndim = Psi.dim() if hasattr(Psi, "dim") else np.ndim(Psi)
+        if ndim in (1, 2):
+            raise ValueError(f"{name} takes Psi as the d x d x n cube: n x d, n x 1 or n variances go to "
+                             f"{what}_noisy_missing_cov_dev(X, Psi)")
+        if self._method[1] != "C":
+            raise ValueError(f"{name} is for the covariance kinds (GC, VC): fixPsi gives a diagonal kind such as {self._method} only "
+                             f"the cube's diagonal, which goes to {what}_noisy_missing_dev(X, Psi)")
+        if not (1 <= d <= 10 and 1 <= self._k <= 8 and 1 <= self._m <= 256):
+            raise ValueError(f"{name} needs a model inside predict_missing_cov_fits: GC or VC, d <= 10, k <= 8 and m <= 256; this one "
+                             f"is {self._method} with d = {d}, m = {self._m}, k = {self._k} (Predictor.predict takes rows with a Psi "
+                             "cube and missing values for every shape)")
+        if isinstance(Psi, np.ndarray):
+            raise TypeError(f"{name} takes Psi as a torch tensor on cuda:{self.device}; host arrays stay on "
+                            "Predictor.predict(X, Psi=Psi)")
+        if not isinstance(Psi, torch.Tensor):
+            raise TypeError(f"Psi must be a torch.Tensor on cuda:{self.device}, got {type(Psi).__name__}")
+        if Psi.dtype not in (torch.float64, torch.float32):
+            raise TypeError(f"Psi must be float64 or float32, got {Psi.dtype}")
+        if tuple(Psi.shape) != (d, d, n):
+            raise ValueError(f"Psi must be d x d x n (d = {d}, n = {n}; an n x d x d tensor goes in as .permute(1, 2, 0)), got shape "
+                             f"{tuple(Psi.shape)}")
+        if self._priors.shape != (self._m,):
+            raise ValueError(f"the priors of the set must be {self._m} values, got {self._priors.size} (Predictor.predict reports "
+                             "the same for such rows)")
+        return X, Psi
+
+    def predict_psi_cube_missing_dev(self, X, Psi, selection=None):
+        """``predict_noisy_missing_cov_dev`` for rows with a full input-noise covariance each (GC, VC;
+        gpz_predictor_run_psi_cube_missing_dev): a catalogue with correlated input errors and, in some rows, missing values.  X and
+        ``selection`` as for ``predict_dev``; ``Psi`` the d x d x n cube as for ``predict_psi_cube_dev`` (float64 or float32, any
+        strides, element (r, c) entering as double(Psi[r, c, i]) / (sdX[r] * sdX[c])).  Returns mu, sigma, nu, beta_i, gamma as
+        ``predict(X, Psi=Psi)`` does, float64 (n, k) on the device.  The rows are grouped by NaN pattern with torch on the device: the
+        complete rows go to gpz_predictor_run_psi_cube_dev and get the bits of ``predict_psi_cube_dev`` on them alone, rows with
+        nothing observed read no Psi and get the bits of ``predict_missing_cov_dev``, and every other group is gathered with its
+        matrices and gets predictNoisyMissing of predictCov.m:233-337 on the handle's tiles (k_predict_psi_cube_missing_pairs) with the
+        priors of the set.  Only the lower triangle of the observed x observed block of a row's matrix is read and scanned: there an
+        element that is NaN or infinite (itself or after its division) or a negative diagonal element is refused (GpzError, outputs
+        untouched); a missing row or column of the matrix is never read and may hold NaN.  A cube with zeros off the diagonal gives the
+        bits of ``predict_noisy_missing_cov_dev`` on its diagonal.  A matrix that passes the scan but is not positive semidefinite is
+        the caller's error: that row gets NaN, and no other row is affected.  It needs a model inside predict_missing_cov_fits (GC or
+        VC, d <= 10, k <= 8, m <= 256), else ValueError; a diagonal kind takes the cube's diagonal through
+        ``predict_noisy_missing_dev``, variances per dimension go to ``predict_noisy_missing_cov_dev``, and PHI and host arrays stay
+        on ``Predictor.predict``.  A row's results do not depend on the tile size, the row order or the other rows of the call.  Type,
+        dtype and shape are checked first, the device last, all before the GPU is touched."""
+        self._check_open()
+        X, Psi = self._check_psi_cube_missing("predict", X, Psi, selection)
+        self._check_dev_device(X=X, selection=selection, Psi=Psi)
+        return self._moments_dev(X, Psi, selection, True, cov="cube")
+
+    def draws_psi_cube_missing_dev(self, X, Psi, n_draws, seed=0, Z=None, selection=None, return_gamma=False):
+        """``draws_noisy_missing_cov_dev`` for such rows (gpz_predictor_draws_psi_cube_missing_dev): X, ``Psi`` (d x d x n) and
+        ``selection`` as for ``predict_psi_cube_missing_dev``, everything else and the result as for ``draws_noisy_missing_cov_dev``:
+        draws[s] is ``predict_psi_cube_missing_dev``'s mu under weight draw s; one weight draw serves all rows of all groups, complete
+        rows get the bits of ``draws_psi_cube_dev`` and rows with nothing observed those of ``draws_missing_cov_dev``.
+        ``return_gamma=True`` (gpz_predictor_draws_gamma_psi_cube_missing_dev) returns ``(F, Gam)``: Gam[s] is predictNoisyMissing's
+        gamma under the weights of draw s, not clamped at 0 (k_predict_psi_cube_missing_gamma).  A row's F and Gam have the same bits
+        for any tile size, row order, other rows of the call and any n_draws > s."""
+        self._check_open()
+        X, Psi = self._check_psi_cube_missing("draws", X, Psi, selection)
+        n_draws, z = self._check_draw_args(n_draws, seed, Z, 1)
+        self._check_dev_device(X=X, selection=selection, Psi=Psi)
+        return self._draws_dev(X, Psi, selection, True, n_draws, seed, z, bool(return_gamma), cov="cube")
+
+    def stack_psi_cube_missing_dev(self, X, Psi, edges, n_draws=64, seed=0, Z=None, groups=None, n_groups=None, weights=None,
+                                   selection=None):
+        """``stack_noisy_missing_cov_dev`` for such rows (gpz_predictor_stack_psi_cube_missing_dev): X, ``Psi`` (d x d x n) and
+        ``selection`` as for ``predict_psi_cube_missing_dev``, everything else as for ``stack_dev``; ``n_draws`` defaults to 64.  The
+        complete rows go to gpz_predictor_stack_psi_cube_dev (a catalogue without NaN gives ``stack_psi_cube_dev``'s bits), rows with
+        nothing observed to gpz_predictor_stack_missing_cov_dev, every other group with its matrices, labels and weights to
+        gpz_predictor_stack_psi_cube_missing_dev, and the groups' results are added field by field in ascending order of the pattern
+        code; one weight draw serves all groups.  For a row with missing values column 0 uses ``predict_psi_cube_missing_dev``'s mu
+        and that call's sigma = (nu + beta_i) + gamma, bit for bit; column 1 + s ``draws_psi_cube_missing_dev``'s draw s and the width
+        beta_i + max(gamma_s, 0), where gamma_s is that method's ``return_gamma=True``.  Refusals as for
+        ``predict_psi_cube_missing_dev``; a label outside [-1, n_groups) and a negative or non-finite weight are found on the device
+        before the first tile and refused with a GpzError."""
+        return self._stack_dev(X, Psi, edges, n_draws, seed, Z, groups, n_groups, weights, selection, missing=True, both=True,
+                               cov="cube")
+
     def _check_noisy_missing_cov(self, what, X, Psi, selection):
         """The checks the three methods for rows with Psi and missing values of a covariance kind share, none of which touches a GPU: X by
         type, dtype and shape, then where such rows go when this is not their route (no Psi, a full Psi cube, a diagonal kind, a shape
@@ -1125,7 +1229,9 @@ class Predictor:
         one entry per NaN-pattern group."""
         import torch
         self._check_open()
-        if both and cov:
+        if both and cov == "cube":
+            X, Psi = self._check_psi_cube_missing("stack", X, Psi, selection)
+        elif both and cov:
             X, Psi = self._check_noisy_missing_cov("stack", X, Psi, selection)
         elif both:
             X, Psi = self._check_noisy_missing("stack", X, Psi, selection, draws=True)

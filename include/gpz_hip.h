@@ -736,6 +736,60 @@ int gpz_predictor_stack_noisy_missing_cov_dev(gpz_predictor *p, const void *X_d,
                                               double *hist, double *sum_w, double *sum_mu, double *sum_mu2,
                                               const double *mu_shift /* k or NULL */, void *stream);
 
+/* ---- rows with a full input-noise covariance AND missing inputs on a covariance kind: all four questions ------------------------------
+ * One group of rows that share a NaN pattern and carry a d x d matrix Psi each (the cube of fixPsi.m:36, which predictCov.m takes):
+ * gpz_predictor_run_psi_cube_missing_dev (the moments), _draws_psi_cube_missing_dev, _draws_gamma_psi_cube_missing_dev and
+ * _stack_psi_cube_missing_dev, where predict_missing_cov_fits holds (GC or VC, 1 <= d <= 10, 1 <= k <= 8, ceil16(m) <= 256; any other
+ * model returns GPZ_ERR_UNSUPPORTED and names that function; a diagonal kind is sent to gpz_predictor_run_noisy_missing_dev /
+ * _draws_noisy_missing_dev with the cube's diagonal).  Each takes the arguments of its noisy_missing_cov twin with Psi passed as the
+ * psi_cube entries pass it: element (r, c) of row i at Psi_d[r psi_mrow_stride + c psi_mcol_stride + i psi_row_stride], f64 or f32, and
+ * div, the d (d + 1) / 2 divisors sdX[r] sdX[c] at r (r + 1) / 2 + c (host or device; NULL exactly when sdX is), in place of sd2.
+ * Element (r, c) enters as double(Psi) / div.  Only the lower triangle of the observed x observed block of a row's matrix is read,
+ * scanned and staged: Psi in a missing row or column is never read and may be NaN.  An element there that is NaN or infinite, itself
+ * or after its division, or a negative diagonal element -> GPZ_ERR_ARG; a row off the mask -> GPZ_ERR_ARG; all found before the first
+ * tile (k_pmd_check, k_pcm_check_psi), outputs untouched.  A matrix that passes the scan but is not positive semidefinite is the
+ * caller's error: a non-positive pivot gives that row NaN and no other row is touched.  Complete rows go to the psi_cube entries
+ * (obs_mask without a missing dimension -> GPZ_ERR_ARG); a group with nothing observed (obs_mask 0) reads no Psi and gets the bits of
+ * the missing_cov entries.  Per tile k_pcm_stage_psi packs the observed triangles into [no (no + 1) / 2][tile rows] and k_pcm_ex,
+ * k_pcm_phi, k_predict_psi_cube_missing_pairs and k_predict_psi_cube_missing_gamma (k_predict_psi_cube_missing.hip,
+ * k_predict_psi_cube_missing_gamma.hip) are the noisy_missing_cov kernels with the packed Cholesky of M + Psi_oo over the whole
+ * triangle, on that group's records, slabs, chunks and tile buffers: a handle that has served that group on the same pattern builds
+ * nothing twice.  A cube with zeros off the diagonal returns the bits of the noisy_missing_cov entries.  A row's results have the same
+ * bits for any tile size, row order, company, split into calls and (gamma_s) any ndraws > s.  The first such call adds to the handle
+ * what its twin adds, with the psi_cube entries' triangle slots in place of the Psi slots; nothing grows with ns or the number of
+ * patterns.  gpz_predictor_route then holds "; noise cube missing: k_predict_psi_cube_missing_pairs (C pair chunks)" and, after gamma
+ * per draw or a stack, "; noise cube missing per draw: k_predict_psi_cube_missing_gamma (C pair chunks)" (" + k_stack_tile_w" once
+ * the stack entry has been called). */
+int gpz_predictor_run_psi_cube_missing_dev(gpz_predictor *p, const void *X_d, int32_t x_type, int64_t ns, int64_t row_stride,
+                                           int64_t col_stride, const void *Psi_d, int32_t psi_type, int64_t psi_mrow_stride,
+                                           int64_t psi_mcol_stride, int64_t psi_row_stride, const double *muX, const double *sdX,
+                                           const double *div, const double *muY /* k or NULL */, const double *priors /* m or NULL */,
+                                           uint32_t obs_mask, double *mu_d, double *sigma_d /* or NULL */, double *nu_d, double *beta_d,
+                                           double *gamma_d /* or NULL */, void *stream);
+int gpz_predictor_draws_psi_cube_missing_dev(gpz_predictor *p, const void *X_d, int32_t x_type, int64_t ns, int64_t row_stride,
+                                             int64_t col_stride, const void *Psi_d, int32_t psi_type, int64_t psi_mrow_stride,
+                                             int64_t psi_mcol_stride, int64_t psi_row_stride, const double *muX, const double *sdX,
+                                             const double *div, const double *muY /* k or NULL */, const double *priors /* m or NULL */,
+                                             uint32_t obs_mask, int32_t ndraws, uint64_t seed,
+                                             const double *Z /* host: NULL or m x ndraws x k */,
+                                             double *F_d /* ns x k x ndraws, column-major */, void *stream);
+int gpz_predictor_draws_gamma_psi_cube_missing_dev(gpz_predictor *p, const void *X_d, int32_t x_type, int64_t ns, int64_t row_stride,
+                                                   int64_t col_stride, const void *Psi_d, int32_t psi_type, int64_t psi_mrow_stride,
+                                                   int64_t psi_mcol_stride, int64_t psi_row_stride, const double *muX, const double *sdX,
+                                                   const double *div, const double *muY /* k or NULL */,
+                                                   const double *priors /* m or NULL */, uint32_t obs_mask, int32_t ndraws, uint64_t seed,
+                                                   const double *Z /* host: NULL or m x ndraws x k */,
+                                                   double *F_d /* ns x k x ndraws, column-major */,
+                                                   double *Gam_d /* ns x k x ndraws, column-major */, void *stream);
+int gpz_predictor_stack_psi_cube_missing_dev(gpz_predictor *p, const void *X_d, int32_t x_type, int64_t ns, int64_t row_stride,
+                                             int64_t col_stride, const void *Psi_d, int32_t psi_type, int64_t psi_mrow_stride,
+                                             int64_t psi_mcol_stride, int64_t psi_row_stride, const double *muX, const double *sdX,
+                                             const double *div, const double *priors /* m or NULL */, uint32_t obs_mask,
+                                             int32_t ndraws, uint64_t seed, const double *Z, const double *edges, int32_t nbins,
+                                             const int32_t *group_d /* ns or NULL */, int32_t ngroups, const double *weight_d /* ns or NULL */,
+                                             double *hist, double *sum_w, double *sum_mu, double *sum_mu2,
+                                             const double *mu_shift /* k or NULL */, void *stream);
+
 /* ---- device-resident L-BFGS memory: minFunc's lbfgsAdd.m / lbfgsProd.m (mex/lbfgsAddC.c, mex/lbfgsProdC.c) ----
  * S and Y (p x corrections) live on the device; all vector arguments are device pointers.
  * gpz_lbfgs_add:        y = g - g_old, s = t*d; skipped (added = 0) when y's <= 1e-10        (lbfgsAdd.m:2-4)
