@@ -71,8 +71,7 @@ struct gpz_predictor {
         bool used = false;
         double *s2_d = nullptr;    // [(1 + nd) k][tile] widths^2 of the stack
         size_t s2_cap = 0;         // doubles
-    } gam[7];                      // [kind - 1] of the call's RowKind: ROWS_NOISY .. ROWS_PSI_CUBE (clean rows have no gamma per draw)
-    PerDraw gam_pcm;               // the same for ROWS_PSI_CUBE_MISSING, the eighth kind with gamma per draw (rows_gamma_state picks)
+    } gam[8];                      // [kind - 1] of the call's RowKind: ROWS_NOISY .. ROWS_PSI_CUBE_MISSING (clean rows have no gamma per draw)
     // ---- rows with missing inputs on the handle (gpz_predictor_*_missing_dev): nothing of this exists before the first of their calls
     bool miss_used = false;
     int64_t mtile = 0;             // rows per tile of a group: min(tile_rows, GPZ_PREDICTOR_TILE_MISSING)

@@ -790,34 +790,40 @@ static int predictor_noisy_missing_cov_prepare(gpz_predictor *p, const char *who
     return 0;
 }
 
+// The two forms of Psi on a group of a covariance kind (Rows::group_psi()) differ on the host as NcovForm's do: in the tile's Psi slot
+// (Psic in Xc's layout, or Psiq with the observed triangles), in the launchers of their four kernels (the same signatures:
+// k_predict_noisy_missing_cov*.hip and k_predict_psi_cube_missing*.hip) and in the names the failure texts give those kernels
+struct GroupPsiForm {
+    double *const *Psi;
+    decltype(&launch_pnmc_rows) rows;
+    decltype(&launch_predict_noisy_missing_cov_pairs) pairs;
+    decltype(&launch_predict_noisy_missing_cov_gamma) gamma;
+    const char *rows_name, *name;     // rows_name, k_predict_<name>_pairs, _gamma
+};
+static GroupPsiForm group_psi_form(const gpz_predictor *p, const Rows &r) {
+    if (r.kind == ROWS_PSI_CUBE_MISSING)
+        return {p->Psiq, launch_pcm_rows, launch_predict_psi_cube_missing_pairs, launch_predict_psi_cube_missing_gamma, "k_pcm",
+                "psi_cube_missing"};
+    return {p->Psic, launch_pnmc_rows, launch_predict_noisy_missing_cov_pairs, launch_predict_noisy_missing_cov_gamma, "k_pnmc",
+            "noisy_missing_cov"};
+}
+
 // predictMissing of one tile of nt rows of the group, covariance kinds: Xc[s] -> Pio in mPio ([m][tile]), PHI in mNo, mu | ElnS - b in mhd
 // and, with pairs, mout ([4k][nt] = mu | nu | beta | gamma)
-// A group with input noise too (predictNoisyMissing) runs the kernels of k_predict_noisy_missing_cov.hip on their own record tables with
-// the tile's Psi slot, or, with a full Psi per row, those of k_predict_psi_cube_missing.hip on the same tables with the observed triangles
+// A group with input noise too (predictNoisyMissing) runs its form's kernels on their own record tables with the form's Psi slot
 static int predictor_missing_cov_tile(gpz_predictor *p, const char *who, const Rows &r, int s, int nt, bool pairs) {
     hipStream_t st = p->s_cmp;
     const int np = rup(nt, 128);   // the rows of the draws' product: k_tgemm's row tile
     const long mtp = rup(p->mtile, 1024);
     const uint32_t obs = r.obs;
-    const double *Psic = r.psi() ? p->Psic[s] : nullptr;
-    if (r.cube_obs()) {
-        if (launch_pcm_rows(st, p->Xc[s], p->Psiq[s], p->tile_pad, nt, np, p->m, p->mp, p->d, p->k, obs, p->nmcex, p->nmcphi, p->w_d,
-                            p->hetero ? p->pr.v : nullptr, p->mPio, mtp, p->mNo, p->mhd, mtp))
-            return gpz_fail(GPZ_ERR_HIP, "%s: k_pcm launch failed", who);
-        if (pairs && launch_predict_psi_cube_missing_pairs(st, p->Xc[s], p->Psiq[s], p->tile_pad, nt, p->mPio, mtp, p->m, p->d, p->k, obs,
-                                                           p->mcraw, p->mcbas, p->mccoef, p->nmcslab, &p->nmcslab_kept, p->mchunks,
-                                                           p->mpart, mtp, p->mhd, mtp, p->pr.b, p->mout))
-            return gpz_fail(GPZ_ERR_HIP, "%s: k_predict_psi_cube_missing_pairs launch failed", who);
-        return 0;
-    }
-    if (Psic) {
-        if (launch_pnmc_rows(st, p->Xc[s], Psic, p->tile_pad, nt, np, p->m, p->mp, p->d, p->k, obs, p->nmcex, p->nmcphi, p->w_d,
-                             p->hetero ? p->pr.v : nullptr, p->mPio, mtp, p->mNo, p->mhd, mtp))
-            return gpz_fail(GPZ_ERR_HIP, "%s: k_pnmc launch failed", who);
-        if (pairs && launch_predict_noisy_missing_cov_pairs(st, p->Xc[s], Psic, p->tile_pad, nt, p->mPio, mtp, p->m, p->d, p->k, obs,
-                                                            p->mcraw, p->mcbas, p->mccoef, p->nmcslab, &p->nmcslab_kept, p->mchunks,
-                                                            p->mpart, mtp, p->mhd, mtp, p->pr.b, p->mout))
-            return gpz_fail(GPZ_ERR_HIP, "%s: k_predict_noisy_missing_cov_pairs launch failed", who);
+    if (r.group_psi()) {
+        const GroupPsiForm f = group_psi_form(p, r);
+        if (f.rows(st, p->Xc[s], f.Psi[s], p->tile_pad, nt, np, p->m, p->mp, p->d, p->k, obs, p->nmcex, p->nmcphi, p->w_d,
+                   p->hetero ? p->pr.v : nullptr, p->mPio, mtp, p->mNo, p->mhd, mtp))
+            return gpz_fail(GPZ_ERR_HIP, "%s: %s launch failed", who, f.rows_name);
+        if (pairs && f.pairs(st, p->Xc[s], f.Psi[s], p->tile_pad, nt, p->mPio, mtp, p->m, p->d, p->k, obs, p->mcraw, p->mcbas, p->mccoef,
+                             p->nmcslab, &p->nmcslab_kept, p->mchunks, p->mpart, mtp, p->mhd, mtp, p->pr.b, p->mout))
+            return gpz_fail(GPZ_ERR_HIP, "%s: k_predict_%s_pairs launch failed", who, f.name);
         return 0;
     }
     if (launch_pmcv_rows(st, p->Xc[s], p->tile_pad, nt, np, p->m, p->mp, p->d, p->k, obs, p->mcex, p->mcphi, p->w_d,
@@ -918,12 +924,8 @@ int rows_chunks(const gpz_predictor *p, const Rows &r) { return r.group() ? p->m
 
 // What a call that needs gamma under nd draws on tiles of T rows adds to the handle (after rows_prepare with pairs: the pair table, or U
 // and the records): the chunk slab of the pair sums and, for a stack of Q column-outputs, the kind's widths.  nd = 0 takes no slab.
-static gpz_predictor::PerDraw &rows_gamma_state(gpz_predictor *p, const Rows &r) {
-    return r.kind == ROWS_PSI_CUBE_MISSING ? p->gam_pcm : p->gam[r.kind - 1];
-}
-
 int rows_gamma_prepare(gpz_predictor *p, const Rows &r, int ncol, int Q, int64_t T) {
-    gpz_predictor::PerDraw &g = rows_gamma_state(p, r);
+    gpz_predictor::PerDraw &g = p->gam[r.kind - 1];
     int rc = 0;
     if (r.kind == ROWS_NOISY || r.ncov()) p->gchunks = predict_gamma_chunks(p->m);   // (a handle has one of the two kinds)
     if (ncol > 0 && (rc = predictor_grow(p, &p->gpart, &p->gpart_cap, (size_t)rows_chunks(p, r) * ncol * T))) return rc;
@@ -941,30 +943,20 @@ int rows_gamma_tile(gpz_predictor *p, const char *who, const Rows &r, int s, int
             return gpz_fail(GPZ_ERR_HIP, "%s: k_predict_%s_gamma launch failed", who, f.name);
         return 0;
     }
-    if (r.kind == ROWS_MISSING_COV) {   // the slab of the pattern's pair records: kept, or written here as the pair kernel writes it
-        if (launch_predict_missing_cov_gamma(p->s_cmp, p->Xc[s], p->tile_pad, nt, p->mPio, rup(p->mtile, 1024), p->m, p->d, r.obs, p->mcraw,
-                                             p->mcbas, p->mcslab, &p->mcslab_kept, p->Wd, ldw, ncol, p->mchunks, p->gpart, nt))
-            return gpz_fail(GPZ_ERR_HIP, "%s: k_predict_missing_cov_gamma launch failed", who);
-        return 0;
-    }
-    if (r.kind == ROWS_NOISY_MISSING_COV) {   // its own records and slab; nothing observed: no Psi to read, the group is the kind's above
-        if (!r.psi() ? launch_predict_missing_cov_gamma(p->s_cmp, p->Xc[s], p->tile_pad, nt, p->mPio, rup(p->mtile, 1024), p->m, p->d, r.obs,
-                                                        p->mcraw, p->mcbas, p->mcslab, &p->mcslab_kept, p->Wd, ldw, ncol, p->mchunks,
-                                                        p->gpart, nt)
-                     : launch_predict_noisy_missing_cov_gamma(p->s_cmp, p->Xc[s], p->Psic[s], p->tile_pad, nt, p->mPio, rup(p->mtile, 1024),
-                                                              p->m, p->d, r.obs, p->mcraw, p->mcbas, p->nmcslab, &p->nmcslab_kept, p->Wd,
-                                                              ldw, ncol, p->mchunks, p->gpart, nt))
-            return gpz_fail(GPZ_ERR_HIP, "%s: k_predict_noisy_missing_cov_gamma launch failed", who);
-        return 0;
-    }
-    if (r.kind == ROWS_PSI_CUBE_MISSING) {   // that kind's records and slab with the observed triangles; nothing observed: as above
-        if (!r.cube_obs() ? launch_predict_missing_cov_gamma(p->s_cmp, p->Xc[s], p->tile_pad, nt, p->mPio, rup(p->mtile, 1024), p->m, p->d,
-                                                             r.obs, p->mcraw, p->mcbas, p->mcslab, &p->mcslab_kept, p->Wd, ldw, ncol,
-                                                             p->mchunks, p->gpart, nt)
-                          : launch_predict_psi_cube_missing_gamma(p->s_cmp, p->Xc[s], p->Psiq[s], p->tile_pad, nt, p->mPio,
-                                                                  rup(p->mtile, 1024), p->m, p->d, r.obs, p->mcraw, p->mcbas, p->nmcslab,
-                                                                  &p->nmcslab_kept, p->Wd, ldw, ncol, p->mchunks, p->gpart, nt))
-            return gpz_fail(GPZ_ERR_HIP, "%s: k_predict_psi_cube_missing_gamma launch failed", who);
+    if (r.cov_group()) {   // the slab of the pattern's pair records: kept, or written here as the pair kernel writes it.  With Psi: the
+        // form's own records and slab; with nothing observed there is no Psi to read and the group runs the kernel without Psi
+        const long mtp = rup(p->mtile, 1024);
+        if (r.group_psi()) {
+            const GroupPsiForm g = group_psi_form(p, r);
+            if (g.gamma(p->s_cmp, p->Xc[s], g.Psi[s], p->tile_pad, nt, p->mPio, mtp, p->m, p->d, r.obs, p->mcraw, p->mcbas,
+                        p->nmcslab, &p->nmcslab_kept, p->Wd, ldw, ncol, p->mchunks, p->gpart, nt))
+                return gpz_fail(GPZ_ERR_HIP, "%s: k_predict_%s_gamma launch failed", who, g.name);
+            return 0;
+        }
+        if (launch_predict_missing_cov_gamma(p->s_cmp, p->Xc[s], p->tile_pad, nt, p->mPio, mtp, p->m, p->d, r.obs, p->mcraw, p->mcbas,
+                                             p->mcslab, &p->mcslab_kept, p->Wd, ldw, ncol, p->mchunks, p->gpart, nt))
+            return gpz_fail(GPZ_ERR_HIP, "%s: k_predict_%s_gamma launch failed", who,   // (a group of the two Psi kinds with nothing observed
+                            r.kind == ROWS_MISSING_COV ? "missing_cov" : group_psi_form(p, r).name);   //  keeps its own kind's name)
         return 0;
     }
     // a group with Psi: the second record table
@@ -1032,7 +1024,7 @@ int predictor_stack_tile(gpz_predictor *p, const char *who, const Rows &r, const
     if (r.kind == ROWS_CLEAN) {
         bad = launch_stack_tile(st, mom, F, lab, wt, p->edges_d, sh, nt, p->k, c.nd, c.B, c.G, c.R, p->slab_d);
     } else {
-        double *s2 = rows_gamma_state(p, r).s2_d;
+        double *s2 = p->gam[r.kind - 1].s2_d;
         if (c.nd > 0 && (rc = rows_gamma_tile(p, who, r, s, (int)nt, c.ncol, c.ldw))) return rc;
         if (launch_gamma_finish_s2(st, p->gpart, rows_chunks(p, r), nt, mom, F, (int)nt, p->k, c.nd, s2))
             return gpz_fail(GPZ_ERR_HIP, "%s: k_gamma_finish_s2 launch failed", who);
@@ -1178,8 +1170,8 @@ extern "C" int gpz_predictor_route(const gpz_predictor *p, char *buf, int cap) {
         {"; noisy missing per draw: k_predict_noisy_missing_cov_gamma (%d pair chunks)", true},
         {"; noise cube per draw: k_predict_psi_cube_gamma (%d pair chunks)", false},
         {"; noise cube missing per draw: k_predict_psi_cube_missing_gamma (%d pair chunks)", true}};
-    auto gamma_line = [&](int i) {   // (the eighth kind's state is gam_pcm)
-        const gpz_predictor::PerDraw &g = i < 7 ? p->gam[i] : p->gam_pcm;
+    auto gamma_line = [&](int i) {
+        const gpz_predictor::PerDraw &g = p->gam[i];
         if (!g.used) return;
         snprintf(tmp, sizeof tmp, PER_DRAW[i].fmt, PER_DRAW[i].group ? p->mchunks : p->gchunks);
         r += tmp;

@@ -1,6 +1,6 @@
-// What the units for rows with input noise and missing inputs on a covariance kind share (k_predict_noisy_missing_cov.hip, where the
-// records are described and written, and k_predict_noisy_missing_cov_gamma.hip): the density of one record and the switch over the
-// observed dimensions, in one place so that every kernel forms a density with the same operations.
+// The density of one record for rows with input noise and missing inputs on a covariance kind (k_predict_noisy_missing_cov.hip, where
+// the records are described and written) and the switch over the observed dimensions, in one place so that every body of
+// k_predict_nmcov_impl.h forms a density with the same operations.
 #pragma once
 #include "gpz_dev.h"
 #include "k_pmcv_density.h"   // PMCV_MAXD, PmcvPat, pmcv_pat
@@ -33,12 +33,6 @@ __device__ __forceinline__ double pnmc_density(const double *t, int nu, const do
     double M[TRI], rd[NO], prd;
     P::factor(t + 1 + NO, ps, M, rd, &prd);
     return ncov_density<NO>(t + 1, t[0] - 0.5 * q2, w, M, rd, prd);
-}
-
-// a variance per observed dimension: the spelling of the units that were there first
-template <int NO>
-__device__ __forceinline__ double pnmc_density(const double *t, int nu, const double (&x)[NO], const double (&ps)[NO]) {
-    return pnmc_density<PsiDiag<NO>>(t, nu, x, ps);
 }
 
 #define PNMC_CASES(MACRO)                                                                                  \

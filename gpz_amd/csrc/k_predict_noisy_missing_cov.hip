@@ -25,23 +25,15 @@
 //                    (k_pmcv_basis), Sigma_i / the raw pair records: run-time loops over d and no, temporaries in scratch memory, off
 //                    the hot path.  The pair-component table passes through slabs of whole pairs of at most 64 MB
 //                    (predict_noisy_missing_cov_slabs(m, d, no): the rule of predict_missing_cov_slabs at this record length).
-//   k_pnmc_ex<NO>    lane = row, x_o and psi_o in registers: Ex over the m records in index order, Pio [l][ldr] = Ex_l / sum (:266, :281)
-//   k_pnmc_phi<NO>   lane = row: PHI(i) = sum_j Pio_j z(rec_ij) in index order -> Phi [nrow][mp] as launch_tgemm takes it   (:291-299)
-//   k_predict_noisy_missing_cov_pairs<NO, KM>   the frame of k_predict_missing_cov_pairs: 64 rows per workgroup, lane = row in each of
-//                    four waves, the Pio block [m][64] in dynamic LDS, the waves deal the chunk's pairs round-robin and stage their
-//                    pair's records through LDS PNMC_SB at a time, read as broadcasts; the m components in index order, 3 KM
-//                    multiply-adds per pair; partials in wave order, slabs in slab order; gridDim.y = predict_missing_cov_chunks(m).
-// k_pmcv_hd, k_pmcv_coef, k_pmd_finish and the draws' product are k_predict_missing_cov.hip's.  No atomics; every sum starts from zero
-// in an order fixed by m, d and no: the same bits for any tile size, row order, company, position in the block and split into calls.
+//   k_pnmc_ex<NO>, k_pnmc_phi<NO>, k_predict_noisy_missing_cov_pairs<NO, KM>   the tile kernels: wrappers of the bodies of
+//                    k_predict_nmcov_impl.h with PsiDiag<NO>, where the frame, the LDS and what keeps them from faulting are written
+//                    once for this unit, its gamma unit and the twins with a full Psi per row (k_predict_psi_cube_missing*.hip).
+// k_pmcv_hd, k_pmcv_coef, k_pmd_finish and the draws' product are k_predict_missing_cov.hip's.
 // A group with nothing observed (no = 0) has no Psi to read and is k_predict_missing_cov.hip's own (the host sends it there).
-// pnmc_density<NO>, the density of one record that every tile kernel here shares, and the switch over NO live in k_pnmc_density.h:
-// k_predict_noisy_missing_cov_gamma.hip (gamma under every weight draw) forms its densities with them from this unit's slabs.
 #include "gpz_dev.h"
 #include "gpz_kernels.h"
-#include "k_pnmc_density.h"   // pnmc_density, PNMC_CASES; PMCV_MAXD, PmcvPat, pmcv_pat; LT
+#include "k_predict_nmcov_impl.h"   // the bodies, the launchers and the stage sizes; PMCV_MAXD, PmcvPat, pmcv_pat; LT
 
-#define PNMC_STD 2048                 // doubles per LDS stage of the Ex and PHI kernels (whole records: at least 13)
-#define PNMC_SB 4                     // records per LDS stage of a wave of the pair kernel
 #define PNMC_SLAB_BYTES (64L << 20)   // most bytes of a slab of pair-component records
 
 // ---- records ---------------------------------------------------------------------------------------------------------------------------
@@ -185,147 +177,21 @@ __global__ __launch_bounds__(64) void k_pnmc_triples(PmcvPat pt, long q0, long c
 }
 
 // ---- the tile kernels ------------------------------------------------------------------------------------------------------------------
-struct PnmcArgs {
-    const double *Xc, *Psic; long ldx; int n;   // the tile's rows and variances, [d][ldx] each
-    int oidx[PMCV_MAXD];                        // the observed dimensions in ascending order
-    int nu, rl;                                 // the missing dimensions; doubles per record
-    int m, k;
-    double *Pio; long ldr;                      // [m][ldr]
-    const double *rec;                          // Ex: m records; PHI: m * m; pairs: the slab
-    double *Phi; int nrow, mp, ipc;             // PHI: [nrow][mp], basis functions per gridDim.y chunk
-    const double *coef; long q0; int cnt, ppc;  // pairs: the slab's first pair, its pairs, pairs per chunk
-    double *part; long ldp; int first;          // pairs: [chunks][3k][ldp]; first: the slab's sums are stored, not added
-};
+template <int NO>
+__global__ __launch_bounds__(256) void k_pnmc_ex(PredNmcovArgs a) { nmcov_ex_body<PsiDiag<NO>, false>(a); }
 
 template <int NO>
-__global__ __launch_bounds__(256) void k_pnmc_ex(PnmcArgs a) {
-    __shared__ double sT[PNMC_STD];
-    const int tid = threadIdx.x, rl = a.rl, nu = a.nu, per = PNMC_STD / rl;   // whole records per stage
-    const long i = (long)blockIdx.x * 256 + tid;
-    const bool act = i < a.n;
-    const long ic = act ? i : a.n - 1;
-    double x[NO], ps[NO];
-#pragma unroll
-    for (int c = 0; c < NO; ++c) {
-        x[c] = a.Xc[(size_t)a.oidx[c] * a.ldx + ic];
-        ps[c] = a.Psic[(size_t)a.oidx[c] * a.ldx + ic];
-    }
-    double s = 0.0;
-    for (int lb = 0; lb < a.m; lb += per) {
-        const int nl = min(per, a.m - lb);
-        __syncthreads();
-        for (int t = tid; t < nl * rl; t += 256) sT[t] = a.rec[(size_t)lb * rl + t];
-        __syncthreads();
-#pragma unroll 1
-        for (int e = 0; e < nl; ++e) {
-            const double z = pnmc_density<NO>(sT + e * rl, nu, x, ps);
-            s += z;                                                        // index order                          :281
-            if (act) a.Pio[(size_t)(lb + e) * a.ldr + i] = z;
-        }
-    }
-    if (!act) return;
-    for (int l = 0; l < a.m; ++l) a.Pio[(size_t)l * a.ldr + i] /= s;
-}
-
-template <int NO>
-__global__ __launch_bounds__(256) void k_pnmc_phi(PnmcArgs a) {
-    __shared__ double sT[PNMC_STD];
-    const int tid = threadIdx.x, rl = a.rl, nu = a.nu, per = PNMC_STD / rl;
-    const long i = (long)blockIdx.x * 256 + tid;
-    const bool act = i < a.n, st = i < a.nrow;   // rows n .. nrow - 1 are written as zeros
-    const long ic = act ? i : a.n - 1;
-    double x[NO], ps[NO];
-#pragma unroll
-    for (int c = 0; c < NO; ++c) {
-        x[c] = a.Xc[(size_t)a.oidx[c] * a.ldx + ic];
-        ps[c] = a.Psic[(size_t)a.oidx[c] * a.ldx + ic];
-    }
-    double *row = a.Phi + (size_t)(st ? i : 0) * a.mp;
-    const int i0 = blockIdx.y * a.ipc, i1 = min(a.m, i0 + a.ipc);
-    for (int b = i0; b < i1; ++b) {
-        double z = 0.0;
-        for (int lb = 0; lb < a.m; lb += per) {
-            const int nl = min(per, a.m - lb);
-            const double *src = a.rec + ((size_t)b * a.m + lb) * rl;
-            __syncthreads();
-            for (int t = tid; t < nl * rl; t += 256) sT[t] = src[t];
-            __syncthreads();
-#pragma unroll 1
-            for (int e = 0; e < nl; ++e) z = fma(a.Pio[(size_t)(lb + e) * a.ldr + ic], pnmc_density<NO>(sT + e * rl, nu, x, ps), z);
-        }
-        if (st) row[b] = act ? z : 0.0;
-    }
-    if (blockIdx.y == 0 && st)
-        for (int j = a.m; j < a.mp; ++j) row[j] = 0.0;
-}
+__global__ __launch_bounds__(256) void k_pnmc_phi(PredNmcovArgs a) { nmcov_phi_body<PsiDiag<NO>, false>(a); }
 
 template <int NO, int KM>
-__global__ __launch_bounds__(256) void k_predict_noisy_missing_cov_pairs(PnmcArgs a) {
-    extern __shared__ double sm[];
-    double *sPio = sm;                                   // [m][64]
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, m = a.m, k = a.k, rl = a.rl, nu = a.nu;
-    double *sRec = sm + (size_t)m * 64 + (size_t)w * (PNMC_SB * rl);   // this wave's stage
-    const long row0 = (long)blockIdx.x * 64, i = row0 + lane;
-    const bool act = i < a.n;
-    const long ic = act ? i : a.n - 1;
-    for (int e = tid; e < m * 64; e += 256) {
-        const long r = min(row0 + (e & 63), (long)a.n - 1);
-        sPio[e] = a.Pio[(size_t)(e >> 6) * a.ldr + r];
-    }
-    double x[NO], ps[NO];
-#pragma unroll
-    for (int c = 0; c < NO; ++c) {
-        x[c] = a.Xc[(size_t)a.oidx[c] * a.ldx + ic];
-        ps[c] = a.Psic[(size_t)a.oidx[c] * a.ldx + ic];
-    }
-    double acc[3 * KM];
-#pragma unroll
-    for (int e = 0; e < 3 * KM; ++e) acc[e] = 0.0;
-    const int ch = blockIdx.y, p0 = ch * a.ppc, p1 = min(a.cnt, p0 + a.ppc);
-    for (int pb = p0; pb < p1; pb += 4) {                // the four waves take pairs pb .. pb + 3
-        const int p = pb + w;
-        const bool on = p < p1;
-        const double *src = a.rec + (size_t)(on ? p : p0) * m * rl;
-        double z = 0.0;
-        for (int lb = 0; lb < m; lb += PNMC_SB) {
-            const int nl = min(PNMC_SB, m - lb);
-            __syncthreads();                             // the stage before is read (and, the first time, sPio is written)
-            if (on)
-                for (int t = lane; t < nl * rl; t += 64) sRec[t] = src[(size_t)lb * rl + t];
-            __syncthreads();
-            if (on) {
-#pragma unroll 1
-                for (int e = 0; e < nl; ++e) z = fma(sPio[(lb + e) * 64 + lane], pnmc_density<NO>(sRec + e * rl, nu, x, ps), z);
-            }
-        }
-        if (on) {
-            const double *cf = a.coef + (size_t)(a.q0 + p) * 3 * k;
-#pragma unroll
-            for (int o = 0; o < KM; ++o)
-                if (o < k) {
-                    acc[o] = fma(z, cf[3 * o], acc[o]);                    // gamma                                :308-320
-                    acc[KM + o] = fma(z, cf[3 * o + 1], acc[KM + o]);      // VlnS
-                    acc[2 * KM + o] = fma(z, cf[3 * o + 2], acc[2 * KM + o]);   // nu
-                }
-        }
-    }
-    __syncthreads();                                     // LDS is free: the partials of waves 1 .. 3, [wave - 1][3 KM][64]
-    if (w > 0) {
-#pragma unroll
-        for (int e = 0; e < 3 * KM; ++e) sm[((w - 1) * 3 * KM + e) * 64 + lane] = acc[e];
-    }
-    __syncthreads();
-    if (w > 0 || !act) return;
-#pragma unroll
-    for (int e = 0; e < 3 * KM; ++e) {
-        const int q = e / KM, o = e - q * KM;
-        if (o >= k) continue;
-        double s = acc[e];
-        for (int ww = 0; ww < 3; ++ww) s += sm[(ww * 3 * KM + e) * 64 + lane];   // wave order
-        double *dst = a.part + ((size_t)ch * 3 * k + (size_t)q * k + o) * a.ldp + i;
-        *dst = a.first ? s : *dst + s;                                     // slab order
-    }
-}
+__global__ __launch_bounds__(256) void k_predict_noisy_missing_cov_pairs(PredNmcovArgs a) { nmcov_pairs_body<PsiDiag<NO>, KM>(a); }
+
+struct PnmcKernels {
+    static constexpr size_t stage_lds = 0;
+    template <int NO> static auto ex() { return k_pnmc_ex<NO>; }
+    template <int NO> static auto phi() { return k_pnmc_phi<NO>; }
+    template <int NO, int KM> static auto pairs() { return k_predict_noisy_missing_cov_pairs<NO, KM>; }
+};
 
 // ---- host side -------------------------------------------------------------------------------------------------------------------------
 // [lnw | -j (no) | M (no (no + 1) / 2) | J (no no) | A2 ((d - no) no) | b2 (d - no)]
@@ -364,38 +230,7 @@ int launch_pnmc_tables(hipStream_t st, int m, int d, int de, unsigned obs, const
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
-static PnmcArgs pnmc_args(const PmcvPat &pt, const double *Xc, const double *Psic, long ldx, int n, int m, int k, double *Pio, long ldr,
-                          const double *rec) {
-    PnmcArgs a{};
-    a.Xc = Xc; a.Psic = Psic; a.ldx = ldx; a.n = n; a.m = m; a.k = k; a.Pio = Pio; a.ldr = ldr; a.rec = rec;
-    a.nu = pt.nu; a.rl = predict_noisy_missing_cov_rec(pt.d, pt.no);
-    for (int c = 0; c < pt.no; ++c) a.oidx[c] = pt.o[c];
-    return a;
-}
-
-int launch_pnmc_rows(hipStream_t st, const double *Xc, const double *Psic, long ldx, int n, int nrow, int m, int mp, int d, int k,
-                     unsigned obs, const double *exrec, const double *phirec, const double *w, const double *v, double *Pio, long ldr,
-                     double *Phi, double *hd, long ldh) {
-    if (n <= 0) return 0;
-    if (d < 1 || d > PMCV_MAXD || m < 1 || nrow < n || mp < m || ldr < n || !Psic) return -1;
-    const PmcvPat pt = pmcv_pat(d, obs);
-    if (pt.no < 1 || pt.nu < 1 || predict_noisy_missing_cov_rec(d, pt.no) > PNMC_STD) return -1;
-    PnmcArgs a = pnmc_args(pt, Xc, Psic, ldx, n, m, k, Pio, ldr, exrec);
-    PnmcArgs b = a;
-    b.rec = phirec; b.Phi = Phi; b.nrow = nrow; b.mp = mp; b.ipc = 8;
-    const dim3 ge((unsigned)((n + 255) / 256)), gp((unsigned)((nrow + 255) / 256), (unsigned)((m + b.ipc - 1) / b.ipc));
-#define PNMC_ROWS(NN)                                                          \
-    do {                                                                       \
-        hipLaunchKernelGGL(k_pnmc_ex<NN>, ge, dim3(256), 0, st, a);            \
-        hipLaunchKernelGGL(k_pnmc_phi<NN>, gp, dim3(256), 0, st, b);           \
-    } while (0)
-    PNMC_CASES(PNMC_ROWS)
-#undef PNMC_ROWS
-    if (hipGetLastError() != hipSuccess) return -1;
-    return launch_pmcv_hd(st, Phi, n, m, mp, k, w, v, hd, ldh);
-}
-
-// records [0, cnt * m) of the slab that starts at pair q0 (k_predict_noisy_missing_cov_gamma.hip fills a slab through it too)
+// records [0, cnt * m) of the slab that starts at pair q0 (the slab loop of k_predict_nmcov_impl.h fills every slab through it)
 int launch_pnmc_triples(hipStream_t st, int d, unsigned obs, long q0, long cnt, int m, const double *raw, const double *bas, double *slab) {
     if (cnt <= 0) return 0;
     if (d < 1 || d > PMCV_MAXD || m < 1) return -1;
@@ -406,46 +241,17 @@ int launch_pnmc_triples(hipStream_t st, int d, unsigned obs, long q0, long cnt, 
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
-// per launch, not once per process: the attribute belongs to the current device's copy of the kernel
-template <int NO, int KM>
-static int pnmc_launch_pairs(hipStream_t st, dim3 grid, size_t lds, const PnmcArgs &a) {
-    if (lds > 65536 && hipFuncSetAttribute((const void *)k_predict_noisy_missing_cov_pairs<NO, KM>,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-        return -1;
-    hipLaunchKernelGGL((k_predict_noisy_missing_cov_pairs<NO, KM>), grid, dim3(256), lds, st, a);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
+int launch_pnmc_rows(hipStream_t st, const double *Xc, const double *Psic, long ldx, int n, int nrow, int m, int mp, int d, int k,
+                     unsigned obs, const double *exrec, const double *phirec, const double *w, const double *v, double *Pio, long ldr,
+                     double *Phi, double *hd, long ldh) {
+    return nmcov_launch_rows<PnmcKernels>(st, Xc, Psic, ldx, n, nrow, m, mp, d, k, obs, exrec, phirec, w, v, Pio, ldr, Phi, hd, ldh);
 }
 
-// launch_predict_missing_cov_pairs with Psic and this unit's records and slabs.  *slab_kept: slab holds the pattern's whole table (one
-// slab) in this unit's form and is not written again; the caller clears it where the pattern's tables change.
+// launch_predict_missing_cov_pairs with Psic and this unit's records and slabs
 int launch_predict_noisy_missing_cov_pairs(hipStream_t st, const double *Xc, const double *Psic, long ldx, int n, const double *Pio,
                                            long ldr, int m, int d, int k, unsigned obs, const double *raw, const double *bas,
                                            const double *coef, double *slab, bool *slab_kept, int nchunk, double *part, long ldp,
                                            const double *hd, long ldh, const double *bvec, double *out) {
-    if (n <= 0) return 0;
-    if (d < 1 || d > PMCV_MAXD || k < 1 || k > 8 || m < 1 || ((m + 15) / 16) * 16 > 256 || nchunk != predict_missing_cov_chunks(m) ||
-        ldr < n || ldp < n || !Psic)
-        return -1;
-    const PmcvPat pt = pmcv_pat(d, obs);
-    if (pt.nu < 1 || pt.no < 1) return -1;
-    const int nslab = predict_noisy_missing_cov_slabs(m, d, pt.no);
-    const long npair = (long)m * (m + 1) / 2, sp = predict_noisy_missing_cov_slab_pairs(m, d, pt.no);
-    PnmcArgs a = pnmc_args(pt, Xc, Psic, ldx, n, m, k, const_cast<double *>(Pio), ldr, slab);
-    a.coef = coef; a.part = part; a.ldp = ldp;
-    const size_t lds = predict_noisy_missing_cov_lds(m, d, pt.no, k);
-    const dim3 grid((unsigned)((n + 63) / 64), (unsigned)nchunk);
-    for (int s = 0; s < nslab; ++s) {
-        const long q0 = s * sp, cnt = (npair - q0 < sp) ? npair - q0 : sp;
-        if (cnt <= 0) break;
-        // the whole table is one slab: it stays until the pattern's tables change, whichever kernel filled it
-        if (!(nslab == 1 && *slab_kept) && launch_pnmc_triples(st, d, obs, q0, cnt, m, raw, bas, slab)) return -1;
-        a.q0 = q0; a.cnt = (int)cnt; a.ppc = (int)((cnt + nchunk - 1) / nchunk); a.first = s == 0;
-        int rc;
-#define PNMC_PAIRS(NN) rc = k == 1 ? pnmc_launch_pairs<NN, 1>(st, grid, lds, a) : pnmc_launch_pairs<NN, 8>(st, grid, lds, a)
-        PNMC_CASES(PNMC_PAIRS)
-#undef PNMC_PAIRS
-        if (rc) return -1;
-    }
-    *slab_kept = nslab == 1;
-    return launch_pmd_finish(st, part, nchunk, ldp, hd, ldh, n, k, bvec, out);
+    return nmcov_launch_pairs<PnmcKernels>(st, Xc, Psic, ldx, n, Pio, ldr, m, d, k, obs, raw, bas, coef, slab, slab_kept, nchunk, part, ldp,
+                                           hd, ldh, bvec, out);
 }

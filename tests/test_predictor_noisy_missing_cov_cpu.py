@@ -105,13 +105,23 @@ def test_noisy_missing_cov_kernels_compiled_form(tmp_path):
 
 def test_chunks_slabs_and_lds_are_functions_of_the_model_and_the_pattern_alone():
     src = open(SRC).read()
-    assert "predict_missing_cov_chunks(m)" in src and "int predict_missing_cov_chunks(" not in src      # the chunk rule: used, not restated
+    impl = open(os.path.join(CSRC, "k_predict_nmcov_impl.h")).read()                   # the launchers of both forms of Psi
+    # the chunk rule: used by the pair launcher and the gamma launcher, not restated
+    assert impl.count("nchunk != predict_missing_cov_chunks(m)") == 2 and "int predict_missing_cov_chunks(" not in src + impl
+    # the slab rule and the one generation kernel: one loop, which the pair launcher and the gamma launcher both go through
+    loop = re.search(r"static int nmcov_slabs\(.*?\n\}", impl, flags=re.S).group(0)
+    assert "predict_noisy_missing_cov_slabs(m, d, pt.no)" in loop and "predict_noisy_missing_cov_slab_pairs(m, d, pt.no)" in loop
+    assert "if (!(nslab == 1 && *slab_kept) && launch_pnmc_triples(st, d, obs, q0, cnt, m, raw, bas, slab)) return -1;" in loop
+    assert "*slab_kept = nslab == 1;" in loop and impl.count("launch_pnmc_triples(st") == 1
+    assert len(re.findall(r"\bnmcov_slabs\(st, pt, obs, m, raw, bas, slab, slab_kept, nchunk, a, launch\)", impl)) == 2
     assert ("int predict_noisy_missing_cov_rec(int d, int no) { return 1 + no + no * (no + 1) / 2 + no * no + (d - no) * (no + 1); }"
             in src)
     sbody = re.search(r"int predict_noisy_missing_cov_slabs\(int m, int d, int no\) \{(.*?)\n\}", src, flags=re.S).group(1)
     assert "while (((npair + s - 1) / s) * per > PNMC_SLAB_BYTES) s *= 2;" in sbody
     assert "per = (long)m * predict_noisy_missing_cov_rec(d, no) * (long)sizeof(double)" in sbody
-    assert re.search(r"#define PNMC_SLAB_BYTES \(64L << 20\)", src) and re.search(r"#define PNMC_SB 4\b", src)
+    assert re.search(r"#define PNMC_SLAB_BYTES \(64L << 20\)", src) and re.search(r"#define PNMC_SB 4\b", impl)
+    assert "PNMC_SB" not in src.replace("4 * (size_t)PNMC_SB * predict_noisy_missing_cov_rec(d, no)", "")   # counted by the LDS figure alone
+    assert re.search(r"#define PNMC_STD 2048\b", impl) and "predict_noisy_missing_cov_lds(m, d, pt.no, k)" in impl
     for word in ("n", "ns", "nt", "tile", "rows", "k"):
         assert not re.search(r"\b" + word + r"\b", sbody), word
     old = open(os.path.join(CSRC, "k_predict_missing_cov.hip")).read()                 # the records the other entries read keep their form

@@ -139,7 +139,7 @@ def test_each_body_has_one_definition_and_the_host_no_cube_flag():
     assert "den.bind(" not in code["k_predict_gamma_impl.h"] and "gamma_psi_width" not in code["k_predict_gamma_impl.h"]
     host = code["gpz_predictor.hip"]
     assert len(re.findall(r"ROWS_NOISY_COV\s*\|\|", host + code["gpz_predictor_dev.hip"] + code["gpz_predictor_host.hip"])) == 0
-    assert "} gam[7];" in src["gpz_predictor.h"] and "p->gam[r.kind - 1]" in host
+    assert "} gam[8];" in src["gpz_predictor.h"] and "p->gam[r.kind - 1]" in host
 
 
 def _compile(unit, tmp_path):

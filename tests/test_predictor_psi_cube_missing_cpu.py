@@ -83,16 +83,81 @@ def test_header_binding_library_and_entry_table_agree():
     host = open(os.path.join(CSRC, "gpz_predictor.hip")).read()
     assert '"; noise cube missing: k_predict_psi_cube_missing_pairs (%d pair chunks)"' in host
     assert '"; noise cube missing per draw: k_predict_psi_cube_missing_gamma (%d pair chunks)"' in host
-    # the density has one definition with the Psi policy as its parameter, and both new units form theirs through PsiTri
-    head = open(os.path.join(CSRC, "k_pnmc_density.h")).read()
-    assert len(re.findall(r"P::factor\(", head)) == 1 and "pnmc_density<PsiDiag<NO>>(t, nu, x, ps)" in head
-    for unit in UNITS:
+    # the density has one definition and one spelling, the Psi policy its parameter, and both units' kernels are the shared bodies with
+    # PsiTri (the chunk, slab and LDS rules those bodies' launchers use: tests/test_predictor_noisy_missing_cov_cpu.py)
+    head = re.sub(r"//.*", "", open(os.path.join(CSRC, "k_pnmc_density.h")).read())
+    assert len(re.findall(r"P::factor\(", head)) == 1 and len(re.findall(r"double pnmc_density\(", head)) == 1
+    assert "double pnmc_density(const double *t, int nu, const double (&x)[P::D], const double (&ps)[P::W])" in head
+    for unit, bodies in zip(UNITS, (("nmcov_ex_body<PsiTri<NO>, true>(a)", "nmcov_phi_body<PsiTri<NO>, true>(a)", "nmcov_pairs_body<PsiTri<NO>, KM>(a)"),
+                                    ("nmcov_gamma_body<PsiTri<NO>, pcmg_nb(NO)>(a)",))):
         code = re.sub(r"//.*", "", open(os.path.join(CSRC, unit)).read())
-        assert "pnmc_density<PsiTri<NO>>(" in code and "ncov_factor" not in code, unit
-        assert "predict_missing_cov_chunks(m)" in code and "int predict_missing_cov_chunks(" not in code, unit   # used, not restated
-        assert "predict_noisy_missing_cov_slabs(m, d, pt.no)" in code and "launch_pnmc_triples(" in code, unit    # section 31's slabs
-    assert "predict_noisy_missing_cov_lds(m, d, pt.no, k)" in open(os.path.join(CSRC, UNITS[0])).read()          # LDS is unchanged
-    assert "predict_noisy_missing_cov_gamma_lds(m, d, pt.no)" in open(os.path.join(CSRC, UNITS[1])).read()
+        for body in bodies:
+            assert body in code, (unit, body)
+        assert "ncov_factor" not in code and "int predict_missing_cov_chunks(" not in code, unit
+    impl = open(os.path.join(CSRC, "k_predict_nmcov_impl.h")).read()
+    assert "predict_noisy_missing_cov_gamma_lds(m, d, pt.no)" in impl                                             # LDS is unchanged
+
+
+def test_each_body_has_one_definition_and_the_host_one_form_table():
+    """The tile and gamma kernels of a group with Psi, a variance per observed input or a full matrix per row, are the four bodies of
+    k_predict_nmcov_impl.h: each body, both argument structs and the row loader are defined once in the tree, the four units hold
+    wrappers only, the names of the copies are gone, and the host reaches the launchers of either form through group_psi_form alone."""
+    code = {f: re.sub(r"//.*", "", open(os.path.join(CSRC, f)).read()) for f in sorted(os.listdir(CSRC)) if f.endswith((".h", ".hip"))}
+    home = "k_predict_nmcov_impl.h"
+    for what, pat in (("nmcov_ex_body", r"void nmcov_ex_body\(const PredNmcovArgs &a\)\s*\{"),
+                      ("nmcov_phi_body", r"void nmcov_phi_body\(PredNmcovArgs a\)\s*\{"),
+                      ("nmcov_pairs_body", r"void nmcov_pairs_body\(PredNmcovArgs a\)\s*\{"),
+                      ("nmcov_gamma_body", r"void nmcov_gamma_body\(PredNmcovGammaArgs a\)\s*\{"),
+                      ("PredNmcovArgs", r"struct PredNmcovArgs\s*\{"), ("PredNmcovGammaArgs", r"struct PredNmcovGammaArgs\s*\{"),
+                      ("nmcov_load", r"void nmcov_load\(const A &a, long ic, double \(&x\)\[P::D\], double \(&ps\)\[P::W\]\)\s*\{")):
+        assert [f for f, t in code.items() if re.search(pat, t)] == [home], what
+    impl = code[home]
+    for body in ("nmcov_ex_body", "nmcov_phi_body", "nmcov_pairs_body", "nmcov_gamma_body"):   # by value, its own LDS, one density
+        text = re.search(r"__device__ __forceinline__ void " + body + r"\(.*?\n\}", impl, flags=re.S).group(0)
+        stage = "double *sT = nmcov_stage<DYNAMIC>();" if body in ("nmcov_ex_body", "nmcov_phi_body") else "extern __shared__ double sm[];"
+        assert text.count(stage) == 1 and len(re.findall(r"__shared__", text)) == (stage[0] == "e"), body
+        assert "nmcov_load<P>(a, ic, x, ps);" in text, body
+        assert len(re.findall(r"\w*density\w*[<(]", text)) == 1 and "pnmc_density<P>(" in text, body
+    # the record stage of the Ex and PHI bodies: one helper, static (k_pnmc_*, as it was) or the launch's dynamic LDS (k_pcm_*, as it was)
+    stage = re.search(r"double \*nmcov_stage\(\) \{.*?\n\}", impl, flags=re.S).group(0)
+    assert "extern __shared__ double dyn[];" in stage and "__shared__ double fix[PNMC_STD];" in stage and impl.count("__shared__") == 4
+    assert "nmcov_ex_body<PsiDiag<NO>, false>(a)" in code["k_predict_noisy_missing_cov.hip"]
+    assert "nmcov_phi_body<PsiDiag<NO>, false>(a)" in code["k_predict_noisy_missing_cov.hip"]
+    assert "stage_lds = 0;" in code["k_predict_noisy_missing_cov.hip"]
+    assert "stage_lds = PNMC_STD * sizeof(double);" in code["k_predict_psi_cube_missing.hip"] and impl.count("K::stage_lds, st") == 2
+    assert "bool" not in re.search(r"void nmcov_load_psi\(.*?void nmcov_load\([^{]*\{", impl, flags=re.S).group(0)   # by policy, no flag
+    assert "nmcov_load_psi(PsiDiag<NO>, const A &a" in impl and "nmcov_load_psi(PsiTri<NO>, const A &a" in impl
+    assert "ps[c] = a.Psi[(size_t)a.oidx[c] * a.ldx + ic];" in impl and "ncov_psi_load(a.Psi + ic, a.ldx, ps);" in impl
+    assert len(re.findall(r"P::factor\(", code["k_pnmc_density.h"])) == 1
+    for unit in ("k_predict_noisy_missing_cov.hip", "k_predict_psi_cube_missing.hip", "k_predict_noisy_missing_cov_gamma.hip",
+                 "k_predict_psi_cube_missing_gamma.hip"):
+        for word in ("__shared__", "__syncthreads", "pnmc_density"):
+            assert word not in code[unit], (unit, word)
+        assert '#include "k_predict_nmcov_impl.h"' in code[unit], unit
+    for f, t in code.items():
+        for word in ("PnmcArgs", "PcmArgs", "PcmgArgs", "NmcgArgs", "PCM_STD", "PCM_SB", "GPZ_PCMG_SB", "GPZ_PCMG_PF", "pcmg_stride",
+                     "gam_pcm", "rows_gamma_state"):
+            assert word not in t, (f, word)
+    for name in ("PNMC_STD", "PNMC_SB", "GPZ_NMCG_SB", "GPZ_NMCG_PF"):                   # one definition of each stage size
+        assert [f for f, t in code.items() if re.search(r"#define " + name + r"\b", t)] == [home], name
+    assert [f for f, t in code.items() if re.search(r"\bint nmcg_stride\(", t)] == [home]
+    assert "ldx < n" in re.search(r"static int nmcov_launch_rows\(.*?\n\}", impl, flags=re.S).group(0)   # both forms refuse it now
+    assert "ldx < n" in re.search(r"static int nmcov_launch_pairs\(.*?\n\}", impl, flags=re.S).group(0)
+    assert "ldx < n" in re.search(r"static int nmcov_launch_gamma\(.*?\n\}", impl, flags=re.S).group(0)
+    host = code["gpz_predictor.hip"]
+    form = re.search(r"static GroupPsiForm group_psi_form\(.*?\n\}", host, flags=re.S).group(0)
+    for fn in ("launch_pnmc_rows", "launch_predict_noisy_missing_cov_pairs", "launch_predict_noisy_missing_cov_gamma", "launch_pcm_rows",
+               "launch_predict_psi_cube_missing_pairs", "launch_predict_psi_cube_missing_gamma"):
+        assert len(re.findall(r"\b" + fn + r"\b(?!\))", host)) == 1 and re.search(r"\b" + fn + r"\b", form), fn   # (decltype(&fn) aside)
+    assert '"k_pcm"' in form and '"psi_cube_missing"' in form and '"k_pnmc"' in form and '"noisy_missing_cov"' in form
+    assert "p->Psiq, launch_pcm_rows" in form and "p->Psic, launch_pnmc_rows" in form
+    tile = re.search(r"static int predictor_missing_cov_tile\(.*?\n\}", host, flags=re.S).group(0)
+    assert len(re.findall(r"\bf\.rows\(", tile)) == 1 and len(re.findall(r"\bf\.pairs\(", tile)) == 1 and "launch_pmcv_rows(" in tile
+    assert '"%s: %s launch failed", who, f.rows_name' in tile and '"%s: k_predict_%s_pairs launch failed", who, f.name' in tile
+    gtile = re.search(r"int rows_gamma_tile\(.*?\n\}", host, flags=re.S).group(0)
+    assert len(re.findall(r"\bg\.gamma\(", gtile)) == 1 and len(re.findall(r"launch_predict_missing_cov_gamma\(", gtile)) == 1
+    assert "} gam[8];" in code["gpz_predictor.h"] and "p->gam[i]" in host
+    assert "k_predict_nmcov_impl.h" in open(os.path.join(ROOT, "build.sh")).read()
 
 
 # ---- 2. the identity with a full Psi_oo ----------------------------------------------------------------------------------------------------

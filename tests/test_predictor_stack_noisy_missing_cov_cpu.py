@@ -26,6 +26,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "gpz_amd", "csrc")
 SRC = os.path.join(CSRC, "k_predict_noisy_missing_cov_gamma.hip")
 OLD = os.path.join(CSRC, "k_predict_noisy_missing_cov.hip")
+IMPL = os.path.join(CSRC, "k_predict_nmcov_impl.h")
 HEADER = os.path.join(ROOT, "include", "gpz_hip.h")
 ENTRIES = {"gpz_predictor_draws_gamma_noisy_missing_cov_dev": "gpz_predictor_draws_gamma_noisy_missing_dev",
            "gpz_predictor_stack_noisy_missing_cov_dev": "gpz_predictor_stack_noisy_missing_dev"}
@@ -58,10 +59,13 @@ def test_header_binding_library_and_entry_table_agree():
     host = open(os.path.join(CSRC, "gpz_predictor.hip")).read()
     assert "; noisy missing per draw: k_predict_noisy_missing_cov_gamma (%d pair chunks)" in host
     assert "p->nmcslab, &p->nmcslab_kept, p->Wd" in host                  # the pair kernel's own slab and its state
-    assert "} gam[7];" in open(os.path.join(CSRC, "gpz_predictor.h")).read()   # one slot per kind of rows with gamma per draw, this kind's the sixth
+    assert "} gam[8];" in open(os.path.join(CSRC, "gpz_predictor.h")).read()   # one slot per kind of rows with gamma per draw, this kind's the sixth
+    for f in ("gpz_predictor.h", "gpz_predictor.hip", "gpz_predictor_host.hip", "gpz_predictor_dev.hip"):   # indexed by kind - 1, no accessor
+        text = open(os.path.join(CSRC, f)).read()
+        assert "gam_pcm" not in text and "rows_gamma_state" not in text, f
     old = open(OLD).read()                                               # one generation kernel, reached through its launcher
     assert old.count("void k_pnmc_triples(") == 1 and "k_pnmc_triples" not in open(SRC).read().replace("launch_pnmc_triples", "")
-    assert "pnmc_density(" not in old.replace("pnmc_density<NO>(", "") and "#define PNMC_CASES" not in old   # they moved to the header
+    assert "pnmc_density" not in old and "#define PNMC_CASES" not in old   # they moved to the header
     head = open(os.path.join(CSRC, "k_pnmc_density.h")).read()
     assert "double pnmc_density(" in head and "#define PNMC_CASES(MACRO)" in head
 
@@ -114,12 +118,14 @@ def test_the_lds_rule_fits_the_compute_unit_and_the_rules_are_borrowed():
     assert "((size_t)m * 64 + 4 * (size_t)nmcg_stride(predict_noisy_missing_cov_rec(d, no))) * sizeof(double)" in body
     for word in ("n", "ns", "nt", "tile", "rows", "k", "ncol"):            # m, d and no alone
         assert not re.search(r"\b" + word + r"\b", body), word
-    assert "int nmcg_stride(int rl) { return (GPZ_NMCG_SB * rl) | 1; }" in src and re.search(r"#define GPZ_NMCG_SB 4\b", src)
-    assert "hipFuncAttributeMaxDynamicSharedMemorySize" in src
-    # the chunk and slab rules: used, not restated
-    assert "nchunk != predict_missing_cov_chunks(m)" in src and "int predict_missing_cov_chunks(" not in src
-    assert "predict_noisy_missing_cov_slabs(m, d, pt.no)" in src and "int predict_noisy_missing_cov_slabs(" not in src
-    assert "PNMC_SLAB_BYTES" not in src and "int predict_noisy_missing_cov_rec(" not in src
+    impl = open(IMPL).read()                                             # the stride and the stage: one definition, beside the body
+    assert "int nmcg_stride(int rl) { return (GPZ_NMCG_SB * rl) | 1; }" in impl and re.search(r"#define GPZ_NMCG_SB 4\b", impl)
+    assert "nmcg_stride" not in src.replace("nmcg_stride(predict_noisy_missing_cov_rec(d, no))", "") and "GPZ_NMCG_SB" not in src
+    assert "hipFuncAttributeMaxDynamicSharedMemorySize" in impl
+    # the chunk and slab rules: not restated (tests/test_predictor_noisy_missing_cov_cpu.py holds their use by the launchers)
+    for text in (src, impl):
+        assert "int predict_missing_cov_chunks(" not in text and "int predict_noisy_missing_cov_slabs(" not in text
+        assert "PNMC_SLAB_BYTES" not in text and "int predict_noisy_missing_cov_rec(" not in text
     # the blocks of a pass and the launch bound are functions of NO alone
     assert "constexpr int nmcg_nb(int no)" in src and "constexpr int nmcg_wg(int no)" in src
     assert "__launch_bounds__(256, nmcg_wg(NO)) void k_predict_noisy_missing_cov_gamma" in src

@@ -36,6 +36,12 @@ between them), 9, 10 (the widths above 256 registers), each with m = 20, k = 1 a
 over two tiles: predict_psi_cube_dev, draws_psi_cube_dev with and without gamma, stack_psi_cube_dev with 1 draw and with one column
 more than a gamma pass holds; one handle that meets a cube call first and predict_noisy_cov_dev / stack_noisy_cov_dev second, and one
 the other way round (the two kinds share cbrec, cprec, nout, npart, cphi and gpart).
+Behind those (run_cube_missing, profiles/r27_predict_nmcov_fold.txt: before and after the tile and gamma kernels of GC / VC groups
+with Psi and missing inputs were folded onto the bodies of k_predict_nmcov_impl.h): such rows with NaN patterns on GC and VC at d = 5
+(one pattern per NO = 1 .. 4), 10 (NO = 9) and 2 (NO = 1), m = 7 and 17, k = 1 and 2, 200 rows that mix complete rows, rows with
+nothing observed and the patterns: predict_psi_cube_missing_dev, draws_psi_cube_missing_dev with and without gamma (17 and 65 columns)
+and stack_psi_cube_missing_dev with 3 groups, on a float64 cube and a float32 one with other strides; two handles that serve
+predict_noisy_missing_cov_dev and the cube calls on one pattern in both orders; and m = 250, where the pattern's table takes several slabs.
 After each call one line: the call, the digest of each array it returned, and the handle's route and info."""
 import hashlib
 import os
@@ -257,6 +263,72 @@ def run_cube(method, d, m, k):
         cube(p, 80, draws[-1], "diagonal first, ")
 
 
+def run_cube_missing(method, d, m, k):
+    """Rows with a full Psi each and missing inputs (profiles/r27_predict_nmcov_fold.txt): of every eight rows two complete, one with
+    nothing observed and the others on the patterns of d - one per NO = 1 .. 4 at d = 5, dimension 1 of 5 missing among them, NO = 9
+    at d = 10 and NO = 1 at d = 2.  All four questions on a float64 cube and on a float32 one with other strides, gamma per draw at 17
+    and 65 columns (18 and 66 at k = 2), a stack with 3 groups, and two handles that serve the diagonal form and the cube on one
+    pattern in both orders (they share the slab and its flag)."""
+    from predict_edges import psi_cube
+    tag = f"{method} d={d} m={m} k={k} cube missing"
+    n = 200
+    model = synth_model(method, m, d, k, True, seed=2000 * d + 10 * m + k + (method == "GC"))
+    rng = np.random.default_rng(27 * d + m + k)
+    X = catalogue(model, n, seed=d + m)
+    missing = {5: ((1,), (0, 4), (0, 2, 4), (0, 1, 3, 4)), 10: ((3,),), 2: ((0,),)}[d]   # the dimensions each pattern lacks
+    r = np.arange(n) % 8
+    X[r == 2, :] = np.nan
+    for slot, dims in zip((3, 4, 5, 6), missing):
+        X[np.ix_(r == slot, dims)] = np.nan
+    X[np.ix_(r == 7, missing[0])] = np.nan
+    sd = np.asarray(model.sdX).reshape(-1)
+    g = rng.gamma(1.0, 0.05, (n, d)) * sd ** 2
+    C = psi_cube(g.copy(), 0.2 * rng.standard_normal((n, d)) * sd)
+    Xd, Pd, Cd = (torch.from_numpy(a).to(DEV) for a in (X, g, C))
+    C32 = torch.from_numpy(np.ascontiguousarray(C.transpose(2, 0, 1)).astype(np.float32)).to(DEV).permute(1, 2, 0)   # strides (d, 1, d d)
+    gd = torch.from_numpy(rng.integers(-1, 3, n)).to(DEV)
+    wd = torch.from_numpy(rng.uniform(0.5, 1.5, n)).to(DEV)
+    edges = np.linspace(-3.0, 3.0, 13)
+    first = torch.from_numpy(np.flatnonzero((r == 3) | (r == 7))).to(DEV)   # the rows of one pattern
+    with gpz_amd.Predictor(model, tile_rows=128) as p:
+        for name, c in (("f64", Cd), ("f32", C32)):
+            report(f"{tag} predict {name}", p, p.predict_psi_cube_missing_dev(Xd, c))
+            report(f"{tag} draws {name}", p, p.draws_psi_cube_missing_dev(Xd, c, 3, seed=11))
+            for cols in (17, 65):
+                nd = -(-cols // k)
+                report(f"{tag} draws gamma {nd} {name}", p, p.draws_psi_cube_missing_dev(Xd, c, nd, seed=11, return_gamma=True))
+            report(f"{tag} stack {name}", p,
+                   tuple(p.stack_psi_cube_missing_dev(Xd, c, edges, n_draws=5, seed=11, groups=gd, n_groups=3, weights=wd)))
+        report(f"{tag} stack plain", p, tuple(p.stack_psi_cube_missing_dev(Xd[:80], Cd[:, :, :80], edges, n_draws=0)))
+    x1, p1, c1 = Xd[first], Pd[first], Cd[:, :, first]
+    with gpz_amd.Predictor(model, tile_rows=128) as p:                   # a variance per dimension first, the cube second
+        report(f"{tag} diagonal first, predict_noisy_missing_cov_dev", p, p.predict_noisy_missing_cov_dev(x1, p1))
+        report(f"{tag} diagonal first, predict", p, p.predict_psi_cube_missing_dev(x1, c1))
+        report(f"{tag} diagonal first, draws gamma", p, p.draws_psi_cube_missing_dev(x1, c1, 3, seed=11, return_gamma=True))
+    with gpz_amd.Predictor(model, tile_rows=128) as p:                   # and the other way round, gamma in front
+        report(f"{tag} cube first, draws gamma", p, p.draws_psi_cube_missing_dev(x1, c1, 3, seed=11, return_gamma=True))
+        report(f"{tag} cube first, predict_noisy_missing_cov_dev", p, p.predict_noisy_missing_cov_dev(x1, p1))
+        report(f"{tag} cube first, stack_noisy_missing_cov_dev", p, tuple(p.stack_noisy_missing_cov_dev(x1, p1, edges, n_draws=3, seed=11)))
+        report(f"{tag} cube first, predict", p, p.predict_psi_cube_missing_dev(x1, c1))
+
+
+def run_cube_missing_slabs(method):
+    """m = 250, d = 5: the pair-component table of a pattern with NO = 4 passes through several slabs.  70 rows of that pattern."""
+    from predict_edges import psi_cube
+    m, d, k, n = 250, 5, 1, 70
+    tag = f"{method} d={d} m={m} k={k} cube missing slabs"
+    model = synth_model(method, m, d, k, True, seed=2750 + (method == "GC"))
+    rng = np.random.default_rng(275)
+    X = catalogue(model, n, seed=27)
+    X[:, 1] = np.nan
+    sd = np.asarray(model.sdX).reshape(-1)
+    C = psi_cube(rng.gamma(1.0, 0.05, (n, d)) * sd ** 2, 0.2 * rng.standard_normal((n, d)) * sd)
+    Xd, Cd = torch.from_numpy(X).to(DEV), torch.from_numpy(C).to(DEV)
+    with gpz_amd.Predictor(model, tile_rows=128) as p:
+        report(f"{tag} predict", p, p.predict_psi_cube_missing_dev(Xd, Cd))
+        report(f"{tag} draws gamma 16", p, p.draws_psi_cube_missing_dev(Xd, Cd, 16, seed=11, return_gamma=True))
+
+
 def main():
     for method in ("VD", "VC"):
         for k in (1, 3):
@@ -271,6 +343,11 @@ def main():
         for d in (1, 6, 7, 9, 10):
             run_cube(method, d, 20, 1)
             run_cube(method, d, 91, 3)
+    for method in ("GC", "VC"):
+        for d in (5, 10, 2):
+            for m, k in ((7, 1), (17, 2), (7, 2), (17, 1)):              # both KM instantiations of the pair kernel at both m
+                run_cube_missing(method, d, m, k)
+        run_cube_missing_slabs(method)
 
 
 if __name__ == "__main__":
