@@ -202,14 +202,20 @@ int launch_pred_finish_dev(hipStream_t st, const double *out, int nt, int k, con
 int launch_pred_phi_dev(hipStream_t st, const double *phi, int nt, int m, long ns, long r0, double *PHI);
 int launch_draws_finish_dev(hipStream_t st, const double *dout, int nt, int k, int nd, const double *muY, long ns, long r0, double *F);
 // ---- rows with input noise through the streaming predictor (k_predict_noisy.hip; gpz_predictor_*_noisy*) --------------------------
-// fits: a diagonal kind, an instantiated de <= 20, k <= 8 and ceil16(m) <= 256 (the limit of the fused draws).  Psi: per-dimension
+// fits: a diagonal kind, an instantiated de <= 20, k <= 8 and ceil16(m) <= 256 (the limit of the fused draws; 1024 with large_m).  Psi: per-dimension
 // variances in the layout of Xc ([d][ldx], dimensions >= d zero).  The pair records are predict_noisy_rec(d, k) = 1 + 2 d + 3 k doubles:
 // launch_pair_table (record stride rec) writes [lnZ | c_ab | C_ab], launch_noisy_pair_coef the 3 k coefficients behind them (iS: m x m x k
 // column-major, read at a >= b only).  launch_predict_noisy_small: part [nchunk][5k][ldp] -> out [4k][n] = mu | nu | beta | gamma.
 // predict_noisy_chunks: the pair chunks, a function of the model's shape only - never of the rows - so that a row's results have the
 // same bits for any tile size, position and row order.  The launchers return -1 when a launch failed.
-bool predict_noisy_fits(int kind, int de, int m, int k);
+// large_m (a handle with GPZ_PREDICT_LARGE_M): ceil16(m) <= GPZ_PREDICT_LARGE_M_MAX in place of 256, for this fits and the covariance
+// kinds' below.  launch_predict_noisy_phi: Phi [nrow][mp] row-major <- E_x[PHI] of the n rows, zeros in rows >= n and columns >= m (what
+// launch_tgemm takes); nrow a multiple of 64; nchunk splits the columns over gridDim.y and changes no bit.
+#define GPZ_PREDICT_LARGE_M_MAX 1024
+bool predict_noisy_fits(int kind, int de, int m, int k, bool large_m = false);
 int predict_noisy_chunks(int m, int d, int k);
+int launch_predict_noisy_phi(hipStream_t st, int d, int de, const double *Xc, const double *Psic, long ldx, int n, int nrow, int m, int mp,
+                             const double *P, const double *G2, int nchunk, double *Phi);
 int predict_noisy_rec(int d, int k);
 int launch_noisy_pair_coef(hipStream_t st, int m, int k, int d, const double *w, const double *v, const double *iS, double *tab, int rec);
 int launch_predict_noisy_small(hipStream_t st, int d, int de, const double *Xc, const double *Psic, long ldx, int n, int m, int k,
@@ -230,7 +236,7 @@ int launch_pred_finish_noisy_dev(hipStream_t st, const double *out, int nt, int 
 // the finish kernel behind launch_predict_noisy_small, on its own: part [nchunk][5k][ldp] -> out [4k][n]
 int launch_predict_noisy_finish(hipStream_t st, const double *part, int nchunk, long ldp, int n, int k, const double *bvec, double *out);
 // ---- rows with input noise, covariance kinds (k_predict_noisy_cov.hip; gpz_predictor_*_noisy_cov_dev) -------------------------------
-// fits: GC or VC, 1 <= d <= 10, 1 <= k <= 8 and ceil16(m) <= 256.  Xc, Psic: [d][ldx] as above.  The tables are the model's alone:
+// fits: GC or VC, 1 <= d <= 10, 1 <= k <= 8 and ceil16(m) <= 256 (1024 with large_m).  Xc, Psic: [d][ldx] as above.  The tables are the model's alone:
 // basis records brec [m][predict_noisy_cov_brec(d, k)] = [1/2 ln|Sigma_j| | p_j | Sigma_j packed lower | w_j (k) | v_j (k)], pair records
 // prec [m (m + 1) / 2][predict_noisy_cov_prec(d, k)] = [lnZ | c_ab | C_ab packed lower | 3 k coefficients as gpz_pair_coef writes them].
 // launch_noisy_cov_records repacks them from launch_gen_prep's Sig (m x d x d) and lnS (m) and launch_pair_table's records (raw,
@@ -238,7 +244,7 @@ int launch_predict_noisy_finish(hipStream_t st, const double *part, int nchunk, 
 // out [4k][n] = mu | nu | beta | gamma.  launch_predict_noisy_cov_phi: Phi [nrow][mp] row-major <- E_x[PHI] of the n rows, zeros in rows
 // >= n and columns >= m (what launch_tgemm takes).  shared: GC, one covariance for every basis function.  nchunk =
 // predict_noisy_cov_chunks(m, d, k), the model's shape only.  The launchers return -1 when a launch failed or d is outside 1 .. 10.
-bool predict_noisy_cov_fits(int kind, int d, int m, int k);
+bool predict_noisy_cov_fits(int kind, int d, int m, int k, bool large_m = false);
 int predict_noisy_cov_chunks(int m, int d, int k);
 int predict_noisy_cov_brec(int d, int k);
 int predict_noisy_cov_prec(int d, int k);

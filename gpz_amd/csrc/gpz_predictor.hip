@@ -31,6 +31,9 @@
 // gpz_predictor_draws_noisy / _draws_noisy_dev the draws kernel behind a PHI block built from X and Psi.  The pair table (which depends on
 // the model only), the Psi slots, the 4k-row outputs and the chunk slab are allocated on the first such call (predictor_noisy_prepare).
 // gpz_predictor_run with Psi keeps the one-shot route above.
+// On a handle created with GPZ_PREDICT_LARGE_M the complete rows with Psi (this paragraph, the covariance kinds' and the cube's below;
+// not the groups with missing inputs) stay on the handle up to ceil16(m) <= 1024: the same kernels and chunk counts on a larger pair
+// table, and off the fused draws route the draws of a diagonal kind as E_x[PHI] of the tile (k_predict_noisy_phi) against W on k_tgemm.
 // The covariance kinds (GC, VC) have the same two questions where predict_noisy_cov_fits holds (1 <= d <= 10, k <= 8, m <= 256), for a
 // variance per input dimension: gpz_predictor_run_noisy_cov_dev runs k_predict_noisy_cov_small per tile (k_predict_noisy_cov.hip: a
 // packed Cholesky per row and record in registers) with the same finish, and gpz_predictor_draws_noisy_cov_dev E_x[PHI] of the tile
@@ -118,6 +121,7 @@ static int predictor_setup(gpz_predictor *p, const double *theta, const double *
         HIPCHK(hipEventRecord(p->ev_out[s], p->s_out));
     }
     p->force_tiles = (flags & GPZ_PREDICT_FORCE_TILES) != 0;
+    p->large_m = (flags & GPZ_PREDICT_LARGE_M) != 0;
     p->route = (!p->force_tiles && predict_small_fits(p->de, p->m, p->k)) ? 0 : 1;
     if (tile_rows <= 0) {
         if (p->route == 0) tile_rows = GPZ_PREDICTOR_TILE_FUSED;
@@ -244,7 +248,13 @@ int predictor_want_phi(gpz_predictor *p, bool pinned) {
 
 // ---- input noise on the handle ----------------------------------------------------------------------------------------------------
 static int predictor_noisy_check(const char *who, const gpz_predictor *p) {
-    if (!predict_noisy_fits(p->kind, p->de, p->m, p->k))
+    if (p->large_m && !predict_noisy_fits(p->kind, p->de, p->m, p->k, true))
+        return gpz_fail(GPZ_ERR_UNSUPPORTED,
+                        "%s: input noise on the handle needs predict_noisy_fits: a diagonal kind (GL, VL, GD, VD), d <= 20, k <= 8 and, "
+                        "with GPZ_PREDICT_LARGE_M, ceil16(m) <= %d (method %.2s, d %d, m %d, k %d); gpz_predictor_run takes Psi for every "
+                        "shape",
+                        who, GPZ_PREDICT_LARGE_M_MAX, p->desc.method, p->d, p->m, p->k);
+    if (!p->large_m && !predict_noisy_fits(p->kind, p->de, p->m, p->k))
         return gpz_fail(GPZ_ERR_UNSUPPORTED,
                         "%s: input noise on the handle needs predict_noisy_fits: a diagonal kind (GL, VL, GD, VD), d <= 20, k <= 8 and "
                         "ceil16(m) <= 256 (method %.2s, d %d, m %d, k %d); gpz_predictor_run takes Psi for every shape",
@@ -275,14 +285,26 @@ static int predictor_cube_slots(gpz_predictor *p) {
     return 0;
 }
 
-// The 4k-row output slots and the chunk slab of predictNoisy's moments over nchunks pair chunks, each where it is missing
+// a handle with GPZ_PREDICT_LARGE_M whose model is past the limit without it
+static bool predictor_is_large(const gpz_predictor *p) { return p->large_m && rup(p->m, 16) > 256; }
+
+// the row stride of the chunk slab npart: the handle's padded tile, or that of the shrunk tile ntile of a large model
+static long predictor_npart_ld(const gpz_predictor *p) { return p->ntile ? (long)rup(p->ntile, 1024) : (long)p->tile_pad; }
+
+// The 4k-row output slots and the chunk slab of predictNoisy's moments over nchunks pair chunks, each where it is missing.  On a large
+// model the calls that fill the slab run on tiles of ntile rows: the handle's tile, shrunk in whole granules of 1024 rows so that the
+// slab is at most 1 GiB (rows_tile); everywhere else ntile stays 0 and the slab has the handle's tile, as it always had.
 static int predictor_noisy_slots(gpz_predictor *p, int nchunks) {
     const size_t k = p->k, tp = (size_t)p->tile_pad;
     int rc = 0;
     for (int s = 0; s < 2; ++s)
         if (!p->nout[s] && (rc = p->ar.alloc(&p->nout[s], 4 * k * tp))) return rc;
-    if (!p->npart && (rc = p->ar.alloc(&p->npart, (size_t)nchunks * 5 * k * tp))) return rc;
-    return 0;
+    if (p->npart) return 0;
+    if (predictor_is_large(p)) {
+        const int64_t most = std::max<int64_t>(1024, (int64_t)((1L << 27) / ((long)nchunks * 5 * p->k)) / 1024 * 1024);
+        p->ntile = std::min<int64_t>(p->tile_rows, most);
+    }
+    return p->ar.alloc(&p->npart, (size_t)nchunks * 5 * k * (size_t)predictor_npart_ld(p));
 }
 
 // What the first predictNoisy call adds to the handle beyond that: the pair table [lnZ | c_ab | C_ab | coefficients] (the model's alone:
@@ -310,14 +332,20 @@ static int predictor_noisy_prepare(gpz_predictor *p) {
 // predictNoisy of one tile of nt rows: Xc[s], Psic[s] -> nout[s] ([4k][nt] = mu | nu | beta | gamma)
 static int predictor_noisy_tile(gpz_predictor *p, const char *who, int s, int nt) {
     if (launch_predict_noisy_small(p->s_cmp, p->d, p->de, p->Xc[s], p->Psic[s], p->tile_pad, nt, p->m, p->k, p->pr.P, p->pr.G2, p->w_d,
-                                   p->hetero ? p->pr.v : nullptr, p->pr.b, p->ptab, p->nchunks, p->npart, p->tile_pad, p->nout[s]))
+                                   p->hetero ? p->pr.v : nullptr, p->pr.b, p->ptab, p->nchunks, p->npart, predictor_npart_ld(p), p->nout[s]))
         return gpz_fail(GPZ_ERR_HIP, "%s: k_predict_noisy_small launch failed", who);
     return 0;
 }
 
 // ---- input noise on the handle, covariance kinds --------------------------------------------------------------------------------------
 static int predictor_noisy_cov_check(const char *who, const gpz_predictor *p) {
-    if (!predict_noisy_cov_fits(p->kind, p->d, p->m, p->k))
+    if (p->large_m && !predict_noisy_cov_fits(p->kind, p->d, p->m, p->k, true))
+        return gpz_fail(GPZ_ERR_UNSUPPORTED,
+                        "%s: input noise for a covariance kind on the handle needs predict_noisy_cov_fits: GC or VC, 1 <= d <= 10, "
+                        "1 <= k <= 8 and, with GPZ_PREDICT_LARGE_M, ceil16(m) <= %d (method %.2s, d %d, m %d, k %d); a diagonal kind goes "
+                        "to gpz_predictor_run_noisy_dev / _draws_noisy_dev, and gpz_predictor_run takes Psi for every shape",
+                        who, GPZ_PREDICT_LARGE_M_MAX, p->desc.method, p->d, p->m, p->k);
+    if (!p->large_m && !predict_noisy_cov_fits(p->kind, p->d, p->m, p->k))
         return gpz_fail(GPZ_ERR_UNSUPPORTED,
                         "%s: input noise for a covariance kind on the handle needs predict_noisy_cov_fits: GC or VC, 1 <= d <= 10, "
                         "1 <= k <= 8 and ceil16(m) <= 256 (method %.2s, d %d, m %d, k %d); a diagonal kind goes to "
@@ -416,7 +444,7 @@ static NcovForm ncov_form(const gpz_predictor *p, const Rows &r) {
 static int predictor_noisy_cov_tile(gpz_predictor *p, const char *who, const Rows &r, int s, int nt) {
     const NcovForm f = ncov_form(p, r);
     if (f.small(p->s_cmp, p->d, p->mid == 4, p->Xc[s], f.Psi[s], p->tile_pad, nt, p->m, p->k, p->cbrec, p->cprec, p->pr.b, p->cchunks,
-                p->npart, p->tile_pad, p->nout[s]))
+                p->npart, predictor_npart_ld(p), p->nout[s]))
         return gpz_fail(GPZ_ERR_HIP, "%s: k_predict_%s_small launch failed", who, f.name);
     return 0;
 }
@@ -537,13 +565,22 @@ static int predictor_phi_times_w(gpz_predictor *p, const char *who, const double
 
 // the draws kernels of one tile of nt rows: Xc[s] -> dout[s] ([nd k][nt]).  phi_built: predictor_tile has just run on the same slot and
 // rows on the tile route, so p->Phi already holds this tile's PHI (the same launch_phi with the same arguments; launch_tgemm only reads it)
-// Psic: the tile's Psi slot for rows with input noise (fused route, diagonal kinds), else nullptr
+// Psic: the tile's Psi slot for rows with input noise (diagonal kinds), else nullptr.  Off the fused route such rows need a handle with
+// GPZ_PREDICT_LARGE_M: E_x[PHI] of the tile (k_predict_noisy_phi) into the tile route's PHI, which a handle off the fused draws route
+// always has (predictor_draws_prepare), then the product against W as for every other kind
 static int predictor_draws_tile(gpz_predictor *p, int s, int64_t nt, int ncol, int ldw, bool phi_built = false,
                                 const double *Psic = nullptr) {
     const int m = p->m;
     hipStream_t st = p->s_cmp;
     const double *G = p->kind == GPZ_KIND_COV ? p->pr.Rc : p->pr.G2;
     if (Psic) {
+        if (p->droute != 0 && p->large_m) {
+            const int np = (int)rup(nt, 1024);   // <= tile_pad: zeros in the rows of the last partial block, as launch_tgemm takes them
+            if (launch_predict_noisy_phi(st, p->d, p->de, p->Xc[s], Psic, p->tile_pad, (int)nt, np, m, p->mp, p->pr.P, p->pr.G2,
+                                         predict_noisy_chunks(m, p->d, p->k), p->Phi))
+                return gpz_fail(GPZ_ERR_HIP, "gpz_predictor_draws: k_predict_noisy_phi launch failed");
+            return predictor_phi_times_w(p, "gpz_predictor_draws", p->Phi, np, s, nt, ncol, ldw);
+        }
         if (p->droute != 0) return gpz_fail(GPZ_ERR_UNSUPPORTED, "gpz_predictor_draws: input noise needs the fused draws route");
         if (launch_predict_draws_psi(st, p->de, p->Xc[s], Psic, p->tile_pad, (int)nt, m, p->pr.P, G, p->Wd, ldw, ncol, p->dout[s], nt))
             return gpz_fail(GPZ_ERR_HIP, "gpz_predictor_draws: k_predict_draws_psi launch failed");
@@ -849,7 +886,7 @@ int rows_check(const char *who, const gpz_predictor *p, const Rows &r, bool draw
     if (r.kind == ROWS_CLEAN) return 0;
     if (r.ncov()) return predictor_noisy_cov_check(who, p);   // (its draws are a product on the T-GEMM: any route)
     if (int rc = predictor_noisy_check(who, p)) return rc;
-    if (draws && p->force_tiles)
+    if (draws && p->force_tiles && !p->large_m)   // (with GPZ_PREDICT_LARGE_M: k_predict_noisy_phi + k_tgemm)
         return gpz_fail(GPZ_ERR_UNSUPPORTED, "%s: input noise needs the fused draws route (GPZ_PREDICT_FORCE_TILES is set)", who);
     return 0;
 }
@@ -866,6 +903,7 @@ int rows_prepare(gpz_predictor *p, const char *who, const Rows &r, bool pairs) {
         return 0;
     }
     if (r.group()) return predictor_missing_prepare(p, who, r.obs, r.priors, pairs, r.kind == ROWS_NOISY_MISSING);
+    if ((r.kind == ROWS_NOISY || r.ncov()) && predictor_is_large(p)) p->large_seen = true;
     if (r.kind == ROWS_NOISY) return pairs ? predictor_noisy_prepare(p) : predictor_psi_slots(p);
     if (r.ncov()) {
         if (int rc = predictor_noisy_cov_prepare(p, r, pairs)) return rc;
@@ -874,8 +912,12 @@ int rows_prepare(gpz_predictor *p, const char *who, const Rows &r, bool pairs) {
     return 0;
 }
 
-// the rows per tile of a call that would take T: No, Pio and T of a group hold mtile rows
-int64_t rows_tile(const gpz_predictor *p, const Rows &r, int64_t T) { return r.group() ? std::min<int64_t>(T, p->mtile) : T; }
+// the rows per tile of a call that would take T: No, Pio and T of a group hold mtile rows; complete rows with Psi on a large model take
+// at most the ntile rows of their chunk slab (predictor_noisy_slots; 0 before the first call that reads the pairs)
+int64_t rows_tile(const gpz_predictor *p, const Rows &r, int64_t T) {
+    if (r.group()) return std::min<int64_t>(T, p->mtile);
+    return (r.kind == ROWS_NOISY || r.ncov()) && p->ntile ? std::min<int64_t>(T, p->ntile) : T;
+}
 
 // the moments of one tile of nt rows in slot s -> rows_moments: [3k][nt] = mu | nu | beta for clean rows (and PHI when asked), else
 // [4k][nt] = mu | nu | beta | gamma
@@ -1117,7 +1159,7 @@ extern "C" int gpz_predictor_create(const gpz_desc *desc, const double *theta, c
     *out = nullptr;
     if (!desc || !theta || !w || !iSigma_w) return gpz_fail(GPZ_ERR_ARG, "gpz_predictor_create: null argument");
     if (desc->dtype != GPZ_F64) return gpz_fail(GPZ_ERR_ARG, "gpz_predictor_create: fp64 only");
-    if (flags & ~GPZ_PREDICT_FORCE_TILES) return gpz_fail(GPZ_ERR_ARG, "gpz_predictor_create: unknown flags %d", (int)flags);
+    if (flags & ~(GPZ_PREDICT_FORCE_TILES | GPZ_PREDICT_LARGE_M)) return gpz_fail(GPZ_ERR_ARG, "gpz_predictor_create: unknown flags %d", (int)flags);
     gpz_predictor *p = new gpz_predictor();
     p->desc = *desc;
     p->desc.world = 1;
@@ -1203,6 +1245,10 @@ extern "C" int gpz_predictor_route(const gpz_predictor *p, char *buf, int cap) {
     }
     gamma_line(6);
     gamma_line(0);
+    if (p->large_seen) {   // a handle with GPZ_PREDICT_LARGE_M past ceil16(m) = 256, after its first call with Psi
+        snprintf(tmp, sizeof tmp, "; noisy large-m: tiles, %d chunks", predict_noisy_chunks(p->m, p->d, p->k));
+        r += tmp;
+    }
     if (p->miss_used) {   // after the first call for a group of rows with missing inputs
         snprintf(tmp, sizeof tmp, "; missing: k_predict_missing_pairs (%d pair chunks), %lld-row tiles", p->mchunks, (long long)p->mtile);
         r += tmp;

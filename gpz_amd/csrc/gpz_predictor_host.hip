@@ -192,7 +192,8 @@ static int predictor_run_draws(gpz_predictor *p, const double *Xs, int64_t ns, i
     int64_t T = 0;
     if (Psi && ((rc = predictor_psi_slots(p)) || (rc = predictor_psi_pinned(p)))) return rc;
     if ((rc = rows_draws_prepare(p, Rows{}, nd, seed, Z, true, &T))) return rc;
-    if (Psi && p->droute != 0) return gpz_fail(GPZ_ERR_UNSUPPORTED, "gpz_predictor_draws_noisy: input noise needs the fused draws route");
+    if (Psi && p->large_m && rup(p->m, 16) > 256) p->large_seen = true;
+    if (Psi && p->droute != 0 && !p->large_m) return gpz_fail(GPZ_ERR_UNSUPPORTED, "gpz_predictor_draws_noisy: input noise needs the fused draws route");
     DrawsJob job{p, ns, nd, nd * p->k, rup(nd * p->k, 16), Psi, F};
     return predictor_drain(p, job.who, predictor_pipeline(p, Xs, ns, T, job));   // on tiles of T rows
 }

@@ -20,7 +20,21 @@
 //                                   mu | nu | beta | gamma with VlnS -= (ElnS - b)^2, gamma -= mu^2, beta = exp(ElnS) (1 + VlnS / 2).
 // The chunk count C = predict_noisy_chunks(m, d, k) depends on the model's shape only, and every sum runs in a fixed order from zero: no
 // atomics, and a row's results have the same bits for any tile size, position in the tile and row order.
+// The chunk rule: C = clamp(floor(npair / 2048), 1, 4) with npair = m (m + 1) / 2, for every m - with GPZ_PREDICT_LARGE_M
+// (256 < ceil16(m) <= 1024) the cap of 4 stays, so C = 4 from m = 128 on.  No measurement decided that: a 16 384-row call is 64 workgroups
+// per chunk, 256 in all on 256 compute units, and a higher cap was not timed.  predict_noisy_cov_chunks and predict_gamma_chunks keep
+// their caps of 4 in the same way.  Index ranges at m = 1024: npair = 524 800 and npair * rec <= 524 800 * 65 fit 32 bits; the table is
+// addressed in size_t.
 //
+//   k_predict_noisy_phi<DT>         E_x[PHI] of a tile as launch_tgemm takes it, Phi [nrow][mp] row-major with zeros in the rows >= n and the
+//                                   columns >= m: the draws of a handle with GPZ_PREDICT_LARGE_M off the fused route (PHI W on k_tgemm, as
+//                                   the covariance kinds' predict_ncov_phi_body).  The arithmetic of the mu phase above.  A workgroup owns
+//                                   64 rows: every wave has lane = row (x and psi in registers) and forms 8 of the 32 basis functions of a
+//                                   stage, whose records [P_j | G2_j] lie in LDS and are read as broadcasts.  The 64 x 32 values pass
+//                                   through an LDS tile with a row stride of 33 doubles (ds_write_b64 of 16 lanes: 32 banks, no conflict;
+//                                   the read is along a row) and leave as 256-byte runs of a PHI row, two rows per wave store; gridDim.y
+//                                   splits the columns in multiples of 32, so every run starts on a 256-byte boundary.  No sum: an
+//                                   element's bits depend on its row and column alone.
 //   k_predict_draws_psi<D>          k_predict_draws' body (k_predict_draws_impl.h) with PsPhiBuilder<D, false, true>: 11 widths.
 //   k_pred_check_psi                word 3 of the device entries' record is set when an element of Psi is NaN, negative, or infinite
 //                                   (itself or once divided by the smallest sd2).
@@ -193,8 +207,9 @@ __global__ __launch_bounds__(256) void k_noisy_pair_coef(int m, int k, int d, co
     gpz_pair_coef(tab + (size_t)e * rec + 1 + 2 * d, a, b, m, k, w, v, iS);
 }
 
-bool predict_noisy_fits(int kind, int de, int m, int k) {
-    return kind == GPZ_KIND_DIAG && de <= 20 && ps_width_instantiated(de) && k <= 8 && ((m + 15) / 16) * 16 <= 256;
+bool predict_noisy_fits(int kind, int de, int m, int k, bool large_m) {
+    return kind == GPZ_KIND_DIAG && de <= 20 && ps_width_instantiated(de) && k <= 8 &&
+           ((m + 15) / 16) * 16 <= (large_m ? GPZ_PREDICT_LARGE_M_MAX : 256);
 }
 
 // pair chunks (= chunks of the basis functions): one per 2048 pairs, at most 4.  The model's shape only, never the rows.
@@ -247,6 +262,98 @@ int launch_predict_noisy_finish(hipStream_t st, const double *part, int nchunk, 
     if (n <= 0) return 0;
     hipLaunchKernelGGL(k_predict_noisy_finish, dim3((unsigned)((n + 255) / 256), (unsigned)k), dim3(256), 0, st, part, nchunk, ldp, n, k,
                        bvec, out);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+// ---- E_x[PHI] of a tile for the T-GEMM (the draws with Psi off the fused route) -----------------------------------------------------
+struct PredNoisyPhiArgs {
+    const double *Xc, *Psic; long ldx;   // [d][ldx] column layout, n rows
+    int n, nrow, m, mp, de;              // nrow rows of mp doubles are written (nrow a multiple of 64); de: row stride of P and G2
+    const double *P, *G2;
+    int jpc;                             // columns per chunk, a multiple of PNP_TJ
+    double *Phi;
+};
+
+#define PNP_TJ 32            // basis functions per stage
+#define PNP_LD (PNP_TJ + 1)  // row stride of the tile in LDS
+
+template <int DT>
+__global__ __launch_bounds__(256) void k_predict_noisy_phi(PredNoisyPhiArgs a) {
+    __shared__ double sR[PNP_TJ * 2 * DT];   // one stage of basis records [P_j | G2_j]
+    __shared__ double sP[64 * PNP_LD];       // the stage's values, [row][basis function]
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const long r0 = (long)blockIdx.x * 64, i = r0 + lane;
+    const bool act = i < a.n;
+    const long ic = act ? i : a.n - 1;
+    const int m = a.m;
+    const int j0 = blockIdx.y * a.jpc, jend = min(a.mp, j0 + a.jpc);   // this chunk's columns; those >= m are zeros
+    if (j0 >= jend) return;
+    double x[DT], ps[DT];
+#pragma unroll
+    for (int c = 0; c < DT; ++c) {
+        x[c] = a.Xc[(size_t)c * a.ldx + ic];
+        ps[c] = a.Psic[(size_t)c * a.ldx + ic];
+    }
+    constexpr int rj = 2 * DT;
+    for (int jb = j0; jb < jend; jb += PNP_TJ) {
+        const int nj = min(PNP_TJ, jend - jb), njr = max(0, min(PNP_TJ, m - jb));   // columns to write, and those with a basis function
+        // (sR was last read, and sP last written, before the second barrier of the stage before; sP is read behind it, and every
+        // thread is through with that before it passes the first barrier here)
+        for (int t = tid; t < njr * rj; t += 256) {
+            const int jj = t / rj, f = t - jj * rj;
+            sR[t] = f < DT ? a.P[(size_t)(jb + jj) * a.de + f] : a.G2[(size_t)(jb + jj) * a.de + f - DT];
+        }
+        __syncthreads();
+#pragma unroll 2
+        for (int q = 0; q < PNP_TJ / 4; ++q) {
+            const int jj = wv * (PNP_TJ / 4) + q;
+            double ph = 0.0;
+            if (jj < njr) {                       // the same in every lane of the wave
+                const double *t = sR + jj * rj;   // the same address in every lane: a broadcast read
+                double qq = 0.0, pr = 1.0;
+#pragma unroll
+                for (int c = 0; c < DT; ++c) {
+                    const double dl = x[c] - t[c], gc = t[DT + c];
+                    const double u = fma(ps[c], gc, 1.0);                  // 1 + psi / sigma
+                    qq = fma(dl * dl, gc * gpz_rcp1(u), qq);               // getPHI.m:104  Delta.^2 ./ (Psi + Sigma)
+                    pr *= u;
+                }
+                qq += log(pr);
+                ph = act ? exp(-0.5 * qq) : 0.0;
+            }
+            sP[lane * PNP_LD + jj] = ph;
+        }
+        __syncthreads();
+        // 8 rows per pass: 32 consecutive lanes write 256 consecutive bytes of one row of PHI
+        const int c = tid & 31;
+#pragma unroll
+        for (int ps8 = 0; ps8 < 8; ++ps8) {
+            const int row = ps8 * 8 + (tid >> 5);
+            if (c < nj && r0 + row < a.nrow) a.Phi[(size_t)(r0 + row) * a.mp + jb + c] = sP[row * PNP_LD + c];
+        }
+    }
+}
+
+template <int DT>
+static void launch_pnphi(hipStream_t st, const PredNoisyPhiArgs &a, dim3 grid) {
+    hipLaunchKernelGGL((k_predict_noisy_phi<DT>), grid, dim3(256), 0, st, a);
+}
+
+int launch_predict_noisy_phi(hipStream_t st, int d, int de, const double *Xc, const double *Psic, long ldx, int n, int nrow, int m, int mp,
+                             const double *P, const double *G2, int nchunk, double *Phi) {
+    if (n <= 0) return 0;
+    if (d < 1 || d > 20 || m < 1 || mp < m || nrow < n || nrow % 64 || ldx < n || nchunk < 1) return -1;
+    PredNoisyPhiArgs a{};
+    a.Xc = Xc; a.Psic = Psic; a.ldx = ldx; a.n = n; a.nrow = nrow; a.m = m; a.mp = mp; a.de = de; a.P = P; a.G2 = G2; a.Phi = Phi;
+    a.jpc = ((mp + nchunk - 1) / nchunk + PNP_TJ - 1) / PNP_TJ * PNP_TJ;
+    const dim3 grid((unsigned)(nrow / 64), (unsigned)((mp + a.jpc - 1) / a.jpc));
+    switch (d) {
+#define PNP_CASE(DD) case DD: launch_pnphi<DD>(st, a, grid); break;
+        PNP_CASE(1) PNP_CASE(2) PNP_CASE(3) PNP_CASE(4) PNP_CASE(5) PNP_CASE(6) PNP_CASE(7) PNP_CASE(8) PNP_CASE(9) PNP_CASE(10)
+        PNP_CASE(11) PNP_CASE(12) PNP_CASE(13) PNP_CASE(14) PNP_CASE(15) PNP_CASE(16) PNP_CASE(17) PNP_CASE(18) PNP_CASE(19) PNP_CASE(20)
+#undef PNP_CASE
+        default: return -1;
+    }
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

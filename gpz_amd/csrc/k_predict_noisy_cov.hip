@@ -54,11 +54,14 @@ __global__ __launch_bounds__(256) void k_noisy_cov_records(int m, int d, int de,
     }
 }
 
-bool predict_noisy_cov_fits(int kind, int d, int m, int k) {
-    return kind == GPZ_KIND_COV && d >= 1 && d <= 10 && k >= 1 && k <= 8 && m >= 1 && ((m + 15) / 16) * 16 <= 256;
+bool predict_noisy_cov_fits(int kind, int d, int m, int k, bool large_m) {
+    return kind == GPZ_KIND_COV && d >= 1 && d <= 10 && k >= 1 && k <= 8 && m >= 1 &&
+           ((m + 15) / 16) * 16 <= (large_m ? GPZ_PREDICT_LARGE_M_MAX : 256);
 }
 
-// pair chunks (= chunks of the basis functions): one per 2048 pairs, at most 4.  The model's shape only, never the rows.
+// pair chunks (= chunks of the basis functions): one per 2048 pairs, at most 4.  The model's shape only, never the rows.  The cap stays
+// at 4 for 256 < ceil16(m) <= 1024 (GPZ_PREDICT_LARGE_M; no measurement decided that: see k_predict_noisy.hip).  At m = 1024 the
+// 524 800 pairs and their record offsets (at most 524 800 * 90 doubles) fit 32 bits; the tables are addressed in size_t.
 int predict_noisy_cov_chunks(int m, int d, int k) {
     (void)d; (void)k;
     const long c = ((long)m * (m + 1) / 2) / 2048;

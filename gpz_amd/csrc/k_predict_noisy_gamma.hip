@@ -64,6 +64,8 @@ __global__ __launch_bounds__(256) void k_gamma_finish_s2(const double *__restric
 }
 
 // pair chunks: one per 4096 pairs, at most 4 (it changes at m = 91, 128, 157).  The model's shape only, never the rows or the draws.
+// The cap stays at 4 for 256 < ceil16(m) <= 1024 (GPZ_PREDICT_LARGE_M; no measurement decided that).  predict_gamma_body's p0, p1, npair
+// and (pa, pb) are ints: npair = 524 800 at m = 1024, and pa (pa + 1) / 2 stays below it.
 int predict_gamma_chunks(int m) {
     const long c = ((long)m * (m + 1) / 2 + 4095) / 4096;
     return (int)(c < 1 ? 1 : (c > 4 ? 4 : c));

@@ -25,6 +25,8 @@ from . import _lib
 from .api import _desc, _f64, nan_row_groups
 
 GPZ_PREDICT_FORCE_TILES = 1   # gpz_predictor_create flags (include/gpz_hip.h)
+GPZ_PREDICT_LARGE_M = 2       # complete rows with Psi stay on the handle up to GPZ_PREDICT_LARGE_M_MAX basis functions
+GPZ_PREDICT_LARGE_M_MAX = 1024
 GPZ_DRAWS_MAX_COLUMNS = 16384   # n_draws * k per gpz_predictor_draws call (include/gpz_hip.h)
 GPZ_STACK_MAX_GROUP_BINS = 4096   # n_groups * n_bins per gpz_predictor_stack call (include/gpz_hip.h)
 
@@ -76,9 +78,17 @@ class Predictor:
     handle's own tiles from ``predict_dev`` / ``draws`` / ``draws_dev`` with ``Psi=`` for a diagonal kind, d <= 20, k <= 8, m <= 256); rows with
     missing values are grouped by NaN pattern and go to gpz_predict_missing as in ``predict``.  Shapes are checked before the GPU is
     touched; the handle itself is created on first use.  ``route`` / ``info`` (tile rows, device bytes held, route 0 fused / 1 tiles,
-    runs) describe it."""
+    runs) describe it.
 
-    def __init__(self, model, whichSet="best", device=0, tile_rows=None, force_tiles=False):
+    ``large_m=True`` (GPZ_PREDICT_LARGE_M) keeps complete rows with Psi on the handle up to m = 1024 where the limit is otherwise
+    m = 256: the methods of a diagonal kind with ``Psi=`` (``predict_dev``, ``draws``, ``draws_dev``, ``stack_noisy``,
+    ``stack_noisy_dev``), ``*_noisy_cov_dev`` and ``*_psi_cube_dev``.  The methods for rows with missing values keep m <= 256.  It
+    costs nothing before the first call with Psi and changes nothing for m <= 256; beyond, the first call builds a table of
+    m (m + 1) / 2 pair records (0.1 to 0.4 GB at m = 1024, and for GC / VC a temporary of (1 + d + d * d) doubles per pair while it
+    is built) and every row costs m (m + 1) / 2 pair densities, 524 800 at m = 1024.  With ``force_tiles=True`` as well, the draws of
+    a diagonal kind with Psi run as E_x[PHI] of a tile (k_predict_noisy_phi) against the weights on the T-GEMM at any m."""
+
+    def __init__(self, model, whichSet="best", device=0, tile_rows=None, force_tiles=False, large_m=False):
         if whichSet not in getattr(model, "sets", {}):
             raise ValueError(f"whichSet {whichSet!r} is not one of the model's sets {sorted(getattr(model, 'sets', {}))}")
         m, d, k = int(model.m), int(model.d), int(model.k)
@@ -105,7 +115,7 @@ class Predictor:
         self.model, self.whichSet, self.device = model, whichSet, int(device)
         self._m, self._d, self._k, self._method = m, d, k, method
         self._tile_rows = 0 if tile_rows is None else int(tile_rows)
-        self._flags = GPZ_PREDICT_FORCE_TILES if force_tiles else 0
+        self._flags = (GPZ_PREDICT_FORCE_TILES if force_tiles else 0) | (GPZ_PREDICT_LARGE_M if large_m else 0)
         self._h = None
         self._closed = False
         self._lib = None
@@ -275,7 +285,7 @@ class Predictor:
         error from the finite training set, cross-row covariance included; y-draws add sqrt(beta_i) times independent normals per row.
         With ``Psi`` (a host array as ``predict`` takes it; gpz_predictor_draws_noisy) draws[s] is ``predict(X, Psi=Psi)``'s mu under draw
         s, E_x[PHI] w_s + muY: the mean is linear in the weights, so this is exact.  Psi needs a model inside predict_noisy_fits (a
-        diagonal kind, d <= 20, k <= 8, m <= 256), else ValueError.
+        diagonal kind, d <= 20, k <= 8, m <= 256, or 1024 on a predictor made with large_m=True), else ValueError.
 
         ``seed`` (an integer in [0, 2^64)) selects the standard normals, generated on the device from Philox4x32-10: draw s of a seed
         is the same on every call and for every n_draws > s.  ``Z`` (m x n_draws x k, or m x n_draws when k = 1) gives them instead;
@@ -326,7 +336,7 @@ class Predictor:
         ``predict_dev(X, Psi=Psi)``'s mu and sigma = (nu + beta_i) + gamma.  Column 1 + s uses ``draws(X, ..., Psi=Psi)``'s draw s and
         the width beta_i + max(gamma_s, 0), where gamma_s is predictNoisy's gamma under the weights of draw s, the variance of
         PHI(x) w_s over the input noise (``draws_dev(..., Psi=Psi, return_gamma=True)`` returns it).  Needs a model inside
-        predict_noisy_fits (a diagonal kind, d <= 20, k <= 8, m <= 256) on the fused route, else ValueError.  ``selection`` applies to
+        predict_noisy_fits (a diagonal kind, d <= 20, k <= 8, m <= 256, or 1024 with large_m=True) on the fused route (any route with large_m=True), else ValueError.  ``selection`` applies to
         rows, Psi, labels and weights alike.  Returns a StackResult with the bits of ``stack_noisy_dev`` on the same handle and rows."""
         if Psi is None:
             raise ValueError("stack_noisy needs Psi: noise-free rows go to Predictor.stack")
@@ -416,12 +426,32 @@ class Predictor:
 
     def _check_noisy_model(self, what, draws=False):
         """predict_noisy_fits (k_predict_noisy.hip) for this model, before the GPU is touched."""
+        large = bool(self._flags & GPZ_PREDICT_LARGE_M)
+        if large and (self._method[1] == "C" or self._d > 20 or self._k > 8 or self._m > GPZ_PREDICT_LARGE_M_MAX):
+            raise ValueError(f"{what} with Psi needs a model inside predict_noisy_fits: a diagonal kind (GL, VL, GD, VD), d <= 20, "
+                             f"k <= 8 and, with large_m=True, m <= {GPZ_PREDICT_LARGE_M_MAX}; this one is {self._method} with "
+                             f"d = {self._d}, m = {self._m}, k = {self._k} (Predictor.predict takes Psi for every shape)")
+        if large:
+            return                                                       # (its draws with Psi run off the fused route too)
         if self._method[1] == "C" or self._d > 20 or self._k > 8 or self._m > 256:
             raise ValueError(f"{what} with Psi needs a model inside predict_noisy_fits: a diagonal kind (GL, VL, GD, VD), d <= 20, "
                              f"k <= 8 and m <= 256; this one is {self._method} with d = {self._d}, m = {self._m}, k = {self._k} "
                              "(Predictor.predict takes Psi for every shape)")
         if draws and self._flags & GPZ_PREDICT_FORCE_TILES:
             raise ValueError(f"{what} with Psi needs the fused draws route: the predictor was made with force_tiles=True")
+
+    def _check_noisy_cov_shape(self, name):
+        """predict_noisy_cov_fits (k_predict_noisy_cov.hip) for this model: m <= 256, or m <= 1024 on a predictor with large_m=True."""
+        inside = 1 <= self._d <= 10 and 1 <= self._k <= 8
+        if self._flags & GPZ_PREDICT_LARGE_M:
+            if not (inside and 1 <= self._m <= GPZ_PREDICT_LARGE_M_MAX):
+                raise ValueError(f"{name} needs a model inside predict_noisy_cov_fits: GC or VC, d <= 10, k <= 8 and, with large_m=True, "
+                                 f"m <= {GPZ_PREDICT_LARGE_M_MAX}; this one is {self._method} with d = {self._d}, m = {self._m}, "
+                                 f"k = {self._k} (Predictor.predict takes Psi for every shape)")
+        elif not (inside and 1 <= self._m <= 256):
+            raise ValueError(f"{name} needs a model inside predict_noisy_cov_fits: GC or VC, d <= 10, k <= 8 and m <= 256; this one is "
+                             f"{self._method} with d = {self._d}, m = {self._m}, k = {self._k} (Predictor.predict takes Psi for every "
+                             "shape)")
 
     def _check_missing_model(self, what, Psi, how=" with missing=True"):
         """predict_missing_fits (k_predict_missing.hip) for this model and call, before the GPU is touched."""
@@ -629,7 +659,7 @@ class Predictor:
         shape (n, d), (n, 1) or (n,), with any strides (read as it lies; one variance per row is broadcast, not copied).  The five
         tensors are then ``predict(X, Psi=Psi)``'s, gamma no longer zero, computed on the handle's tiles by k_predict_noisy_small; a
         row's results do not depend on the tile size or the row order.  It needs a model inside predict_noisy_fits (a diagonal kind,
-        d <= 20, k <= 8, m <= 256) and does not return PHI; an element of Psi that is NaN, infinite or negative is refused (GpzError).
+        d <= 20, k <= 8, m <= 256, or 1024 with large_m=True) and does not return PHI; an element of Psi that is NaN, infinite or negative is refused (GpzError).
         ``missing=True`` (gpz_predictor_run_missing_dev): rows with NaN are taken instead of refused.  The rows are grouped by NaN
         pattern with torch on the device; complete rows get exactly what they get without the keyword, every other group
         predictMissing (predictDiag.m:127-209) on the handle's tiles with the priors of the set (1 / m without any), gamma > 0 there.
@@ -795,10 +825,7 @@ class Predictor:
                              "Predictor.predict(X, Psi=Psi)")
         if self._method[1] != "C":
             raise ValueError(f"{name} is for the covariance kinds (GC, VC): a diagonal kind such as {self._method} goes to {diag}")
-        if not (1 <= self._d <= 10 and 1 <= self._k <= 8 and 1 <= self._m <= 256):
-            raise ValueError(f"{name} needs a model inside predict_noisy_cov_fits: GC or VC, d <= 10, k <= 8 and m <= 256; this one is "
-                             f"{self._method} with d = {self._d}, m = {self._m}, k = {self._k} (Predictor.predict takes Psi for every "
-                             "shape)")
+        self._check_noisy_cov_shape(name)
         if what == "stack" and isinstance(Psi, np.ndarray):               # (no host stack takes Psi of a covariance kind)
             raise TypeError(f"{name} takes Psi as a torch tensor on cuda:{self.device}; host arrays of a covariance kind stay on "
                             "Predictor.predict(X, Psi=Psi)")
@@ -810,7 +837,7 @@ class Predictor:
         sigma, nu, beta_i, gamma as ``predict(X, Psi=Psi)`` does, as float64 tensors of shape (n, k) on the device: predictNoisy of
         predictCov.m on the handle's tiles by k_predict_noisy_cov_small, with the variances on the diagonal of each row's Psi as fixPsi
         puts them there.  A row's results do not depend on the tile size, the row order or the other rows of the call.  It needs a
-        model inside predict_noisy_cov_fits (GC or VC, d <= 10, k <= 8, m <= 256), else ValueError; a full d x d x n Psi, PHI, host
+        model inside predict_noisy_cov_fits (GC or VC, d <= 10, k <= 8, m <= 256, or 1024 with large_m=True), else ValueError; a full d x d x n Psi, PHI, host
         arrays and rows with missing values are not on this route (``Predictor.predict`` takes them); the stack of such rows is
         ``stack_noisy_cov_dev``'s and gamma per draw ``draws_noisy_cov_dev(..., return_gamma=True)``'s.  Rows
         with NaN and an element of Psi that is NaN, infinite or negative are refused (GpzError).  Type, dtype and shape are checked
@@ -853,9 +880,7 @@ class Predictor:
         if self._method[1] != "C":
             raise ValueError(f"{name} is for the covariance kinds (GC, VC): fixPsi gives a diagonal kind such as {self._method} only "
                              f"the cube's diagonal, which goes to {diag}")
-        if not (1 <= d <= 10 and 1 <= self._k <= 8 and 1 <= self._m <= 256):
-            raise ValueError(f"{name} needs a model inside predict_noisy_cov_fits: GC or VC, d <= 10, k <= 8 and m <= 256; this one is "
-                             f"{self._method} with d = {d}, m = {self._m}, k = {self._k} (Predictor.predict takes Psi for every shape)")
+        self._check_noisy_cov_shape(name)
         if isinstance(Psi, np.ndarray):
             raise TypeError(f"{name} takes Psi as a torch tensor on cuda:{self.device}; host arrays stay on "
                             "Predictor.predict(X, Psi=Psi)")
@@ -880,7 +905,7 @@ class Predictor:
         lower triangle that is NaN or infinite (itself or after its division), a negative diagonal element and rows with NaN in X are
         refused (GpzError), outputs untouched.  A matrix that passes this scan but is not positive semidefinite is the caller's error:
         that row's results are unspecified, and no other row is affected.  It needs a model inside predict_noisy_cov_fits (GC or VC,
-        d <= 10, k <= 8, m <= 256), else ValueError; a diagonal kind takes the cube's diagonal through ``predict_dev(X, Psi=)``; rows
+        d <= 10, k <= 8, m <= 256, or 1024 with large_m=True), else ValueError; a diagonal kind takes the cube's diagonal through ``predict_dev(X, Psi=)``; rows
         with NaN together with a cube, PHI and host arrays stay on ``Predictor.predict``.  Type, dtype and shape are checked first,
         the device last, all before the GPU is touched."""
         self._check_open()
@@ -1170,7 +1195,7 @@ class Predictor:
         ``predict_noisy_cov_dev``'s mu and that call's sigma = (nu + beta_i) + gamma, bit for bit; column 1 + s
         ``draws_noisy_cov_dev``'s draw s and the width beta_i + max(gamma_s, 0), where gamma_s is that method's ``return_gamma=True``.
         The fields are plain sums over the rows, so calls over parts of a catalogue add.  It needs a model inside
-        predict_noisy_cov_fits (GC or VC, d <= 10, k <= 8, m <= 256), else ValueError, and takes any route of the handle; a diagonal
+        predict_noisy_cov_fits (GC or VC, d <= 10, k <= 8, m <= 256, or 1024 with large_m=True), else ValueError, and takes any route of the handle; a diagonal
         kind goes to ``stack_noisy_dev``.  Rows with NaN, a bad element of Psi, a label outside [-1, n_groups) and a negative or
         non-finite weight are found on the device before the first tile and refused with a GpzError."""
         return self._stack_dev(X, Psi, edges, n_draws, seed, Z, groups, n_groups, weights, selection, cov=True)
@@ -1218,7 +1243,7 @@ class Predictor:
         column 1 + s ``draws_noisy_missing_dev``'s draw s and the width beta_i + max(gamma_s, 0), where gamma_s is
         predictNoisyMissing's gamma under the weights of draw s (``draws_noisy_missing_dev(..., return_gamma=True)`` returns it).
         ``n_groups`` and the range of the labels are decided over all rows.  It needs a model inside predict_missing_fits (a diagonal
-        kind, d <= 20, k <= 8, m <= 256), else ValueError, and a predictor that was not made with force_tiles=True; host arrays are
+        kind, d <= 20, k <= 8, m <= 256, or 1024 with large_m=True), else ValueError, and a predictor that was not made with force_tiles=True (unless with large_m=True); host arrays are
         not on the handle, and the covariance kinds go to ``stack_noisy_missing_cov_dev``."""
         return self._stack_dev(X, Psi, edges, n_draws, seed, Z, groups, n_groups, weights, selection, missing=True, both=True)
 

@@ -224,6 +224,13 @@ int gpz_predict_last_route(char *buf, int64_t cap);
  * gpz_predictor_route: as gpz_ctx_route (returns the description's full length).  gpz_predictor_info: [tile_rows, device bytes held, route (0 fused, 1 tiles), runs]. */
 typedef struct gpz_predictor gpz_predictor;
 #define GPZ_PREDICT_FORCE_TILES 1   /* flags: take the tile route even where the fused kernel fits (A/B and tests) */
+/* flags: complete rows with input noise stay on the handle up to ceil16(m) <= 1024 (without it: 256).  predict_noisy_fits and
+ * predict_noisy_cov_fits widen in m only; the entries for rows with missing inputs keep ceil16(m) <= 256.  Nothing is allocated before
+ * the first call with Psi, and where ceil16(m) <= 256 the flag changes no kernel, chunk count, byte or bit (except that the draws of a
+ * diagonal kind with Psi then also run off the fused route: k_predict_noisy_phi + k_tgemm).  The cost at m = 1024: a pair table of
+ * m (m + 1) / 2 = 524 800 records (0.1 to 0.4 GB, and for GC / VC a temporary of 524 800 (1 + d + d d) doubles while it is built) and
+ * 524 800 pair densities per row. */
+#define GPZ_PREDICT_LARGE_M 2
 int gpz_predictor_create(const gpz_desc *desc, const double *theta, const double *w, const double *iSigma_w,
                          int64_t tile_rows, int32_t flags, gpz_predictor **out);
 void gpz_predictor_destroy(gpz_predictor *p);
@@ -316,7 +323,7 @@ int gpz_predictor_stack_dev(gpz_predictor *p, const void *X_d, int32_t x_type, i
 
 /* ---- rows with input noise on the predictor handle --------------------------------------------------------------------------------
  * predictNoisy (predictDiag.m:75-125) and the draws for rows with a variance per input dimension, on the handle's own tiles, where
- * predict_noisy_fits holds: a diagonal kind (GL, VL, GD, VD), d <= 20, k <= 8 and ceil16(m) <= 256.  Any other shape returns
+ * predict_noisy_fits holds: a diagonal kind (GL, VL, GD, VD), d <= 20, k <= 8 and ceil16(m) <= 256 (1024 on a handle with GPZ_PREDICT_LARGE_M).  Any other shape returns
  * GPZ_ERR_UNSUPPORTED and names the condition; gpz_predictor_run takes Psi for every shape on its one-shot route.  Complete rows only.
  * The device entries take what gpz_predictor_run_dev / _draws_dev take, plus Psi_d: element (i, c) of the ns x d variances at
  * Psi_d[i * psi_row_stride + c * psi_col_stride], psi_type GPZ_X_F64 or GPZ_X_F32, a column stride of 0 for one variance per row; and
@@ -343,7 +350,7 @@ int gpz_predictor_draws_noisy(gpz_predictor *p, const double *Xs, int64_t ns, co
                               int32_t ndraws, uint64_t seed, const double *Z /* NULL or m x ndraws x k */,
                               double *F /* ns x k x ndraws, column-major */);
 /* The same two questions for the covariance kinds (predictCov.m:70-132), where predict_noisy_cov_fits holds: GC or VC, 1 <= d <= 10,
- * 1 <= k <= 8 and ceil16(m) <= 256.  Any other shape returns GPZ_ERR_UNSUPPORTED and names the condition.  The arguments are exactly
+ * 1 <= k <= 8 and ceil16(m) <= 256 (1024 on a handle with GPZ_PREDICT_LARGE_M).  Any other shape returns GPZ_ERR_UNSUPPORTED and names the condition.  The arguments are exactly
  * those of gpz_predictor_run_noisy_dev / _draws_noisy_dev: Psi is a variance per input dimension (or one per row), the diagonal that
  * fixPsi puts into the d x d x n cube of these kinds, entering the kernels as double(psi) / sd2[c]; a full Psi cube stays on
  * gpz_predictor_run.  Complete rows only; NaN rows and bad elements of Psi are refused as above, before the first tile, outputs
