@@ -672,4 +672,4 @@ def getPrior(X, Psi, theta, model, selection=None, device=0, return_iterations=F
 
 # the streaming predictor stays reachable from here; last, because predictor.py takes _desc, _f64 and nan_row_groups from this module
 from .predictor import GPZ_DRAWS_MAX_COLUMNS, GPZ_PREDICT_FORCE_TILES, GPZ_STACK_MAX_GROUP_BINS, Predictor, StackResult  # noqa: E402,F401
-from .predictor import GPZ_PREDICT_LARGE_M, GPZ_PREDICT_LARGE_M_MAX  # noqa: E402,F401
+from .predictor import GPZ_PREDICT_LARGE_M, GPZ_PREDICT_LARGE_M_MAX, GPZ_PREDICT_LARGE_M_MISSING  # noqa: E402,F401

@@ -345,6 +345,22 @@ size_t predict_missing_gamma_lds(int m, int d, bool psi);   // dynamic LDS of th
 int launch_predict_missing_gamma(hipStream_t st, const double *Xc, const double *Psic, long ldx, int n, const double *Pio, int ldpio, int m,
                                  int d, int k, unsigned obs, const double *U, const double *rec, const double *W, int ldw, int ncol,
                                  int nchunk, double *part, long ldp);
+// ---- the same two products past ceil16(m) = 256, for a handle with GPZ_PREDICT_LARGE_M_MISSING (k_pml_pairs.hip, k_pml_gamma.hip, the
+// body in k_predict_group_large_impl.h): Pio passes through LDS in K panels of GPZ_PML_KP columns and a workgroup keeps the accumulators
+// of GPZ_PML_GB groups of 64 pairs, so LDS does not grow with m.  fits: predict_missing_fits with ceil16(m) <= GPZ_PREDICT_LARGE_M_MAX.
+// The tables, the chunk count (predict_missing_chunks), the slabs and the finish are launch_predict_missing_pairs' / _gamma's, and so
+// are the arguments.  gamma: the LDS of the gamma kernels (the short record and the group's (a, b)).
+#define GPZ_PML_KP 128   // columns of Pio per K panel
+#define GPZ_PML_GB 4     // groups of 64 pairs per batch
+#define GPZ_PML_GB8 2    // the same with 8 outputs in registers (k > 1, the pairs sink)
+bool predict_missing_large_fits(int kind, int de, int m, int k);
+size_t predict_missing_large_lds(int m, int d, int k, bool psi, bool gamma = false);   // dynamic LDS, bytes; the same for every m
+int launch_predict_missing_large_pairs(hipStream_t st, const double *Xc, const double *Psic, long ldx, int n, const double *Pio, int ldpio,
+                                       int m, int d, int k, unsigned obs, const double *U, const double *rec, int nchunk, double *part,
+                                       long ldp, const double *hd, long ldh, const double *bvec, double *out);
+int launch_predict_missing_large_gamma(hipStream_t st, const double *Xc, const double *Psic, long ldx, int n, const double *Pio, int ldpio,
+                                       int m, int d, int k, unsigned obs, const double *U, const double *rec, const double *W, int ldw,
+                                       int ncol, int nchunk, double *part, long ldp);
 // ---- rows with missing inputs, covariance kinds (k_predict_missing_cov.hip; gpz_predictor_*_missing_cov_dev) --------------------------
 // One group of rows sharing a NaN pattern with no observed dimensions.  fits: GC or VC, 1 <= d <= 10, 1 <= k <= 8, ceil16(m) <= 256.
 // A record is predict_missing_cov_rec(no) = 1 + no + no (no + 1) / 2 doubles, [lnw | a | U]: -1/2 q = lnw - 1/2 |U (x_o - a)|^2.

@@ -19,6 +19,8 @@ struct gpz_predictor {
     bool force_tiles = false;      // GPZ_PREDICT_FORCE_TILES
     bool large_m = false;          // GPZ_PREDICT_LARGE_M: complete rows with Psi up to ceil16(m) <= 1024
     bool large_seen = false;       // such a handle past ceil16(m) = 256 has had a call with Psi (the route text)
+    bool large_m_missing = false;  // GPZ_PREDICT_LARGE_M_MISSING: a group with missing inputs (diagonal kinds) up to ceil16(m) <= 1024
+    bool mlarge_seen = false;      // such a handle past ceil16(m) = 256 has had a call for a group (the route text)
     int64_t ntile = 0;             // rows per tile of the calls that fill npart (the handle's tile, shrunk so that the slab is <= 1 GiB)
     int64_t tile_rows = 0, tile_pad = 0, runs = 0;
     int nk = 0, ldb = 0;           // fused: B_o is nk x ldb

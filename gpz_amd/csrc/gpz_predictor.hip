@@ -53,6 +53,9 @@
 // shapes): gpz_predictor_run_missing_dev / _draws_missing_dev run predictMissing on tiles of at most GPZ_PREDICTOR_TILE_MISSING rows
 // (k_predict_missing.hip): No and Pio, PHI through k_tgemm, then the fused pair kernel, or for the draws k_tgemm against W.  The tables
 // of a pattern (NijS, the pair records, U) are kept until the pattern or the priors change; all of it is allocated on the first such call.
+// On a handle created with GPZ_PREDICT_LARGE_M_MISSING these groups (and those with Psi below, their stacks and gamma per draw) stay on
+// the handle up to ceil16(m) <= 1024 (predict_missing_large_fits): the same tables, tiles, chunk count, slabs and finish, with the pair
+// product past 256 in k_pml_pairs / k_pml_gamma (k_predict_group_large_impl.h), whose LDS does not grow with m.
 // The covariance kinds have these two entries as gpz_predictor_run_missing_cov_dev / _draws_missing_cov_dev where
 // predict_missing_cov_fits holds (1 <= d <= 10, k <= 8, m <= 256; k_predict_missing_cov.hip): every density of predictMissing of
 // predictCov.m is a quadratic in the row's observed inputs, written once per pattern as a record; Ex, Pio and PHI per tile from the m
@@ -122,6 +125,7 @@ static int predictor_setup(gpz_predictor *p, const double *theta, const double *
     }
     p->force_tiles = (flags & GPZ_PREDICT_FORCE_TILES) != 0;
     p->large_m = (flags & GPZ_PREDICT_LARGE_M) != 0;
+    p->large_m_missing = (flags & GPZ_PREDICT_LARGE_M_MISSING) != 0;
     p->route = (!p->force_tiles && predict_small_fits(p->de, p->m, p->k)) ? 0 : 1;
     if (tile_rows <= 0) {
         if (p->route == 0) tile_rows = GPZ_PREDICTOR_TILE_FUSED;
@@ -599,6 +603,9 @@ static int predictor_draws_tile(gpz_predictor *p, int s, int64_t nt, int ncol, i
 // ---- rows with missing inputs on the handle -----------------------------------------------------------------------------------------
 // cov: the entries of the covariance kinds (ROWS_MISSING_COV); each of the two refuses the other's kinds and names their entry
 // noisy (with cov): the entries for such a group with Psi (ROWS_NOISY_MISSING_COV), whose diagonal kinds have gpz_predictor_*_noisy_missing_dev
+// a handle with GPZ_PREDICT_LARGE_M_MISSING whose model is past the limit without it: its groups run the panelled pair kernels
+static bool predictor_missing_is_large(const gpz_predictor *p) { return p->large_m_missing && rup(p->m, 16) > 256; }
+
 static int predictor_missing_check(const char *who, const gpz_predictor *p, uint32_t obs, bool cov, bool noisy = false) {
     if (cov && noisy && p->kind != GPZ_KIND_COV)
         return gpz_fail(GPZ_ERR_UNSUPPORTED,
@@ -615,7 +622,14 @@ static int predictor_missing_check(const char *who, const gpz_predictor *p, uint
                         "%s: missing inputs for a covariance kind on the handle need predict_missing_cov_fits: GC or VC, 1 <= d <= 10, "
                         "1 <= k <= 8 and ceil16(m) <= 256 (method %.2s, d %d, m %d, k %d); gpz_predict_missing takes every shape",
                         who, p->desc.method, p->d, p->m, p->k);
-    if (!cov && !predict_missing_fits(p->kind, p->de, p->m, p->k))
+    if (!cov && predictor_missing_is_large(p)) {   // (GPZ_PREDICT_LARGE_M_MISSING past 256: the limit in m alone is wider)
+        if (!predict_missing_large_fits(p->kind, p->de, p->m, p->k))
+            return gpz_fail(GPZ_ERR_UNSUPPORTED,
+                            "%s: missing inputs on the handle need predict_missing_large_fits: a diagonal kind (GL, VL, GD, VD), d <= 20, "
+                            "k <= 8 and, with GPZ_PREDICT_LARGE_M_MISSING, ceil16(m) <= %d (method %.2s, d %d, m %d, k %d); "
+                            "gpz_predict_missing takes every shape",
+                            who, GPZ_PREDICT_LARGE_M_MAX, p->desc.method, p->d, p->m, p->k);
+    } else if (!cov && !predict_missing_fits(p->kind, p->de, p->m, p->k))
         return gpz_fail(GPZ_ERR_UNSUPPORTED,
                         "%s: missing inputs on the handle need predict_missing_fits: a diagonal kind (GL, VL, GD, VD), d <= 20, k <= 8 and "
                         "ceil16(m) <= 256 (method %.2s, d %d, m %d, k %d); gpz_predict_missing takes every shape",
@@ -665,6 +679,7 @@ static int predictor_missing_prepare(gpz_predictor *p, const char *who, uint32_t
         if (!p->mout && (rc = ar.alloc(&p->mout, 4 * k * mtp))) return rc;
     }
     if (!noisy) p->miss_used = true;
+    if (predictor_missing_is_large(p)) p->mlarge_seen = true;
     const bool same_pri = priors ? (!p->mtab_uniform && p->mtab_pri.size() == m && std::equal(priors, priors + m, p->mtab_pri.begin()))
                                  : p->mtab_uniform;
     if (p->mtab_valid && p->mtab_obs == obs && same_pri && (p->mtab_pairs || !pairs)) return 0;
@@ -699,6 +714,12 @@ static int predictor_missing_tile(gpz_predictor *p, const char *who, int s, int 
     if (launch_pmd_phi(st, p->mNo, p->mT, nt, p->m, p->mp, p->k, p->w_d, v, p->mhd, mtp))
         return gpz_fail(GPZ_ERR_HIP, "%s: k_pmd_phi launch failed", who);
     // with Psi: the second record table (C, not 1 / C, and lnZ without the determinant, which depends on the row's Psi)
+    if (pairs && predictor_missing_is_large(p)) {   // the same tables, slab and finish behind the panelled kernel
+        if (launch_predict_missing_large_pairs(st, p->Xc[s], Psic, p->tile_pad, nt, p->mPio, p->mp, p->m, p->d, p->k, obs, p->mU,
+                                               Psic ? p->nmrec : p->mrec, p->mchunks, p->mpart, mtp, p->mhd, mtp, p->pr.b, p->mout))
+            return gpz_fail(GPZ_ERR_HIP, "%s: k_pml_pairs%s launch failed", who, Psic ? "_psi" : "");
+        return 0;
+    }
     if (pairs && launch_predict_missing_pairs(st, p->Xc[s], Psic, p->tile_pad, nt, p->mPio, p->mp, p->m, p->d, p->k, obs, p->mU,
                                               Psic ? p->nmrec : p->mrec, p->mchunks, p->mpart, mtp, p->mhd, mtp, p->pr.b, p->mout))
         return gpz_fail(GPZ_ERR_HIP, "%s: k_predict_%smissing_pairs launch failed", who, Psic ? "noisy_" : "");
@@ -1001,6 +1022,13 @@ int rows_gamma_tile(gpz_predictor *p, const char *who, const Rows &r, int s, int
                             r.kind == ROWS_MISSING_COV ? "missing_cov" : group_psi_form(p, r).name);   //  keeps its own kind's name)
         return 0;
     }
+    if (r.group() && predictor_missing_is_large(p)) {   // a group with Psi: the second record table
+        if (launch_predict_missing_large_gamma(p->s_cmp, p->Xc[s], r.psi() ? p->Psic[s] : nullptr, p->tile_pad, nt, p->mPio, p->mp, p->m,
+                                               p->d, p->k, r.obs, p->mU, r.psi() ? p->nmrec : p->mrec, p->Wd, ldw, ncol, p->mchunks,
+                                               p->gpart, nt))
+            return gpz_fail(GPZ_ERR_HIP, "%s: k_pml_gamma%s launch failed", who, r.psi() ? "_psi" : "");
+        return 0;
+    }
     // a group with Psi: the second record table
     if (r.kind == ROWS_NOISY
             ? launch_predict_noisy_gamma(p->s_cmp, p->d, p->Xc[s], p->Psic[s], p->tile_pad, nt, p->m, p->ptab, p->nrec, p->Wd, ldw, ncol,
@@ -1159,7 +1187,7 @@ extern "C" int gpz_predictor_create(const gpz_desc *desc, const double *theta, c
     *out = nullptr;
     if (!desc || !theta || !w || !iSigma_w) return gpz_fail(GPZ_ERR_ARG, "gpz_predictor_create: null argument");
     if (desc->dtype != GPZ_F64) return gpz_fail(GPZ_ERR_ARG, "gpz_predictor_create: fp64 only");
-    if (flags & ~(GPZ_PREDICT_FORCE_TILES | GPZ_PREDICT_LARGE_M)) return gpz_fail(GPZ_ERR_ARG, "gpz_predictor_create: unknown flags %d", (int)flags);
+    if (flags & ~(GPZ_PREDICT_FORCE_TILES | GPZ_PREDICT_LARGE_M) & ~GPZ_PREDICT_LARGE_M_MISSING) return gpz_fail(GPZ_ERR_ARG, "gpz_predictor_create: unknown flags %d", (int)flags);
     gpz_predictor *p = new gpz_predictor();
     p->desc = *desc;
     p->desc.world = 1;
@@ -1215,7 +1243,11 @@ extern "C" int gpz_predictor_route(const gpz_predictor *p, char *buf, int cap) {
     auto gamma_line = [&](int i) {
         const gpz_predictor::PerDraw &g = p->gam[i];
         if (!g.used) return;
-        snprintf(tmp, sizeof tmp, PER_DRAW[i].fmt, PER_DRAW[i].group ? p->mchunks : p->gchunks);
+        if (p->mlarge_seen && (i == 1 || i == 2))   // a diagonal kind's group past 256: the panelled kernels
+            snprintf(tmp, sizeof tmp, i == 1 ? "; missing per draw: k_pml_gamma (%d pair chunks)" : "; noisy missing per draw: k_pml_gamma_psi (%d pair chunks)",
+                     p->mchunks);
+        else
+            snprintf(tmp, sizeof tmp, PER_DRAW[i].fmt, PER_DRAW[i].group ? p->mchunks : p->gchunks);
         r += tmp;
         if (g.s2_d) r += " + k_stack_tile_w";   // the widths exist: a stack call was among them
     };
@@ -1249,8 +1281,14 @@ extern "C" int gpz_predictor_route(const gpz_predictor *p, char *buf, int cap) {
         snprintf(tmp, sizeof tmp, "; noisy large-m: tiles, %d chunks", predict_noisy_chunks(p->m, p->d, p->k));
         r += tmp;
     }
+    if (p->mlarge_seen) {   // a handle with GPZ_PREDICT_LARGE_M_MISSING past ceil16(m) = 256, after its first call for a group: the kernels
+        snprintf(tmp, sizeof tmp, "; missing past 256: k_pml_pairs / k_pml_gamma (K panels of %d, %d groups per batch)", GPZ_PML_KP,   // behind
+                 p->k == 1 ? GPZ_PML_GB : GPZ_PML_GB8);                                                                          // the lines below
+        r += tmp;
+    }
     if (p->miss_used) {   // after the first call for a group of rows with missing inputs
-        snprintf(tmp, sizeof tmp, "; missing: k_predict_missing_pairs (%d pair chunks), %lld-row tiles", p->mchunks, (long long)p->mtile);
+        snprintf(tmp, sizeof tmp, "; missing: %s (%d pair chunks), %lld-row tiles", p->mlarge_seen ? "k_pml_pairs" : "k_predict_missing_pairs",
+                 p->mchunks, (long long)p->mtile);
         r += tmp;
     }
     if (p->mcov_used) {   // after the first call for a group of rows with missing inputs on a covariance kind
@@ -1260,7 +1298,8 @@ extern "C" int gpz_predictor_route(const gpz_predictor *p, char *buf, int cap) {
     gamma_line(4);
     gamma_line(1);
     if (p->nm_used) {   // after the first call for a group of rows with input noise and missing inputs
-        snprintf(tmp, sizeof tmp, "; noisy missing: k_predict_noisy_missing_pairs (%d pair chunks)", p->mchunks);
+        snprintf(tmp, sizeof tmp, "; noisy missing: %s (%d pair chunks)", p->mlarge_seen ? "k_pml_pairs_psi" : "k_predict_noisy_missing_pairs",
+                 p->mchunks);
         r += tmp;
     }
     gamma_line(2);

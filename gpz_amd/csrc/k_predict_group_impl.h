@@ -173,6 +173,62 @@ struct PredGammaSink {
     }
 };
 
+// z of one group from its accumulators into the sink: the epilogue of predict_group_body and of predict_group_large_body
+// (k_predict_group_large_impl.h).  acc0[r], acc1[r] = sum_l Pio(row, l) Nu_q(l) for rows l & 15, 16 + (l & 15) and pair q = (l >> 4) + 4 r   :185-186, :271-272
+// The exponent lnZ - q / 2 is ONE fma, written out: the compiler contracts "lz - 0.5 * q" to it only where product and difference
+// land in one basic block, which the sink decides, and a row's bits must not depend on the sink.
+template <bool PSI, class Sink>
+__device__ __forceinline__ void pred_group_epilogue(const PredGroupArgs &a, const PredGroupAt &at, Sink &sink, const int2 *sAB, d4_t acc0, d4_t acc1,
+                                             const double *rb, int rl, const double *x0, const double *x1, const double *s0,
+                                             const double *s1) {
+    const int d = a.d;
+    double qa[4] = {0.0, 0.0, 0.0, 0.0}, qb[4] = {0.0, 0.0, 0.0, 0.0};
+    if constexpr (!PSI) {
+        for (int c = 0; c < d; ++c) {
+            const double xa = x0[c], xb = x1[c];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const double *t = rb + 4 * r * rl;
+                const double cc = t[1 + c], ic = t[1 + d + c];
+                const double da = xa - cc, db = xb - cc;
+                qa[r] = fma(da * da, ic, qa[r]);                   // :178-179
+                qb[r] = fma(db * db, ic, qb[r]);
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const double *t = rb + 4 * r * rl;
+            const double lz = t[0];
+            const double za = acc0[r] * exp(fma(-0.5, qa[r], lz)), zb = acc1[r] * exp(fma(-0.5, qb[r], lz));   // :189
+            sink.take(a, at, sAB, r, za, zb, t);
+        }
+    } else {
+        double ra[4] = {1.0, 1.0, 1.0, 1.0}, rb4[4] = {1.0, 1.0, 1.0, 1.0};
+        for (unsigned mk = a.obs; mk; mk &= mk - 1) {   // the observed dimensions only (uniform: scalar control flow)
+            const int c = __builtin_ctz(mk);
+            const double xa = x0[c], xb = x1[c], pa = s0[c], pb = s1[c];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const double *t = rb + 4 * r * rl;
+                const double cc = t[1 + c], C = t[1 + d + c];
+                const double ia = rsqrt_nr2(C + pa), ib = rsqrt_nr2(C + pb);   // (Cij + Psi)^-1/2            :264-265
+                const double da = (xa - cc) * ia, db = (xb - cc) * ib;
+                qa[r] = fma(da, da, qa[r]);
+                qb[r] = fma(db, db, qb[r]);
+                ra[r] *= ia;
+                rb4[r] *= ib;
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const double *t = rb + 4 * r * rl;
+            const double lz = t[0];
+            const double za = acc0[r] * (exp(fma(-0.5, qa[r], lz)) * ra[r]), zb = acc1[r] * (exp(fma(-0.5, qb[r], lz)) * rb4[r]);   // :275
+            sink.take(a, at, sAB, r, za, zb, t);
+        }
+    }
+}
+
 template <bool PSI, class Sink>
 __device__ __forceinline__ void predict_group_body(const PredGroupArgs &a) {
     extern __shared__ double smem[];
@@ -239,54 +295,7 @@ __device__ __forceinline__ void predict_group_body(const PredGroupArgs &a) {
             for (int q = 0; q < 4; ++q) ua[q] = un[q];
         }
         __syncthreads();   // the records (and the sink's own staging) are in LDS
-        // ---- epilogue: acc0[r], acc1[r] = sum_l Pio(row, l) Nu_q(l) for rows l & 15, 16 + (l & 15) and pair q = (l >> 4) + 4 r   :185-186, :271-272
-        // The exponent lnZ - q / 2 is ONE fma, written out: the compiler contracts "lz - 0.5 * q" to it only where product and difference
-        // land in one basic block, which the sink decides, and a row's bits must not depend on the sink.
-        double qa[4] = {0.0, 0.0, 0.0, 0.0}, qb[4] = {0.0, 0.0, 0.0, 0.0};
-        if constexpr (!PSI) {
-            for (int c = 0; c < d; ++c) {
-                const double xa = x0[c], xb = x1[c];
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const double *t = rb + 4 * r * rl;
-                    const double cc = t[1 + c], ic = t[1 + d + c];
-                    const double da = xa - cc, db = xb - cc;
-                    qa[r] = fma(da * da, ic, qa[r]);                   // :178-179
-                    qb[r] = fma(db * db, ic, qb[r]);
-                }
-            }
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const double *t = rb + 4 * r * rl;
-                const double lz = t[0];
-                const double za = acc0[r] * exp(fma(-0.5, qa[r], lz)), zb = acc1[r] * exp(fma(-0.5, qb[r], lz));   // :189
-                sink.take(a, at, sAB, r, za, zb, t);
-            }
-        } else {
-            double ra[4] = {1.0, 1.0, 1.0, 1.0}, rb4[4] = {1.0, 1.0, 1.0, 1.0};
-            for (unsigned mk = obs; mk; mk &= mk - 1) {   // the observed dimensions only (uniform: scalar control flow)
-                const int c = __builtin_ctz(mk);
-                const double xa = x0[c], xb = x1[c], pa = s0[c], pb = s1[c];
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const double *t = rb + 4 * r * rl;
-                    const double cc = t[1 + c], C = t[1 + d + c];
-                    const double ia = rsqrt_nr2(C + pa), ib = rsqrt_nr2(C + pb);   // (Cij + Psi)^-1/2            :264-265
-                    const double da = (xa - cc) * ia, db = (xb - cc) * ib;
-                    qa[r] = fma(da, da, qa[r]);
-                    qb[r] = fma(db, db, qb[r]);
-                    ra[r] *= ia;
-                    rb4[r] *= ib;
-                }
-            }
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const double *t = rb + 4 * r * rl;
-                const double lz = t[0];
-                const double za = acc0[r] * (exp(fma(-0.5, qa[r], lz)) * ra[r]), zb = acc1[r] * (exp(fma(-0.5, qb[r], lz)) * rb4[r]);   // :275
-                sink.take(a, at, sAB, r, za, zb, t);
-            }
-        }
+        pred_group_epilogue<PSI, Sink>(a, at, sink, sAB, acc0, acc1, rb, rl, x0, x1, s0, s1);
     }
     sink.reduce(a, at, smem);
 }

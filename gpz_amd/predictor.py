@@ -27,6 +27,7 @@ from .api import _desc, _f64, nan_row_groups
 GPZ_PREDICT_FORCE_TILES = 1   # gpz_predictor_create flags (include/gpz_hip.h)
 GPZ_PREDICT_LARGE_M = 2       # complete rows with Psi stay on the handle up to GPZ_PREDICT_LARGE_M_MAX basis functions
 GPZ_PREDICT_LARGE_M_MAX = 1024
+GPZ_PREDICT_LARGE_M_MISSING = 4   # one NaN-pattern group of a diagonal kind stays on the handle up to the same limit
 GPZ_DRAWS_MAX_COLUMNS = 16384   # n_draws * k per gpz_predictor_draws call (include/gpz_hip.h)
 GPZ_STACK_MAX_GROUP_BINS = 4096   # n_groups * n_bins per gpz_predictor_stack call (include/gpz_hip.h)
 
@@ -86,9 +87,17 @@ class Predictor:
     costs nothing before the first call with Psi and changes nothing for m <= 256; beyond, the first call builds a table of
     m (m + 1) / 2 pair records (0.1 to 0.4 GB at m = 1024, and for GC / VC a temporary of (1 + d + d * d) doubles per pair while it
     is built) and every row costs m (m + 1) / 2 pair densities, 524 800 at m = 1024.  With ``force_tiles=True`` as well, the draws of
-    a diagonal kind with Psi run as E_x[PHI] of a tile (k_predict_noisy_phi) against the weights on the T-GEMM at any m."""
+    a diagonal kind with Psi run as E_x[PHI] of a tile (k_predict_noisy_phi) against the weights on the T-GEMM at any m.
 
-    def __init__(self, model, whichSet="best", device=0, tile_rows=None, force_tiles=False, large_m=False):
+    ``large_m_missing=True`` (GPZ_PREDICT_LARGE_M_MISSING, and GPZ_PREDICT_LARGE_M with it for the complete rows of a catalogue with
+    Psi) widens the methods for rows with missing values of a diagonal kind to m = 1024 as well: ``predict_dev(X, missing=True)``,
+    ``draws_dev(X, n, missing=True[, return_gamma=True])``, ``stack_missing_dev``, ``predict_noisy_missing_dev``,
+    ``draws_noisy_missing_dev`` and ``stack_noisy_missing_dev``; the ``*_missing_cov_dev``, ``*_noisy_missing_cov_dev`` and
+    ``*_psi_cube_missing_dev`` methods of GC / VC keep m <= 256.  It changes nothing for m <= 256; beyond, the first call for a group
+    builds the pattern's tables, m (m + 1) / 2 x ceil16(m) doubles of U (0.54 GB at m = 512, 4.3 GB at m = 1024), rebuilt in place
+    when the pattern or the priors change, and every such row costs m (m + 1) / 2 x ceil16(m) multiply-adds on the f64 MFMA."""
+
+    def __init__(self, model, whichSet="best", device=0, tile_rows=None, force_tiles=False, large_m=False, large_m_missing=False):
         if whichSet not in getattr(model, "sets", {}):
             raise ValueError(f"whichSet {whichSet!r} is not one of the model's sets {sorted(getattr(model, 'sets', {}))}")
         m, d, k = int(model.m), int(model.d), int(model.k)
@@ -115,7 +124,8 @@ class Predictor:
         self.model, self.whichSet, self.device = model, whichSet, int(device)
         self._m, self._d, self._k, self._method = m, d, k, method
         self._tile_rows = 0 if tile_rows is None else int(tile_rows)
-        self._flags = (GPZ_PREDICT_FORCE_TILES if force_tiles else 0) | (GPZ_PREDICT_LARGE_M if large_m else 0)
+        self._flags = (GPZ_PREDICT_FORCE_TILES if force_tiles else 0) | (GPZ_PREDICT_LARGE_M if large_m else 0) | \
+                      (GPZ_PREDICT_LARGE_M | GPZ_PREDICT_LARGE_M_MISSING if large_m_missing else 0)
         self._h = None
         self._closed = False
         self._lib = None
@@ -458,9 +468,10 @@ class Predictor:
         if Psi is not None:
             raise ValueError(f"{what} with missing=True does not take Psi: rows with both input noise and missing values "
                              "(predictNoisyMissing) go to predict_noisy_missing_dev / draws_noisy_missing_dev")
+        most = GPZ_PREDICT_LARGE_M_MAX if self._flags & GPZ_PREDICT_LARGE_M_MISSING else 256   # (predict_missing_large_fits)
         bad = [text for outside, text in ((self._method[1] == "C", f"a diagonal kind (GL, VL, GD, VD), not {self._method}"),
                                           (self._d > 20, f"d <= 20, not d = {self._d}"), (self._k > 8, f"k <= 8, not k = {self._k}"),
-                                          (self._m > 256, f"m <= 256, not m = {self._m}")) if outside]
+                                          (self._m > most, f"m <= {most}, not m = {self._m}")) if outside]
         if bad:
             raise ValueError(f"{what}{how} needs a model inside predict_missing_fits: " + "; ".join(bad) +
                              " (Predictor.predict takes rows with missing values for every shape)")

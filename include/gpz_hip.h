@@ -231,6 +231,16 @@ typedef struct gpz_predictor gpz_predictor;
  * m (m + 1) / 2 = 524 800 records (0.1 to 0.4 GB, and for GC / VC a temporary of 524 800 (1 + d + d d) doubles while it is built) and
  * 524 800 pair densities per row. */
 #define GPZ_PREDICT_LARGE_M 2
+/* flags: one group of rows with missing inputs stays on the handle up to ceil16(m) <= 1024 for the diagonal kinds (GL, VL, GD, VD),
+ * d <= 20, k <= 8.  Read only by the entries that take one NaN-pattern group of such a kind: gpz_predictor_run_missing_dev,
+ * _draws_missing_dev, _draws_gamma_missing_dev, _stack_missing_dev and their noisy_missing twins; the covariance kinds' entries
+ * (*_missing_cov_dev, *_noisy_missing_cov_dev, *_psi_cube_missing_dev) and every entry for complete rows do not look at it (complete rows
+ * with Psi past 256 need GPZ_PREDICT_LARGE_M as well).  Where ceil16(m) <= 256 the flag changes no kernel, chunk count, byte or bit;
+ * beyond, the pair product runs in k_pml_pairs / k_pml_gamma (k_predict_group_large_impl.h), whose LDS does not grow with m.  The cost
+ * at m = 1024, on the first call for a group: U of 524 800 x 1024 doubles (4.3 GB) and the pair records (0.1 to 0.3 GB), rebuilt in
+ * place when the pattern or the priors change; every row costs 524 800 x 1024 multiply-adds on the f64 MFMA.  Past 1024:
+ * GPZ_ERR_UNSUPPORTED, naming m and the limit. */
+#define GPZ_PREDICT_LARGE_M_MISSING 4
 int gpz_predictor_create(const gpz_desc *desc, const double *theta, const double *w, const double *iSigma_w,
                          int64_t tile_rows, int32_t flags, gpz_predictor **out);
 void gpz_predictor_destroy(gpz_predictor *p);
@@ -502,7 +512,10 @@ int gpz_predictor_stack_psi_cube_dev(gpz_predictor *p, const void *X_d, int32_t 
  * (4.5 MB at m = 100, 67 MB at m = 256), the pair records and an mp x mp factor; per handle three [tile][mp] buffers with tile =
  * min(tile_rows, 16384).  All of it is allocated on the first such call and does not grow with ns or the number of patterns; a
  * handle that never sees such a call holds what it held.  A row's results have the same bits for any tile size, row order or split
- * of the rows into calls.  gpz_predictor_route then ends in "; missing: k_predict_missing_pairs (C pair chunks), T-row tiles". */
+ * of the rows into calls.  gpz_predictor_route then ends in "; missing: k_predict_missing_pairs (C pair chunks), T-row tiles".
+ * On a handle with GPZ_PREDICT_LARGE_M_MISSING these entries, the stack and gamma-per-draw entries below and their noisy_missing
+ * twins take ceil16(m) <= 1024 (predict_missing_large_fits); past 256 the route text then adds "; missing past 256: k_pml_pairs / k_pml_gamma
+ * (K panels of 128, 4 groups per batch)", 2 groups where k > 1. */
 int gpz_predictor_run_missing_dev(gpz_predictor *p, const void *X_d, int32_t x_type, int64_t ns, int64_t row_stride, int64_t col_stride,
                                   const double *muX, const double *sdX, const double *muY /* k or NULL */,
                                   const double *priors /* m or NULL */, uint32_t obs_mask,
